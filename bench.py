@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the reference's headline metric on MI355X: Mray/s (ray segments per second).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one full frame through the hot path: rays generated on the device, every one of the
@@ -18,9 +18,14 @@ Workload (BASELINE.json `configs`):
             values are directly comparable with the N = 1 line.  (--workload c2-weak: one C2 band per rank instead.)
 
 The JSON line carries `roofline` (VALU-issue bound: SURVEY.md 8(d), F(Ns)=20*Ns+33 fp32 operations per segment against
-the vector fp32 peak) and, at N=1 on rank 0, `cpu_baseline` (the oracle's C restatement timed on the host cores on a
-bounded pixel sample of the same workload) plus `extra` (the same frame in O-mode, with compaction, and through the
-reference's exact MT19937 pipeline).
+the vector fp32 peak, from the timed steps' own HIP events).  A plain run does nothing else: set-up, warm-up, the timed
+steps, the line.  `--full` adds what takes runs or checks of its own: the live rocprofv3 counters of the roofline block
+(N = 1), and on rank 0 `quality` (the frame against the oracle), at N = 1 `cpu_baseline` (the oracle's C restatement timed
+on the host cores on a bounded pixel sample of the same workload), `roofline_o_mode` and `extra` (the same frame in
+O-mode, with compaction, and through the reference's exact MT19937 pipeline).
+
+`--dump-outputs DIR` writes the frame the last timed step produced (see dump_outputs), so that two builds can be compared
+output for output: the inputs are fixed by the arguments (seed 0, the gen_spheres() scene).
 """
 import argparse
 import json
@@ -153,6 +158,31 @@ def gathered_frame_check(full_fb, full_u8, case_names=("C3_bands", "C3_spread", 
             pixels += c
     return {"checked_against": "tests/golden/fullsize_hashes.json: " + ", ".join(case_names) + " (oracle-made hashes of ranges of the gathered frame)",
             "ranges": n, "pixels_checked": pixels, "mismatching_ranges": bad, "ok": not bad}
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20     # a larger frame is written on this many pixels of a fixed seeded sample
+
+
+def dump_outputs(out_dir, fb, u8):
+    """--dump-outputs: the frame as a caller of the render path receives it -- framebuffer.npy (float32 [3][pixels], the
+    per-pixel mean radiance) and image_u8.npy (the 8-bit image [pixels][3], as float32).  Whole when both fit in DUMP_BYTES;
+    otherwise the same arrays on DUMP_SAMPLE_PIXELS pixels drawn with a fixed seed, in ascending order, whose indices are
+    in pixel_index.npy (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    npix = fb.shape[1]
+    arrays = {}
+    if 24 * npix > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(npix, DUMP_SAMPLE_PIXELS, replace=False))
+        sel = torch.from_numpy(idx).to(fb.device)
+        fb, u8 = fb[:, sel], u8[sel]
+        arrays["pixel_index"] = idx.astype(np.float64)
+    arrays["framebuffer"] = fb.cpu().numpy().astype(np.float32)
+    arrays["image_u8"] = u8.cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def timed(torch, fn, reps):
@@ -475,15 +505,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=["auto", "c2", "c3", "c2-weak"], default="auto")
     ap.add_argument("--stripes", type=int, default=1, help="interleaved stripes per rank (N > 1; see dist.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-traffic-probe", action="store_true", help="do not measure roofline.traffic / the VALU counters with rocprofv3 child processes (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR/*.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: live rocprofv3 counters (N = 1), the frame against the "
+                         "oracle, and at N = 1 the CPU baseline, O-mode and the extra configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no quality check at N = 1")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no `extra` block")
+    ap.add_argument("--no-traffic-probe", action="store_true", help="with --full: do not measure roofline.traffic / the VALU counters with rocprofv3 child processes (N = 1)")
     ap.add_argument("--traffic-probe", action="store_true", help="internal: the launches measure_counters() profiles")
     ap.add_argument("--dry-run", action="store_true",
                     help="control-flow rehearsal without a GPU (tests/test_bench_dry_run.py): gloo, CPU tensors, a tiny frame and NO "
                          "render at all (the launch is a no-op) -- exercises the rendezvous, sharding, double-buffered gather, "
                          "reductions and the JSON line; the numbers mean nothing and the line says so")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)         # plain `python bench.py --gpus N`: start the N ranks ourselves
     if args.dry_run:
@@ -494,7 +530,7 @@ def main():
     __graft_entry__.build()                   # incremental, serialised by a file lock; does not touch the GPU
 
     live = None
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.workload in ("auto", "c2") and not args.no_traffic_probe:
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.workload in ("auto", "c2") and not args.no_traffic_probe:
         live = measure_counters()             # child processes (they find the library built); this process has not touched the GPU yet
 
     import torch
@@ -563,6 +599,8 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)     # HIP events around this rank's launch(es)
+    if args.dump_outputs and rank == 0:       # the last step's frame: the gathered one on the root, else this rank's slot
+        dump_outputs(args.dump_outputs, *(full if world > 1 else slots[(args.steps - 1) % 2][0]))
 
     per_rank_ms = [kern_ms]
     if world > 1:
@@ -648,9 +686,9 @@ def main():
                         "gather": shard.timings(),
                         "gather_bytes_per_rank": shard.packed_bytes,
                         "load_imbalance_max_over_mean": round(max(per_rank_ms) / (sum(per_rank_ms) / world), 4)}
-    if rank == 0 and world > 1 and workload == "c3":
+    if args.full and rank == 0 and world > 1 and workload == "c3":
         out["quality"] = gathered_frame_check(*full)       # the last frame's gather has finished (sync above)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             fbv, u8v = slots[(args.steps - 1) % 2][0]
             out["quality"] = quality_check(cfg, fbv, u8v)

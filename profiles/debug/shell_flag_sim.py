@@ -1,5 +1,5 @@
-import numpy as np, sys
-sys.path.insert(0,'/root/repo')
+import numpy as np, os, sys
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 from ascendpathtracing_amd import gen_data
 ns=10000
 scene=gen_data.gen_scene(ns, seed=1)

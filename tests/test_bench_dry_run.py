@@ -215,3 +215,57 @@ def test_multi_rank_profile_summary_reports_valu_occupancy_and_hbm_rate_per_rank
         assert s["valu_insts_per_simd_cycle"] == 0.2 and s["waves_per_simd"] == 4.0 and s["lane_activity"] == 0.9375 and s["effective_clock_ghz"] == 2.0
     out = json.loads((tmp_path / "summary.json").read_text())
     assert out["n_gpus"] == 2 and out["segments_per_gpu"] == seg and len(out["ranks"]) == 2
+
+
+def test_dump_outputs_writes_the_whole_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the frame as float32 .npy files, whole when it fits in the byte budget, else the same
+    arrays on a seeded sample of pixels (ascending, their indices beside them) -- identical from run to run."""
+    import numpy as np
+    import torch
+    import bench
+    n = 1000
+    fb = torch.arange(3 * n, dtype=torch.float32).view(3, n) / 7
+    u8 = (torch.arange(3 * n) % 251).to(torch.uint8).view(n, 3)
+    bench.dump_outputs(str(tmp_path / "whole"), fb, u8)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["framebuffer.npy", "image_u8.npy"]
+    got_fb, got_u8 = np.load(tmp_path / "whole" / "framebuffer.npy"), np.load(tmp_path / "whole" / "image_u8.npy")
+    assert got_fb.dtype == np.float32 and np.array_equal(got_fb, fb.numpy())
+    assert got_u8.dtype == np.float32 and np.array_equal(got_u8, u8.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 24 * n - 1)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), fb, u8)
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    sel = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "framebuffer.npy"), fb.numpy()[:, sel])
+    assert np.array_equal(np.load(tmp_path / "a" / "image_u8.npy"), u8.numpy()[sel].astype(np.float32))
+    for f in ("pixel_index.npy", "framebuffer.npy", "image_u8.npy"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """A plain `bench.py --gpus 1` is the headline only (nothing `--full` adds), times exactly --steps steps, and
+    --dump-outputs writes the C2 frame of the last step: bit for bit the oracle's (tests/golden/fullsize_hashes.json)."""
+    import hashlib
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "Mray/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert not {"cpu_baseline", "quality", "roofline_o_mode", "extra"} & set(out)
+    assert "traffic_probe_error" not in out["roofline"] and "valu_insts_per_simd_cycle" not in out["roofline"]
+    fb = np.load(tmp_path / "framebuffer.npy")
+    u8 = np.load(tmp_path / "image_u8.npy").astype(np.uint8)
+    assert fb.shape == (3, 1920 * 1080) and u8.shape == (1920 * 1080, 3)
+    with open(os.path.join(ROOT, "tests", "golden", "fullsize_hashes.json")) as f:
+        case = json.load(f)["cases"]["C2"]
+    for k, (b, c) in enumerate(case["ranges"]):
+        assert hashlib.sha256(np.ascontiguousarray(fb[:, b:b + c]).tobytes()).hexdigest() == case["fb_sha256"][k], k
+        assert hashlib.sha256(np.ascontiguousarray(u8[b:b + c]).tobytes()).hexdigest() == case["u8_sha256"][k], k
