@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/render_mi355x.h"
@@ -30,6 +31,23 @@ namespace {
 using apt::clear_error;
 int fail(int code, const char *fmt, const char *detail = "") { return apt::set_error(code, fmt, detail); }
 int hip_fail(hipError_t e) { return fail(APT_ERR_DEVICE, "HIP: %s", hipGetErrorString(e)); }
+// the outcome of the launches just made
+int launched() {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? APT_OK : hip_fail(e);
+}
+
+// Run-time settings -> template arguments: `f` is called with the value as a std::integral_constant, so a launch inside it
+// names its kernel as kernel<m, ...>.  Every combination `f` can reach is instantiated: a call site that must not reach one
+// (render_frame_kernel's and render_paths_kernel's static_asserts) handles that case before it dispatches.
+template <class F> void with_mode(uint32_t mode, F &&f) {
+    if (mode == APT_MODE_ORACLE) f(std::integral_constant<int, kModeOracle>{});
+    else f(std::integral_constant<int, kModeKernel>{});
+}
+template <class F> void with_flag(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 int make_leaf_prog(uint32_t samples, LeafProg &lp) {   // the plan itself: pt_leaf.h
     return make_leaf_plan(samples, lp) ? APT_OK : fail(APT_ERR_ARG, "samples too large: its pairwise-sum plan needs more than 64 leaves (every count <= 7688 fits, and 8192)%s");
@@ -87,41 +105,40 @@ TraceArgs make_trace_args(const apt_render_params *p, const Launch &ls) {
     return ta;
 }
 
+// The path range [b, b + c) of a buffer-mode call (path_count 0: to the end of the image) among the image's n_image paths.  With
+// APT_FLAG_BAND_BUFFERS the caller's buffers are planes of c floats holding the range only: plane() is their length either way, and
+// base() shifts such a buffer so that path p sits at index p, the indexing of a whole-image buffer.
+struct PathRange {
+    uint64_t n_image, b, c;
+    bool band;
+    uint64_t plane() const { return band ? c : n_image; }
+    template <class T> T *base(T *buf) const { return band ? buf - b : buf; }
+};
+// -> APT_OK with r.c == 0 for an empty range: the call is a no-op, the caller returns APT_OK without launching anything
+int path_range(const apt_render_params *p, PathRange &r) {
+    r.n_image = (uint64_t)p->width * p->height * 4u * p->samples;
+    r.b = p->path_begin;
+    if (r.b > r.n_image) return fail(APT_ERR_ARG, "path_begin beyond the image%s");
+    r.c = p->path_count ? p->path_count : r.n_image - r.b;
+    if (r.b + r.c > r.n_image) return fail(APT_ERR_ARG, "path range beyond the image%s");
+    r.band = p->flags & APT_FLAG_BAND_BUFFERS;
+    return APT_OK;
+}
+
+FrameArgs make_frame_args(const apt_render_params *p, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+    FrameArgs fa;
+    camera_init(fa.cam, p->width, p->height);
+    fa.width = p->width; fa.height = p->height; fa.samples = p->samples; fa.seed = p->seed;
+    fa.pixel_begin = pixel_begin; fa.pixel_count = pixel_count; fa.fb = fb; fa.fb_u8 = fb_u8;
+    return fa;
+}
+
+// bytes of the zero-padded [10][Ns] sphere table (a 512-byte multiple, gen_data.py:120-127)
+size_t sphere_table_bytes(uint32_t num_spheres) { return ((size_t)num_spheres * 10 + 127) / 128 * 128 * sizeof(float); }
+
 // Buffer mode takes the two-paths-per-lane kernel from this many paths on: below it the one-path kernel's twice as many workgroups fill the
 // chip better (C1, the reference's own CPU-runnable configuration, is 262 144 paths = 1024 workgroups of it: launch-bound either way).
 constexpr uint64_t kTwoPathBufferMin = 1ull << 20;
-
-template <int MODE, int SC>
-void launch_paths(bool retire, dim3 grid, hipStream_t st, const float *rays, const float *sph, float *colors,
-                  uint64_t n, uint64_t b, uint64_t c, const TraceArgs &ta) {
-    if (retire) hipLaunchKernelGGL((render_paths_kernel<MODE, SC, true>), grid, dim3(kBlock), 0, st, rays, sph, colors, n, b, c, ta);
-    else hipLaunchKernelGGL((render_paths_kernel<MODE, SC, false>), grid, dim3(kBlock), 0, st, rays, sph, colors, n, b, c, ta);
-}
-
-template <int MODE, int SC, int GROUP>
-void launch_frame(bool retire, dim3 grid, size_t lds, hipStream_t st, const float *sph, const FrameArgs &fa,
-                  const TraceArgs &ta, const LeafProg &lp) {
-    if constexpr (SC == kScene8 && GROUP == 8) {
-        // With APT_FLAG_RETIRE these frames belong to the sample-queue kernel (pt_queue.h); what arrives here with the flag set is
-        // depth 0, where there is nothing to retire.  (Round 2's wave queue inside render_frame_kernel for this case is gone.)
-        hipLaunchKernelGGL((render_frame_kernel<MODE, SC, GROUP, false>), grid, dim3(kBlock), lds, st, sph, fa, ta, lp);
-    } else {
-        if (retire) hipLaunchKernelGGL((render_frame_kernel<MODE, SC, GROUP, true>), grid, dim3(kBlock), lds, st, sph, fa, ta, lp);
-        else hipLaunchKernelGGL((render_frame_kernel<MODE, SC, GROUP, false>), grid, dim3(kBlock), lds, st, sph, fa, ta, lp);
-    }
-}
-
-template <int MODE, int SC>
-void launch_frame_g(int group, bool retire, dim3 grid, size_t lds, hipStream_t st, const float *sph,
-                    const FrameArgs &fa, const TraceArgs &ta, const LeafProg &lp) {
-    // the headline case -- 8 spheres, >= 16 samples, every segment traced, no roulette -- runs two paths per lane
-    if (SC == kScene8 && group == 8 && !retire && ta.rr_start == 0 && fa.samples >= 16) {
-        hipLaunchKernelGGL((render_frame_kernel<MODE, kScene8, 8, false, true>), grid, dim3(kBlock), lds, st, sph, fa, ta, lp);
-        return;
-    }
-    if (group == 8) launch_frame<MODE, SC, 8>(retire, grid, lds, st, sph, fa, ta, lp);
-    else launch_frame<MODE, SC, 1>(retire, grid, lds, st, sph, fa, ta, lp);
-}
 
 // ---- the two render launches, on an explicit snapshot of a context's values -----------------
 int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, const float *rays,
@@ -129,12 +146,9 @@ int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, 
     int rc = check_params(p);
     if (rc) return rc;
     if (!rays || !spheres || !colors) return fail(APT_ERR_ARG, "rays/spheres/colors must be non-null%s");
-    const uint64_t n_image = (uint64_t)p->width * p->height * 4u * p->samples;
-    const uint64_t b = p->path_begin;
-    if (b > n_image) return fail(APT_ERR_ARG, "path_begin beyond the image%s");
-    const uint64_t c = p->path_count ? p->path_count : n_image - b;
-    if (b + c > n_image) return fail(APT_ERR_ARG, "path range beyond the image%s");
-    if (c == 0) return APT_OK;
+    PathRange r;
+    if ((rc = path_range(p, r)) || r.c == 0) return rc;
+    const uint64_t n = r.plane(), b = r.b, c = r.c;
     const uint64_t blocks = (c + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
     hipStream_t st = (hipStream_t)stream;
@@ -142,34 +156,26 @@ int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, 
     const TraceArgs ta = make_trace_args(p, ls);
     const bool retire = p->flags & APT_FLAG_RETIRE;
     const dim3 grid((unsigned)blocks);
-    const int sck = ns8 ? kScene8 : (ta.grid ? kSceneGrid : kSceneTiles);
-    uint64_t n = n_image;
-    if (p->flags & APT_FLAG_BAND_BUFFERS) { // planes of c floats holding paths [b, b+c): same indexing through a shifted base
-        n = c;
-        rays -= b;
-        colors -= b;
-    }
-    if (ns8 && !retire && ta.rr_start == 0 && c >= kTwoPathBufferMin) {   // a large range of the reference scene, every segment traced: two paths per lane
-        const uint64_t per_block = 2ull * kBlock * kPaths2Pairs;
-        const dim3 grid2((unsigned)((c + per_block - 1) / per_block));
-        if (p->mode == APT_MODE_ORACLE) hipLaunchKernelGGL((render_paths2_kernel<kModeOracle>), grid2, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
-        else hipLaunchKernelGGL((render_paths2_kernel<kModeKernel>), grid2, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
-    } else if (retire && ns8) { // wave-level queue: one wave per kQueueChunk consecutive paths
-        const uint64_t waves = (c + kQueueChunk - 1) / kQueueChunk;
-        const dim3 qgrid((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64)));
-        if (p->mode == APT_MODE_ORACLE) hipLaunchKernelGGL((render_paths_queue_kernel<kModeOracle>), qgrid, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
-        else hipLaunchKernelGGL((render_paths_queue_kernel<kModeKernel>), qgrid, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
-    } else if (p->mode == APT_MODE_ORACLE) {
-        if (sck == kScene8) launch_paths<kModeOracle, kScene8>(retire, grid, st, rays, spheres, colors, n, b, c, ta);
-        else if (sck == kSceneGrid) launch_paths<kModeOracle, kSceneGrid>(retire, grid, st, rays, spheres, colors, n, b, c, ta);
-        else launch_paths<kModeOracle, kSceneTiles>(retire, grid, st, rays, spheres, colors, n, b, c, ta);
-    } else {
-        if (sck == kScene8) launch_paths<kModeKernel, kScene8>(retire, grid, st, rays, spheres, colors, n, b, c, ta);
-        else if (sck == kSceneGrid) launch_paths<kModeKernel, kSceneGrid>(retire, grid, st, rays, spheres, colors, n, b, c, ta);
-        else launch_paths<kModeKernel, kSceneTiles>(retire, grid, st, rays, spheres, colors, n, b, c, ta);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    rays = r.base(rays);
+    colors = r.base(colors);
+    with_mode(p->mode, [&](auto m) {
+        if (ns8 && !retire && ta.rr_start == 0 && c >= kTwoPathBufferMin) {   // a large range of the reference scene, every segment traced: two paths per lane
+            const uint64_t per_block = 2ull * kBlock * kPaths2Pairs;
+            const dim3 grid2((unsigned)((c + per_block - 1) / per_block));
+            hipLaunchKernelGGL((render_paths2_kernel<m>), grid2, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
+        } else if (ns8 && retire) { // wave-level queue: one wave per kQueueChunk consecutive paths
+            const uint64_t waves = (c + kQueueChunk - 1) / kQueueChunk;
+            const dim3 qgrid((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64)));
+            hipLaunchKernelGGL((render_paths_queue_kernel<m>), qgrid, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
+        } else if (ns8) {
+            hipLaunchKernelGGL((render_paths_kernel<m, kScene8, false>), grid, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
+        } else {
+            with_flag(ta.grid != nullptr, [&](auto gr) { with_flag(retire, [&](auto rt) {
+                hipLaunchKernelGGL((render_paths_kernel<m, gr ? kSceneGrid : kSceneTiles, rt>), grid, dim3(kBlock), 0, st, rays, spheres, colors, n, b, c, ta);
+            }); });
+        }
+    });
+    return launched();
 }
 
 // The sample-queue kernels' launch shape (pt_queue.h): colour buffers, pixels per wave, dynamic LDS.  -> false: too many waves.
@@ -206,30 +212,20 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
-    const TraceArgs ta = make_trace_args(p, ls);
-    FrameArgs fa;
-    camera_init(fa.cam, p->width, p->height);
-    fa.width = p->width; fa.height = p->height; fa.samples = p->samples; fa.seed = p->seed;
-    fa.pixel_begin = pixel_begin; fa.pixel_count = pixel_count; fa.fb = fb; fa.fb_u8 = fb_u8;
-    const bool retire = p->flags & APT_FLAG_RETIRE;
+    TraceArgs ta = make_trace_args(p, ls);
+    const FrameArgs fa = make_frame_args(p, pixel_begin, pixel_count, fb, fb_u8);
+    const bool retire = p->flags & APT_FLAG_RETIRE, rrk = ta.rr_start != 0;
     if (retire && ns8 && group == 8 && p->depth > 0) {
         // 8-sphere scene with compaction: one wave per workgroup, a stream of `ppw` pixels per wave (pt_queue.h)
         QueueArgs qa;
         uint64_t waves;
         size_t qlds;
-        const bool rrk = ta.rr_start != 0;
         if (!queue_launch_shape(dbg, lp, rrk, false, pixel_count, true, qa, waves, qlds)) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
-        if (p->mode == APT_MODE_ORACLE) {
-            if (rrk) hipLaunchKernelGGL((render_frame_queue8_kernel<kModeOracle, true>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta, lp, qa);
-            else hipLaunchKernelGGL((render_frame_queue8_kernel<kModeOracle, false>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta, lp, qa);
-        } else {
-            if (rrk) hipLaunchKernelGGL((render_frame_queue8_kernel<kModeKernel, true>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta, lp, qa);
-            else hipLaunchKernelGGL((render_frame_queue8_kernel<kModeKernel, false>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta, lp, qa);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? APT_OK : hip_fail(e);
+        with_mode(p->mode, [&](auto m) { with_flag(rrk, [&](auto rr) {
+            hipLaunchKernelGGL((render_frame_queue8_kernel<m, rr>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta, lp, qa);
+        }); });
+        return launched();
     }
-    TraceArgs ta_frame = ta;
     if (!ns8 && ta.grid && group == 8 && p->depth > 0 && dbg.grid_walk != 1u) {
         // A scene behind a grid: the sample-queue kernel's grid form (pt_queue.h run_grid), with or without APT_FLAG_RETIRE.  Whether
         // the grid carries the pair-slot tables that form needs is written in the buffer on the DEVICE: rather than reading it back in
@@ -238,11 +234,7 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
         QueueArgs qa;
         uint64_t waves;
         size_t qlds;
-        const bool rrk = ta.rr_start != 0;
         if (!queue_launch_shape(dbg, lp, rrk, true, pixel_count, retire, qa, waves, qlds)) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
-        // (the walk statistics behind apt_set_trace_counter are a template flag: a frame without a counter does not carry them)
-        const bool oracle = p->mode == APT_MODE_ORACLE, stats = ta.traced != nullptr;
-        const dim3 qgrid((unsigned)waves), qblock(64);
         // APT_FLAG_GRID_SLOTS: the caller vouches for the grid (apt_grid_flags): this launch is the frame's only one, and a grid that does not
         // keep the promise is reported through the status word (grid_walk == 3 tells the kernel to report instead of returning silently)
         // (Only with a status word to report through: without one -- a context's first launch inside a stream capture, a device index beyond
@@ -250,35 +242,35 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
         const bool vouched = (p->flags & APT_FLAG_GRID_SLOTS) && eps_allows_rootkey(p->eps) && ta.status != nullptr;
         TraceArgs ta_q = ta;
         ta_q.grid_walk = vouched ? 3u : 0u;
-#define APT_LAUNCH_GRID_QUEUE(M, R, S) hipLaunchKernelGGL((render_frame_queue8_kernel<M, R, kSceneGrid, S>), qgrid, qblock, qlds, st, spheres, fa, ta_q, lp, qa)
-        if (oracle) {
-            if (rrk) { if (stats) APT_LAUNCH_GRID_QUEUE(kModeOracle, true, true); else APT_LAUNCH_GRID_QUEUE(kModeOracle, true, false); }
-            else { if (stats) APT_LAUNCH_GRID_QUEUE(kModeOracle, false, true); else APT_LAUNCH_GRID_QUEUE(kModeOracle, false, false); }
-        } else {
-            if (rrk) { if (stats) APT_LAUNCH_GRID_QUEUE(kModeKernel, true, true); else APT_LAUNCH_GRID_QUEUE(kModeKernel, true, false); }
-            else { if (stats) APT_LAUNCH_GRID_QUEUE(kModeKernel, false, true); else APT_LAUNCH_GRID_QUEUE(kModeKernel, false, false); }
-        }
-#undef APT_LAUNCH_GRID_QUEUE
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e);
-        if (vouched) return APT_OK;
-        ta_frame.grid_walk = 2;
+        // (the walk statistics behind apt_set_trace_counter are a template flag: a frame without a counter does not carry them)
+        with_mode(p->mode, [&](auto m) { with_flag(rrk, [&](auto rr) { with_flag(ta.traced != nullptr, [&](auto stats) {
+            hipLaunchKernelGGL((render_frame_queue8_kernel<m, rr, kSceneGrid, stats>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta_q, lp, qa);
+        }); }); });
+        if ((rc = launched()) || vouched) return rc;
+        ta.grid_walk = 2;
     }
     size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
     if (retire && !ns8 && !ta.grid && group == 8) lds += (size_t)(kBlock / 64) * 3 * 8 * lp.maxleaf * sizeof(float); // colour queue of the LDS-tile form
     const dim3 grid((unsigned)blocks);
-    const int sck = ns8 ? kScene8 : (ta.grid ? kSceneGrid : kSceneTiles);
-    if (p->mode == APT_MODE_ORACLE) {
-        if (sck == kScene8) launch_frame_g<kModeOracle, kScene8>(group, retire, grid, lds, st, spheres, fa, ta, lp);
-        else if (sck == kSceneGrid) launch_frame_g<kModeOracle, kSceneGrid>(group, retire, grid, lds, st, spheres, fa, ta_frame, lp);
-        else launch_frame_g<kModeOracle, kSceneTiles>(group, retire, grid, lds, st, spheres, fa, ta, lp);
-    } else {
-        if (sck == kScene8) launch_frame_g<kModeKernel, kScene8>(group, retire, grid, lds, st, spheres, fa, ta, lp);
-        else if (sck == kSceneGrid) launch_frame_g<kModeKernel, kSceneGrid>(group, retire, grid, lds, st, spheres, fa, ta_frame, lp);
-        else launch_frame_g<kModeKernel, kSceneTiles>(group, retire, grid, lds, st, spheres, fa, ta, lp);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    with_mode(p->mode, [&](auto m) {
+        if (ns8 && group == 8) {
+            // With APT_FLAG_RETIRE these frames belong to the sample-queue kernel (above); what arrives here with the flag set is depth 0,
+            // where there is nothing to retire.  The headline case -- >= 16 samples, every segment traced, no roulette -- runs two paths per lane.
+            if (!retire && !rrk && p->samples >= 16)
+                hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 8, false, true>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);
+            else
+                hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 8, false>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);
+        } else if (ns8) {
+            with_flag(retire, [&](auto rt) {
+                hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 1, rt>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);
+            });
+        } else {
+            with_flag(ta.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) { with_flag(retire, [&](auto rt) {
+                hipLaunchKernelGGL((render_frame_kernel<m, gr ? kSceneGrid : kSceneTiles, g8 ? 8 : 1, rt>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);
+            }); }); });
+        }
+    });
+    return launched();
 }
 
 // contiguous near-equal split of [0,total) into `parts`: part r -> (begin, count); the first total%parts get one more
@@ -459,7 +451,7 @@ int apt_render_host(uint32_t blockDim, const uint8_t *rays, const uint8_t *spher
     // The reference's call renders the whole ray array (src/main.cpp:18-25); with a STRICT path sub-range in the default parameters the
     // colours outside it would be copied back from memory no kernel wrote.  (path_begin 0 with path_count 0 or N is the whole frame.)
     if (p.path_begin != 0 || (p.path_count != 0 && p.path_count != n)) return fail(APT_ERR_ARG, "apt_render_host: the default parameters carry a path sub-range; it renders whole frames only%s");
-    const size_t sph_bytes = ((size_t)p.num_spheres * 10 + 127) / 128 * 128 * sizeof(float);
+    const size_t sph_bytes = sphere_table_bytes(p.num_spheres);
     float *d_rays = nullptr, *d_sph = nullptr, *d_col = nullptr;
     hipError_t e = hipMalloc(&d_rays, n * 24);
     if (e == hipSuccess) e = hipMalloc(&d_sph, sph_bytes);
@@ -512,7 +504,7 @@ int apt_multi_create(const int *device_ids, uint32_t num_bands, uint32_t stripes
     split_range(npix, 0, parts, b0, c0);
     m->max_stripe = c0;
     m->bands.resize(num_bands);
-    const size_t sph_bytes = ((size_t)p->num_spheres * 10 + 127) / 128 * 128 * sizeof(float);
+    const size_t sph_bytes = sphere_table_bytes(p->num_spheres);
     hipError_t e = hipSuccess;
     for (uint32_t b = 0; b < num_bands && e == hipSuccess; ++b) {
         apt_multi::Band &bd = m->bands[b];
@@ -697,8 +689,7 @@ int apt_selftest_sqrt(int variant, void *stream, uint64_t first_bits, uint64_t c
     if (count == 0) return APT_OK;
     hipLaunchKernelGGL(selftest_sqrt_kernel, dim3(256 * 16), dim3(kBlock), 0, (hipStream_t)stream, variant, first_bits,
                        count, (unsigned long long *)device_result2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    return launched();
 }
 
 int apt_selftest_div3(void *stream, uint64_t first, uint64_t count, uint64_t *device_result3) {
@@ -707,8 +698,7 @@ int apt_selftest_div3(void *stream, uint64_t first, uint64_t count, uint64_t *de
     if (count == 0) return APT_OK;
     hipLaunchKernelGGL(selftest_div3_kernel, dim3(256 * 16), dim3(kBlock), 0, (hipStream_t)stream, first, count,
                        (unsigned long long *)device_result3);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    return launched();
 }
 
 int apt_test_scene(const apt_render_params *p, void *stream, const float *rays, const float *spheres, float *out) {
@@ -721,8 +711,7 @@ int apt_test_scene(const apt_render_params *p, void *stream, const float *rays, 
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "image too large for one launch%s");
     hipLaunchKernelGGL(test_scene_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, rays, spheres,
                        out, n, p->num_spheres, p->light_index, p->eps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    return launched();
 }
 
 int apt_gen_rays_device(const apt_render_params *p, void *stream, float *rays) {
@@ -730,21 +719,15 @@ int apt_gen_rays_device(const apt_render_params *p, void *stream, float *rays) {
     int rc = check_params(p);
     if (rc) return rc;
     if (!rays) return fail(APT_ERR_ARG, "rays must be non-null%s");
-    const uint64_t n = (uint64_t)p->width * p->height * 4u * p->samples;
-    const uint64_t b = p->path_begin;
-    if (b > n) return fail(APT_ERR_ARG, "path_begin beyond the image%s");
-    const uint64_t c = p->path_count ? p->path_count : n - b;
-    if (b + c > n) return fail(APT_ERR_ARG, "path range beyond the image%s");
-    if (c == 0) return APT_OK;
-    const uint64_t blocks = (c + kBlock - 1) / kBlock;
+    PathRange r;
+    if ((rc = path_range(p, r)) || r.c == 0) return rc;
+    const uint64_t blocks = (r.c + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
     Camera cam;
     camera_init(cam, p->width, p->height);
-    const bool band = p->flags & APT_FLAG_BAND_BUFFERS;
     hipLaunchKernelGGL(gen_rays_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, cam, p->width,
-                       p->height, p->samples, p->seed, band ? c : n, b, c, band ? rays - b : rays);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+                       p->height, p->samples, p->seed, r.plane(), r.b, r.c, r.base(rays));
+    return launched();
 }
 
 int apt_gen_rays_mt_device_ex(const apt_render_params *p, void *stream, const uint32_t *checkpoints, uint32_t stride,
@@ -753,13 +736,10 @@ int apt_gen_rays_mt_device_ex(const apt_render_params *p, void *stream, const ui
     int rc = check_params(p);
     if (rc) return rc;
     if (!rays || !checkpoints || stride == 0) return fail(APT_ERR_ARG, "rays/checkpoints must be non-null, stride > 0%s");
-    const uint64_t n = (uint64_t)p->width * p->height * 4u * p->samples;
-    const uint64_t b = p->path_begin;
-    if (b > n) return fail(APT_ERR_ARG, "path_begin beyond the image%s");
-    const uint64_t c = p->path_count ? p->path_count : n - b;
-    if (b + c > n) return fail(APT_ERR_ARG, "path range beyond the image%s");
-    if (c == 0) return APT_OK;
-    const uint64_t num_blocks = (n + kPathsPerBlock - 1) / kPathsPerBlock;           // of the whole stream
+    PathRange r;
+    if ((rc = path_range(p, r)) || r.c == 0) return rc;
+    const uint64_t b = r.b, c = r.c;
+    const uint64_t num_blocks = (r.n_image + kPathsPerBlock - 1) / kPathsPerBlock;   // of the whole stream
     const uint64_t blk_lo = b / kPathsPerBlock, blk_hi = (b + c + kPathsPerBlock - 1) / kPathsPerBlock; // blocks the range touches
     if (blk_lo < first_block) return fail(APT_ERR_ARG, "path range starts before the checkpoint window%s");
     const uint64_t cp_lo = (blk_lo - first_block) / stride, cp_hi = (blk_hi - first_block + stride - 1) / stride;
@@ -767,13 +747,11 @@ int apt_gen_rays_mt_device_ex(const apt_render_params *p, void *stream, const ui
     if (cp_hi - cp_lo > 0x7fffffffull) return fail(APT_ERR_ARG, "too many checkpoints for one launch%s");
     Camera cam;
     camera_init(cam, p->width, p->height);
-    const bool band = p->flags & APT_FLAG_BAND_BUFFERS;
     // one workgroup per checkpoint the range touches (workgroups of untouched checkpoints would only skip)
     hipLaunchKernelGGL(gen_rays_mt_kernel, dim3((unsigned)(cp_hi - cp_lo)), dim3(kBlock), 0, (hipStream_t)stream,
                        checkpoints + cp_lo * kMtN, stride, first_block + cp_lo * stride, num_blocks, cam, p->width, p->height,
-                       p->samples, band ? c : n, b, b + c, band ? rays - b : rays);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+                       p->samples, r.plane(), b, b + c, r.base(rays));
+    return launched();
 }
 
 int apt_gen_rays_mt_device(const apt_render_params *p, void *stream, const uint32_t *checkpoints, uint32_t stride,
@@ -803,22 +781,16 @@ int apt_render_frame_mt(const apt_render_params *p, void *stream, const uint32_t
     if (g_lo < first_group || g_hi - first_group > num_checkpoints) return fail(APT_ERR_ARG, "apt_render_frame_mt: the checkpoint table does not cover the pixel range%s");
     if (g_hi - g_lo > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
     const TraceArgs ta = make_trace_args(p, launch_state(apt::default_context(), stream));
-    FrameArgs fa;
-    camera_init(fa.cam, p->width, p->height);
-    fa.width = p->width; fa.height = p->height; fa.samples = p->samples; fa.seed = p->seed;
-    fa.pixel_begin = pixel_begin; fa.pixel_count = pixel_count; fa.fb = fb; fa.fb_u8 = fb_u8;
+    const FrameArgs fa = make_frame_args(p, pixel_begin, pixel_count, fb, fb_u8);
     MtFrameArgs ma;
     ma.checkpoints = checkpoints + (g_lo - first_group) * 624; ma.first_group = g_lo; ma.log2_s = log2_s;
     const dim3 grid((unsigned)(g_hi - g_lo));
-    if (pow2_kernel) {
-        if (p->mode == APT_MODE_ORACLE) hipLaunchKernelGGL((render_frame_mt_kernel<kModeOracle>), grid, dim3(kBlock), 0, (hipStream_t)stream, spheres, fa, ta, ma);
-        else hipLaunchKernelGGL((render_frame_mt_kernel<kModeKernel>), grid, dim3(kBlock), 0, (hipStream_t)stream, spheres, fa, ta, ma);
-    } else {
-        if (p->mode == APT_MODE_ORACLE) hipLaunchKernelGGL((render_frame_mt_any_kernel<kModeOracle>), grid, dim3(kBlock), 0, (hipStream_t)stream, spheres, fa, ta, ma, lp);
-        else hipLaunchKernelGGL((render_frame_mt_any_kernel<kModeKernel>), grid, dim3(kBlock), 0, (hipStream_t)stream, spheres, fa, ta, ma, lp);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    hipStream_t st = (hipStream_t)stream;
+    with_mode(p->mode, [&](auto m) {
+        if (pow2_kernel) hipLaunchKernelGGL((render_frame_mt_kernel<m>), grid, dim3(kBlock), 0, st, spheres, fa, ta, ma);
+        else hipLaunchKernelGGL((render_frame_mt_any_kernel<m>), grid, dim3(kBlock), 0, st, spheres, fa, ta, ma, lp);
+    });
+    return launched();
 }
 
 int apt_decode_color_band(const apt_render_params *p, void *stream, const float *colors, uint64_t pixel_count, float *fb,
@@ -832,8 +804,9 @@ int apt_decode_color_band(const apt_render_params *p, void *stream, const float 
     if ((rc = make_leaf_prog(p->samples, lp))) return rc;
     const uint64_t npix = pixel_count;                    // the band is decoded like an image of pixel_count pixels
     const bool wide = p->samples >= 8;                    // 8 lanes per sub-pixel row: coalesced loads
-    // few samples: 2 lanes per row with float4 loads (decode_color_kernel4); every row then starts at a multiple of 16 bytes from `colors`
-    const bool quad = wide && p->samples <= 8u * kDecode4Blocks && p->samples % 4 == 0 && ((uintptr_t)colors & 15u) == 0;
+    // few samples: 2 lanes per row with float4 loads (decode_color_kernel4); every row then starts at a multiple of 16 bytes from `colors`.
+    // decode_color_kernel4 adds ONE leaf and relies on lp.nleaves == 1 (which every count <= 128 has)
+    const bool quad = wide && p->samples <= 8u * kDecode4Blocks && lp.nleaves == 1 && p->samples % 4 == 0 && ((uintptr_t)colors & 15u) == 0;
     const uint64_t lanes = npix * 3 * 4 * (quad ? 2 : (wide ? 8 : 1));
     const uint64_t blocks = (lanes + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "band too large for one launch%s");
@@ -848,8 +821,7 @@ int apt_decode_color_band(const apt_render_params *p, void *stream, const float 
     else
         hipLaunchKernelGGL(decode_color_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, colors,
                            p->samples, npix, lp, fb, fb_u8);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    return launched();
 }
 
 int apt_decode_color_device(const apt_render_params *p, void *stream, const float *colors, float *fb, uint8_t *fb_u8) {

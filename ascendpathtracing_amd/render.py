@@ -37,6 +37,32 @@ def sphere_floats(num_spheres):
     return (num_spheres * 10 + 127) // 128 * 128
 
 
+# The bodies of render_do_ex / render_frame, shared by the default-context functions and Context's methods: `entry` is the C entry
+# (also the name errors are reported under), `handle` its leading context argument, if any.
+def _render_do_ex(entry, handle, params, stream, rays, spheres, colors):
+    require_gpu()
+    n = _buffer_paths(params)
+    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
+                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                                _dev_f32(colors, "colors", 3 * n)), entry)
+
+
+def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8):
+    require_gpu()
+    npix = params.width * params.height
+    if pixel_count is None:
+        pixel_count = npix - pixel_begin
+    if fb is None:
+        fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
+    if fb_u8 is None:
+        fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
+    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
+                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                                ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(fb, "fb", 3 * pixel_count),
+                                ctypes.c_void_p(fb_u8.data_ptr())), entry)
+    return fb, fb_u8
+
+
 def render_do(blockDim, l2ctrl, stream, rays, spheres, colors):
     """void render_do(blockDim, l2ctrl, stream, rays, spheres, colors) -- src/main.cpp:9-10,74.
     Asynchronous on `stream`; uses the process-wide defaults (apt_set_default_params)."""
@@ -94,27 +120,10 @@ class Context:
         check(lib().apt_last_status(), "apt_context_render_do")
 
     def render_do_ex(self, params, stream, rays, spheres, colors):
-        require_gpu()
-        n = _buffer_paths(params)
-        check(lib().apt_context_render_do_ex(self._h, ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
-                                             _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
-                                             _dev_f32(colors, "colors", 3 * n)), "apt_context_render_do_ex")
+        _render_do_ex("apt_context_render_do_ex", (self._h,), params, stream, rays, spheres, colors)
 
     def render_frame(self, params, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None):
-        require_gpu()
-        npix = params.width * params.height
-        if pixel_count is None:
-            pixel_count = npix - pixel_begin
-        if fb is None:
-            fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
-        if fb_u8 is None:
-            fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
-        check(lib().apt_context_render_frame(self._h, ctypes.byref(params), _stream_handle(stream),
-                                             _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
-                                             ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count),
-                                             _dev_f32(fb, "fb", 3 * pixel_count), ctypes.c_void_p(fb_u8.data_ptr())),
-              "apt_context_render_frame")
-        return fb, fb_u8
+        return _render_frame("apt_context_render_frame", (self._h,), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8)
 
 
 def render_host(blockDim, rays, spheres, colors):
@@ -212,11 +221,7 @@ def check_device_status(stream=None):
 def render_do_ex(params: RenderParams, stream, rays, spheres, colors):
     """Run-time-parameter form of render_do: rays [6][N], spheres [10][Ns] padded, colors [3][N] (with APT_FLAG_BAND_BUFFERS: planes of
     path_count floats holding only the range)."""
-    require_gpu()
-    n = _buffer_paths(params)
-    check(lib().render_do_ex(ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
-                             _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
-                             _dev_f32(colors, "colors", 3 * n)), "render_do_ex")
+    _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors)
 
 
 def render_paths(params: RenderParams, rays, spheres, stream=None):
@@ -229,19 +234,7 @@ def render_paths(params: RenderParams, rays, spheres, stream=None):
 def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None):
     """Fused ray-generate + trace + decode for pixels [pixel_begin, pixel_begin+pixel_count).
     Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised."""
-    require_gpu()
-    npix = params.width * params.height
-    if pixel_count is None:
-        pixel_count = npix - pixel_begin
-    if fb is None:
-        fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
-    if fb_u8 is None:
-        fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
-    check(lib().render_frame(ctypes.byref(params), _stream_handle(stream),
-                             _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
-                             ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(fb, "fb", 3 * pixel_count),
-                             ctypes.c_void_p(fb_u8.data_ptr())), "render_frame")
-    return fb, fb_u8
+    return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8)
 
 
 def gen_rays_device(params: RenderParams, stream=None, device="cuda"):
