@@ -27,8 +27,8 @@ def _dev_f32(t, name, numel=None):
 
 def _buffer_paths(params):
     """Paths per plane of the ray / colour buffers of a buffer-mode call: the whole image, or the range alone with band-relative buffers."""
-    if (params.flags & _lib.APT_FLAG_BAND_BUFFERS) and params.path_count:
-        return params.path_count
+    if params.flags & _lib.APT_FLAG_BAND_BUFFERS:
+        return params.path_count or (params.num_paths - params.path_begin)   # path_count 0: to the end of the image (path_range)
     return params.num_paths
 
 

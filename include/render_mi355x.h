@@ -69,9 +69,12 @@ enum {
 
 /* flags */
 enum {
-    APT_FLAG_RETIRE = 1u,  /* result-preserving retirement of finished paths: a path     */
-                           /* whose alive bit is cleared or whose throughput is (0,0,0)   */
-                           /* stops bouncing; colours are bit-identical either way.       */
+    APT_FLAG_RETIRE = 1u,  /* retirement of finished paths: a path whose alive bit is     */
+                           /* cleared or whose throughput is (0,0,0) stops bouncing.      */
+                           /* Colours are bit-identical either way when every albedo      */
+                           /* component is finite with a clear sign bit; otherwise 0 *    */
+                           /* albedo is -0 or NaN and a RETIRE frame equals the oracle's  */
+                           /* RETIRE frame, not the full trace.                           */
     APT_FLAG_BAND_BUFFERS = 8u, /* render_do_ex / apt_gen_rays_device / apt_gen_rays_mt_device_ex: `rays` and  */
                            /* `colors` hold ONLY paths [path_begin, path_begin+path_count): planes of      */
                            /* path_count floats, element (plane k, path p) at [k*path_count + p-path_begin] */
