@@ -1,0 +1,42 @@
+// apt_materials.h -- what render_kernels.hip (argument checks, C-ABI) hands to materials.hip (the material kernels and their
+// launches; include/render_mi355x.h "per-sphere materials").  The material kernels live in a translation unit of their own, so
+// that the code object of render_kernels.hip -- every kernel the mirror renderer had before -- is built exactly as before.
+// Plain data only: the kernels' own argument types are internal to each translation unit.
+#pragma once
+#include <stdint.h>
+
+namespace apt {
+
+struct MatTrace {                 // the parts of apt_render_params the material kernels read, after the checks
+    uint32_t ns, depth, rr_start; // rr_start: first bounce count of APT_FLAG_RR, 0 = no roulette
+    float eps;
+    uint64_t seed;
+    uint32_t *status;             // the context's device status word, or null
+    unsigned long long *traced;   // apt_set_trace_counter block, or null
+};
+
+struct MatFrameCall {             // render_frame with materials: pixels [pixel_begin, pixel_begin + pixel_count), pixel_count > 0
+    MatTrace t;
+    const float *spheres;
+    const uint32_t *materials;
+    uint32_t width, height, samples;
+    uint64_t pixel_begin, pixel_count;
+    float *fb;
+    uint8_t *fb_u8;
+    void *stream;
+};
+
+struct MatPathsCall {             // render_do_ex with materials: paths [b, b + c) of buffers whose planes hold n paths (already shifted)
+    MatTrace t;
+    const float *rays, *spheres;
+    const uint32_t *materials;
+    float *colors;
+    uint64_t n, b, c;
+    void *stream;
+};
+
+// Enqueue the launch (hipGetLastError() tells the caller whether it was accepted).
+void mat_render_frame(const MatFrameCall &call);
+void mat_render_paths(const MatPathsCall &call);
+
+} // namespace apt

@@ -258,6 +258,27 @@ int apt_gen_spheres_host(float *spheres128) {
     return APT_OK;
 }
 
+// The demo scene of the material entries: gen_spheres' eight spheres (light still index 7) and, as sphere 8, the glass ball the
+// reference's scene list carries commented out (gen_data.py:84, :103): r 16.5 at (73, 16.5, 78), albedo 0.999.  smallpt's materials
+// (gen_data.py:77-87): the walls and the light DIFF, the mirror SPEC, the ball REFR.  [10][9] planes in 128 floats, like gen_spheres.
+int apt_gen_spheres_materials_host(float *spheres, uint32_t *materials) {
+    apt::clear_error();
+    if (!spheres || !materials) return set_error(APT_ERR_ARG, "apt_gen_spheres_materials_host: spheres/materials is null%s");
+    constexpr int kNs = 9;
+    memset(spheres, 0, padded_floats(kNs * 10) * sizeof(float));
+    for (int k = 0; k < kNs; ++k) {
+        float rec[10];
+        if (k < 8) sphere_record(k, rec);
+        else {
+            const double glass[10] = {16.5, 73, 16.5, 78, 0, 0, 0, 0.999, 0.999, 0.999};
+            for (int m = 0; m < 10; ++m) rec[m] = (float)(m == 0 ? glass[m] * glass[m] : glass[m]);
+        }
+        for (int m = 0; m < 10; ++m) spheres[m * kNs + k] = rec[m];
+        materials[k] = k == 6 ? APT_MAT_SPEC : (k == 8 ? APT_MAT_REFR : APT_MAT_DIFF);
+    }
+    return APT_OK;
+}
+
 int apt_gen_scene_host(uint32_t num_spheres, uint64_t seed, float *spheres, size_t *out_floats) {
     apt::clear_error();
     if (num_spheres < 8) return set_error(APT_ERR_SCENE, "apt_gen_scene_host: needs num_spheres >= 8 (six walls, at least one sphere, the light)%s");

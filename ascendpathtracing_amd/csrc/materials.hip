@@ -1,0 +1,61 @@
+// materials.hip -- the material kernels' translation unit (pt_materials.h) and their launches.  render_kernels.hip checks the
+// arguments and calls in through apt_materials.h; keeping these kernels out of its code object leaves every kernel that was there
+// before byte for byte as it was (`make asm` writes this code object to materials.s).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/render_mi355x.h"
+#include "apt_materials.h"
+#include "pt_core.h"
+#include "pt_dispatch.h"
+#include "pt_materials.h"
+
+namespace {
+
+TraceArgs mat_trace_args(const apt::MatTrace &t) {
+    TraceArgs ta;
+    ta.ns = t.ns; ta.depth = t.depth; ta.light = -1;
+    ta.eps = t.eps; ta.gain = 0.0f; ta.traced = t.traced;
+    ta.status = t.status;
+    ta.refill_lanes = 0;
+    ta.grid = nullptr;
+    ta.grid_walk = 0;
+    ta.emission = 0;
+    ta.rr_start = t.rr_start;
+    ta.seed = t.seed;
+    return ta;
+}
+
+} // namespace
+
+namespace apt {
+
+void mat_render_frame(const MatFrameCall &c) {
+    FrameArgs fa;
+    camera_init(fa.cam, c.width, c.height);
+    fa.width = c.width; fa.height = c.height; fa.samples = c.samples; fa.seed = c.t.seed;
+    fa.pixel_begin = c.pixel_begin; fa.pixel_count = c.pixel_count; fa.fb = c.fb; fa.fb_u8 = c.fb_u8;
+    const TraceArgs ta = mat_trace_args(c.t);
+    LeafProg lp;
+    (void)make_leaf_plan(c.samples, lp);                   // the caller checked that the plan exists
+    const int group = c.samples >= 8 ? 8 : 1;
+    const uint64_t blocks = (c.pixel_count * 4u * (uint64_t)group + kBlock - 1) / kBlock;   // <= 2^31 - 1: checked by the caller
+    const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
+    hipStream_t st = (hipStream_t)c.stream;
+    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(group == 8, [&](auto g8) {
+        hipLaunchKernelGGL((render_frame_mat_kernel<ns8 ? kScene8 : kSceneTiles, g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds, st,
+                           c.spheres, c.materials, fa, ta, lp);
+    }); });
+}
+
+void mat_render_paths(const MatPathsCall &c) {
+    const TraceArgs ta = mat_trace_args(c.t);
+    const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
+    hipStream_t st = (hipStream_t)c.stream;
+    with_flag(c.t.ns == 8, [&](auto ns8) {
+        hipLaunchKernelGGL((render_paths_mat_kernel<ns8 ? kScene8 : kSceneTiles>), dim3((unsigned)blocks), dim3(kBlock), 0, st, c.rays, c.spheres,
+                           c.materials, c.colors, c.n, c.b, c.c, ta);
+    });
+}
+
+} // namespace apt

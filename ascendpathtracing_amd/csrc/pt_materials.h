@@ -1,0 +1,420 @@
+// pt_materials.h -- the material kernels (include/render_mi355x.h "per-sphere materials": smallpt's DIFF / SPEC / REFR with emitted
+// radiance), included by materials.hip only.  Same scene forms as the mirror kernels -- the 8-sphere scene with its geometry in SGPRs,
+// any scene through LDS tiles -- and the same sample scheduling, pairwise-leaf accumulation and fused decode as render_frame_kernel;
+// only the body of one sample differs.  Every fp32 operation is the one the header specifies, in its order (-ffp-contract=off):
+// tests/materials_ref.py restates it and the GPU tests compare bit for bit.
+#pragma once
+#include "pt_queue.h"   // FrameArgs; pt_trace.h
+
+namespace {
+
+constexpr uint64_t kMatKeySalt = 0x6A09E667F3BCC909ull;
+constexpr int kMatTab = 24;     // 8-sphere LDS table: geometry [0, 8), albedo [8, 16), emission [16, 24)
+
+struct MatPath {
+    float ox, oy, oz, dx, dy, dz;
+    float tx, ty, tz;           // throughput T
+    float lx, ly, lz;           // radiance L gathered so far
+    int skip;                   // sphere the next segment does not test, or -1
+    bool live;                  // the path has not ended (miss or bad material code)
+};
+
+__device__ __forceinline__ uint64_t mat_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kMatKeySalt); }
+__device__ __forceinline__ void mat_uniforms(uint64_t mkey, uint32_t d, float &u1, float &u2) {
+    const uint64_t h = splitmix64(mkey + 0x9E3779B97F4A7C15ull * (uint64_t)(d + 1u));
+    u1 = (float)(uint32_t)(h >> 40) * 0x1p-24f;
+    u2 = (float)((uint32_t)(h >> 16) & 0xFFFFFFu) * 0x1p-24f;
+}
+
+// (sin, cos) of 2*pi*u1 for u1 = m * 2^-24: quadrant and fraction of u1 * 4, one fixed polynomial pair, swap / negate.
+__device__ __forceinline__ void mat_sincos(float u1, float &sn, float &cs) {
+    const float x = u1 * 4.0f;
+    const int q = (int)x;
+    const float f = x - (float)q;
+    const float z = f * f;
+    float p = APT_MAT_S11;
+    p = APT_MAT_S9 + z * p; p = APT_MAT_S7 + z * p; p = APT_MAT_S5 + z * p; p = APT_MAT_S3 + z * p; p = APT_MAT_S1 + z * p;
+    const float s = f * p;
+    float c = APT_MAT_C12;
+    c = APT_MAT_C10 + z * c; c = APT_MAT_C8 + z * c; c = APT_MAT_C6 + z * c; c = APT_MAT_C4 + z * c; c = APT_MAT_C2 + z * c;
+    c = 1.0f + z * c;
+    const float a = (q & 1) ? c : s, b = (q & 1) ? s : c;
+    sn = (q >= 2) ? -a : a;
+    cs = (q == 1 || q == 2) ? -b : b;
+}
+
+// The bounce after the hit: light, throughput, new direction, skip.  `code` is APT_MAT_SPEC / DIFF / REFR (checked by the caller).
+// The DIFF and REFR blocks are per-lane branches: exec-masked, skipped by a wave with none of its lanes in them.
+__device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 geo, float4 alb, float4 em, uint32_t code,
+                                          uint64_t mkey, uint32_t d) {
+    float hx = s.dx * tmin, hy = s.dy * tmin, hz = s.dz * tmin;
+    hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
+    const float nx0 = hx - geo.x, ny0 = hy - geo.y, nz0 = hz - geo.z;
+    float len2 = 0.0f + nx0 * nx0;
+    len2 = len2 + ny0 * ny0;
+    len2 = len2 + nz0 * nz0;
+    const float ln = sqrtf(len2);
+    const float nx = nx0 / ln, ny = ny0 / ln, nz = nz0 / ln;
+    s.lx = s.lx + s.tx * em.x; s.ly = s.ly + s.ty * em.y; s.lz = s.lz + s.tz * em.z;
+    s.tx = s.tx * alb.x; s.ty = s.ty * alb.y; s.tz = s.tz * alb.z;
+    float ddn = 0.0f + s.dx * nx;
+    ddn = ddn + s.dy * ny;
+    ddn = ddn + s.dz * nz;
+    const bool into = ddn < 0.0f;
+    bool outward = into;
+    float ndx, ndy, ndz;
+    if (code == APT_MAT_DIFF) {
+        const float nlx = into ? nx : -nx, nly = into ? ny : -ny, nlz = into ? nz : -nz;
+        float u1, u2;
+        mat_uniforms(mkey, d, u1, u2);
+        float sn, cs;
+        mat_sincos(u1, sn, cs);
+        const float r = sqrtf(u2);
+        const float sg = copysignf(1.0f, nlz);
+        const float a = -1.0f / (sg + nlz);
+        const float b = (nlx * nly) * a;
+        const float tx = 1.0f + ((sg * nlx) * nlx) * a, ty = sg * b, tz = (-sg) * nlx;
+        const float bx = b, by = sg + (nly * nly) * a, bz = -nly;
+        const float cr = cs * r, sr = sn * r, w = sqrtf(1.0f - u2);
+        const float vx = (tx * cr + bx * sr) + nlx * w, vy = (ty * cr + by * sr) + nly * w, vz = (tz * cr + bz * sr) + nlz * w;
+        float v2 = 0.0f + vx * vx;
+        v2 = v2 + vy * vy;
+        v2 = v2 + vz * vz;
+        const float vl = sqrtf(v2);
+        ndx = vx / vl; ndy = vy / vl; ndz = vz / vl;
+    } else {
+        const float k2 = ddn * 2.0f;                          // SPEC, and the reflection of REFR
+        ndx = s.dx - nx * k2; ndy = s.dy - ny * k2; ndz = s.dz - nz * k2;
+        if (code == APT_MAT_REFR) {
+            const float dn = into ? ddn : -ddn;
+            const float nnt = into ? APT_MAT_NNT_IN : 1.5f;
+            const float cos2t = 1.0f - (nnt * nnt) * (1.0f - dn * dn);
+            if (!(cos2t < 0.0f)) {                            // otherwise total internal reflection: the reflection, weight 1
+                float g = dn * nnt + sqrtf(cos2t);
+                g = into ? g : -g;
+                const float vx = s.dx * nnt - nx * g, vy = s.dy * nnt - ny * g, vz = s.dz * nnt - nz * g;
+                float v2 = 0.0f + vx * vx;
+                v2 = v2 + vy * vy;
+                v2 = v2 + vz * vz;
+                const float vl = sqrtf(v2);
+                const float tdx = vx / vl, tdy = vy / vl, tdz = vz / vl;
+                float dt = 0.0f + tdx * nx;
+                dt = dt + tdy * ny;
+                dt = dt + tdz * nz;
+                const float c = 1.0f - (into ? -ddn : dt);
+                const float c5 = (((c * c) * c) * c) * c;
+                const float re = APT_MAT_R0 + APT_MAT_1MR0 * c5;
+                const float tr = 1.0f - re;
+                const float P = 0.25f + 0.5f * re;
+                float u1, u2;
+                mat_uniforms(mkey, d, u1, u2);
+                float wt;
+                if (u1 < P) {
+                    wt = re / P;
+                } else {
+                    wt = tr / (1.0f - P);
+                    ndx = tdx; ndy = tdy; ndz = tdz;
+                    outward = !into;
+                }
+                s.tx = s.tx * wt; s.ty = s.ty * wt; s.tz = s.tz * wt;
+            }
+        }
+    }
+    s.dx = ndx; s.dy = ndy; s.dz = ndz;
+    s.ox = hx; s.oy = hy; s.oz = hz;
+    s.skip = outward ? k : -1;
+}
+
+// ---- intersection with the skip rule ------------------------------------------------------------------------------------------
+// The 8-sphere scene: sphere pairs from SGPRs through the packed discriminant of the mirror kernels (each half rounds like the
+// scalar form), then render_do_ex's K-mode root selection with IEEE sqrtf() and the strict '<' arg-min.  SKIP: the path's skip
+// sphere is not a candidate (false for camera rays, which have none).
+template <bool SKIP>
+__device__ __forceinline__ void mat_hit8(const Scene8 &sc, const MatPath &s, float eps, float &tmin, int &idx) {
+    tmin = kMissT;
+    idx = -1;
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+        const HitPre2 h = intersect_pre2(f2{sc.cx[k], sc.cx[k + 1]}, f2{sc.cy[k], sc.cy[k + 1]}, f2{sc.cz[k], sc.cz[k + 1]},
+                                         f2{sc.r2[k], sc.r2[k + 1]}, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz);
+        const float t0 = intersect_post(HitPre{h.b.x, h.disc.x}, eps), t1 = intersect_post(HitPre{h.b.y, h.disc.y}, eps);
+        if (t0 < tmin && (!SKIP || s.skip != k)) { tmin = t0; idx = k; }
+        if (t1 < tmin && (!SKIP || s.skip != k + 1)) { tmin = t1; idx = k + 1; }
+    }
+}
+
+// Any scene: brute force over LDS-staged tiles of sphere pairs, as dyn_segment (pt_trace.h).  Every thread of the workgroup calls this
+// together (barriers).  A lane skips nothing but its own skip sphere; the order of the candidates is ascending, so ties keep the lowest index.
+__device__ __forceinline__ void mat_hit_tiles(const float *__restrict__ sph, float4 *tile, const MatPath &s, uint32_t ns, float eps,
+                                              float &tmin, int &idx) {
+    const float *r2 = sph, *cx = sph + ns, *cy = sph + 2 * (size_t)ns, *cz = sph + 3 * (size_t)ns;
+    tmin = kMissT;
+    idx = -1;
+    for (uint32_t base = 0; base < ns; base += kTile) {
+        const uint32_t n = min((uint32_t)kTile, ns - base);
+        __syncthreads();
+        {
+            float *tf = reinterpret_cast<float *>(tile);
+            const uint32_t n4 = (n + 3u) & ~3u;
+            for (uint32_t k = threadIdx.x; k < n4; k += kBlock) {
+                const bool real = k < n;
+                const float qn = __uint_as_float(0x7fc00000u);
+                const uint32_t o = (k >> 1) * 8u + (k & 1u);
+                tf[o] = real ? cx[base + k] : qn;
+                tf[o + 2] = real ? cy[base + k] : qn;
+                tf[o + 4] = real ? cz[base + k] : qn;
+                tf[o + 6] = real ? r2[base + k] : qn;
+            }
+        }
+        __syncthreads();
+        auto hit = [&](float b, float disc, uint32_t sphere) {
+            if (__any(disc >= 0.0f)) {
+                const float t = intersect_post(HitPre{b, disc}, eps);
+                if (t < tmin && (int)sphere != s.skip) { tmin = t; idx = (int)sphere; }
+            }
+        };
+        for (uint32_t k = 0; k < n; k += 4) {
+            const float4 a0 = tile[k], c0 = tile[k + 1], a1 = tile[k + 2], c1 = tile[k + 3];
+            const HitPre2 h01 = intersect_pre2(a0, c0, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz);
+            const HitPre2 h23 = intersect_pre2(a1, c1, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz);
+            const float m = fmaxf(fmaxf(h01.disc.x, h01.disc.y), fmaxf(h23.disc.x, h23.disc.y));
+            if (__any(m >= 0.0f)) {
+                hit(h01.b.x, h01.disc.x, base + k);
+                hit(h01.b.y, h01.disc.y, base + k + 1);
+                hit(h23.b.x, h23.disc.x, base + k + 2);
+                hit(h23.b.y, h23.disc.y, base + k + 3);
+            }
+        }
+    }
+}
+
+// What the 8-sphere form keeps per workgroup: geometry in SGPRs (Scene8), geometry / albedo / emission in LDS, and the 8 material codes
+// in ONE SGPR word (4 bits each, saturated at 15: every code above 2 is bad).
+struct MatScene8 {
+    Scene8 sc;
+    const float4 *tab;
+    uint32_t codes;
+};
+__device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ sph, const uint32_t *__restrict__ mat, float4 *tab) {
+    MatScene8 m;
+    if (threadIdx.x < 8) {
+        const int k = threadIdx.x;
+        tab[16 + k] = make_float4(sph[32 + k], sph[40 + k], sph[48 + k], 0.0f);
+    }
+    (void)load_scene8<false>(sph, m.sc, tab);   // geometry and albedo entries; its barrier covers the emission entries too
+    m.tab = tab;
+    uint32_t codes = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) codes |= min(mat[k], 15u) << (4 * k);
+    m.codes = codes;
+    return m;
+}
+
+// One path, `depth` segments (fewer when every path of the wave -- of the workgroup for the tile form -- has ended).  -> segments traced.
+template <int SC>
+__device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
+                                              float4 *tile, MatPath &s, const TraceArgs &ta, uint64_t path) {
+    const uint64_t mkey = mat_path_key(ta.seed, path);
+    const uint64_t rr_key = ta.rr_start ? rr_path_key(ta.seed, path) : 0;
+    uint32_t traced = 0;
+    for (uint32_t d = 0; d < ta.depth; ++d) {
+        float tmin;
+        int k;
+        float4 geo, alb, em;
+        uint32_t code;
+        if (SC == kScene8) {
+            if (__all(!s.live)) break;
+            if (d == 0) mat_hit8<false>(m8.sc, s, ta.eps, tmin, k);
+            else mat_hit8<true>(m8.sc, s, ta.eps, tmin, k);
+            const int g = k < 0 ? 0 : k;
+            geo = m8.tab[g]; alb = m8.tab[8 + g]; em = m8.tab[16 + g];
+            code = (m8.codes >> (4 * g)) & 15u;
+        } else {
+            if (__syncthreads_and(!s.live)) break;
+            mat_hit_tiles(sph, tile, s, ta.ns, ta.eps, tmin, k);
+            const size_t ns = ta.ns, g = k < 0 ? 0 : (size_t)k;
+            geo = make_float4(sph[ns + g], sph[2 * ns + g], sph[3 * ns + g], 0.0f);
+            alb = make_float4(sph[7 * ns + g], sph[8 * ns + g], sph[9 * ns + g], 0.0f);
+            em = make_float4(sph[4 * ns + g], sph[5 * ns + g], sph[6 * ns + g], 0.0f);
+            code = mat[g];
+        }
+        const bool hit = s.live && k >= 0;
+        const bool bad = hit && code > (uint32_t)APT_MAT_REFR;
+        if (__any(bad)) report_status(ta, APT_DEV_BAD_MATERIAL);
+        s.live = hit && !bad;
+        if (s.live) {
+            mat_shade(s, tmin, k, geo, alb, em, code, mkey, d);
+            ++traced;
+        }
+        if (ta.rr_start && d + 1 >= ta.rr_start) {          // wave-uniform; APT_FLAG_RR on T
+            PathState t;
+            t.rxy = f2{s.tx, s.ty}; t.rz = s.tz; t.alive = s.live ? 1u : 0u;
+            russian_roulette(t, rr_key, d);
+            s.tx = t.rxy.x; s.ty = t.rxy.y; s.tz = t.rz;
+        }
+    }
+    return traced;
+}
+
+__device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, float oz, float dx, float dy, float dz) {
+    s.ox = ox; s.oy = oy; s.oz = oz; s.dx = dx; s.dy = dy; s.dz = dz;
+    s.tx = s.ty = s.tz = 1.0f;
+    s.lx = s.ly = s.lz = 0.0f;
+    s.skip = -1;
+    s.live = true;
+}
+
+// ---- kernel: rays from a buffer -----------------------------------------------------------------------------------------------
+template <int SC>
+__global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *__restrict__ rays, const float *__restrict__ sph,
+                                                                  const uint32_t *__restrict__ mat, float *__restrict__ colors,
+                                                                  uint64_t n_total, uint64_t begin, uint64_t count, TraceArgs ta) {
+    __shared__ float4 tab[kMatTab];
+    __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
+    MatScene8 m8;
+    if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
+    const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = local < count;
+    const uint64_t p = begin + (valid ? local : 0);
+    MatPath s;
+    mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
+    const uint32_t traced = trace_mat<SC>(sph, mat, m8, tile, s, ta, p);
+    if (valid) {
+        colors[p] = s.lx;
+        colors[n_total + p] = s.ly;
+        colors[2 * n_total + p] = s.lz;
+    }
+    count_traced(ta, valid ? traced : 0);
+}
+
+// ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
+// render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: the same lanes per sub-pixel (GROUP), the same
+// pairwise leaves, tail and decode; the sample is a material path and its colour is L.
+template <int SC, int GROUP>
+__global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
+                                                                  FrameArgs fa, TraceArgs ta, LeafProg lp) {
+    __shared__ float4 tab[kMatTab];
+    __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
+    extern __shared__ float dyn_lds[];
+    float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
+    __shared__ Camera cam;
+    if (threadIdx.x < sizeof(Camera) / sizeof(double)) (&cam.pos[0])[threadIdx.x] = (&fa.cam.pos[0])[threadIdx.x];
+    MatScene8 m8;
+    if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
+    else __syncthreads();
+
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t L = (uint64_t)xcd_chunked_block<16>(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
+    const uint32_t j = (GROUP == 8) ? (uint32_t)(L & 7) : 0u;
+    const uint32_t sub = (uint32_t)(L / GROUP) & 3u;
+    const uint64_t pl = L / (4 * GROUP);
+    const bool valid = pl < fa.pixel_count;
+    const uint64_t q = fa.pixel_begin + (valid ? pl : 0);
+    const uint32_t pi = (uint32_t)(q / fa.height), pj = (uint32_t)(q % fa.height);
+    const uint32_t sy = sub >> 1, sx = sub & 1;
+    const uint64_t pbase = (q * 4 + sub) * fa.samples;
+    uint32_t traced = 0;
+
+    struct Col { float r, g, b; };
+    auto sample = [&](uint32_t k) __attribute__((always_inline)) -> Col {
+        double u1, u2;
+        path_uniforms(fa.seed, pbase + k, u1, u2);
+        float rox, roy, roz, rdx, rdy, rdz;
+        camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
+        MatPath s;
+        mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
+        traced += trace_mat<SC>(sph, mat, m8, tile, s, ta, pbase + k);
+        return Col{s.lx, s.ly, s.lz};
+    };
+    auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };
+
+    float res[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t start = 0;
+    int sp = 0;
+    for (uint32_t leaf = 0; leaf < lp.nleaves; ++leaf) {
+        const uint32_t n = lp.len(leaf);
+        float acc[3];
+        if (GROUP == 1) { // n < 8: res = 0; res += a[i]
+            Col a = {0.0f, 0.0f, 0.0f};
+            for (uint32_t k = 0; k < n; ++k) a = add(a, sample(start + k));
+            acc[0] = a.r; acc[1] = a.g; acc[2] = a.b;
+        } else {          // 8 <= n <= 128: r[j] chains, tree, tail
+            const uint32_t nfull = n & ~7u;
+            Col a = sample(start + j);
+            for (uint32_t i8 = 8; i8 < nfull; i8 += 8) a = add(a, sample(start + i8 + j));
+            acc[0] = a.r; acc[1] = a.g; acc[2] = a.b;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) { // ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7))
+                float v = acc[ch];
+                v = v + __shfl_xor(v, 1, 64);
+                v = v + __shfl_xor(v, 2, 64);
+                v = v + __shfl_xor(v, 4, 64);
+                acc[ch] = v;
+            }
+            const uint32_t nt = n - nfull;
+            if (nt) { // res += a[i] for the n % 8 trailing samples, in order
+                const uint32_t traced_before = traced;
+                const Col c = sample(start + nfull + (j < nt ? j : 0));
+                if (j >= nt) traced = traced_before;
+                for (uint32_t t = 0; t < nt; ++t) {
+                    const int src = (int)((lane & ~7u) + t);
+                    acc[0] = acc[0] + __shfl(c.r, src, 64);
+                    acc[1] = acc[1] + __shfl(c.g, src, 64);
+                    acc[2] = acc[2] + __shfl(c.b, src, 64);
+                }
+            }
+        }
+        start += n;
+        if (lp.nleaves == 1) {
+            res[0] = acc[0]; res[1] = acc[1]; res[2] = acc[2];
+        } else { // pairwise(left) + pairwise(right), innermost first
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) stack_lds[(sp * 3 + ch) * kStackSlots + (threadIdx.x >> 3)] = acc[ch];
+            ++sp;
+            for (uint32_t mm = 0; mm < lp.ncomb(leaf); ++mm) {
+                --sp;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float a = stack_lds[((sp - 1) * 3 + ch) * kStackSlots + (threadIdx.x >> 3)];
+                    const float b = stack_lds[(sp * 3 + ch) * kStackSlots + (threadIdx.x >> 3)];
+                    stack_lds[((sp - 1) * 3 + ch) * kStackSlots + (threadIdx.x >> 3)] = a + b;
+                }
+            }
+        }
+    }
+    if (lp.nleaves > 1) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) res[ch] = stack_lds[ch * kStackSlots + (threadIdx.x >> 3)];
+    }
+
+    // decode_color: data_visualization.py:36-57, as render_frame_kernel (dword stores of the 8-bit pixels assembled in LDS)
+    constexpr uint32_t kPixPerBlock = kBlock / (4 * GROUP), kU8Words = kPixPerBlock * 3 / 4;
+    static_assert(kPixPerBlock * 3 % 4 == 0, "a workgroup's 8-bit pixels are whole dwords");
+    __shared__ uint32_t u8pack[kU8Words];
+    const uint64_t pl0 = pl - (threadIdx.x / (4 * GROUP));
+    const bool pack = fa.fb_u8 && pl0 + kPixPerBlock <= fa.pixel_count && (((uintptr_t)fa.fb_u8 + pl0 * 3) & 3u) == 0;
+    const float fs = (float)fa.samples;
+    const int gbase = (int)(lane & ~(uint32_t)(4 * GROUP - 1));
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float mean = res[ch] / fs;
+        double acc = 0.0;
+#pragma unroll
+        for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP, 64);
+        const double v = acc / 4;
+        const double cl = v < 0 ? 0 : (v > 1 ? 1 : v);
+        if (valid && (lane & (4 * GROUP - 1)) == 0) {
+            fa.fb[(uint64_t)ch * fa.pixel_count + pl] = (float)cl;
+            const uint8_t b8 = (uint8_t)(cl * 255);
+            if (pack) reinterpret_cast<uint8_t *>(u8pack)[(threadIdx.x / (4 * GROUP)) * 3 + ch] = b8;
+            else if (fa.fb_u8) fa.fb_u8[pl * 3 + ch] = b8;
+        }
+    }
+    if (pack) {
+        __syncthreads();
+        if (threadIdx.x < kU8Words) reinterpret_cast<uint32_t *>(fa.fb_u8 + pl0 * 3)[threadIdx.x] = u8pack[threadIdx.x];
+    }
+    count_traced(ta, valid ? traced : 0);
+}
+
+} // namespace

@@ -20,7 +20,9 @@
 
 #include "../../include/render_mi355x.h"
 #include "apt_host.h"
+#include "apt_materials.h"
 #include "pt_core.h"
+#include "pt_dispatch.h"
 
 #include "pt_kernels.h"
 #include "pt_grid_build.h"
@@ -37,30 +39,29 @@ int launched() {
     return e == hipSuccess ? APT_OK : hip_fail(e);
 }
 
-// Run-time settings -> template arguments: `f` is called with the value as a std::integral_constant, so a launch inside it
-// names its kernel as kernel<m, ...>.  Every combination `f` can reach is instantiated: a call site that must not reach one
-// (render_frame_kernel's and render_paths_kernel's static_asserts) handles that case before it dispatches.
-template <class F> void with_mode(uint32_t mode, F &&f) {
-    if (mode == APT_MODE_ORACLE) f(std::integral_constant<int, kModeOracle>{});
-    else f(std::integral_constant<int, kModeKernel>{});
-}
-template <class F> void with_flag(bool b, F &&f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
+// Run-time settings -> template arguments: with_mode / with_flag, pt_dispatch.h.
 
 int make_leaf_prog(uint32_t samples, LeafProg &lp) {   // the plan itself: pt_leaf.h
     return make_leaf_plan(samples, lp) ? APT_OK : fail(APT_ERR_ARG, "samples too large: its pairwise-sum plan needs more than 64 leaves (every count <= 7688 fits, and 8192)%s");
 }
 
-int check_params(const apt_render_params *p) {
+// materials: the *_materials entries, which do not read light_index with APT_FLAG_EMISSION (include/render_mi355x.h)
+int check_params(const apt_render_params *p, bool materials = false) {
     if (!p) return fail(APT_ERR_ARG, "params is null%s");
     if (p->struct_size != sizeof(apt_render_params)) return fail(APT_ERR_STRUCT, "apt_render_params.struct_size mismatch%s");
     if (!p->width || !p->height || !p->samples) return fail(APT_ERR_ARG, "width/height/samples must be non-zero%s");
     if (p->mode > APT_MODE_ORACLE) return fail(APT_ERR_ARG, "unknown mode%s");
     if (p->num_spheres == 0) return fail(APT_ERR_SCENE, "num_spheres is 0%s");
     if (p->light_index >= (int32_t)p->num_spheres) return fail(APT_ERR_SCENE, "light_index out of range%s");
-    if ((p->flags & APT_FLAG_EMISSION) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_EMISSION needs a light_index >= 0%s");
+    if (!materials && (p->flags & APT_FLAG_EMISSION) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_EMISSION needs a light_index >= 0%s");
+    return APT_OK;
+}
+
+// What the material entries refuse on top of check_params (after it, before any pointer or range check of the entry itself).
+int check_materials(const apt_render_params *p, const uint32_t *materials) {
+    if (!materials) return fail(APT_ERR_ARG, "materials must be non-null%s");
+    if (p->mode != APT_MODE_KERNEL) return fail(APT_ERR_ARG, "materials need APT_MODE_KERNEL (O-mode restates test_soa, which has none)%s");
+    if (p->accel) return fail(APT_ERR_ARG, "materials: accel (grid) is not supported%s");
     return APT_OK;
 }
 
@@ -105,6 +106,11 @@ TraceArgs make_trace_args(const apt_render_params *p, const Launch &ls) {
     return ta;
 }
 
+apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls) {
+    const TraceArgs ta = make_trace_args(p, ls);
+    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.eps, ta.seed, ta.status, ta.traced};
+}
+
 // The path range [b, b + c) of a buffer-mode call (path_count 0: to the end of the image) among the image's n_image paths.  With
 // APT_FLAG_BAND_BUFFERS the caller's buffers are planes of c floats holding the range only: plane() is their length either way, and
 // base() shifts such a buffer so that path p sits at index p, the indexing of a whole-image buffer.
@@ -141,16 +147,22 @@ size_t sphere_table_bytes(uint32_t num_spheres) { return ((size_t)num_spheres * 
 constexpr uint64_t kTwoPathBufferMin = 1ull << 20;
 
 // ---- the two render launches, on an explicit snapshot of a context's values -----------------
+// mat: a material entry (include/render_mi355x.h "per-sphere materials"; a null `materials` is refused).
 int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, const float *rays,
-                    const float *spheres, float *colors) {
-    int rc = check_params(p);
+                    const float *spheres, float *colors, bool mat = false, const uint32_t *materials = nullptr) {
+    int rc = check_params(p, mat);
     if (rc) return rc;
+    if (mat && (rc = check_materials(p, materials))) return rc;
     if (!rays || !spheres || !colors) return fail(APT_ERR_ARG, "rays/spheres/colors must be non-null%s");
     PathRange r;
     if ((rc = path_range(p, r)) || r.c == 0) return rc;
     const uint64_t n = r.plane(), b = r.b, c = r.c;
     const uint64_t blocks = (c + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
+    if (mat) {   // per-sphere materials: materials.hip
+        apt::mat_render_paths(apt::MatPathsCall{make_mat_trace(p, ls), r.base(rays), spheres, materials, r.base(colors), n, b, c, stream});
+        return launched();
+    }
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
     const TraceArgs ta = make_trace_args(p, ls);
@@ -196,10 +208,11 @@ bool queue_launch_shape(const apt::Debug &dbg, const LeafProg &lp, bool rr, bool
 }
 
 int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, const float *spheres,
-                    uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
-    const apt::Debug &dbg = ls.cv.debug;
-    int rc = check_params(p);
+                    uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8, bool mat = false,
+                    const uint32_t *materials = nullptr) {
+    int rc = check_params(p, mat);
     if (rc) return rc;
+    if (mat && (rc = check_materials(p, materials))) return rc;
     if (!spheres || !fb) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");
     const uint64_t npix = (uint64_t)p->width * p->height;
     if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
@@ -210,6 +223,12 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     const uint64_t lanes = pixel_count * 4u * (uint64_t)group;
     const uint64_t blocks = (lanes + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    const apt::Debug &dbg = ls.cv.debug;
+    if (mat) {   // per-sphere materials: materials.hip
+        apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls), spheres, materials, p->width, p->height, p->samples, pixel_begin,
+                                                pixel_count, fb, fb_u8, stream});
+        return launched();
+    }
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
     TraceArgs ta = make_trace_args(p, ls);
@@ -361,7 +380,8 @@ int apt_context_check(apt_context *ctx, void *stream) {
     if (bits & APT_DEV_GRID_TURNS) what += " grid-walk-bound";
     if (bits & APT_DEV_LDS_BASE) what += " lds-base";
     if (bits & APT_DEV_GRID_MISMATCH) what += " grid-mismatch";
-    if (bits & ~(uint32_t)(APT_DEV_QUEUE_GUARD | APT_DEV_GRID_TURNS | APT_DEV_LDS_BASE | APT_DEV_GRID_MISMATCH)) what += " unknown-bits";
+    if (bits & APT_DEV_BAD_MATERIAL) what += " bad-material";
+    if (bits & ~(uint32_t)(APT_DEV_QUEUE_GUARD | APT_DEV_GRID_TURNS | APT_DEV_LDS_BASE | APT_DEV_GRID_MISMATCH | APT_DEV_BAD_MATERIAL)) what += " unknown-bits";
     return fail(APT_ERR_DEVICE, "a kernel reported a failure through the device status word:%s (the frame it wrote is incomplete)", what.c_str());
 }
 
@@ -411,6 +431,36 @@ int apt_context_render_frame(apt_context *ctx, const apt_render_params *p, void 
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
     return do_render_frame(launch_state(*ctx, stream), p, stream, spheres, pixel_begin, pixel_count, fb, fb_u8);
+}
+
+// Per-sphere materials.  check_params and check_materials run before the context's launch state is taken (the one place the other
+// entries touch HIP before their checks); do_render_* repeat them and check the rest.
+int apt_context_render_frame_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                       const uint32_t *materials, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+    clear_error();
+    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
+    int rc = check_params(p, true);
+    if (rc || (rc = check_materials(p, materials))) return rc;
+    return do_render_frame(launch_state(*ctx, stream), p, stream, spheres, pixel_begin, pixel_count, fb, fb_u8, true, materials);
+}
+
+int apt_context_render_paths_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays,
+                                       const float *spheres, const uint32_t *materials, float *colors) {
+    clear_error();
+    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
+    int rc = check_params(p, true);
+    if (rc || (rc = check_materials(p, materials))) return rc;
+    return do_render_paths(launch_state(*ctx, stream), p, stream, rays, spheres, colors, true, materials);
+}
+
+int apt_render_frame_materials(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials,
+                               uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+    return apt_context_render_frame_materials(&apt::default_context(), p, stream, spheres, materials, pixel_begin, pixel_count, fb, fb_u8);
+}
+
+int apt_render_paths_materials(const apt_render_params *p, void *stream, const float *rays, const float *spheres,
+                               const uint32_t *materials, float *colors) {
+    return apt_context_render_paths_materials(&apt::default_context(), p, stream, rays, spheres, materials, colors);
 }
 
 // ---- the context-free forms: the process-wide default context -----------------------------------------

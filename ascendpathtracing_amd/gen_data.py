@@ -84,6 +84,16 @@ def gen_spheres(out_dir=None):
     return sph
 
 
+def gen_spheres_materials():
+    """The material entries' demo scene (apt_gen_spheres_materials_host): gen_spheres' eight spheres plus smallpt's glass ball as
+    sphere 8 -> (spheres float32 [128] = [10][9] planes zero padded, materials int32 [9] of MAT_* codes; light index 7)."""
+    sph = np.zeros(128, dtype=np.float32)
+    mat = np.zeros(9, dtype=np.uint32)
+    check(lib().apt_gen_spheres_materials_host(_fptr(sph), mat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+          "apt_gen_spheres_materials_host")
+    return sph, mat.view(np.int32)
+
+
 def gen_scene(num_spheres, seed=0, out_dir=None):
     """Build-defined large scene (BASELINE config 4): six walls, Ns-7 random small spheres,
     light at index Ns-1.  -> zero-padded [10][Ns] table."""

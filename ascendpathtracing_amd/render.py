@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import RenderParams, check, lib, require_gpu
+from ._lib import MAT_DIFF, MAT_REFR, MAT_SPEC, RenderParams, check, lib, require_gpu  # noqa: F401  (MAT_*: the materials= codes)
 
 
 def _stream_handle(stream):
@@ -32,6 +32,14 @@ def _buffer_paths(params):
     return params.num_paths
 
 
+def _dev_materials(t, num_spheres):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise _lib.AptError("materials must be a contiguous int32 tensor on the GPU")
+    if t.numel() != num_spheres:
+        raise _lib.AptError(f"materials has {t.numel()} elements, expected num_spheres = {num_spheres}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
 def sphere_floats(num_spheres):
     """Length of the zero-padded [10][Ns] table (512-byte multiple, gen_data.py:120-127)."""
     return (num_spheres * 10 + 127) // 128 * 128
@@ -39,15 +47,23 @@ def sphere_floats(num_spheres):
 
 # The bodies of render_do_ex / render_frame, shared by the default-context functions and Context's methods: `entry` is the C entry
 # (also the name errors are reported under), `handle` its leading context argument, if any.
-def _render_do_ex(entry, handle, params, stream, rays, spheres, colors):
+# materials (int32 tensor of num_spheres codes, MAT_*): the entry's *_materials form; None: the entry itself, untouched.
+def _render_do_ex(entry, handle, params, stream, rays, spheres, colors, materials=None):
     require_gpu()
     n = _buffer_paths(params)
+    mat = ()
+    if materials is not None:
+        entry, mat = _MATERIALS_ENTRY[entry], (_dev_materials(materials, params.num_spheres),)
     check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
-                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat,
                                 _dev_f32(colors, "colors", 3 * n)), entry)
 
 
-def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8):
+_MATERIALS_ENTRY = {"render_do_ex": "apt_render_paths_materials", "apt_context_render_do_ex": "apt_context_render_paths_materials",
+                    "render_frame": "apt_render_frame_materials", "apt_context_render_frame": "apt_context_render_frame_materials"}
+
+
+def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials=None):
     require_gpu()
     npix = params.width * params.height
     if pixel_count is None:
@@ -56,8 +72,11 @@ def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stre
         fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
     if fb_u8 is None:
         fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
+    mat = ()
+    if materials is not None:
+        entry, mat = _MATERIALS_ENTRY[entry], (_dev_materials(materials, params.num_spheres),)
     check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
-                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat,
                                 ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(fb, "fb", 3 * pixel_count),
                                 ctypes.c_void_p(fb_u8.data_ptr())), entry)
     return fb, fb_u8
@@ -119,11 +138,12 @@ class Context:
                                     _dev_f32(spheres, "spheres"), _dev_f32(colors, "colors"))
         check(lib().apt_last_status(), "apt_context_render_do")
 
-    def render_do_ex(self, params, stream, rays, spheres, colors):
-        _render_do_ex("apt_context_render_do_ex", (self._h,), params, stream, rays, spheres, colors)
+    def render_do_ex(self, params, stream, rays, spheres, colors, materials=None):
+        _render_do_ex("apt_context_render_do_ex", (self._h,), params, stream, rays, spheres, colors, materials)
 
-    def render_frame(self, params, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None):
-        return _render_frame("apt_context_render_frame", (self._h,), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8)
+    def render_frame(self, params, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None):
+        return _render_frame("apt_context_render_frame", (self._h,), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8,
+                             materials)
 
 
 def render_host(blockDim, rays, spheres, colors):
@@ -218,23 +238,24 @@ def check_device_status(stream=None):
     check(lib().apt_check(_stream_handle(stream)), "apt_check")
 
 
-def render_do_ex(params: RenderParams, stream, rays, spheres, colors):
+def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=None):
     """Run-time-parameter form of render_do: rays [6][N], spheres [10][Ns] padded, colors [3][N] (with APT_FLAG_BAND_BUFFERS: planes of
-    path_count floats holding only the range)."""
-    _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors)
+    path_count floats holding only the range).  materials: contiguous int32 CUDA tensor of num_spheres MAT_* codes -> per-path radiance
+    of the material renderer (apt_render_paths_materials); None: the mirror renderer."""
+    _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors, materials)
 
 
-def render_paths(params: RenderParams, rays, spheres, stream=None):
+def render_paths(params: RenderParams, rays, spheres, stream=None, materials=None):
     """Convenience: allocate colours, launch, return the [3][N] tensor (not synchronised)."""
     colors = torch.empty(3 * params.num_paths, dtype=torch.float32, device=rays.device)
-    render_do_ex(params, stream, rays, spheres, colors)
+    render_do_ex(params, stream, rays, spheres, colors, materials)
     return colors.view(3, -1)
 
 
-def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None):
+def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None):
     """Fused ray-generate + trace + decode for pixels [pixel_begin, pixel_begin+pixel_count).
-    Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised."""
-    return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8)
+    Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised.  materials: as render_do_ex (apt_render_frame_materials)."""
+    return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials)
 
 
 def gen_rays_device(params: RenderParams, stream=None, device="cuda"):

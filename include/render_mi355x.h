@@ -186,7 +186,8 @@ enum {
     APT_DEV_QUEUE_GUARD = 1u,  /* sample-queue kernel (APT_FLAG_RETIRE, 8 spheres): the bound on a wave's loop turns ran out      */
     APT_DEV_GRID_TURNS = 2u,   /* sample-queue kernel, grid form: the bound on a wave's walk turns ran out                         */
     APT_DEV_LDS_BASE = 4u,     /* sample-queue kernels: the dynamic LDS region does not start at LDS address 0 (a build problem)    */
-    APT_DEV_GRID_MISMATCH = 8u /* APT_FLAG_GRID_SLOTS: the grid at `accel` is not this scene's or has no pair-slot tables           */
+    APT_DEV_GRID_MISMATCH = 8u, /* APT_FLAG_GRID_SLOTS: the grid at `accel` is not this scene's or has no pair-slot tables          */
+    APT_DEV_BAD_MATERIAL = 16u  /* *_materials entries: a path hit a sphere whose material code is not an APT_MAT_* value            */
 };
 int  apt_context_check(apt_context *ctx, void *stream);
 int  apt_check(void *stream);
@@ -229,6 +230,77 @@ int render_do_ex(const apt_render_params *p, void *stream,
  * p->path_begin/path_count are ignored here. */
 int render_frame(const apt_render_params *p, void *stream, const float *spheres,
                  uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8);
+
+/* ---- per-sphere materials (EXTENSION: smallpt's DIFF / SPEC / REFR, scripts/gen_data.py:77-102) ----------------------------------
+ * Opt-in: the entries below take a DEVICE uint32_t materials[num_spheres]; every other entry point renders mirrors as before.  Callers
+ * detect the feature by its symbols (APT_ABI_VERSION is unchanged).  Arguments are checked before any HIP call: check_params' rules
+ * (except that a light_index of -1 is accepted with APT_FLAG_EMISSION, which is not read here), then APT_ERR_ARG for materials == NULL,
+ * mode != APT_MODE_KERNEL, accel != 0, and the pixel / path ranges as render_frame / render_do_ex check them.  APT_FLAG_RR applies;
+ * APT_FLAG_RETIRE is accepted and changes nothing (paths run to full depth); gain, light_index and APT_FLAG_EMISSION are not read.
+ *
+ * The arithmetic, operation by operation (fp32, every operation rounded on its own: no FMA; sqrt and division are IEEE; a dot
+ * product dot(x, y) is the chain ((0 + x0*y0) + x1*y1) + x2*y2):
+ *   state   o, d = the camera ray (render_frame) or the ray buffer (render_paths); L = (0,0,0), T = (1,1,1); skip = none.
+ *   bounce d = 0 .. depth-1:
+ *     hit     the K-mode test of render_do_ex for every sphere but `skip` (t = t0 > eps ? t0 : t1, accepted when t > eps, strict '<'
+ *             arg-min, lowest index on ties, kMissT = 1e20 never wins).  No sphere: the path ends (L keeps its value).
+ *     code    m = materials[k] of the hit sphere k; m > 2: the kernel ORs APT_DEV_BAD_MATERIAL into the status word and the path ends.
+ *     point   h = o + d*t (mul, then add); n = (h - c) / sqrt(dot(h - c, h - c)) (three divisions), as render_do_ex's K-mode.
+ *     light   L += T * emission(k) per channel (planes 4..6), then T *= albedo(k) (planes 7..9).
+ *     orient  ddn = dot(d, n); into = ddn < 0; nl = into ? n : -n.
+ *     draws   mkey = splitmix64(seed ^ splitmix64(path) ^ 0x6A09E667F3BCC909), h = splitmix64(mkey + 0x9E3779B97F4A7C15 * (d + 1))
+ *             (uint64 wrap-around), u1 = (float)(h >> 40) * 2^-24, u2 = (float)((h >> 16) & 0xFFFFFF) * 2^-24.  A stream of its own,
+ *             separate from APT_FLAG_RR's.  `path` = the path index of the header's layout.
+ *     reflect k2 = ddn * 2; d = d - n * k2 per component (render_do_ex's K-mode mirror).
+ *     SPEC    reflect.
+ *     DIFF    x = u1 * 4 (exact), quadrant q = (int)x, f = x - q (exact), z = f * f;
+ *             s = f * (S1 + z*(S3 + z*(S5 + z*(S7 + z*(S9 + z*S11))))), c = 1 + z*(C2 + z*(C4 + z*(C6 + z*(C8 + z*(C10 + z*C12))))),
+ *             evaluated innermost first, with the APT_MAT_S* / APT_MAT_C* constants below (fp32 hex literals); then
+ *             (sin, cos) of 2*pi*u1 = q 0: (s, c)  1: (c, -s)  2: (-s, -c)  3: (-c, s)  (|error| <= 2^-22 against float64 sin / cos).
+ *             r = sqrt(u2); Duff et al. 2017 basis of nl: sg = copysign(1, nl.z), a = -1 / (sg + nl.z), b = (nl.x * nl.y) * a,
+ *             t = (1 + ((sg * nl.x) * nl.x) * a, sg * b, -sg * nl.x), bt = (b, sg + (nl.y * nl.y) * a, -nl.y);
+ *             v = (t * (cos * r) + bt * (sin * r)) + nl * sqrt(1 - u2) per component; d = v / sqrt(dot(v, v)).
+ *     REFR    smallpt's glass, nc = 1, nt = 1.5: dn = into ? ddn : -ddn; nnt = into ? APT_MAT_NNT_IN : 1.5;
+ *             cos2t = 1 - (nnt * nnt) * (1 - dn * dn).  cos2t < 0 (total internal reflection): reflect, weight 1.  Otherwise
+ *             g = dn * nnt + sqrt(cos2t), g = into ? g : -g; v = d * nnt - n * g per component; tdir = v / sqrt(dot(v, v));
+ *             c = 1 - (into ? -ddn : dot(tdir, n)); Re = APT_MAT_R0 + APT_MAT_1MR0 * ((((c * c) * c) * c) * c); Tr = 1 - Re;
+ *             P = 0.25 + 0.5 * Re; u1 < P: reflect, weight Re / P; otherwise d = tdir, weight Tr / (1 - P); T *= weight per channel.
+ *     skip    o = h.  A branch that leaves on the sphere's OUTER side does not test sphere k on the next segment (skip = k; a convex
+ *             sphere cannot be re-hit going outward, while the near root of a wall of radius 1e5 is fp32 noise of ~5e-3 >> eps):
+ *             DIFF, SPEC and the REFR reflection leave outward iff `into`, the REFR refraction iff `!into`; otherwise skip = none.
+ *     roulette  APT_FLAG_RR as specified above, on T (the path counts as alive until it ends).
+ *   colour  L.  render_frame's decode (numpy's pairwise mean, float64 sum of the 4 sub-pixels, clip, x255 truncation) is unchanged. */
+enum { APT_MAT_SPEC = 0, APT_MAT_DIFF = 1, APT_MAT_REFR = 2 };   /* a zero-filled table = all mirrors */
+#define APT_MAT_S1  0x1.921fb6p+0f
+#define APT_MAT_S3  -0x1.4abbcep-1f
+#define APT_MAT_S5  0x1.466bc2p-4f
+#define APT_MAT_S7  -0x1.32d168p-8f
+#define APT_MAT_S9  0x1.501ce2p-13f
+#define APT_MAT_S11 -0x1.cd915cp-19f
+#define APT_MAT_C2  -0x1.3bd3ccp+0f
+#define APT_MAT_C4  0x1.03c1f0p-2f
+#define APT_MAT_C6  -0x1.55d3c2p-6f
+#define APT_MAT_C8  0x1.e1f2bcp-11f
+#define APT_MAT_C10 -0x1.a65e60p-16f
+#define APT_MAT_C12 0x1.e3718cp-22f
+#define APT_MAT_NNT_IN 0x1.555556p-1f  /* RN(1 / 1.5)                    */
+#define APT_MAT_R0     0x1.47ae14p-5f  /* RN(0.04), smallpt's (nt - nc)^2 / (nt + nc)^2 */
+#define APT_MAT_1MR0   0x1.eb851ep-1f  /* RN(1 - APT_MAT_R0)                            */
+
+/* render_frame / apt_context_render_frame with materials (the frame entry's pixel range, fb and fb_u8 rules). */
+int apt_render_frame_materials(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials,
+                               uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8);
+int apt_context_render_frame_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                       const uint32_t *materials, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8);
+/* render_do_ex with materials: colors [3][N] = L per path; path_begin / path_count and APT_FLAG_BAND_BUFFERS as render_do_ex. */
+int apt_render_paths_materials(const apt_render_params *p, void *stream, const float *rays, const float *spheres,
+                               const uint32_t *materials, float *colors);
+int apt_context_render_paths_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays,
+                                       const float *spheres, const uint32_t *materials, float *colors);
+/* HOST demo scene: gen_spheres' 8 spheres plus smallpt's glass ball (r 16.5 at (73, 16.5, 78), albedo 0.999) as sphere 8, light 7.
+ * spheres = HOST float[128] ([10][9] planes, zero padded like gen_spheres), materials = HOST uint32_t[9]: walls and light DIFF,
+ * mirror SPEC, glass REFR. */
+int apt_gen_spheres_materials_host(float *spheres, uint32_t *materials);
 
 /* ---- one process, several GPUs (the reference's 8-block split, src/render.cpp:9-10,24-27, across devices) ----
  * The frame's x-major pixel range is cut into num_bands*stripes contiguous stripes; band b renders stripes
