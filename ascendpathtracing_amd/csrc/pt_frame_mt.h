@@ -23,7 +23,7 @@
 #pragma once
 #include "pt_trace.h"
 #include "pt_trace2.h"
-#include "pt_queue.h" // FrameArgs
+#include "pt_frame.h" // FrameArgs
 
 namespace {
 

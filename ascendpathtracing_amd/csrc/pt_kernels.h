@@ -187,12 +187,7 @@ __global__ __launch_bounds__(kBlock) void render_paths_queue_kernel(const float 
 }
 
 // ---- kernel: fused frame ----------------------------------------------------------------
-// FrameArgs: pt_queue.h
-
-// GROUP lanes share one sub-pixel: lane j of the group owns numpy's pairwise accumulator
-// r[j] (samples j, 8+j, 16+j, ...), so the summation order of np.mean is reproduced with
-// a 3-step butterfly and no shared memory.  GROUP == 1 serves samples < 8 (numpy sums
-// those sequentially).
+// FrameArgs, the lanes' sub-pixels (GROUP), the camera in LDS and the decode: pt_frame.h
 // TWO: two samples of a lane's chain are traced at a time (pt_trace2.h); only with SC == kScene8, GROUP == 8, no
 // retirement, no roulette (the host picks the kernel).
 template <int MODE, int SC, int GROUP, bool RETIRE, bool TWO = false>
@@ -206,10 +201,8 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
     extern __shared__ float dyn_lds[];
     float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
     float *queue_lds = dyn_lds + (lp.nleaves > 1 ? kMaxStack * 3 * kStackSlots : 0); // [waves][3][8*maxleaf] (refill)
-    // The camera frame (14 doubles) is only needed by ray-generate; parked in LDS it does not
-    // occupy 28 SGPRs across the bounce loop (they spilled to VGPR lanes otherwise).
     __shared__ Camera cam;
-    if (threadIdx.x < sizeof(Camera) / sizeof(double)) (&cam.pos[0])[threadIdx.x] = (&fa.cam.pos[0])[threadIdx.x];
+    park_camera(cam, fa);
     Scene8 sc;
     Tab8 tab8{tab, tab + 8};
     if (NS8) tab8 = load_scene8(sph, sc, tab);
@@ -218,15 +211,12 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
     (void)planes;
 
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t L = (uint64_t)xcd_chunked_block<16>(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
-    const uint32_t j = (GROUP == 8) ? (uint32_t)(L & 7) : 0u;
-    const uint32_t sub = (uint32_t)(L / GROUP) & 3u;
-    const uint64_t pl = L / (4 * GROUP);
-    const bool valid = pl < fa.pixel_count;
-    const uint64_t q = fa.pixel_begin + (valid ? pl : 0);
-    const uint32_t pi = (uint32_t)(q / fa.height), pj = (uint32_t)(q % fa.height);
-    const uint32_t sy = sub >> 1, sx = sub & 1;
-    const uint64_t pbase = (q * 4 + sub) * fa.samples;
+    const FrameLane<GROUP> fl = frame_lane<GROUP>(fa);
+    const uint32_t j = fl.j, sub = fl.sub;
+    const uint64_t pl = fl.pl;
+    const bool valid = fl.valid;
+    const uint32_t pi = fl.pi, pj = fl.pj, sy = fl.sy, sx = fl.sx;
+    const uint64_t pbase = fl.pbase;
     uint32_t traced = 0;       // segments of this lane's own pixel (gated by `valid` at the end)
     uint32_t queue_traced = 0; // refill queue: segments this lane traced for ANY valid item of its wave
 
@@ -451,37 +441,8 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
         for (int ch = 0; ch < 3; ++ch) res[ch] = stack_lds[ch * kStackSlots + (threadIdx.x >> 3)];
     }
 
-    // decode_color: data_visualization.py:36-57
-    // The 8-bit pixels of a workgroup (kBlock / (4 * GROUP) consecutive pixels, 3 bytes each: a whole number of dwords that starts on a
-    // dword when the image does) leave as DWORD stores assembled in LDS instead of three byte stores per pixel from different waves: no partial
-    // dwords for the L2 to merge.  (Measured: what brought the frame's write traffic to exactly its size was the XCD-aware block mapping,
-    // pt_trace.h; this took the launch's fetched bytes from 0.88 to 0.83 MB.  Kept: it costs one barrier per workgroup.)
-    constexpr uint32_t kPixPerBlock = kBlock / (4 * GROUP), kU8Words = kPixPerBlock * 3 / 4;
-    static_assert(kPixPerBlock * 3 % 4 == 0, "a workgroup's 8-bit pixels are whole dwords");
-    __shared__ uint32_t u8pack[kU8Words];
-    const uint64_t pl0 = pl - (threadIdx.x / (4 * GROUP));                          // first pixel of this workgroup (wave-uniform arithmetic on L)
-    const bool pack = fa.fb_u8 && pl0 + kPixPerBlock <= fa.pixel_count && (((uintptr_t)fa.fb_u8 + pl0 * 3) & 3u) == 0;   // workgroup-uniform
-    const float fs = (float)fa.samples;
-    const int gbase = (int)(lane & ~(uint32_t)(4 * GROUP - 1));
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float mean = res[ch] / fs;            // np.mean: float32 sum / count
-        double acc = 0.0;                           // :38 sum_color = zeros (float64)
-#pragma unroll
-        for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP, 64); // :41-45
-        const double v = acc / 4;                   // :46
-        const double cl = v < 0 ? 0 : (v > 1 ? 1 : v); // :54
-        if (valid && (lane & (4 * GROUP - 1)) == 0) {
-            fa.fb[(uint64_t)ch * fa.pixel_count + pl] = (float)cl;
-            const uint8_t b8 = (uint8_t)(cl * 255);                               // :55-57 truncation
-            if (pack) reinterpret_cast<uint8_t *>(u8pack)[(threadIdx.x / (4 * GROUP)) * 3 + ch] = b8;
-            else if (fa.fb_u8) fa.fb_u8[pl * 3 + ch] = b8;
-        }
-    }
-    if (pack) {                                     // (workgroup-uniform: every thread reaches the barrier)
-        __syncthreads();
-        if (threadIdx.x < kU8Words) reinterpret_cast<uint32_t *>(fa.fb_u8 + pl0 * 3)[threadIdx.x] = u8pack[threadIdx.x];
-    }
+    __shared__ uint32_t u8pack[frame_u8_words(GROUP)];
+    frame_decode<GROUP>(fa, pl, valid, res, u8pack);
     count_traced(ta, (valid ? traced : 0) + queue_traced);
 }
 

@@ -1,10 +1,11 @@
 // pt_materials.h -- the material kernels (include/render_mi355x.h "per-sphere materials": smallpt's DIFF / SPEC / REFR with emitted
 // radiance), included by materials.hip only.  Same scene forms as the mirror kernels -- the 8-sphere scene with its geometry in SGPRs,
-// any scene through LDS tiles -- and the same sample scheduling, pairwise-leaf accumulation and fused decode as render_frame_kernel;
-// only the body of one sample differs.  Every fp32 operation is the one the header specifies, in its order (-ffp-contract=off):
-// tests/materials_ref.py restates it and the GPU tests compare bit for bit.
+// any scene through LDS tiles (tile_scan, pt_trace.h, shared with dyn_segment) -- and render_frame_kernel's frame skeleton: the lane
+// mapping, camera and decode come from pt_frame.h, the pairwise-leaf accumulation is written out as in render_frame_kernel (pt_frame.h
+// says why); only the body of one sample differs.  Every fp32 operation is the one the header specifies, in its order
+// (-ffp-contract=off): tests/materials_ref.py restates it and the GPU tests compare bit for bit.
 #pragma once
-#include "pt_queue.h"   // FrameArgs; pt_trace.h
+#include "pt_frame.h"   // FrameArgs, frame_lane, park_camera, frame_decode; pt_trace.h
 
 namespace {
 
@@ -143,49 +144,15 @@ __device__ __forceinline__ void mat_hit8(const Scene8 &sc, const MatPath &s, flo
     }
 }
 
-// Any scene: brute force over LDS-staged tiles of sphere pairs, as dyn_segment (pt_trace.h).  Every thread of the workgroup calls this
-// together (barriers).  A lane skips nothing but its own skip sphere; the order of the candidates is ascending, so ties keep the lowest index.
+// Any scene: tile_scan (pt_trace.h), as dyn_segment, with the strict '<' arg-min.  Every thread of the workgroup calls this together
+// (barriers).  A lane skips nothing but its own skip sphere; the candidates come in ascending order, so ties keep the lowest index.
 __device__ __forceinline__ void mat_hit_tiles(const float *__restrict__ sph, float4 *tile, const MatPath &s, uint32_t ns, float eps,
                                               float &tmin, int &idx) {
-    const float *r2 = sph, *cx = sph + ns, *cy = sph + 2 * (size_t)ns, *cz = sph + 3 * (size_t)ns;
     tmin = kMissT;
     idx = -1;
-    for (uint32_t base = 0; base < ns; base += kTile) {
-        const uint32_t n = min((uint32_t)kTile, ns - base);
-        __syncthreads();
-        {
-            float *tf = reinterpret_cast<float *>(tile);
-            const uint32_t n4 = (n + 3u) & ~3u;
-            for (uint32_t k = threadIdx.x; k < n4; k += kBlock) {
-                const bool real = k < n;
-                const float qn = __uint_as_float(0x7fc00000u);
-                const uint32_t o = (k >> 1) * 8u + (k & 1u);
-                tf[o] = real ? cx[base + k] : qn;
-                tf[o + 2] = real ? cy[base + k] : qn;
-                tf[o + 4] = real ? cz[base + k] : qn;
-                tf[o + 6] = real ? r2[base + k] : qn;
-            }
-        }
-        __syncthreads();
-        auto hit = [&](float b, float disc, uint32_t sphere) {
-            if (__any(disc >= 0.0f)) {
-                const float t = intersect_post(HitPre{b, disc}, eps);
-                if (t < tmin && (int)sphere != s.skip) { tmin = t; idx = (int)sphere; }
-            }
-        };
-        for (uint32_t k = 0; k < n; k += 4) {
-            const float4 a0 = tile[k], c0 = tile[k + 1], a1 = tile[k + 2], c1 = tile[k + 3];
-            const HitPre2 h01 = intersect_pre2(a0, c0, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz);
-            const HitPre2 h23 = intersect_pre2(a1, c1, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz);
-            const float m = fmaxf(fmaxf(h01.disc.x, h01.disc.y), fmaxf(h23.disc.x, h23.disc.y));
-            if (__any(m >= 0.0f)) {
-                hit(h01.b.x, h01.disc.x, base + k);
-                hit(h01.b.y, h01.disc.y, base + k + 1);
-                hit(h23.b.x, h23.disc.x, base + k + 2);
-                hit(h23.b.y, h23.disc.y, base + k + 3);
-            }
-        }
-    }
+    tile_scan(sph, tile, ns, eps, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz, [&](float t, uint32_t sphere) __attribute__((always_inline)) {
+        if (t < tmin && (int)sphere != s.skip) { tmin = t; idx = (int)sphere; }
+    });
 }
 
 // What the 8-sphere form keeps per workgroup: geometry in SGPRs (Scene8), geometry / albedo / emission in LDS, and the 8 material codes
@@ -288,8 +255,8 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
 }
 
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
-// render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: the same lanes per sub-pixel (GROUP), the same
-// pairwise leaves, tail and decode; the sample is a material path and its colour is L.
+// render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
+// camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
 template <int SC, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, TraceArgs ta, LeafProg lp) {
@@ -298,21 +265,18 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     extern __shared__ float dyn_lds[];
     float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
     __shared__ Camera cam;
-    if (threadIdx.x < sizeof(Camera) / sizeof(double)) (&cam.pos[0])[threadIdx.x] = (&fa.cam.pos[0])[threadIdx.x];
+    park_camera(cam, fa);
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
     else __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t L = (uint64_t)xcd_chunked_block<16>(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
-    const uint32_t j = (GROUP == 8) ? (uint32_t)(L & 7) : 0u;
-    const uint32_t sub = (uint32_t)(L / GROUP) & 3u;
-    const uint64_t pl = L / (4 * GROUP);
-    const bool valid = pl < fa.pixel_count;
-    const uint64_t q = fa.pixel_begin + (valid ? pl : 0);
-    const uint32_t pi = (uint32_t)(q / fa.height), pj = (uint32_t)(q % fa.height);
-    const uint32_t sy = sub >> 1, sx = sub & 1;
-    const uint64_t pbase = (q * 4 + sub) * fa.samples;
+    const FrameLane<GROUP> fl = frame_lane<GROUP>(fa);
+    const uint32_t j = fl.j, sub = fl.sub;
+    const uint64_t pl = fl.pl;
+    const bool valid = fl.valid;
+    const uint32_t pi = fl.pi, pj = fl.pj, sy = fl.sy, sx = fl.sx;
+    const uint64_t pbase = fl.pbase;
     uint32_t traced = 0;
 
     struct Col { float r, g, b; };
@@ -387,33 +351,8 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         for (int ch = 0; ch < 3; ++ch) res[ch] = stack_lds[ch * kStackSlots + (threadIdx.x >> 3)];
     }
 
-    // decode_color: data_visualization.py:36-57, as render_frame_kernel (dword stores of the 8-bit pixels assembled in LDS)
-    constexpr uint32_t kPixPerBlock = kBlock / (4 * GROUP), kU8Words = kPixPerBlock * 3 / 4;
-    static_assert(kPixPerBlock * 3 % 4 == 0, "a workgroup's 8-bit pixels are whole dwords");
-    __shared__ uint32_t u8pack[kU8Words];
-    const uint64_t pl0 = pl - (threadIdx.x / (4 * GROUP));
-    const bool pack = fa.fb_u8 && pl0 + kPixPerBlock <= fa.pixel_count && (((uintptr_t)fa.fb_u8 + pl0 * 3) & 3u) == 0;
-    const float fs = (float)fa.samples;
-    const int gbase = (int)(lane & ~(uint32_t)(4 * GROUP - 1));
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float mean = res[ch] / fs;
-        double acc = 0.0;
-#pragma unroll
-        for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP, 64);
-        const double v = acc / 4;
-        const double cl = v < 0 ? 0 : (v > 1 ? 1 : v);
-        if (valid && (lane & (4 * GROUP - 1)) == 0) {
-            fa.fb[(uint64_t)ch * fa.pixel_count + pl] = (float)cl;
-            const uint8_t b8 = (uint8_t)(cl * 255);
-            if (pack) reinterpret_cast<uint8_t *>(u8pack)[(threadIdx.x / (4 * GROUP)) * 3 + ch] = b8;
-            else if (fa.fb_u8) fa.fb_u8[pl * 3 + ch] = b8;
-        }
-    }
-    if (pack) {
-        __syncthreads();
-        if (threadIdx.x < kU8Words) reinterpret_cast<uint32_t *>(fa.fb_u8 + pl0 * 3)[threadIdx.x] = u8pack[threadIdx.x];
-    }
+    __shared__ uint32_t u8pack[frame_u8_words(GROUP)];
+    frame_decode<GROUP>(fa, pl, valid, res, u8pack);
     count_traced(ta, valid ? traced : 0);
 }
 

@@ -38,18 +38,9 @@
 #pragma once
 #include <type_traits>
 
-#include "pt_trace.h"
+#include "pt_frame.h"   // FrameArgs; pt_trace.h
 
 namespace {
-
-struct FrameArgs {
-    Camera cam;
-    uint32_t width, height, samples;
-    uint64_t seed;
-    uint64_t pixel_begin, pixel_count;
-    float *fb;       // [3][pixel_count]
-    uint8_t *fb_u8;  // [pixel_count][3] or null
-};
 
 #ifndef APT_Q8_POOL
 #define APT_Q8_POOL 64 // 64 entries (2 KB): measured against 128 in round 3 -- the LDS it frees is worth more occupancy (C5 -3 %)

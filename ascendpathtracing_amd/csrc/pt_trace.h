@@ -670,18 +670,14 @@ __device__ __forceinline__ uint32_t trace_ns8(const Scene8 &sc, const Tab8 tab, 
 }
 
 // ---- trace: any scene, LDS-staged tiles -------------------------------------------------
-// Every thread of the workgroup must call this together (it contains barriers).
-// One segment of every lane of the WORKGROUP against the whole scene (brute force over LDS-staged tiles) followed by the
-// shading step; the state of lanes with `fin` is left alone.  Every thread of the workgroup must call this together
-// (it contains barriers).  Roulette and counters are the caller's.
-template <int MODE>
-__device__ __forceinline__ void dyn_segment(const float *__restrict__ sph, float4 *tile, PathState &s, bool fin,
-                                            const TraceArgs &ta) {
-    const uint32_t ns = ta.ns;
+// The candidates of one segment of every lane of the WORKGROUP against the whole scene, brute force over LDS-staged tiles:
+// update(t, sphere) with the reference's root of every sphere that a lane of the wave may hit, in ascending sphere order.
+// Every thread of the workgroup must call this together (it contains barriers).  (`sph` is not __restrict__ here: the callers'
+// pointer is, and a second alias scope changed their code.)
+template <class Update>
+__device__ __forceinline__ void tile_scan(const float *sph, float4 *tile, uint32_t ns, float eps, float ox, float oy, float oz,
+                                          float dx, float dy, float dz, Update &&update) {
     const float *r2 = sph, *cx = sph + ns, *cy = sph + 2 * (size_t)ns, *cz = sph + 3 * (size_t)ns;
-    const float *colx = sph + 7 * (size_t)ns, *coly = sph + 8 * (size_t)ns, *colz = sph + 9 * (size_t)ns;
-        float tmin = kMissT;
-    int idx = (MODE == kModeOracle) ? -1 : 0;
     for (uint32_t base = 0; base < ns; base += kTile) {
         const uint32_t n = min((uint32_t)kTile, ns - base);
         __syncthreads(); // previous tile fully consumed
@@ -702,19 +698,16 @@ __device__ __forceinline__ void dyn_segment(const float *__restrict__ sph, float
         __syncthreads();
         // Four spheres per step: four wave-uniform ds_read_b128 broadcasts in flight together, two
         // packed discriminant evaluations, ONE test "can any lane hit any of the four?".  A
-        // negative discriminant yields kMissT, which never wins the strict '<', so skipping the
+        // negative discriminant yields kMissT, which never wins a strict '<', so skipping the
         // sqrt/root half for misses is result preserving; hits are then taken in ascending
         // sphere order, which keeps the lowest-index-on-ties rule.
         auto hit = [&](float b, float disc, uint32_t sphere) {
-            if (__any(disc >= 0.0f)) {
-                const float t = intersect_post(HitPre{b, disc}, ta.eps);
-                if (t < tmin) { tmin = t; idx = (int)sphere; }
-            }
+            if (__any(disc >= 0.0f)) update(intersect_post(HitPre{b, disc}, eps), sphere);
         };
         for (uint32_t k = 0; k < n; k += 4) {
             const float4 a0 = tile[k], c0 = tile[k + 1], a1 = tile[k + 2], c1 = tile[k + 3];
-            const HitPre2 h01 = intersect_pre2(a0, c0, s.oxy.x, s.oxy.y, s.oz, s.dxy.x, s.dxy.y, s.dz);
-            const HitPre2 h23 = intersect_pre2(a1, c1, s.oxy.x, s.oxy.y, s.oz, s.dxy.x, s.dxy.y, s.dz);
+            const HitPre2 h01 = intersect_pre2(a0, c0, ox, oy, oz, dx, dy, dz);
+            const HitPre2 h23 = intersect_pre2(a1, c1, ox, oy, oz, dx, dy, dz);
             const float m = fmaxf(fmaxf(h01.disc.x, h01.disc.y), fmaxf(h23.disc.x, h23.disc.y)); // NaNs drop out
             if (__any(m >= 0.0f)) {
                 hit(h01.b.x, h01.disc.x, base + k);
@@ -724,6 +717,22 @@ __device__ __forceinline__ void dyn_segment(const float *__restrict__ sph, float
             }
         }
     }
+}
+
+// One segment of every lane of the WORKGROUP against the whole scene (tile_scan, strict '<' arg-min) followed by the
+// shading step; the state of lanes with `fin` is left alone.  Every thread of the workgroup must call this together
+// (it contains barriers).  Roulette and counters are the caller's.
+template <int MODE>
+__device__ __forceinline__ void dyn_segment(const float *__restrict__ sph, float4 *tile, PathState &s, bool fin,
+                                            const TraceArgs &ta) {
+    const uint32_t ns = ta.ns;
+    const float *cx = sph + ns, *cy = sph + 2 * (size_t)ns, *cz = sph + 3 * (size_t)ns;
+    const float *colx = sph + 7 * (size_t)ns, *coly = sph + 8 * (size_t)ns, *colz = sph + 9 * (size_t)ns;
+    float tmin = kMissT;
+    int idx = (MODE == kModeOracle) ? -1 : 0;
+    tile_scan(sph, tile, ns, ta.eps, s.oxy.x, s.oxy.y, s.oz, s.dxy.x, s.dxy.y, s.dz, [&](float t, uint32_t sphere) __attribute__((always_inline)) {
+        if (t < tmin) { tmin = t; idx = (int)sphere; }
+    });
     const uint32_t g = (idx < 0) ? ns - 1 : (uint32_t)idx;
     PathState n = s;
     shade_and_reflect<MODE>(n, tmin, cx[g], cy[g], cz[g], colx[g], coly[g], colz[g], idx == ta.light);

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Kernel-by-kernel comparison of two builds' `make asm` output:
+   python profiles/isa_compare.py OLD_CSRC [NEW_CSRC]     (NEW_CSRC: this tree's ascendpathtracing_amd/csrc)
+Runs `make -B asm` in both directories.  For every kernel of render_kernels.s and materials.s it compares the instruction lines
+between the symbol and its .Lfunc_end (labels, directives and comments dropped; block labels renumbered per function, since a
+function's index in the file moves them; differences counted by a sequence diff) and the kernel-resource-usage remarks (registers,
+spills, scratch, LDS, occupancy).
+Prints one line per kernel that differs and a summary; exit status 1 when any kernel or resource row differs."""
+import difflib, os, re, subprocess, sys
+from concurrent.futures import ThreadPoolExecutor
+
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build(csrc):
+    r = subprocess.run(["make", "-B", "-C", csrc, "asm"], capture_output=True, text=True)
+    if r.returncode:
+        sys.exit(f"make asm failed in {csrc}:\n{r.stderr[-4000:]}")
+    res, cur = {}, None
+    for l in r.stderr.split("\n"):
+        m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", l)
+        if not m:
+            continue
+        t = m.group(1)
+        if t.startswith("Function Name:"):
+            cur = res.setdefault(t.split(": ", 1)[1].strip(), {})
+        elif cur is not None and ":" in t:
+            k, v = t.split(":", 1)
+            cur[k.strip()] = v.strip()
+    return res
+
+
+def kernels(path):
+    out, name, body = {}, None, None
+    for l in open(path):
+        if name is None:
+            m = re.match(r"^(_Z\S+):", l)
+            if m:
+                name, body = m.group(1), []
+            continue
+        if l.startswith(".Lfunc_end"):
+            out[name] = body
+            name = None
+            continue
+        s = l.split(";", 1)[0].strip()
+        if not s or s.startswith(".") or s.endswith(":"):
+            continue
+        body.append(re.sub(r"\.LBB\d+_", ".LBB_", s))
+    return out
+
+
+def demangle(names):
+    r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return {n: re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")) for n, d in zip(names, r)}
+
+
+def main():
+    if len(sys.argv) not in (2, 3):
+        sys.exit(__doc__)
+    old, new = sys.argv[1], sys.argv[2] if len(sys.argv) == 3 else os.path.join(root, "ascendpathtracing_amd", "csrc")
+    with ThreadPoolExecutor(2) as ex:
+        ro, rn = ex.map(build, (old, new))
+    differ = 0
+    for s in ("render_kernels.s", "materials.s"):
+        ko, kn = kernels(os.path.join(old, s)), kernels(os.path.join(new, s))
+        dm = demangle(sorted(set(ko) | set(kn)))
+        same = 0
+        for n in sorted(set(ko) | set(kn), key=lambda n: dm[n]):
+            if n not in ko or n not in kn:
+                print(f"{s}: {dm[n]}: only in {'new' if n in kn else 'old'}")
+                differ += 1
+                continue
+            res = "" if ro.get(n) == rn.get(n) else f"  resources {ro.get(n)} -> {rn.get(n)}"
+            if ko[n] == kn[n] and not res:
+                same += 1
+                continue
+            differ += 1
+            ops = [o for o in difflib.SequenceMatcher(None, ko[n], kn[n]).get_opcodes() if o[0] != "equal"]
+            lines = sum(max(i2 - i1, j2 - j1) for _, i1, i2, j1, j2 in ops)
+            print(f"{s}: {dm[n]}: {len(ko[n])} -> {len(kn[n])} instructions, {lines} lines in {len(ops)} hunks differ "
+                  f"(first at instruction {ops[0][1] if ops else '-'}){res}")
+        print(f"{s}: {same} of {len(set(ko) | set(kn))} kernels identical (instructions and resources)")
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main()

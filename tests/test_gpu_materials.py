@@ -79,7 +79,8 @@ def _oracle_params(p):
     return oracle.Params.from_buffer_copy(bytes(p))
 
 
-FRAME_CASES = [(s_, d_, rr) for (s_, d_) in ((1, 1), (3, 2), (8, 5), (13, 8), (32, 32), (8, 32), (32, 5), (3, 8)) for rr in (False, True)]
+# (136, 3): two pairwise leaves (64 + 72, no tail), combined through the LDS stack
+FRAME_CASES = [(s_, d_, rr) for (s_, d_) in ((1, 1), (3, 2), (8, 5), (13, 8), (32, 32), (8, 32), (32, 5), (3, 8), (136, 3)) for rr in (False, True)]
 
 
 @pytest.mark.parametrize("scene", ["demo9", "diff8"])
