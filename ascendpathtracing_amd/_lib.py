@@ -31,7 +31,7 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_decode_color_band", "apt_mt19937_checkpoints_window", "apt_gen_rays_mt_device_ex", "apt_build_grid_device", "apt_render_frame_mt",
                "apt_context_check", "apt_check", "apt_context_set_debug", "apt_set_debug", "apt_context_get_debug", "apt_get_debug", "apt_grid_flags",
                "apt_render_frame_materials", "apt_context_render_frame_materials", "apt_render_paths_materials",
-               "apt_context_render_paths_materials", "apt_gen_spheres_materials_host"]
+               "apt_context_render_paths_materials", "apt_gen_spheres_materials_host", "apt_gen_scene_materials_host"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
 CXX_RENDER_DO = "_Z9render_dojPvS_PhS0_S0_"
 ABI_VERSION = 3

@@ -11,6 +11,8 @@ struct MatTrace {                 // the parts of apt_render_params the material
     uint32_t ns, depth, rr_start; // rr_start: first bounce count of APT_FLAG_RR, 0 = no roulette
     float eps;
     uint64_t seed;
+    const uint32_t *grid;         // the uniform grid the caller vouches for (accel with APT_FLAG_GRID_SLOTS): the grid form; null: the
+                                  // 8-sphere form (ns == 8) or the tile form.  Never set without a status word to report a broken promise through.
     uint32_t *status;             // the context's device status word, or null
     unsigned long long *traced;   // apt_set_trace_counter block, or null
 };

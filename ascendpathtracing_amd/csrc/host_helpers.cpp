@@ -310,6 +310,17 @@ int apt_gen_scene_host(uint32_t num_spheres, uint64_t seed, float *spheres, size
     return APT_OK;
 }
 
+// The material codes that go with apt_gen_scene_host's scene of the same (num_spheres, seed): the walls (0..5) and the light (Ns-1) DIFF,
+// small sphere i one of the three codes by (splitmix64(seed + i) >> 32) % 3 (uint64 wrap-around).
+int apt_gen_scene_materials_host(uint32_t num_spheres, uint64_t seed, uint32_t *materials) {
+    apt::clear_error();
+    if (num_spheres < 8) return set_error(APT_ERR_SCENE, "apt_gen_scene_materials_host: needs num_spheres >= 8 (six walls, at least one sphere, the light)%s");
+    if (!materials) return set_error(APT_ERR_ARG, "apt_gen_scene_materials_host: materials is null%s");
+    for (uint32_t i = 0; i < num_spheres; ++i)
+        materials[i] = (i < 6 || i == num_spheres - 1) ? (uint32_t)APT_MAT_DIFF : (uint32_t)((apt::splitmix64(seed + i) >> 32) % 3u);
+    return APT_OK;
+}
+
 // Uniform grid for scenes with many spheres (apt_render_params.accel).  Spheres whose radius exceeds 8x the median
 // radius, or that are not finite (pt_core.h grid_is_large), are "large" (the walls and the light of the generated scenes, r >= 600):
 // they go to an always-tested list; the others are binned by their bounding boxes, inflated by `margin`

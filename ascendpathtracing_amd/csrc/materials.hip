@@ -18,13 +18,16 @@ TraceArgs mat_trace_args(const apt::MatTrace &t) {
     ta.eps = t.eps; ta.gain = 0.0f; ta.traced = t.traced;
     ta.status = t.status;
     ta.refill_lanes = 0;
-    ta.grid = nullptr;
+    ta.grid = t.grid;
     ta.grid_walk = 0;
     ta.emission = 0;
     ta.rr_start = t.rr_start;
     ta.seed = t.seed;
     return ta;
 }
+
+// The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.
+constexpr int mat_scene_form(bool ns8, bool grid) { return ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles); }
 
 } // namespace
 
@@ -42,20 +45,20 @@ void mat_render_frame(const MatFrameCall &c) {
     const uint64_t blocks = (c.pixel_count * 4u * (uint64_t)group + kBlock - 1) / kBlock;   // <= 2^31 - 1: checked by the caller
     const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
     hipStream_t st = (hipStream_t)c.stream;
-    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(group == 8, [&](auto g8) {
-        hipLaunchKernelGGL((render_frame_mat_kernel<ns8 ? kScene8 : kSceneTiles, g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds, st,
+    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) {
+        hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr), g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds, st,
                            c.spheres, c.materials, fa, ta, lp);
-    }); });
+    }); }); });
 }
 
 void mat_render_paths(const MatPathsCall &c) {
     const TraceArgs ta = mat_trace_args(c.t);
     const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
     hipStream_t st = (hipStream_t)c.stream;
-    with_flag(c.t.ns == 8, [&](auto ns8) {
-        hipLaunchKernelGGL((render_paths_mat_kernel<ns8 ? kScene8 : kSceneTiles>), dim3((unsigned)blocks), dim3(kBlock), 0, st, c.rays, c.spheres,
+    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
+        hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr)>), dim3((unsigned)blocks), dim3(kBlock), 0, st, c.rays, c.spheres,
                            c.materials, c.colors, c.n, c.b, c.c, ta);
-    });
+    }); });
 }
 
 } // namespace apt

@@ -1,7 +1,8 @@
 // pt_materials.h -- the material kernels (include/render_mi355x.h "per-sphere materials": smallpt's DIFF / SPEC / REFR with emitted
 // radiance), included by materials.hip only.  Same scene forms as the mirror kernels -- the 8-sphere scene with its geometry in SGPRs,
-// any scene through LDS tiles (tile_scan, pt_trace.h, shared with dyn_segment) -- and render_frame_kernel's frame skeleton: the lane
-// mapping, camera and decode come from pt_frame.h, the pairwise-leaf accumulation is written out as in render_frame_kernel (pt_frame.h
+// any scene through LDS tiles (tile_scan, pt_trace.h, shared with dyn_segment), any scene behind the uniform grid (mat_hit_grid: a
+// per-lane walk of the grid's item ranges, grid_walk_cells of pt_trace.h, shared with grid_segment) -- and render_frame_kernel's frame
+// skeleton: the lane mapping, camera and decode come from pt_frame.h, the pairwise-leaf accumulation is written out as in render_frame_kernel (pt_frame.h
 // says why); only the body of one sample differs.  Every fp32 operation is the one the header specifies, in its order
 // (-ffp-contract=off): tests/materials_ref.py restates it and the GPU tests compare bit for bit.
 #pragma once
@@ -155,6 +156,76 @@ __device__ __forceinline__ void mat_hit_tiles(const float *__restrict__ sph, flo
     });
 }
 
+// Any scene behind the uniform grid (apt_render_params.accel with APT_FLAG_GRID_SLOTS): the always-tested list, then a per-lane 3D-DDA over
+// the cells' item ranges (cells / items / item_geom: the nested walk's tables, pt_core.h GridHeader), with THIS renderer's root selection
+// -- intersect_pre / intersect_post, IEEE sqrtf(), no root keys -- so every candidate's t is the tile form's, bit for bit.  The walk is
+// grid_segment's own (grid_walk_cells, pt_trace.h: both call it with their candidate test) with its exactness argument and safety rules:
+// a sphere's box was inflated by `margin` when it was binned, the walk ends only once tmin lies clearly before the exit of the current
+// cell (or the ray leaves the grid), and lanes whose |d|^2 is not within 1e-3 of 1, or not finite, test every sphere from the grid's
+// geom table.  It only drops spheres that cannot be hit, so the hit -- and the image -- is the tile form's.  Two things differ from the
+// mirror kernels' candidates:
+//   arg-min  candidates do not come in ascending sphere order: t < tmin || (t == tmin && k < idx), which equals the tile form's strict
+//            '<' over ascending indices; idx starts at -1 (no hit: the path ends).
+//   skip     the sphere whose INDEX is the path's skip sphere is no candidate, in the list and in the cells alike (never decided by
+//            geometry: two spheres may share a record).  A cell candidate's index is one more dependent load, so it is fetched only when
+//            its root could win or tie (t <= tmin); the always-tested list carries its indices with the geometry.
+// No barriers: every lane walks on its own, lanes whose path has ended only take part in the wave-uniform list.  The header is the
+// caller's (load_grid_header: scalar loads, once per kernel); the caller has checked that the grid is this scene's.
+__device__ __forceinline__ void mat_hit_grid(const GridHeader &h, const uint32_t *__restrict__ grid, const MatPath &s, float eps,
+                                             float &tmin, int &idx, uint32_t &n_cells, uint32_t &n_tests) {
+    const uint32_t *large = grid + h.off_large, *cells = grid + h.off_cells, *items = grid + h.off_items;
+    const float4 *geom = reinterpret_cast<const float4 *>(grid + h.off_geom);
+    const float4 *item_geom = reinterpret_cast<const float4 *>(grid + h.off_item_geom);
+    float best = kMissT;
+    int bi = -1;
+    // a sphere of known index: the always-tested list (walls: hit by every ray, so no `disc >= 0` skip) and the every-sphere fallback
+    auto test = [&](const float4 g, uint32_t k) __attribute__((always_inline)) {
+        ++n_tests;
+        const float t = intersect_post(intersect_pre(g.x, g.y, g.z, g.w, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz), eps);
+        if ((int)k != s.skip && (t < best || (t == best && (int)k < bi))) { best = t; bi = (int)k; }
+    };
+    // a candidate of the walk, identified by its position in the item list
+    auto test_item = [&](const float4 g, uint32_t i) __attribute__((always_inline)) {
+        const HitPre hp = intersect_pre(g.x, g.y, g.z, g.w, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz);
+        if (hp.disc >= 0.0f) {                       // a negative or NaN discriminant gives kMissT, which never wins
+            const float t = intersect_post(hp, eps);
+            if (t <= best) {
+                const int k = (int)items[i];
+                if (k != s.skip && (t < best || k < bi)) { best = t; bi = k; }
+            }
+        }
+    };
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (h.off_cellslot) {
+        // The list from its pair slots by explicit SCALAR loads, as grid_segment reads it (wave-uniform data the compiler would fetch
+        // with vector loads and a wait each): two spheres and their indices per pair of loads; an odd list ends with a pad.
+        typedef float f32x8 __attribute__((ext_vector_type(8)));
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const float *sg = reinterpret_cast<const float *>(grid + h.off_slots);
+        const uint32_t *si = grid + h.off_slot_ids;
+        for (uint32_t j = 0; j < h.slot_base; ++j) {
+            f32x8 g8;
+            u32x2 id2;
+            asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(g8), "=&s"(id2) : "s"(sg + 8 * j), "s"(si + 2 * j) : "memory");
+            test(make_float4(g8[0], g8[2], g8[4], g8[6]), id2[0]);
+            if (id2[1] != kGridNoSphere) test(make_float4(g8[1], g8[3], g8[5], g8[7]), id2[1]);
+        }
+    } else
+#endif
+        for (uint32_t i = 0; i < h.nlarge; ++i) { const uint32_t k = large[i]; test(geom[k], k); }   // wave-uniform
+    float dd = s.dx * s.dx;
+    dd = dd + s.dy * s.dy;
+    dd = dd + s.dz * s.dz;
+    const bool unit = fabsf(dd - 1.0f) <= 1e-3f;     // false for NaN / inf
+    if (s.live && !unit) {
+        for (uint32_t k = 0; k < h.num_spheres; ++k) test(geom[k], k);   // every sphere (the list's again: same t, no change)
+    } else if (s.live) {
+        grid_walk_cells(h, cells, item_geom, s.ox, s.oy, s.oz, s.dx, s.dy, s.dz, n_cells, n_tests, test_item, [&]() { return best; });
+    }
+    tmin = best;
+    idx = bi;
+}
+
 // What the 8-sphere form keeps per workgroup: geometry in SGPRs (Scene8), geometry / albedo / emission in LDS, and the 8 material codes
 // in ONE SGPR word (4 bits each, saturated at 15: every code above 2 is bad).
 struct MatScene8 {
@@ -178,12 +249,13 @@ __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ s
 }
 
 // One path, `depth` segments (fewer when every path of the wave -- of the workgroup for the tile form -- has ended).  -> segments traced.
+// gh: the grid's header (kSceneGrid only; not read by the other forms).
 template <int SC>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
-                                              float4 *tile, MatPath &s, const TraceArgs &ta, uint64_t path) {
+                                              const GridHeader &gh, float4 *tile, MatPath &s, const TraceArgs &ta, uint64_t path) {
     const uint64_t mkey = mat_path_key(ta.seed, path);
     const uint64_t rr_key = ta.rr_start ? rr_path_key(ta.seed, path) : 0;
-    uint32_t traced = 0;
+    uint32_t traced = 0, n_cells = 0, n_tests = 0;           // the last two: walk statistics of the grid form
     for (uint32_t d = 0; d < ta.depth; ++d) {
         float tmin;
         int k;
@@ -197,8 +269,13 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
             geo = m8.tab[g]; alb = m8.tab[8 + g]; em = m8.tab[16 + g];
             code = (m8.codes >> (4 * g)) & 15u;
         } else {
-            if (__syncthreads_and(!s.live)) break;
-            mat_hit_tiles(sph, tile, s, ta.ns, ta.eps, tmin, k);
+            if (SC == kSceneGrid) {
+                if (__all(!s.live)) break;
+                mat_hit_grid(gh, ta.grid, s, ta.eps, tmin, k, n_cells, n_tests);
+            } else {
+                if (__syncthreads_and(!s.live)) break;
+                mat_hit_tiles(sph, tile, s, ta.ns, ta.eps, tmin, k);
+            }
             const size_t ns = ta.ns, g = k < 0 ? 0 : (size_t)k;
             geo = make_float4(sph[ns + g], sph[2 * ns + g], sph[3 * ns + g], 0.0f);
             alb = make_float4(sph[7 * ns + g], sph[8 * ns + g], sph[9 * ns + g], 0.0f);
@@ -220,7 +297,20 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
             s.tx = t.rxy.x; s.ty = t.rxy.y; s.tz = t.rz;
         }
     }
+    if (SC == kSceneGrid) grid_stats(ta, n_cells, n_tests);
     return traced;
+}
+
+// The grid form's header, once per kernel.  A grid that does not keep the caller's promise (APT_FLAG_GRID_SLOTS: built for this scene)
+// is not walked: -> false, the kernel writes nothing and says APT_DEV_GRID_MISMATCH (the mirror kernels' rule, pt_queue.h).  Uniform
+// over the whole launch, so every thread of a workgroup returns together.
+template <int SC>
+__device__ __forceinline__ bool mat_grid_header(const TraceArgs &ta, GridHeader &gh) {
+    if (SC != kSceneGrid) return true;
+    gh = load_grid_header(ta.grid);
+    if (gh.magic == kGridMagic && gh.num_spheres == ta.ns) return true;
+    report_status(ta, APT_DEV_GRID_MISMATCH);
+    return false;
 }
 
 __device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, float oz, float dx, float dy, float dz) {
@@ -238,6 +328,8 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
                                                                   uint64_t n_total, uint64_t begin, uint64_t count, TraceArgs ta) {
     __shared__ float4 tab[kMatTab];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
+    GridHeader gh;
+    if (!mat_grid_header<SC>(ta, gh)) return;
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
     const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -245,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
     const uint64_t p = begin + (valid ? local : 0);
     MatPath s;
     mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
-    const uint32_t traced = trace_mat<SC>(sph, mat, m8, tile, s, ta, p);
+    const uint32_t traced = trace_mat<SC>(sph, mat, m8, gh, tile, s, ta, p);
     if (valid) {
         colors[p] = s.lx;
         colors[n_total + p] = s.ly;
@@ -265,6 +357,8 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     extern __shared__ float dyn_lds[];
     float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
     __shared__ Camera cam;
+    GridHeader gh;
+    if (!mat_grid_header<SC>(ta, gh)) return;
     park_camera(cam, fa);
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
@@ -287,7 +381,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        traced += trace_mat<SC>(sph, mat, m8, tile, s, ta, pbase + k);
+        traced += trace_mat<SC>(sph, mat, m8, gh, tile, s, ta, pbase + k);
         return Col{s.lx, s.ly, s.lz};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };

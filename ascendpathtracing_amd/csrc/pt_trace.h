@@ -773,6 +773,90 @@ __device__ __forceinline__ void grid_stats(const TraceArgs &ta, uint32_t n_cells
     }
 }
 
+// The walk itself, for one lane whose direction has unit length: the slab test against the grid's box, the 3D-DDA set-up, and the cells in
+// the order the ray crosses them -- test_item(geometry, item position) for every item of a cell; the walk ends once nearest() (the caller's
+// running minimum) lies clearly before the exit of the current cell, or the ray leaves the grid.  Shared by grid_segment and the material
+// kernels' mat_hit_grid (pt_materials.h), which differ in what a candidate is and how it wins.
+template <class TestItem, class Nearest>
+__device__ __forceinline__ void grid_walk_cells(const GridHeader &h, const uint32_t *cells, const float4 *item_geom, float ox, float oy, float oz,
+                                                float dx, float dy, float dz, uint32_t &n_cells, uint32_t &n_tests, TestItem &&test_item,
+                                                Nearest &&nearest) {
+    const int n0 = (int)h.n[0], n1 = (int)h.n[1], n2 = (int)h.n[2];
+    // slab test against the grid box; all DDA state in scalars (no indexed arrays -> no scratch)
+    float tn = 0.0f, tf = 3.0e38f;
+    bool inbox = true;
+    // One v_rcp_f32 per axis serves the slab test and the DDA increments (1 ulp is irrelevant here: the
+    // walk's exit test carries 1e-3 relative slack plus the binning margin, and a sphere near a cell corner is
+    // listed in every cell its inflated box touches, whichever of two near-simultaneous crossings comes first).
+    auto recip = [&](float dv) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_rcpf(dv);
+#else
+        return 1.0f / dv;
+#endif
+    };
+    const float ix = recip(dx), iy = recip(dy), iz = recip(dz);
+    auto slab = [&](float o, float dv, float inv, float lo, float hi) {
+        if (fabsf(dv) > 1e-20f) {
+            const float t1 = (lo - o) * inv, t2 = (hi - o) * inv;
+            tn = fmaxf(tn, fminf(t1, t2));
+            tf = fminf(tf, fmaxf(t1, t2));
+        } else if (!(o >= lo && o <= hi)) inbox = false;
+    };
+    slab(ox, dx, ix, h.gmin[0], h.gmax[0]);
+    slab(oy, dy, iy, h.gmin[1], h.gmax[1]);
+    slab(oz, dz, iz, h.gmin[2], h.gmax[2]);
+    if (inbox && tn <= tf) {
+        auto axis = [&](float o, float dv, float inv, float lo, float cellw, float invw, int na, int &c, int &step,
+                        float &tmax, float &tdel) {
+            int ci = (int)floorf((o + dv * tn - lo) * invw);
+            ci = ci < 0 ? 0 : (ci >= na ? na - 1 : ci);
+            c = ci;
+            if (dv > 1e-20f) { step = 1; tmax = (lo + (float)(ci + 1) * cellw - o) * inv; tdel = cellw * inv; }
+            else if (dv < -1e-20f) { step = -1; tmax = (lo + (float)ci * cellw - o) * inv; tdel = -cellw * inv; }
+            else { step = 0; tmax = 3.0e38f; tdel = 3.0e38f; }
+        };
+        int c0, c1, c2, st0, st1, st2;
+        float tm0, tm1, tm2, td0, td1, td2;
+        axis(ox, dx, ix, h.gmin[0], h.cell[0], h.inv_cell[0], n0, c0, st0, tm0, td0);
+        axis(oy, dy, iy, h.gmin[1], h.cell[1], h.inv_cell[1], n1, c1, st1, tm1, td1);
+        axis(oz, dz, iz, h.gmin[2], h.cell[2], h.inv_cell[2], n2, c2, st2, tm2, td2);
+        const int max_steps = n0 + n1 + n2 + 3;
+        uint32_t cell = (uint32_t)((c2 * n1 + c1) * n0 + c0);
+        uint32_t b = cells[cell], e = cells[cell + 1];
+        for (int it = 0; it < max_steps; ++it) {
+            ++n_cells;
+            n_tests += e - b;
+            // Which cell comes next depends on the crossing parameters only, not on what the candidates of
+            // this cell turn out to be: fetch its item range now, so that the dependent load is in flight
+            // while they are tested (the fetch is wasted when the walk ends here).
+            const float te = fminf(tm0, fminf(tm1, tm2)); // parameter at which the ray leaves this cell
+            const bool s0 = tm0 <= tm1 && tm0 <= tm2, s1 = !s0 && tm1 <= tm2, s2 = !s0 && !s1;
+            if (s0) { c0 += st0; tm0 += td0; }
+            if (s1) { c1 += st1; tm1 += td1; }
+            if (s2) { c2 += st2; tm2 += td2; }
+            const bool inside = (unsigned)c0 < (unsigned)n0 && (unsigned)c1 < (unsigned)n1 && (unsigned)c2 < (unsigned)n2;
+            uint32_t nb = 0, ne = 0;
+            if (inside) {
+                cell = (uint32_t)((c2 * n1 + c1) * n0 + c0);
+                nb = cells[cell];
+                ne = cells[cell + 1];
+            }
+            uint32_t i = b;
+            for (; i + 2 <= e; i += 2) { // two candidates per step: their loads are in flight together
+                const float4 ga = item_geom[i], gb = item_geom[i + 1];
+                test_item(ga, i);
+                test_item(gb, i + 1);
+            }
+            if (i < e) test_item(item_geom[i], i);
+            if (nearest() < te - (1e-3f * fabsf(te) + h.margin)) break; // nothing nearer can lie ahead
+            if (!inside) break;
+            b = nb;
+            e = ne;
+        }
+    }
+}
+
 struct GridCtx { // what one segment through the grid needs besides the path (wave-uniform)
     const GridHeader *h;
     const float *sph;
@@ -793,7 +877,6 @@ __device__ __forceinline__ void grid_segment(const GridCtx &ctx, PathState &s, b
     const float4 *geom = reinterpret_cast<const float4 *>(grid + h.off_geom);
     const float4 *item_geom = reinterpret_cast<const float4 *>(grid + h.off_item_geom);
     const float *colx = sph + 7 * (size_t)ns, *coly = sph + 8 * (size_t)ns, *colz = sph + 9 * (size_t)ns;
-    const int n0 = (int)h.n[0], n1 = (int)h.n[1], n2 = (int)h.n[2];
     // A grid built for another scene (or a stale / foreign pointer that still carries the magic) would index past
     // the sphere table: such a buffer is not walked at all -- every sphere is tested straight from the [10][Ns]
     // planes instead (same image, brute-force speed).  Wave-uniform.
@@ -872,79 +955,7 @@ __device__ __forceinline__ void grid_segment(const GridCtx &ctx, PathState &s, b
     } else if (!fin && !unit) {
         for (uint32_t k = 0; k < ns; ++k) test(k);
     } else if (!fin) {
-        // slab test against the grid box; all DDA state in scalars (no indexed arrays -> no scratch)
-        float tn = 0.0f, tf = 3.0e38f;
-        bool inbox = true;
-        // One v_rcp_f32 per axis serves the slab test and the DDA increments (1 ulp is irrelevant here: the
-        // walk's exit test carries 1e-3 relative slack plus the binning margin, and a sphere near a cell corner is
-        // listed in every cell its inflated box touches, whichever of two near-simultaneous crossings comes first).
-        auto recip = [&](float dv) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            return __builtin_amdgcn_rcpf(dv);
-#else
-            return 1.0f / dv;
-#endif
-        };
-        const float ix = recip(s.dxy.x), iy = recip(s.dxy.y), iz = recip(s.dz);
-        auto slab = [&](float o, float dv, float inv, float lo, float hi) {
-            if (fabsf(dv) > 1e-20f) {
-                const float t1 = (lo - o) * inv, t2 = (hi - o) * inv;
-                tn = fmaxf(tn, fminf(t1, t2));
-                tf = fminf(tf, fmaxf(t1, t2));
-            } else if (!(o >= lo && o <= hi)) inbox = false;
-        };
-        slab(s.oxy.x, s.dxy.x, ix, h.gmin[0], h.gmax[0]);
-        slab(s.oxy.y, s.dxy.y, iy, h.gmin[1], h.gmax[1]);
-        slab(s.oz, s.dz, iz, h.gmin[2], h.gmax[2]);
-        if (inbox && tn <= tf) {
-            auto axis = [&](float o, float dv, float inv, float lo, float cellw, float invw, int na, int &c, int &step,
-                            float &tmax, float &tdel) {
-                int ci = (int)floorf((o + dv * tn - lo) * invw);
-                ci = ci < 0 ? 0 : (ci >= na ? na - 1 : ci);
-                c = ci;
-                if (dv > 1e-20f) { step = 1; tmax = (lo + (float)(ci + 1) * cellw - o) * inv; tdel = cellw * inv; }
-                else if (dv < -1e-20f) { step = -1; tmax = (lo + (float)ci * cellw - o) * inv; tdel = -cellw * inv; }
-                else { step = 0; tmax = 3.0e38f; tdel = 3.0e38f; }
-            };
-            int c0, c1, c2, st0, st1, st2;
-            float tm0, tm1, tm2, td0, td1, td2;
-            axis(s.oxy.x, s.dxy.x, ix, h.gmin[0], h.cell[0], h.inv_cell[0], n0, c0, st0, tm0, td0);
-            axis(s.oxy.y, s.dxy.y, iy, h.gmin[1], h.cell[1], h.inv_cell[1], n1, c1, st1, tm1, td1);
-            axis(s.oz, s.dz, iz, h.gmin[2], h.cell[2], h.inv_cell[2], n2, c2, st2, tm2, td2);
-            const int max_steps = n0 + n1 + n2 + 3;
-            uint32_t cell = (uint32_t)((c2 * n1 + c1) * n0 + c0);
-            uint32_t b = cells[cell], e = cells[cell + 1];
-            for (int it = 0; it < max_steps; ++it) {
-                ++n_cells;
-                n_tests += e - b;
-                // Which cell comes next depends on the crossing parameters only, not on what the candidates of
-                // this cell turn out to be: fetch its item range now, so that the dependent load is in flight
-                // while they are tested (the fetch is wasted when the walk ends here).
-                const float te = fminf(tm0, fminf(tm1, tm2)); // parameter at which the ray leaves this cell
-                const bool s0 = tm0 <= tm1 && tm0 <= tm2, s1 = !s0 && tm1 <= tm2, s2 = !s0 && !s1;
-                if (s0) { c0 += st0; tm0 += td0; }
-                if (s1) { c1 += st1; tm1 += td1; }
-                if (s2) { c2 += st2; tm2 += td2; }
-                const bool inside = (unsigned)c0 < (unsigned)n0 && (unsigned)c1 < (unsigned)n1 && (unsigned)c2 < (unsigned)n2;
-                uint32_t nb = 0, ne = 0;
-                if (inside) {
-                    cell = (uint32_t)((c2 * n1 + c1) * n0 + c0);
-                    nb = cells[cell];
-                    ne = cells[cell + 1];
-                }
-                uint32_t i = b;
-                for (; i + 2 <= e; i += 2) { // two candidates per step: their loads are in flight together
-                    const float4 ga = item_geom[i], gb = item_geom[i + 1];
-                    test_item(ga, i);
-                    test_item(gb, i + 1);
-                }
-                if (i < e) test_item(item_geom[i], i);
-                if (tmin < te - (1e-3f * fabsf(te) + h.margin)) break; // nothing nearer can lie ahead
-                if (!inside) break;
-                b = nb;
-                e = ne;
-            }
-        }
+        grid_walk_cells(h, cells, item_geom, s.oxy.x, s.oxy.y, s.oz, s.dxy.x, s.dxy.y, s.dz, n_cells, n_tests, test_item, [&]() { return tmin; });
     }
     if (!fin) {
         if (pos != ~0u) idx = (int)items[pos];

@@ -94,6 +94,15 @@ def gen_spheres_materials():
     return sph, mat.view(np.int32)
 
 
+def gen_scene_materials(num_spheres, seed=0):
+    """gen_scene(num_spheres, seed) and the material codes that go with it (apt_gen_scene_materials_host, the same seed): walls and
+    light MAT_DIFF, every small sphere one of the three codes -> (spheres float32 zero-padded [10][Ns], materials int32 [Ns])."""
+    mat = np.zeros(num_spheres, dtype=np.uint32)
+    check(lib().apt_gen_scene_materials_host(ctypes.c_uint32(num_spheres), ctypes.c_uint64(seed),
+                                             mat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "apt_gen_scene_materials_host")
+    return gen_scene(num_spheres, seed), mat.view(np.int32)
+
+
 def gen_scene(num_spheres, seed=0, out_dir=None):
     """Build-defined large scene (BASELINE config 4): six walls, Ns-7 random small spheres,
     light at index Ns-1.  -> zero-padded [10][Ns] table."""

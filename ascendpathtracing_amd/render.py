@@ -241,7 +241,8 @@ def check_device_status(stream=None):
 def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=None):
     """Run-time-parameter form of render_do: rays [6][N], spheres [10][Ns] padded, colors [3][N] (with APT_FLAG_BAND_BUFFERS: planes of
     path_count floats holding only the range).  materials: contiguous int32 CUDA tensor of num_spheres MAT_* codes -> per-path radiance
-    of the material renderer (apt_render_paths_materials); None: the mirror renderer."""
+    of the material renderer (apt_render_paths_materials); None: the mirror renderer.  With materials, params.accel (a built grid)
+    is taken only together with APT_FLAG_GRID_SLOTS (gen_data.grid_flags of that grid): the same colours, found by walking the grid."""
     _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors, materials)
 
 
@@ -254,7 +255,9 @@ def render_paths(params: RenderParams, rays, spheres, stream=None, materials=Non
 
 def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None):
     """Fused ray-generate + trace + decode for pixels [pixel_begin, pixel_begin+pixel_count).
-    Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised.  materials: as render_do_ex (apt_render_frame_materials)."""
+    Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised.  materials: as render_do_ex (apt_render_frame_materials),
+    its rule for params.accel included: a grid needs APT_FLAG_GRID_SLOTS, changes which spheres are tested and never the image; a grid
+    that is not this scene's renders nothing and check_device_status() raises grid-mismatch."""
     return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials)
 
 

@@ -235,8 +235,15 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  * Opt-in: the entries below take a DEVICE uint32_t materials[num_spheres]; every other entry point renders mirrors as before.  Callers
  * detect the feature by its symbols (APT_ABI_VERSION is unchanged).  Arguments are checked before any HIP call: check_params' rules
  * (except that a light_index of -1 is accepted with APT_FLAG_EMISSION, which is not read here), then APT_ERR_ARG for materials == NULL,
- * mode != APT_MODE_KERNEL, accel != 0, and the pixel / path ranges as render_frame / render_do_ex check them.  APT_FLAG_RR applies;
- * APT_FLAG_RETIRE is accepted and changes nothing (paths run to full depth); gain, light_index and APT_FLAG_EMISSION are not read.
+ * mode != APT_MODE_KERNEL, accel != 0 without APT_FLAG_GRID_SLOTS, and the pixel / path ranges as render_frame / render_do_ex check
+ * them.  APT_FLAG_RR applies; APT_FLAG_RETIRE is accepted and changes nothing (paths run to full depth); gain, light_index and
+ * APT_FLAG_EMISSION are not read.
+ * accel: a grid is taken only on the caller's word that it was built for this scene -- APT_FLAG_GRID_SLOTS, what apt_grid_flags() hands
+ * out for a built grid.  Each call is then still ONE launch, which finds every segment's hit by walking the grid.  The grid changes
+ * which spheres are tested, never the result: the image is the one specified below, bit for bit.  A grid that does not keep the
+ * promise (its header's magic or num_spheres is wrong) is not walked: the kernel writes nothing and ORs APT_DEV_GRID_MISMATCH into the
+ * status word.  num_spheres == 8 ignores accel, as the mirror entries do.  When the context has no status word for the device (its
+ * first launch there is inside a stream capture), the call renders the same image without the grid.
  *
  * The arithmetic, operation by operation (fp32, every operation rounded on its own: no FMA; sqrt and division are IEEE; a dot
  * product dot(x, y) is the chain ((0 + x0*y0) + x1*y1) + x2*y2):
@@ -301,6 +308,11 @@ int apt_context_render_paths_materials(apt_context *ctx, const apt_render_params
  * spheres = HOST float[128] ([10][9] planes, zero padded like gen_spheres), materials = HOST uint32_t[9]: walls and light DIFF,
  * mirror SPEC, glass REFR. */
 int apt_gen_spheres_materials_host(float *spheres, uint32_t *materials);
+/* HOST material codes for apt_gen_scene_host's scene of the same num_spheres and seed, materials = HOST uint32_t[num_spheres]: spheres
+ * 0..5 (walls) and num_spheres-1 (light) APT_MAT_DIFF, sphere i in between (splitmix64(seed + i) >> 32) % 3 with the library's
+ * SplitMix64 (x += 0x9E3779B97F4A7C15; x = (x ^ x>>30) * 0xBF58476D1CE4E5B9; x = (x ^ x>>27) * 0x94D049BB133111EB; x ^ x>>31) and
+ * uint64 wrap-around.  num_spheres < 8: APT_ERR_SCENE, like apt_gen_scene_host; materials == NULL: APT_ERR_ARG. */
+int apt_gen_scene_materials_host(uint32_t num_spheres, uint64_t seed, uint32_t *materials);
 
 /* ---- one process, several GPUs (the reference's 8-block split, src/render.cpp:9-10,24-27, across devices) ----
  * The frame's x-major pixel range is cut into num_bands*stripes contiguous stripes; band b renders stripes
