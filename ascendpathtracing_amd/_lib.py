@@ -14,6 +14,7 @@ APT_FLAG_RR = 2
 APT_FLAG_EMISSION = 4
 APT_FLAG_BAND_BUFFERS = 8
 APT_FLAG_GRID_SLOTS = 16
+APT_FLAG_NEE = 32
 APT_ERR_DEVICE = 4
 APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH = 1, 2, 4, 8      # bits of the device status word (apt_context_check)
 APT_DEV_BAD_MATERIAL = 16

@@ -9,6 +9,8 @@ namespace apt {
 
 struct MatTrace {                 // the parts of apt_render_params the material kernels read, after the checks
     uint32_t ns, depth, rr_start; // rr_start: first bounce count of APT_FLAG_RR, 0 = no roulette
+    int32_t light;                // APT_FLAG_NEE: the light sphere, 0 <= light < ns (checked by the entry); not read otherwise
+    bool nee;                     // APT_FLAG_NEE
     float eps;
     uint64_t seed;
     const uint32_t *grid;         // the uniform grid the caller vouches for (accel with APT_FLAG_GRID_SLOTS): the grid form; null: the

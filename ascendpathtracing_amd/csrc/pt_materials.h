@@ -11,6 +11,9 @@
 namespace {
 
 constexpr uint64_t kMatKeySalt = 0x6A09E667F3BCC909ull;
+constexpr uint64_t kNeeKeySalt = 0xBB67AE8584CAA73Bull;   // APT_FLAG_NEE's stream: a third one, next to the bounce's and roulette's
+constexpr int kMatNee = 4;      // APT_FLAG_NEE in the kernels' scene-form template argument (kScene8 / kSceneTiles / kSceneGrid are 0 / 1 / 2)
+static_assert((kMatNee & (kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatNee must be a bit of its own");
 constexpr int kMatTab = 24;     // 8-sphere LDS table: geometry [0, 8), albedo [8, 16), emission [16, 24)
 
 struct MatPath {
@@ -21,6 +24,31 @@ struct MatPath {
     bool live;                  // the path has not ended (miss or bad material code)
 };
 
+// APT_FLAG_NEE ("direct light sampling" in the header).  The light's record, read once per kernel from wave-uniform addresses
+// (scalar loads: it lives in SGPRs), and what a DIFF hit hands to the shadow test that follows the bounce.
+struct MatLight {
+    float cx, cy, cz, r2;
+    float ex, ey, ez;
+    int idx;
+};
+struct MatShadow {
+    float dx, dy, dz;           // l, the sampled direction towards the light
+    float w;                    // cosl * (2 * omc)
+    bool want;                  // cosl > 0: the shadow segment is traced
+};
+template <bool NEE>
+__device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph, const TraceArgs &ta) {
+    MatLight lt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1};
+    if (NEE) {                  // the entry checked 0 <= light < ns
+        const size_t ns = ta.ns, g = (size_t)ta.light;
+        lt.r2 = sph[g]; lt.cx = sph[ns + g]; lt.cy = sph[2 * ns + g]; lt.cz = sph[3 * ns + g];
+        lt.ex = sph[4 * ns + g]; lt.ey = sph[5 * ns + g]; lt.ez = sph[6 * ns + g];
+        lt.idx = ta.light;
+    }
+    return lt;
+}
+
+__device__ __forceinline__ uint64_t nee_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kNeeKeySalt); }
 __device__ __forceinline__ uint64_t mat_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kMatKeySalt); }
 __device__ __forceinline__ void mat_uniforms(uint64_t mkey, uint32_t d, float &u1, float &u2) {
     const uint64_t h = splitmix64(mkey + 0x9E3779B97F4A7C15ull * (uint64_t)(d + 1u));
@@ -45,10 +73,24 @@ __device__ __forceinline__ void mat_sincos(float u1, float &sn, float &cs) {
     cs = (q == 1 || q == 2) ? -b : b;
 }
 
+// Duff et al. 2017: the orthonormal basis (t, b) of the unit vector n, branchless.
+__device__ __forceinline__ void mat_basis(float nx, float ny, float nz, float &tx, float &ty, float &tz, float &bx, float &by, float &bz) {
+    const float sg = copysignf(1.0f, nz);
+    const float a = -1.0f / (sg + nz);
+    const float b = (nx * ny) * a;
+    tx = 1.0f + ((sg * nx) * nx) * a; ty = sg * b; tz = (-sg) * nx;
+    bx = b; by = sg + (ny * ny) * a; bz = -ny;
+}
+
 // The bounce after the hit: light, throughput, new direction, skip.  `code` is APT_MAT_SPEC / DIFF / REFR (checked by the caller).
 // The DIFF and REFR blocks are per-lane branches: exec-masked, skipped by a wave with none of its lanes in them.
+// NEE (APT_FLAG_NEE): the light step leaves out the emission of a light that the previous bounce sampled, and a DIFF hit that may
+// sample (`may`: not the last bounce; wave-uniform) draws the direction of its shadow segment -> sh, sampled.  Without NEE the five
+// last arguments are not read and nothing of this remains in the code.
+template <bool NEE>
 __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 geo, float4 alb, float4 em, uint32_t code,
-                                          uint64_t mkey, uint32_t d) {
+                                          uint64_t mkey, uint32_t d, const MatLight &lt, uint64_t nkey, bool may, bool &sampled,
+                                          MatShadow &sh) {
     float hx = s.dx * tmin, hy = s.dy * tmin, hz = s.dz * tmin;
     hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
     const float nx0 = hx - geo.x, ny0 = hy - geo.y, nz0 = hz - geo.z;
@@ -57,7 +99,8 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
     len2 = len2 + nz0 * nz0;
     const float ln = sqrtf(len2);
     const float nx = nx0 / ln, ny = ny0 / ln, nz = nz0 / ln;
-    s.lx = s.lx + s.tx * em.x; s.ly = s.ly + s.ty * em.y; s.lz = s.lz + s.tz * em.z;
+    if (!(NEE && sampled && k == lt.idx)) { s.lx = s.lx + s.tx * em.x; s.ly = s.ly + s.ty * em.y; s.lz = s.lz + s.tz * em.z; }
+    if (NEE) sampled = false;
     s.tx = s.tx * alb.x; s.ty = s.ty * alb.y; s.tz = s.tz * alb.z;
     float ddn = 0.0f + s.dx * nx;
     ddn = ddn + s.dy * ny;
@@ -72,11 +115,8 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
         float sn, cs;
         mat_sincos(u1, sn, cs);
         const float r = sqrtf(u2);
-        const float sg = copysignf(1.0f, nlz);
-        const float a = -1.0f / (sg + nlz);
-        const float b = (nlx * nly) * a;
-        const float tx = 1.0f + ((sg * nlx) * nlx) * a, ty = sg * b, tz = (-sg) * nlx;
-        const float bx = b, by = sg + (nly * nly) * a, bz = -nly;
+        float tx, ty, tz, bx, by, bz;
+        mat_basis(nlx, nly, nlz, tx, ty, tz, bx, by, bz);
         const float cr = cs * r, sr = sn * r, w = sqrtf(1.0f - u2);
         const float vx = (tx * cr + bx * sr) + nlx * w, vy = (ty * cr + by * sr) + nly * w, vz = (tz * cr + bz * sr) + nlz * w;
         float v2 = 0.0f + vx * vx;
@@ -84,6 +124,40 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
         v2 = v2 + vz * vz;
         const float vl = sqrtf(v2);
         ndx = vx / vl; ndy = vy / vl; ndz = vz / vl;
+        if (NEE && may && k != lt.idx) {
+            const float wx0 = lt.cx - hx, wy0 = lt.cy - hy, wz0 = lt.cz - hz;
+            float d2 = 0.0f + wx0 * wx0;
+            d2 = d2 + wy0 * wy0;
+            d2 = d2 + wz0 * wz0;
+            if (d2 > lt.r2) {                                 // h strictly outside the light (false for NaN)
+                const float x = lt.r2 / d2;
+                const float cmax = sqrtf(1.0f - x);
+                const float omc = x / (1.0f + cmax);          // 1 - cos_max
+                float v1, v2;
+                mat_uniforms(nkey, d, v1, v2);
+                const float cos_a = 1.0f - v1 * omc;
+                const float sin_a = sqrtf(1.0f - cos_a * cos_a);
+                float sp, cp;
+                mat_sincos(v2, sp, cp);
+                const float dl = sqrtf(d2);
+                const float wx = wx0 / dl, wy = wy0 / dl, wz = wz0 / dl;
+                float ax, ay, az, ex, ey, ez;
+                mat_basis(wx, wy, wz, ax, ay, az, ex, ey, ez);
+                const float ca = cp * sin_a, sa = sp * sin_a;
+                const float qx = (ax * ca + ex * sa) + wx * cos_a, qy = (ay * ca + ey * sa) + wy * cos_a, qz = (az * ca + ez * sa) + wz * cos_a;
+                float q2 = 0.0f + qx * qx;
+                q2 = q2 + qy * qy;
+                q2 = q2 + qz * qz;
+                const float ql = sqrtf(q2);
+                sh.dx = qx / ql; sh.dy = qy / ql; sh.dz = qz / ql;
+                float cosl = 0.0f + sh.dx * nlx;
+                cosl = cosl + sh.dy * nly;
+                cosl = cosl + sh.dz * nlz;
+                sh.w = cosl * (2.0f * omc);
+                sh.want = cosl > 0.0f;
+                sampled = true;
+            }
+        }
     } else {
         const float k2 = ddn * 2.0f;                          // SPEC, and the reflection of REFR
         ndx = s.dx - nx * k2; ndy = s.dy - ny * k2; ndz = s.dz - nz * k2;
@@ -249,13 +323,19 @@ __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ s
 }
 
 // One path, `depth` segments (fewer when every path of the wave -- of the workgroup for the tile form -- has ended).  -> segments traced.
-// gh: the grid's header (kSceneGrid only; not read by the other forms).
-template <int SC>
+// gh: the grid's header (kSceneGrid only; not read by the other forms).  lt: the light (NEE only).
+// NEE: after a bounce that drew a shadow segment, that segment goes through the form's own hit routine -- so it sees the scene the bounce
+// ray will see -- whenever some lane of the wave (of the workgroup for the tile form, whose scan has barriers) has one; the light is
+// visible iff the arg-min is the light.  A traced shadow segment counts as a traced segment.
+template <int SC, bool NEE>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
-                                              const GridHeader &gh, float4 *tile, MatPath &s, const TraceArgs &ta, uint64_t path) {
+                                              const GridHeader &gh, const MatLight &lt, float4 *tile, MatPath &s, const TraceArgs &ta,
+                                              uint64_t path) {
     const uint64_t mkey = mat_path_key(ta.seed, path);
     const uint64_t rr_key = ta.rr_start ? rr_path_key(ta.seed, path) : 0;
     uint32_t traced = 0, n_cells = 0, n_tests = 0;           // the last two: walk statistics of the grid form
+    const uint64_t nkey = NEE ? nee_path_key(ta.seed, path) : 0;
+    bool sampled = false;                                    // NEE: the previous bounce sampled the light
     for (uint32_t d = 0; d < ta.depth; ++d) {
         float tmin;
         int k;
@@ -286,9 +366,30 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
         const bool bad = hit && code > (uint32_t)APT_MAT_REFR;
         if (__any(bad)) report_status(ta, APT_DEV_BAD_MATERIAL);
         s.live = hit && !bad;
+        const bool may = NEE && d + 1 < ta.depth;             // no sample at the last bounce: the header says why
+        MatShadow sh;
+        sh.want = false;
         if (s.live) {
-            mat_shade(s, tmin, k, geo, alb, em, code, mkey, d);
+            mat_shade<NEE>(s, tmin, k, geo, alb, em, code, mkey, d, lt, nkey, may, sampled, sh);
             ++traced;
+        }
+        if (may && (SC == kSceneTiles ? __syncthreads_or(sh.want) : __any(sh.want))) {
+            MatPath q;                                        // from h (s.o) along l with this bounce's skip (a DIFF bounce's own)
+            q.ox = s.ox; q.oy = s.oy; q.oz = s.oz;
+            q.dx = sh.want ? sh.dx : s.dx; q.dy = sh.want ? sh.dy : s.dy; q.dz = sh.want ? sh.dz : s.dz;
+            q.skip = s.skip;
+            q.live = sh.want;
+            float ts;
+            int ks;
+            if (SC == kScene8) mat_hit8<true>(m8.sc, q, ta.eps, ts, ks);
+            else if (SC == kSceneGrid) mat_hit_grid(gh, ta.grid, q, ta.eps, ts, ks, n_cells, n_tests);
+            else mat_hit_tiles(sph, tile, q, ta.ns, ta.eps, ts, ks);
+            if (sh.want) {
+                ++traced;
+                if (ks == lt.idx) {
+                    s.lx = s.lx + (s.tx * lt.ex) * sh.w; s.ly = s.ly + (s.ty * lt.ey) * sh.w; s.lz = s.lz + (s.tz * lt.ez) * sh.w;
+                }
+            }
         }
         if (ta.rr_start && d + 1 >= ta.rr_start) {          // wave-uniform; APT_FLAG_RR on T
             PathState t;
@@ -322,22 +423,27 @@ __device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, fl
 }
 
 // ---- kernel: rays from a buffer -----------------------------------------------------------------------------------------------
-template <int SC>
+// SCN: the scene form, with kMatNee set for APT_FLAG_NEE.  The flag travels in the first template argument so that the instantiations
+// a launch without it runs keep the symbol names (and, the NEE code being dead there, the instructions) they had before it existed.
+template <int SCN>
 __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *__restrict__ rays, const float *__restrict__ sph,
                                                                   const uint32_t *__restrict__ mat, float *__restrict__ colors,
                                                                   uint64_t n_total, uint64_t begin, uint64_t count, TraceArgs ta) {
+    constexpr int SC = SCN & ~kMatNee;
+    constexpr bool NEE = (SCN & kMatNee) != 0;
     __shared__ float4 tab[kMatTab];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
+    const MatLight lt = load_mat_light<NEE>(sph, ta);     // here, not after the ray loads: there it reorders the registers of the flag-off kernels
     const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = local < count;
     const uint64_t p = begin + (valid ? local : 0);
     MatPath s;
     mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
-    const uint32_t traced = trace_mat<SC>(sph, mat, m8, gh, tile, s, ta, p);
+    const uint32_t traced = trace_mat<SC, NEE>(sph, mat, m8, gh, lt, tile, s, ta, p);
     if (valid) {
         colors[p] = s.lx;
         colors[n_total + p] = s.ly;
@@ -349,9 +455,12 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
-template <int SC, int GROUP>
+// SCN: the scene form and kMatNee, as for the buffer kernel.
+template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, TraceArgs ta, LeafProg lp) {
+    constexpr int SC = SCN & ~kMatNee;
+    constexpr bool NEE = (SCN & kMatNee) != 0;
     __shared__ float4 tab[kMatTab];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
@@ -363,6 +472,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
     else __syncthreads();
+    const MatLight lt = load_mat_light<NEE>(sph, ta);
 
     const uint32_t lane = threadIdx.x & 63;
     const FrameLane<GROUP> fl = frame_lane<GROUP>(fa);
@@ -381,7 +491,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        traced += trace_mat<SC>(sph, mat, m8, gh, tile, s, ta, pbase + k);
+        traced += trace_mat<SC, NEE>(sph, mat, m8, gh, lt, tile, s, ta, pbase + k);
         return Col{s.lx, s.ly, s.lz};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };

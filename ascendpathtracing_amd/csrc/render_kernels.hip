@@ -63,6 +63,7 @@ int check_materials(const apt_render_params *p, const uint32_t *materials) {
     if (p->mode != APT_MODE_KERNEL) return fail(APT_ERR_ARG, "materials need APT_MODE_KERNEL (O-mode restates test_soa, which has none)%s");
     // a grid only on the caller's word that it is this scene's (apt_grid_flags): the material kernels are one launch, never a second one beside it
     if (p->accel && !(p->flags & APT_FLAG_GRID_SLOTS)) return fail(APT_ERR_ARG, "materials: accel (grid) needs APT_FLAG_GRID_SLOTS (apt_grid_flags of the built grid)%s");
+    if ((p->flags & APT_FLAG_NEE) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_NEE samples the sphere light_index: it needs a light_index >= 0%s");
     return APT_OK;
 }
 
@@ -112,7 +113,7 @@ apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls) {
     // The grid form reports a grid that breaks the caller's promise through the status word and renders nothing.  Without a word (a
     // context's first launch inside a stream capture, a device index beyond the context's table) it would do so silently: the tile
     // form, which needs no promise, renders the same image then.  (ta.grid is null for the 8-sphere scene: make_trace_args.)
-    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced};
+    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, (p->flags & APT_FLAG_NEE) != 0, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced};
 }
 
 // The path range [b, b + c) of a buffer-mode call (path_count 0: to the end of the image) among the image's n_image paths.  With

@@ -103,6 +103,24 @@ def gen_scene_materials(num_spheres, seed=0):
     return gen_scene(num_spheres, seed), mat.view(np.int32)
 
 
+def with_lamp(spheres, num_spheres, light_index, radius=1.5, centre=(50.0, 81.6 - 16.5, 81.6), emission=400.0):
+    """A copy of a [10][Ns] sphere table (gen_spheres, gen_spheres_materials, gen_scene: zero padded or not) whose sphere `light_index`
+    is smallpt's explicit lamp: radius 1.5 at (50, 81.6 - 16.5, 81.6), emission 400 per channel, albedo 0.  A light this small is what
+    APT_FLAG_NEE is for.  r -> r^2 in float64 and one rounding to float32, as gen_spheres stores it.  Build a grid from the returned
+    table, not from the original: the lamp is then binned in cells instead of sitting in the always-tested list.  Pure Python."""
+    ns = int(num_spheres)
+    if not 0 <= int(light_index) < ns:
+        raise AptError("with_lamp: light_index %d is not a sphere of a %d-sphere table" % (light_index, ns))
+    out = np.array(spheres, dtype=np.float32).ravel()
+    if out.size < 10 * ns:
+        raise AptError("with_lamp: the table holds fewer than 10 * num_spheres floats")
+    em = (emission,) * 3 if np.isscalar(emission) else tuple(emission)
+    record = (float(radius) ** 2, *centre, *em, 0.0, 0.0, 0.0)
+    planes = out[:10 * ns].reshape(10, ns)       # a view: writes go to `out`
+    planes[:, int(light_index)] = np.array(record, dtype=np.float64).astype(np.float32)
+    return out
+
+
 def gen_scene(num_spheres, seed=0, out_dir=None):
     """Build-defined large scene (BASELINE config 4): six walls, Ns-7 random small spheres,
     light at index Ns-1.  -> zero-padded [10][Ns] table."""

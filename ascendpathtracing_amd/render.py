@@ -242,7 +242,9 @@ def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=
     """Run-time-parameter form of render_do: rays [6][N], spheres [10][Ns] padded, colors [3][N] (with APT_FLAG_BAND_BUFFERS: planes of
     path_count floats holding only the range).  materials: contiguous int32 CUDA tensor of num_spheres MAT_* codes -> per-path radiance
     of the material renderer (apt_render_paths_materials); None: the mirror renderer.  With materials, params.accel (a built grid)
-    is taken only together with APT_FLAG_GRID_SLOTS (gen_data.grid_flags of that grid): the same colours, found by walking the grid."""
+    is taken only together with APT_FLAG_GRID_SLOTS (gen_data.grid_flags of that grid): the same colours, found by walking the grid.
+    APT_FLAG_NEE in params.flags (materials only): every diffuse hit samples the sphere params.light_index directly -- the same
+    expectation at the same depth, less noise for a small light; it needs light_index >= 0."""
     _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors, materials)
 
 
@@ -257,7 +259,7 @@ def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None,
     """Fused ray-generate + trace + decode for pixels [pixel_begin, pixel_begin+pixel_count).
     Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised.  materials: as render_do_ex (apt_render_frame_materials),
     its rule for params.accel included: a grid needs APT_FLAG_GRID_SLOTS, changes which spheres are tested and never the image; a grid
-    that is not this scene's renders nothing and check_device_status() raises grid-mismatch."""
+    that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE: as render_do_ex."""
     return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials)
 
 

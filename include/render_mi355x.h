@@ -89,6 +89,9 @@ enum {
                            /* launched and the grid's own header decides ON THE DEVICE which one renders; the other returns at once).   */
                            /* A grid that does not keep the promise is not walked: the kernel renders nothing and reports              */
                            /* APT_DEV_GRID_MISMATCH through the device status word.  Same image either way.                            */
+    APT_FLAG_NEE = 32u,    /* EXTENSION, *_materials entries only (every other entry ignores the bit): direct light sampling of  */
+                           /* the sphere light_index at every diffuse hit, "direct light sampling" below.  Needs light_index >= 0  */
+                           /* (APT_ERR_SCENE otherwise).  Unbiased; changes the image by noise only, at any depth.                 */
     APT_FLAG_RR = 2u       /* EXTENSION (not in the reference; BASELINE config 5): Russian */
                            /* roulette.  After shading bounce d (0-based) with d+1 >=       */
                            /* rr_start, a path that is alive with q = max(r,g,b) > 0        */
@@ -236,8 +239,8 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  * detect the feature by its symbols (APT_ABI_VERSION is unchanged).  Arguments are checked before any HIP call: check_params' rules
  * (except that a light_index of -1 is accepted with APT_FLAG_EMISSION, which is not read here), then APT_ERR_ARG for materials == NULL,
  * mode != APT_MODE_KERNEL, accel != 0 without APT_FLAG_GRID_SLOTS, and the pixel / path ranges as render_frame / render_do_ex check
- * them.  APT_FLAG_RR applies; APT_FLAG_RETIRE is accepted and changes nothing (paths run to full depth); gain, light_index and
- * APT_FLAG_EMISSION are not read.
+ * them, then APT_ERR_SCENE for APT_FLAG_NEE with light_index < 0.  APT_FLAG_RR applies; APT_FLAG_RETIRE is accepted and changes nothing
+ * (paths run to full depth); gain and APT_FLAG_EMISSION are not read, light_index is read with APT_FLAG_NEE only.
  * accel: a grid is taken only on the caller's word that it was built for this scene -- APT_FLAG_GRID_SLOTS, what apt_grid_flags() hands
  * out for a built grid.  Each call is then still ONE launch, which finds every segment's hit by walking the grid.  The grid changes
  * which spheres are tested, never the result: the image is the one specified below, bit for bit.  A grid that does not keep the
@@ -276,7 +279,36 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  *             sphere cannot be re-hit going outward, while the near root of a wall of radius 1e5 is fp32 noise of ~5e-3 >> eps):
  *             DIFF, SPEC and the REFR reflection leave outward iff `into`, the REFR refraction iff `!into`; otherwise skip = none.
  *     roulette  APT_FLAG_RR as specified above, on T (the path counts as alive until it ends).
- *   colour  L.  render_frame's decode (numpy's pairwise mean, float64 sum of the 4 sub-pixels, clip, x255 truncation) is unchanged. */
+ *   colour  L.  render_frame's decode (numpy's pairwise mean, float64 sum of the 4 sub-pixels, clip, x255 truncation) is unchanged.
+ *
+ * Direct light sampling (APT_FLAG_NEE; next-event estimation, smallpt's "explicit" form).  Without the flag nothing below applies and
+ * every image is the one specified above.  With it the light is Lt = sphere light_index: centre c and r2 (planes 1..3, 0), emission e
+ * (planes 4..6); one light only.  A path carries a flag `sampled`, false at its start.  The bounce above changes in two places:
+ *     light   L += T * emission(k) is left out when `sampled` and k == light_index: that light was counted by the sample of the
+ *             previous bounce.  Every other emission is added as before: of other spheres, of the light on the camera ray, after a
+ *             SPEC / REFR bounce, and after a DIFF hit that could not sample.  Then sampled = false.
+ *     sample  after the DIFF direction is drawn, when d + 1 < depth, k != light_index and h is strictly outside the light:
+ *             w0 = c - h per component; d2 = dot(w0, w0); the condition is d2 > r2 (false for NaN).  Then
+ *             x = r2 / d2; cmax = sqrt(1 - x); omc = x / (1 + cmax)        (1 - cos_max without the cancellation of 1 - cmax)
+ *             nkey = splitmix64(seed ^ splitmix64(path) ^ 0xBB67AE8584CAA73B); (v1, v2) from nkey exactly as (u1, u2) from mkey
+ *             (a third stream: h = splitmix64(nkey + 0x9E3779B97F4A7C15 * (d + 1)), the same 24-bit split)
+ *             cos_a = 1 - v1 * omc; sin_a = sqrt(1 - cos_a * cos_a); (sin, cos) of 2*pi*v2 by DIFF's polynomial
+ *             dl = sqrt(d2); w = w0 / dl (three divisions); (t, bt) = the Duff basis of w, as DIFF's of nl
+ *             q = (t * (cos * sin_a) + bt * (sin * sin_a)) + w * cos_a per component; l = q / sqrt(dot(q, q)); cosl = dot(l, nl)
+ *             wgt = cosl * (2 * omc)                                        (cos * solid angle / pi; 2 * omc is exact)
+ *             sampled = true, whatever follows.
+ *     shadow  if cosl > 0: a shadow segment from h along l through the hit test above, every sphere but this bounce's skip sphere
+ *             (k if `into`, none otherwise: the DIFF bounce's own).  The light is visible iff the arg-min of that test IS light_index
+ *             (no second epsilon, no "anything before the light" test: the shadow ray sees the scene the bounce ray sees, whatever
+ *             the test does near t = 0).  Visible: L += (T * e) * wgt per channel, T being the throughput after `T *= albedo` and
+ *             before this bounce's roulette.
+ *   There is NO sample at the last bounce (d + 1 == depth): a sample at bounce d stands for the emission the plain renderer gathers at
+ *   hit d + 1, which a path of `depth` segments does not have.  With this rule a frame with the flag has exactly the expectation of
+ *   the same frame without it at the same depth; the flag changes the image by noise only, as APT_FLAG_RR does, and at depth 1 by
+ *   nothing.  A traced shadow segment counts as a traced segment in the trace counter (and its cells / candidates in the grid
+ *   statistics).  Roulette, APT_DEV_BAD_MATERIAL, the grid rules and APT_FLAG_RETIRE are as above.  d2 > r2 is an fp32 decision for
+ *   points near the light's surface: either answer is unbiased because `sampled` follows it.  A light of any material code or albedo
+ *   needs no special case. */
 enum { APT_MAT_SPEC = 0, APT_MAT_DIFF = 1, APT_MAT_REFR = 2 };   /* a zero-filled table = all mirrors */
 #define APT_MAT_S1  0x1.921fb6p+0f
 #define APT_MAT_S3  -0x1.4abbcep-1f
