@@ -18,6 +18,7 @@ APT_FLAG_NEE = 32
 APT_ERR_DEVICE = 4
 APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH = 1, 2, 4, 8      # bits of the device status word (apt_context_check)
 APT_DEV_BAD_MATERIAL = 16
+APT_DEV_LIGHTS_MISMATCH = 32
 MAT_SPEC, MAT_DIFF, MAT_REFR = 0, 1, 2  # material codes of the *_materials entries (include/render_mi355x.h APT_MAT_*)
 
 # every symbol include/render_mi355x.h declares
@@ -32,7 +33,9 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_decode_color_band", "apt_mt19937_checkpoints_window", "apt_gen_rays_mt_device_ex", "apt_build_grid_device", "apt_render_frame_mt",
                "apt_context_check", "apt_check", "apt_context_set_debug", "apt_set_debug", "apt_context_get_debug", "apt_get_debug", "apt_grid_flags",
                "apt_render_frame_materials", "apt_context_render_frame_materials", "apt_render_paths_materials",
-               "apt_context_render_paths_materials", "apt_gen_spheres_materials_host", "apt_gen_scene_materials_host"]
+               "apt_context_render_paths_materials", "apt_gen_spheres_materials_host", "apt_gen_scene_materials_host",
+               "apt_lights_bytes", "apt_build_lights_host", "apt_render_frame_lights", "apt_context_render_frame_lights",
+               "apt_render_paths_lights", "apt_context_render_paths_lights"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
 CXX_RENDER_DO = "_Z9render_dojPvS_PhS0_S0_"
 ABI_VERSION = 3
@@ -94,6 +97,7 @@ def lib():
         h.apt_context_render_do.restype = None
         h.apt_render_do.restype = None
         h.apt_multi_destroy.restype = None
+        h.apt_lights_bytes.restype = ctypes.c_size_t
         getattr(h, CXX_RENDER_DO).restype = None
         if h.apt_abi_version() != ABI_VERSION:
             raise AptError("librender_mi355x.so ABI version mismatch")

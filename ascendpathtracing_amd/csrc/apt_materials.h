@@ -17,6 +17,8 @@ struct MatTrace {                 // the parts of apt_render_params the material
                                   // 8-sphere form (ns == 8) or the tile form.  Never set without a status word to report a broken promise through.
     uint32_t *status;             // the context's device status word, or null
     unsigned long long *traced;   // apt_set_trace_counter block, or null
+    const uint32_t *lights;       // the *_lights entries: the light table (device), which then stands for `light` / `nee`; else null.
+                                  // Never set without a status word: a table that is not this scene's is reported through it.
 };
 
 struct MatFrameCall {             // render_frame with materials: pixels [pixel_begin, pixel_begin + pixel_count), pixel_count > 0

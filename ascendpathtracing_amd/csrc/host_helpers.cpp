@@ -321,6 +321,74 @@ int apt_gen_scene_materials_host(uint32_t num_spheres, uint64_t seed, uint32_t *
     return APT_OK;
 }
 
+// The light table of the *_lights entries (include/render_mi355x.h "several lights" states the construction; pt_core.h the layout).
+size_t apt_lights_bytes(uint32_t num_spheres, uint32_t num_lights) { return apt::lights_words(num_spheres, num_lights) * sizeof(uint32_t); }
+
+int apt_build_lights_host(const float *sph, uint32_t ns, const uint32_t *indices, uint32_t num_indices, void *lights, size_t capacity,
+                          size_t *out_bytes) {
+    apt::clear_error();
+    if (!sph || !lights) return set_error(APT_ERR_ARG, "apt_build_lights_host: spheres/lights must be non-null%s");
+    if (ns == 0) return set_error(APT_ERR_SCENE, "apt_build_lights_host: num_spheres is 0%s");
+    const float *r2 = sph, *ex = sph + 4 * (size_t)ns, *ey = sph + 5 * (size_t)ns, *ez = sph + 6 * (size_t)ns;
+    std::vector<uint32_t> g;
+    if (indices) {
+        g.assign(indices, indices + num_indices);
+    } else {
+        for (uint32_t k = 0; k < ns; ++k)
+            if (ex[k] > 0.0f || ey[k] > 0.0f || ez[k] > 0.0f) g.push_back(k);
+    }
+    if (g.empty()) return set_error(APT_ERR_SCENE, indices ? "apt_build_lights_host: the index list is empty%s" : "apt_build_lights_host: no sphere of the scene emits%s");
+    const size_t n = g.size(), nbits = ((size_t)ns + 31) / 32;
+    std::vector<uint32_t> bits(nbits, 0u);
+    for (uint32_t k : g) {
+        if (k >= ns) return set_error(APT_ERR_SCENE, "apt_build_lights_host: a light index is out of range%s");
+        if (bits[k >> 5] & (1u << (k & 31u))) return set_error(APT_ERR_SCENE, "apt_build_lights_host: a sphere is listed twice%s");
+        bits[k >> 5] |= 1u << (k & 31u);
+    }
+    const size_t bytes = apt_lights_bytes(ns, (uint32_t)n);
+    // power, half of the selection by it and half uniform (the floor), then the cumulative sums on the 24-bit grid of the draw
+    std::vector<double> w(n);
+    double W = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t k = g[i];
+        const double e = ((double)ex[k] + (double)ey[k]) + (double)ez[k];
+        const double p = e * (double)r2[k];
+        w[i] = (p > 0.0 && p < HUGE_VAL) ? p : 0.0;
+        W = W + w[i];
+    }
+    const bool by_power = W > 0.0 && W < HUGE_VAL;
+    const double floor_q = 0.5 / (double)n;
+    std::vector<uint64_t> m(n);
+    double S = 0.0;
+    uint64_t before = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const double a = by_power ? (0.5 * w[i]) / W : floor_q;
+        const double q = a + floor_q;
+        S = S + q;
+        const double scaled = S * 16777216.0;
+        m[i] = i + 1 == n ? (uint64_t)1 << 24 : (uint64_t)std::floor(scaled + 0.5);
+        if (m[i] <= before || m[i] > ((uint64_t)1 << 24)) return set_error(APT_ERR_SCENE, "apt_build_lights_host: a light's selection probability would be below 2^-24 (too many lights)%s");
+        before = m[i];
+    }
+    if (out_bytes) *out_bytes = bytes;
+    if (capacity < bytes) return set_error(APT_ERR_ARG, "apt_build_lights_host: capacity is smaller than apt_lights_bytes(num_spheres, n)%s");
+    std::vector<uint32_t> out(bytes / sizeof(uint32_t), 0u);
+    out[0] = apt::kLightsMagic; out[1] = ns; out[2] = (uint32_t)n; out[3] = (uint32_t)out.size(); out[4] = bits[0];
+    uint32_t *idx = out.data() + apt::kLightsHead;
+    float *cdf = reinterpret_cast<float *>(idx + n), *invp = cdf + n;
+    before = 0;
+    for (size_t i = 0; i < n; ++i) {
+        idx[i] = g[i];
+        cdf[i] = (float)m[i] * 0x1p-24f;                          // exact: m <= 2^24
+        const float P = (float)(m[i] - before) * 0x1p-24f;        // exact
+        invp[i] = 1.0f / P;                                       // RN(1 / P): one IEEE fp32 division
+        before = m[i];
+    }
+    memcpy(invp + n, bits.data(), nbits * sizeof(uint32_t));
+    memcpy(lights, out.data(), bytes);
+    return APT_OK;
+}
+
 // Uniform grid for scenes with many spheres (apt_render_params.accel).  Spheres whose radius exceeds 8x the median
 // radius, or that are not finite (pt_core.h grid_is_large), are "large" (the walls and the light of the generated scenes, r >= 600):
 // they go to an always-tested list; the others are binned by their bounding boxes, inflated by `margin`

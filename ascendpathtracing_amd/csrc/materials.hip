@@ -17,17 +17,21 @@ TraceArgs mat_trace_args(const apt::MatTrace &t) {
     ta.ns = t.ns; ta.depth = t.depth; ta.light = t.light;   // read with APT_FLAG_NEE only
     ta.eps = t.eps; ta.gain = 0.0f; ta.traced = t.traced;
     ta.status = t.status;
-    ta.refill_lanes = 0;
+    // the light table's address: TraceArgs has no field for it and keeps its layout (pt_materials.h mat_lights_ptr); null without a table
+    ta.refill_lanes = (uint32_t)(uintptr_t)t.lights;
     ta.grid = t.grid;
     ta.grid_walk = 0;
-    ta.emission = 0;
+    ta.emission = (uint32_t)((uint64_t)(uintptr_t)t.lights >> 32);
     ta.rr_start = t.rr_start;
     ta.seed = t.seed;
     return ta;
 }
 
-// The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.  APT_FLAG_NEE rides on it (kMatNee).
-constexpr int mat_scene_form(bool ns8, bool grid, bool nee) { return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (nee ? kMatNee : 0); }
+// The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.  APT_FLAG_NEE rides on it (kMatNee), or a
+// light table (kMatLights), which stands for the flag: never both.
+constexpr int mat_scene_form(bool ns8, bool grid, bool nee, bool lights) {
+    return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (lights ? kMatLights : (nee ? kMatNee : 0));
+}
 
 } // namespace
 
@@ -46,10 +50,10 @@ void mat_render_frame(const MatFrameCall &c) {
     const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) {
-        with_flag(c.t.nee, [&](auto nee) {
-            hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee), g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds,
+        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
+            hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt), g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds,
                                st, c.spheres, c.materials, fa, ta, lp);
-        });
+        }); });
     }); }); });
 }
 
@@ -58,10 +62,10 @@ void mat_render_paths(const MatPathsCall &c) {
     const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
-        with_flag(c.t.nee, [&](auto nee) {
-            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee)>), dim3((unsigned)blocks), dim3(kBlock), 0, st, c.rays,
+        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
+            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt)>), dim3((unsigned)blocks), dim3(kBlock), 0, st, c.rays,
                                c.spheres, c.materials, c.colors, c.n, c.b, c.c, ta);
-        });
+        }); });
     }); });
 }
 

@@ -622,6 +622,12 @@ constexpr uint32_t kGridCellOutside = kGridSlotCountMax - 1u;   // cellslot entr
 APT_HD uint32_t grid_bordered_cells(const uint32_t n[3]) { return (n[0] + 2u) * (n[1] + 2u) * (n[2] + 2u); }
 constexpr uint32_t kGridNoSphere = 0xffffffffu;  // id of a pad
 constexpr uint32_t kGridMagic = 0x47524944u; // "GRID"
+// The light table of the *_lights entries (include/render_mi355x.h "several lights"; built by apt_build_lights_host, read by
+// pt_materials.h): words of 4 bytes, a head of kLightsHead words -- magic, num_spheres, n, total words, word 0 of the bitset, zeros --
+// then idx[n] (uint32), cdf[n] (float), invp[n] (float), bits[(num_spheres + 31) / 32] (bit k: sphere k is listed).
+constexpr uint32_t kLightsMagic = 0x4C474854u; // "LGHT"
+constexpr uint32_t kLightsHead = 16;
+APT_HD size_t lights_words(uint32_t num_spheres, uint32_t n) { return (size_t)kLightsHead + 3 * (size_t)n + ((size_t)num_spheres + 31) / 32; }
 constexpr double kGridSpheresPerCell = 0.5;     // default cell size of both builders: sphere centres per cell (APT_GRID_SPHERES_PER_CELL overrides)
 constexpr uint32_t kGridMaxCellsPerAxis = 512;  // round 1 capped the grid at 128 cells per axis
 

@@ -14,6 +14,13 @@ constexpr uint64_t kMatKeySalt = 0x6A09E667F3BCC909ull;
 constexpr uint64_t kNeeKeySalt = 0xBB67AE8584CAA73Bull;   // APT_FLAG_NEE's stream: a third one, next to the bounce's and roulette's
 constexpr int kMatNee = 4;      // APT_FLAG_NEE in the kernels' scene-form template argument (kScene8 / kSceneTiles / kSceneGrid are 0 / 1 / 2)
 static_assert((kMatNee & (kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatNee must be a bit of its own");
+constexpr uint64_t kLightKeySalt = 0x3C6EF372FE94F82Bull; // the light table's selection draw: a fourth stream
+constexpr int kMatLights = 8;   // a light table (the *_lights entries) in the same template argument; never together with kMatNee
+static_assert((kMatLights & (kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatLights must be a bit of its own");
+// How a kernel samples lights (LM, from the two bits above): not at all, the one sphere light_index, one light of a table per bounce.
+constexpr int kLmNone = 0, kLmNee = 1, kLmTable = 2;
+constexpr int mat_light_mode(int scn) { return (scn & kMatLights) ? kLmTable : ((scn & kMatNee) ? kLmNee : kLmNone); }
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights); }
 constexpr int kMatTab = 24;     // 8-sphere LDS table: geometry [0, 8), albedo [8, 16), emission [16, 24)
 
 struct MatPath {
@@ -33,13 +40,14 @@ struct MatLight {
 };
 struct MatShadow {
     float dx, dy, dz;           // l, the sampled direction towards the light
-    float w;                    // cosl * (2 * omc)
+    float w;                    // cosl * (2 * omc), times invp[i] with a light table
     bool want;                  // cosl > 0: the shadow segment is traced
+    int g;                      // light table: the sphere that was sampled (set with `want`)
 };
-template <bool NEE>
+template <int LM>
 __device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph, const TraceArgs &ta) {
     MatLight lt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1};
-    if (NEE) {                  // the entry checked 0 <= light < ns
+    if (LM == kLmNee) {         // the entry checked 0 <= light < ns
         const size_t ns = ta.ns, g = (size_t)ta.light;
         lt.r2 = sph[g]; lt.cx = sph[ns + g]; lt.cy = sph[2 * ns + g]; lt.cz = sph[3 * ns + g];
         lt.ex = sph[4 * ns + g]; lt.ey = sph[5 * ns + g]; lt.ez = sph[6 * ns + g];
@@ -48,6 +56,88 @@ __device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph
     return lt;
 }
 
+// The light table of the *_lights entries ("several lights" in the header; the layout: pt_core.h kLightsMagic).  Its
+// device address has no field of its own in TraceArgs, whose layout every kernel of render_kernels.hip shares: it travels in two words the
+// material kernels never read, refill_lanes (low half) and emission (high half); mat_trace_args (materials.hip) puts it there.
+// The head is read once per kernel by a scalar load and checked before anything else of the table is (mat_lights_header); what the
+// struct keeps is wave-uniform and lives in SGPRs.  cdf / idx / invp are searched and gathered per lane: the lanes of a wave choose
+// different lights.
+struct MatTable {
+    const uint32_t *p;          // the table; its arrays follow the head: idx(), cdf(), invp(), bits()
+    uint32_t n, bits0;          // bits0: spheres 0..31 of the bitset (all of it for the 8-sphere form)
+    __device__ __forceinline__ const uint32_t *idx() const { return p + kLightsHead; }
+    __device__ __forceinline__ const float *cdf() const { return reinterpret_cast<const float *>(p + kLightsHead) + n; }
+    __device__ __forceinline__ const float *invp() const { return reinterpret_cast<const float *>(p + kLightsHead) + 2 * (size_t)n; }
+    __device__ __forceinline__ const uint32_t *bits() const { return p + kLightsHead + 3 * (size_t)n; }
+    const float *sph;           // the sphere planes and, for the 8-sphere form, their LDS copy: where a chosen light's record is gathered
+    const float4 *tab8;
+    uint32_t ns;
+};
+__device__ __forceinline__ const uint32_t *mat_lights_ptr(const TraceArgs &ta) {
+    return reinterpret_cast<const uint32_t *>(((uint64_t)ta.emission << 32) | (uint64_t)ta.refill_lanes);
+}
+// -> false: the table is not one for this scene (magic, num_spheres, 1 <= n <= num_spheres).  It is not read further, the kernel writes
+// nothing and says APT_DEV_LIGHTS_MISMATCH.  Uniform over the launch, like mat_grid_header.
+template <int LM>
+__device__ __forceinline__ bool mat_lights_header(const TraceArgs &ta, const float *__restrict__ sph, const float4 *tab8, MatTable &tb) {
+    if (LM != kLmTable) return true;
+    const uint32_t *p = mat_lights_ptr(ta);
+    uint32_t hw[kLightsHead];
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+    u32x16 w;
+    asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(w) : "s"(p) : "memory");
+#pragma unroll
+    for (int i = 0; i < 16; ++i) hw[i] = w[i];
+#else
+    __builtin_memcpy(hw, p, sizeof hw);
+#endif
+    const uint32_t n = hw[2];
+    if (hw[0] == kLightsMagic && hw[1] == ta.ns && n >= 1u && n <= ta.ns) {
+        tb.p = p; tb.n = n; tb.bits0 = hw[4];
+        tb.sph = sph; tb.tab8 = tab8; tb.ns = ta.ns;
+        return true;
+    }
+    report_status(ta, APT_DEV_LIGHTS_MISMATCH);
+    return false;
+}
+// Is sphere k (0 <= k < num_spheres) listed: one load; the 8-sphere form answers from the SGPR.
+template <int SC>
+__device__ __forceinline__ bool mat_light_listed(const MatTable &tb, int k) {
+    const uint32_t w = SC == kScene8 ? tb.bits0 : tb.bits()[(uint32_t)k >> 5];
+    return (w >> ((uint32_t)k & 31u)) & 1u;
+}
+// The first entry with u < cdf[i]: cdf is strictly increasing and ends with 1 > u, so it exists.  A branchless lower bound, one
+// dependent load per halving (none for one light); the trip count is wave-uniform, the addresses are the lane's own.
+__device__ __forceinline__ uint32_t mat_light_pick(const MatTable &tb, float u) {
+    uint32_t base = 0;
+    for (uint32_t len = tb.n; len > 1u;) {
+        const uint32_t half = len >> 1;
+        if (tb.cdf()[base + half - 1u] <= u) base += half;
+        len -= half;
+    }
+    return base;
+}
+// Centre and r2 of sphere g, per lane (the emission is fetched only once the light turns out visible: mat_light_emission).
+template <int SC>
+__device__ __forceinline__ void mat_light_geometry(const MatTable &tb, int g, MatLight &lt) {
+    if (SC == kScene8) {
+        const float4 c = tb.tab8[g];
+        lt.cx = c.x; lt.cy = c.y; lt.cz = c.z; lt.r2 = c.w;
+    } else {
+        const size_t ns = tb.ns, i = (size_t)g;
+        lt.r2 = tb.sph[i]; lt.cx = tb.sph[ns + i]; lt.cy = tb.sph[2 * ns + i]; lt.cz = tb.sph[3 * ns + i];
+    }
+    lt.idx = g;
+}
+template <int SC>
+__device__ __forceinline__ float4 mat_light_emission(const MatTable &tb, int g) {
+    if (SC == kScene8) return tb.tab8[16 + g];
+    const size_t ns = tb.ns, i = (size_t)g;
+    return make_float4(tb.sph[4 * ns + i], tb.sph[5 * ns + i], tb.sph[6 * ns + i], 0.0f);
+}
+
+__device__ __forceinline__ uint64_t light_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kLightKeySalt); }
 __device__ __forceinline__ uint64_t nee_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kNeeKeySalt); }
 __device__ __forceinline__ uint64_t mat_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kMatKeySalt); }
 __device__ __forceinline__ void mat_uniforms(uint64_t mkey, uint32_t d, float &u1, float &u2) {
@@ -84,13 +174,17 @@ __device__ __forceinline__ void mat_basis(float nx, float ny, float nz, float &t
 
 // The bounce after the hit: light, throughput, new direction, skip.  `code` is APT_MAT_SPEC / DIFF / REFR (checked by the caller).
 // The DIFF and REFR blocks are per-lane branches: exec-masked, skipped by a wave with none of its lanes in them.
-// NEE (APT_FLAG_NEE): the light step leaves out the emission of a light that the previous bounce sampled, and a DIFF hit that may
-// sample (`may`: not the last bounce; wave-uniform) draws the direction of its shadow segment -> sh, sampled.  Without NEE the five
-// last arguments are not read and nothing of this remains in the code.
-template <bool NEE>
+// LM == kLmNee (APT_FLAG_NEE): the light step leaves out the emission of a light that the previous bounce sampled, and a DIFF hit that
+// may sample (`may`: not the last bounce; wave-uniform) draws the direction of its shadow segment -> sh, sampled.
+// LM == kLmTable (a light table): such a hit first picks ONE listed light per lane (the fourth stream, lkey) and samples that one if the
+// predicate S holds for it -- it is not the sphere we stand on and h is strictly outside it --; the bounce counts as sampled either
+// way and remembers its sphere (kprev >= 0 is this mode's `sampled`; -1 otherwise).  The light step then leaves out the emission of a LISTED sphere for which S held at the
+// previous bounce: the same fp32 chain on the same values (s.o is that bounce's h, geo the record the sample gathered).
+// With LM == kLmNone the arguments from `lt` on are not read and nothing of this remains in the code.
+template <int LM, int SC>
 __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 geo, float4 alb, float4 em, uint32_t code,
                                           uint64_t mkey, uint32_t d, const MatLight &lt, uint64_t nkey, bool may, bool &sampled,
-                                          MatShadow &sh) {
+                                          MatShadow &sh, const MatTable &tb, uint64_t lkey, int &kprev) {
     float hx = s.dx * tmin, hy = s.dy * tmin, hz = s.dz * tmin;
     hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
     const float nx0 = hx - geo.x, ny0 = hy - geo.y, nz0 = hz - geo.z;
@@ -99,8 +193,20 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
     len2 = len2 + nz0 * nz0;
     const float ln = sqrtf(len2);
     const float nx = nx0 / ln, ny = ny0 / ln, nz = nz0 / ln;
-    if (!(NEE && sampled && k == lt.idx)) { s.lx = s.lx + s.tx * em.x; s.ly = s.ly + s.ty * em.y; s.lz = s.lz + s.tz * em.z; }
-    if (NEE) sampled = false;
+    bool counted = LM == kLmNee && sampled && k == lt.idx;
+    if (LM == kLmTable && kprev >= 0) {                       // the previous bounce was a sampling bounce (that IS `sampled` here)
+        if (k != kprev && mat_light_listed<SC>(tb, k)) {
+            const float r2k = SC == kScene8 ? geo.w : tb.sph[(size_t)k];
+            const float wx0 = geo.x - s.ox, wy0 = geo.y - s.oy, wz0 = geo.z - s.oz;
+            float d2 = 0.0f + wx0 * wx0;
+            d2 = d2 + wy0 * wy0;
+            d2 = d2 + wz0 * wz0;
+            counted = d2 > r2k;
+        }
+    }
+    if (!counted) { s.lx = s.lx + s.tx * em.x; s.ly = s.ly + s.ty * em.y; s.lz = s.lz + s.tz * em.z; }
+    if (LM == kLmNee) sampled = false;
+    if (LM == kLmTable) kprev = -1;
     s.tx = s.tx * alb.x; s.ty = s.ty * alb.y; s.tz = s.tz * alb.z;
     float ddn = 0.0f + s.dx * nx;
     ddn = ddn + s.dy * ny;
@@ -124,13 +230,24 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
         v2 = v2 + vz * vz;
         const float vl = sqrtf(v2);
         ndx = vx / vl; ndy = vy / vl; ndz = vz / vl;
-        if (NEE && may && k != lt.idx) {
-            const float wx0 = lt.cx - hx, wy0 = lt.cy - hy, wz0 = lt.cz - hz;
+        MatLight chosen;                                      // kLmTable: the lane's light; kLmNee: lt itself
+        const MatLight &cur = LM == kLmTable ? chosen : lt;
+        float invp = 1.0f;
+        if (LM == kLmTable && may) {
+            float u, unused;
+            mat_uniforms(lkey, d, u, unused);
+            const uint32_t i = mat_light_pick(tb, u);
+            invp = tb.invp()[i];
+            mat_light_geometry<SC>(tb, (int)min(tb.idx()[i], tb.ns - 1u), chosen);   // (the clamp: a table is trusted, an address is not)
+            kprev = k;                                        // sampled, whatever follows
+        }
+        if (LM && may && k != cur.idx) {
+            const float wx0 = cur.cx - hx, wy0 = cur.cy - hy, wz0 = cur.cz - hz;
             float d2 = 0.0f + wx0 * wx0;
             d2 = d2 + wy0 * wy0;
             d2 = d2 + wz0 * wz0;
-            if (d2 > lt.r2) {                                 // h strictly outside the light (false for NaN)
-                const float x = lt.r2 / d2;
+            if (d2 > cur.r2) {                                // h strictly outside the light (false for NaN)
+                const float x = cur.r2 / d2;
                 const float cmax = sqrtf(1.0f - x);
                 const float omc = x / (1.0f + cmax);          // 1 - cos_max
                 float v1, v2;
@@ -154,8 +271,9 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
                 cosl = cosl + sh.dy * nly;
                 cosl = cosl + sh.dz * nlz;
                 sh.w = cosl * (2.0f * omc);
+                if (LM == kLmTable) { sh.w = sh.w * invp; sh.g = cur.idx; }
                 sh.want = cosl > 0.0f;
-                sampled = true;
+                if (LM == kLmNee) sampled = true;
             }
         }
     } else {
@@ -323,19 +441,21 @@ __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ s
 }
 
 // One path, `depth` segments (fewer when every path of the wave -- of the workgroup for the tile form -- has ended).  -> segments traced.
-// gh: the grid's header (kSceneGrid only; not read by the other forms).  lt: the light (NEE only).
-// NEE: after a bounce that drew a shadow segment, that segment goes through the form's own hit routine -- so it sees the scene the bounce
+// gh: the grid's header (kSceneGrid only; not read by the other forms).  lt: the light (kLmNee only).  tb: the light table (kLmTable).
+// LM != kLmNone: after a bounce that drew a shadow segment, that segment goes through the form's own hit routine -- so it sees the scene the bounce
 // ray will see -- whenever some lane of the wave (of the workgroup for the tile form, whose scan has barriers) has one; the light is
-// visible iff the arg-min is the light.  A traced shadow segment counts as a traced segment.
-template <int SC, bool NEE>
+// visible iff the arg-min is the light (the lane's own chosen light with a table).  A traced shadow segment counts as a traced segment.
+template <int SC, int LM>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
-                                              const GridHeader &gh, const MatLight &lt, float4 *tile, MatPath &s, const TraceArgs &ta,
-                                              uint64_t path) {
+                                              const GridHeader &gh, const MatLight &lt, const MatTable &tb, float4 *tile, MatPath &s,
+                                              const TraceArgs &ta, uint64_t path) {
     const uint64_t mkey = mat_path_key(ta.seed, path);
     const uint64_t rr_key = ta.rr_start ? rr_path_key(ta.seed, path) : 0;
     uint32_t traced = 0, n_cells = 0, n_tests = 0;           // the last two: walk statistics of the grid form
-    const uint64_t nkey = NEE ? nee_path_key(ta.seed, path) : 0;
-    bool sampled = false;                                    // NEE: the previous bounce sampled the light
+    const uint64_t nkey = LM ? nee_path_key(ta.seed, path) : 0;
+    const uint64_t lkey = LM == kLmTable ? light_path_key(ta.seed, path) : 0;
+    bool sampled = false;                                    // kLmNee: the previous bounce sampled the light
+    int kprev = -1;                                          // kLmTable: the sphere of the previous bounce if it was a sampling bounce, else -1
     for (uint32_t d = 0; d < ta.depth; ++d) {
         float tmin;
         int k;
@@ -366,11 +486,11 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
         const bool bad = hit && code > (uint32_t)APT_MAT_REFR;
         if (__any(bad)) report_status(ta, APT_DEV_BAD_MATERIAL);
         s.live = hit && !bad;
-        const bool may = NEE && d + 1 < ta.depth;             // no sample at the last bounce: the header says why
+        const bool may = LM && d + 1 < ta.depth;              // no sample at the last bounce: the header says why
         MatShadow sh;
         sh.want = false;
         if (s.live) {
-            mat_shade<NEE>(s, tmin, k, geo, alb, em, code, mkey, d, lt, nkey, may, sampled, sh);
+            mat_shade<LM, SC>(s, tmin, k, geo, alb, em, code, mkey, d, lt, nkey, may, sampled, sh, tb, lkey, kprev);
             ++traced;
         }
         if (may && (SC == kSceneTiles ? __syncthreads_or(sh.want) : __any(sh.want))) {
@@ -386,7 +506,12 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
             else mat_hit_tiles(sph, tile, q, ta.ns, ta.eps, ts, ks);
             if (sh.want) {
                 ++traced;
-                if (ks == lt.idx) {
+                if (LM == kLmTable) {
+                    if (ks == sh.g) {
+                        const float4 e = mat_light_emission<SC>(tb, sh.g);
+                        s.lx = s.lx + (s.tx * e.x) * sh.w; s.ly = s.ly + (s.ty * e.y) * sh.w; s.lz = s.lz + (s.tz * e.z) * sh.w;
+                    }
+                } else if (ks == lt.idx) {
                     s.lx = s.lx + (s.tx * lt.ex) * sh.w; s.ly = s.ly + (s.ty * lt.ey) * sh.w; s.lz = s.lz + (s.tz * lt.ez) * sh.w;
                 }
             }
@@ -423,27 +548,30 @@ __device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, fl
 }
 
 // ---- kernel: rays from a buffer -----------------------------------------------------------------------------------------------
-// SCN: the scene form, with kMatNee set for APT_FLAG_NEE.  The flag travels in the first template argument so that the instantiations
-// a launch without it runs keep the symbol names (and, the NEE code being dead there, the instructions) they had before it existed.
+// SCN: the scene form, with kMatNee set for APT_FLAG_NEE or kMatLights for a light table.  Both travel in the first template argument so
+// that the instantiations a launch without them runs keep the symbol names (and, the sampling code being dead there, the instructions)
+// they had before these existed.
 template <int SCN>
 __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *__restrict__ rays, const float *__restrict__ sph,
                                                                   const uint32_t *__restrict__ mat, float *__restrict__ colors,
                                                                   uint64_t n_total, uint64_t begin, uint64_t count, TraceArgs ta) {
-    constexpr int SC = SCN & ~kMatNee;
-    constexpr bool NEE = (SCN & kMatNee) != 0;
+    constexpr int SC = mat_scene_of(SCN);
+    constexpr int LM = mat_light_mode(SCN);
     __shared__ float4 tab[kMatTab];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
+    MatTable tb;
+    if (!mat_lights_header<LM>(ta, sph, tab, tb)) return;
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
-    const MatLight lt = load_mat_light<NEE>(sph, ta);     // here, not after the ray loads: there it reorders the registers of the flag-off kernels
+    const MatLight lt = load_mat_light<LM>(sph, ta);      // here, not after the ray loads: there it reorders the registers of the flag-off kernels
     const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = local < count;
     const uint64_t p = begin + (valid ? local : 0);
     MatPath s;
     mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
-    const uint32_t traced = trace_mat<SC, NEE>(sph, mat, m8, gh, lt, tile, s, ta, p);
+    const uint32_t traced = trace_mat<SC, LM>(sph, mat, m8, gh, lt, tb, tile, s, ta, p);
     if (valid) {
         colors[p] = s.lx;
         colors[n_total + p] = s.ly;
@@ -455,12 +583,12 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
-// SCN: the scene form and kMatNee, as for the buffer kernel.
+// SCN: the scene form and kMatNee / kMatLights, as for the buffer kernel.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, TraceArgs ta, LeafProg lp) {
-    constexpr int SC = SCN & ~kMatNee;
-    constexpr bool NEE = (SCN & kMatNee) != 0;
+    constexpr int SC = mat_scene_of(SCN);
+    constexpr int LM = mat_light_mode(SCN);
     __shared__ float4 tab[kMatTab];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
@@ -468,11 +596,13 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     __shared__ Camera cam;
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
+    MatTable tb;
+    if (!mat_lights_header<LM>(ta, sph, tab, tb)) return;
     park_camera(cam, fa);
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
     else __syncthreads();
-    const MatLight lt = load_mat_light<NEE>(sph, ta);
+    const MatLight lt = load_mat_light<LM>(sph, ta);
 
     const uint32_t lane = threadIdx.x & 63;
     const FrameLane<GROUP> fl = frame_lane<GROUP>(fa);
@@ -491,7 +621,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        traced += trace_mat<SC, NEE>(sph, mat, m8, gh, lt, tile, s, ta, pbase + k);
+        traced += trace_mat<SC, LM>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k);
         return Col{s.lx, s.ly, s.lz};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };

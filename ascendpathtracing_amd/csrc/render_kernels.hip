@@ -58,12 +58,33 @@ int check_params(const apt_render_params *p, bool materials = false) {
 }
 
 // What the material entries refuse on top of check_params (after it, before any pointer or range check of the entry itself).
-int check_materials(const apt_render_params *p, const uint32_t *materials) {
+// lights: a *_lights entry, which reads neither APT_FLAG_NEE nor light_index.
+int check_materials(const apt_render_params *p, const uint32_t *materials, bool lights = false) {
     if (!materials) return fail(APT_ERR_ARG, "materials must be non-null%s");
     if (p->mode != APT_MODE_KERNEL) return fail(APT_ERR_ARG, "materials need APT_MODE_KERNEL (O-mode restates test_soa, which has none)%s");
     // a grid only on the caller's word that it is this scene's (apt_grid_flags): the material kernels are one launch, never a second one beside it
     if (p->accel && !(p->flags & APT_FLAG_GRID_SLOTS)) return fail(APT_ERR_ARG, "materials: accel (grid) needs APT_FLAG_GRID_SLOTS (apt_grid_flags of the built grid)%s");
-    if ((p->flags & APT_FLAG_NEE) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_NEE samples the sphere light_index: it needs a light_index >= 0%s");
+    if (!lights && (p->flags & APT_FLAG_NEE) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_NEE samples the sphere light_index: it needs a light_index >= 0%s");
+    return APT_OK;
+}
+
+// A material entry's own arguments: which entry it is, and what it was given.  lights: with_lights entries only (device light table).
+struct MatArgs {
+    const uint32_t *materials = nullptr;
+    bool with_lights = false;
+    const void *lights = nullptr;
+};
+// check_materials, then what the *_lights entries refuse on top of it.
+int check_mat_args(const apt_render_params *p, const MatArgs &m) {
+    int rc = check_materials(p, m.materials, m.with_lights);
+    if (rc) return rc;
+    if (m.with_lights && !m.lights) return fail(APT_ERR_ARG, "lights must be non-null (a device light table: apt_build_lights_host)%s");
+    return APT_OK;
+}
+// A light table names spheres by index, and the kernel that finds it is not this scene's can only say so through the status word.
+// Without one the call is refused here rather than launched on trust.
+int check_lights_status(const MatArgs &m, const uint32_t *status) {
+    if (m.with_lights && !status) return fail(APT_ERR_DEVICE, "lights: the context has no device status word here (its first launch on this device is inside a stream capture, or the device index is beyond its table)%s");
     return APT_OK;
 }
 
@@ -108,12 +129,14 @@ TraceArgs make_trace_args(const apt_render_params *p, const Launch &ls) {
     return ta;
 }
 
-apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls) {
+apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls, const MatArgs &m) {
     const TraceArgs ta = make_trace_args(p, ls);
     // The grid form reports a grid that breaks the caller's promise through the status word and renders nothing.  Without a word (a
     // context's first launch inside a stream capture, a device index beyond the context's table) it would do so silently: the tile
     // form, which needs no promise, renders the same image then.  (ta.grid is null for the 8-sphere scene: make_trace_args.)
-    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, (p->flags & APT_FLAG_NEE) != 0, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced};
+    // A light table stands for APT_FLAG_NEE and light_index, which its entries do not read.
+    const uint32_t *lights = m.with_lights ? static_cast<const uint32_t *>(m.lights) : nullptr;
+    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, !lights && (p->flags & APT_FLAG_NEE) != 0, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced, lights};
 }
 
 // The path range [b, b + c) of a buffer-mode call (path_count 0: to the end of the image) among the image's n_image paths.  With
@@ -154,10 +177,10 @@ constexpr uint64_t kTwoPathBufferMin = 1ull << 20;
 // ---- the two render launches, on an explicit snapshot of a context's values -----------------
 // mat: a material entry (include/render_mi355x.h "per-sphere materials"; a null `materials` is refused).
 int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, const float *rays,
-                    const float *spheres, float *colors, bool mat = false, const uint32_t *materials = nullptr) {
+                    const float *spheres, float *colors, bool mat = false, const MatArgs &ma = MatArgs()) {
     int rc = check_params(p, mat);
     if (rc) return rc;
-    if (mat && (rc = check_materials(p, materials))) return rc;
+    if (mat && (rc = check_mat_args(p, ma))) return rc;
     if (!rays || !spheres || !colors) return fail(APT_ERR_ARG, "rays/spheres/colors must be non-null%s");
     PathRange r;
     if ((rc = path_range(p, r)) || r.c == 0) return rc;
@@ -165,7 +188,8 @@ int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, 
     const uint64_t blocks = (c + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
     if (mat) {   // per-sphere materials: materials.hip
-        apt::mat_render_paths(apt::MatPathsCall{make_mat_trace(p, ls), r.base(rays), spheres, materials, r.base(colors), n, b, c, stream});
+        if ((rc = check_lights_status(ma, ls.status))) return rc;
+        apt::mat_render_paths(apt::MatPathsCall{make_mat_trace(p, ls, ma), r.base(rays), spheres, ma.materials, r.base(colors), n, b, c, stream});
         return launched();
     }
     hipStream_t st = (hipStream_t)stream;
@@ -214,10 +238,10 @@ bool queue_launch_shape(const apt::Debug &dbg, const LeafProg &lp, bool rr, bool
 
 int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, const float *spheres,
                     uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8, bool mat = false,
-                    const uint32_t *materials = nullptr) {
+                    const MatArgs &ma = MatArgs()) {
     int rc = check_params(p, mat);
     if (rc) return rc;
-    if (mat && (rc = check_materials(p, materials))) return rc;
+    if (mat && (rc = check_mat_args(p, ma))) return rc;
     if (!spheres || !fb) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");
     const uint64_t npix = (uint64_t)p->width * p->height;
     if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
@@ -230,7 +254,8 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
     const apt::Debug &dbg = ls.cv.debug;
     if (mat) {   // per-sphere materials: materials.hip
-        apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls), spheres, materials, p->width, p->height, p->samples, pixel_begin,
+        if ((rc = check_lights_status(ma, ls.status))) return rc;
+        apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
                                                 pixel_count, fb, fb_u8, stream});
         return launched();
     }
@@ -303,6 +328,27 @@ void split_range(uint64_t total, uint64_t r, uint64_t parts, uint64_t &begin, ui
     begin = r * base + (r < extra ? r : extra);
     count = base + (r < extra ? 1 : 0);
 }
+
+// ---- the material entries: their checks run before the context's launch state is taken (the one place the other entries touch HIP
+// before their checks); do_render_* repeat them and check the rest.
+int mat_frame_entry(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres, const MatArgs &ma,
+                    uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+    clear_error();
+    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
+    int rc = check_params(p, true);
+    if (rc || (rc = check_mat_args(p, ma))) return rc;
+    return do_render_frame(launch_state(*ctx, stream), p, stream, spheres, pixel_begin, pixel_count, fb, fb_u8, true, ma);
+}
+int mat_paths_entry(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres, const MatArgs &ma,
+                    float *colors) {
+    clear_error();
+    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
+    int rc = check_params(p, true);
+    if (rc || (rc = check_mat_args(p, ma))) return rc;
+    return do_render_paths(launch_state(*ctx, stream), p, stream, rays, spheres, colors, true, ma);
+}
+MatArgs mat_args(const uint32_t *materials) { MatArgs m; m.materials = materials; return m; }
+MatArgs mat_args_lights(const uint32_t *materials, const void *lights) { MatArgs m; m.materials = materials; m.with_lights = true; m.lights = lights; return m; }
 
 } // namespace
 
@@ -386,7 +432,8 @@ int apt_context_check(apt_context *ctx, void *stream) {
     if (bits & APT_DEV_LDS_BASE) what += " lds-base";
     if (bits & APT_DEV_GRID_MISMATCH) what += " grid-mismatch";
     if (bits & APT_DEV_BAD_MATERIAL) what += " bad-material";
-    if (bits & ~(uint32_t)(APT_DEV_QUEUE_GUARD | APT_DEV_GRID_TURNS | APT_DEV_LDS_BASE | APT_DEV_GRID_MISMATCH | APT_DEV_BAD_MATERIAL)) what += " unknown-bits";
+    if (bits & APT_DEV_LIGHTS_MISMATCH) what += " lights-mismatch";
+    if (bits & ~(uint32_t)(APT_DEV_QUEUE_GUARD | APT_DEV_GRID_TURNS | APT_DEV_LDS_BASE | APT_DEV_GRID_MISMATCH | APT_DEV_BAD_MATERIAL | APT_DEV_LIGHTS_MISMATCH)) what += " unknown-bits";
     return fail(APT_ERR_DEVICE, "a kernel reported a failure through the device status word:%s (the frame it wrote is incomplete)", what.c_str());
 }
 
@@ -442,20 +489,12 @@ int apt_context_render_frame(apt_context *ctx, const apt_render_params *p, void 
 // entries touch HIP before their checks); do_render_* repeat them and check the rest.
 int apt_context_render_frame_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
                                        const uint32_t *materials, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
-    clear_error();
-    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
-    int rc = check_params(p, true);
-    if (rc || (rc = check_materials(p, materials))) return rc;
-    return do_render_frame(launch_state(*ctx, stream), p, stream, spheres, pixel_begin, pixel_count, fb, fb_u8, true, materials);
+    return mat_frame_entry(ctx, p, stream, spheres, mat_args(materials), pixel_begin, pixel_count, fb, fb_u8);
 }
 
 int apt_context_render_paths_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays,
                                        const float *spheres, const uint32_t *materials, float *colors) {
-    clear_error();
-    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
-    int rc = check_params(p, true);
-    if (rc || (rc = check_materials(p, materials))) return rc;
-    return do_render_paths(launch_state(*ctx, stream), p, stream, rays, spheres, colors, true, materials);
+    return mat_paths_entry(ctx, p, stream, rays, spheres, mat_args(materials), colors);
 }
 
 int apt_render_frame_materials(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials,
@@ -466,6 +505,28 @@ int apt_render_frame_materials(const apt_render_params *p, void *stream, const f
 int apt_render_paths_materials(const apt_render_params *p, void *stream, const float *rays, const float *spheres,
                                const uint32_t *materials, float *colors) {
     return apt_context_render_paths_materials(&apt::default_context(), p, stream, rays, spheres, materials, colors);
+}
+
+// The material entries with a light table ("several lights" in the header): the same checks, then lights == NULL.
+int apt_context_render_frame_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                    const uint32_t *materials, const void *lights, uint64_t pixel_begin, uint64_t pixel_count, float *fb,
+                                    uint8_t *fb_u8) {
+    return mat_frame_entry(ctx, p, stream, spheres, mat_args_lights(materials, lights), pixel_begin, pixel_count, fb, fb_u8);
+}
+
+int apt_context_render_paths_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres,
+                                    const uint32_t *materials, const void *lights, float *colors) {
+    return mat_paths_entry(ctx, p, stream, rays, spheres, mat_args_lights(materials, lights), colors);
+}
+
+int apt_render_frame_lights(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials, const void *lights,
+                            uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+    return apt_context_render_frame_lights(&apt::default_context(), p, stream, spheres, materials, lights, pixel_begin, pixel_count, fb, fb_u8);
+}
+
+int apt_render_paths_lights(const apt_render_params *p, void *stream, const float *rays, const float *spheres, const uint32_t *materials,
+                            const void *lights, float *colors) {
+    return apt_context_render_paths_lights(&apt::default_context(), p, stream, rays, spheres, materials, lights, colors);
 }
 
 // ---- the context-free forms: the process-wide default context -----------------------------------------

@@ -121,6 +121,57 @@ def with_lamp(spheres, num_spheres, light_index, radius=1.5, centre=(50.0, 81.6 
     return out
 
 
+def with_lamps(spheres, num_spheres, indices, radius=1.5, centres=None, emission=400.0):
+    """with_lamp for several spheres at once: a copy of the table whose spheres `indices` are lamps.  radius / emission: one value for
+    all, or a list with one per lamp (each emission a number or an (r, g, b) triple, so colours may differ per lamp); centres: one (x, y, z)
+    per lamp, or None = every sphere keeps the centre it has.  As with with_lamp, build grids and light tables from the returned
+    table.  Pure Python."""
+    idx = [int(i) for i in indices]
+    n = len(idx)
+    if len(set(idx)) != n:
+        raise AptError("with_lamps: a sphere is listed twice")
+    per = lambda v: [v] * n if np.isscalar(v) else list(v)
+    radii, ems = per(radius), per(emission)
+    if len(radii) != n or len(ems) != n or (centres is not None and len(centres) != n):
+        raise AptError("with_lamps: radius / centres / emission must be one value or one per lamp")
+    out = np.array(spheres, dtype=np.float32).ravel()
+    for j, k in enumerate(idx):
+        if not 0 <= k < int(num_spheres):
+            raise AptError("with_lamps: index %d is not a sphere of a %d-sphere table" % (k, num_spheres))
+        here = out[:10 * int(num_spheres)].reshape(10, int(num_spheres))[1:4, k]
+        centre = tuple(float(c) for c in here) if centres is None else tuple(centres[j])
+        out = with_lamp(out, num_spheres, k, radius=radii[j], centre=centre, emission=ems[j])
+    return out
+
+
+def lights_bytes(num_spheres, num_lights):
+    """apt_lights_bytes: the size of a light table of num_lights lights for a scene of num_spheres spheres."""
+    return int(lib().apt_lights_bytes(ctypes.c_uint32(num_spheres), ctypes.c_uint32(num_lights)))
+
+
+def build_lights(spheres, num_spheres, indices=None):
+    """The light table of the lights= argument of render_frame / render_do_ex (apt_build_lights_host) -> uint32 numpy buffer to copy to
+    the device (torch.from_numpy(t.view(np.int32)).cuda()).  indices: the spheres to list, in this order; None: every sphere with an
+    emission channel > 0.  Selection probabilities: half by emitted power, half uniform, exact on the 24-bit grid of the draw."""
+    spheres = np.ascontiguousarray(spheres, dtype=np.float32).ravel()
+    if spheres.size < 10 * int(num_spheres):
+        raise AptError("build_lights: the table holds fewer than 10 * num_spheres floats")
+    if indices is None:
+        ptr, n, bound = None, 0, int(num_spheres)
+    else:
+        ind = np.ascontiguousarray(indices, dtype=np.int64).ravel()
+        if ind.size and (ind.min() < 0 or ind.max() > 0xFFFFFFFF):
+            raise AptError("build_lights: a light index is out of range")
+        ind = ind.astype(np.uint32)
+        ptr, n, bound = ind.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(ind.size), int(ind.size)
+    buf = np.zeros(lights_bytes(num_spheres, bound) // 4, dtype=np.uint32)
+    nbytes = ctypes.c_size_t(0)
+    check(lib().apt_build_lights_host(_fptr(spheres), ctypes.c_uint32(num_spheres), ptr, ctypes.c_uint32(n),
+                                      buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes), ctypes.byref(nbytes)),
+          "apt_build_lights_host")
+    return buf[:nbytes.value // 4].copy()
+
+
 def gen_scene(num_spheres, seed=0, out_dir=None):
     """Build-defined large scene (BASELINE config 4): six walls, Ns-7 random small spheres,
     light at index Ns-1.  -> zero-padded [10][Ns] table."""

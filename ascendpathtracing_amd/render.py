@@ -40,6 +40,24 @@ def _dev_materials(t, num_spheres):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _dev_lights(t):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= 16):
+        raise _lib.AptError("lights must be a contiguous int32 tensor on the GPU holding a light table (gen_data.build_lights)")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _material_args(entry, params, materials, lights):
+    """-> (the entry to call, its extra arguments after `spheres`): the entry itself, its *_materials form, or its *_lights form."""
+    if lights is not None and materials is None:
+        raise _lib.AptError("lights needs materials: the light table belongs to the material renderer")
+    if materials is None:
+        return entry, ()
+    mat = (_dev_materials(materials, params.num_spheres),)
+    if lights is None:
+        return _MATERIALS_ENTRY[entry], mat
+    return _MATERIALS_ENTRY[entry].replace("_materials", "_lights"), mat + (_dev_lights(lights),)
+
+
 def sphere_floats(num_spheres):
     """Length of the zero-padded [10][Ns] table (512-byte multiple, gen_data.py:120-127)."""
     return (num_spheres * 10 + 127) // 128 * 128
@@ -48,12 +66,11 @@ def sphere_floats(num_spheres):
 # The bodies of render_do_ex / render_frame, shared by the default-context functions and Context's methods: `entry` is the C entry
 # (also the name errors are reported under), `handle` its leading context argument, if any.
 # materials (int32 tensor of num_spheres codes, MAT_*): the entry's *_materials form; None: the entry itself, untouched.
-def _render_do_ex(entry, handle, params, stream, rays, spheres, colors, materials=None):
+# lights (int32 tensor, a light table: gen_data.build_lights), with materials only: the entry's *_lights form.
+def _render_do_ex(entry, handle, params, stream, rays, spheres, colors, materials=None, lights=None):
     require_gpu()
     n = _buffer_paths(params)
-    mat = ()
-    if materials is not None:
-        entry, mat = _MATERIALS_ENTRY[entry], (_dev_materials(materials, params.num_spheres),)
+    entry, mat = _material_args(entry, params, materials, lights)
     check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
                                 _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat,
                                 _dev_f32(colors, "colors", 3 * n)), entry)
@@ -63,7 +80,7 @@ _MATERIALS_ENTRY = {"render_do_ex": "apt_render_paths_materials", "apt_context_r
                     "render_frame": "apt_render_frame_materials", "apt_context_render_frame": "apt_context_render_frame_materials"}
 
 
-def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials=None):
+def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials=None, lights=None):
     require_gpu()
     npix = params.width * params.height
     if pixel_count is None:
@@ -72,9 +89,7 @@ def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stre
         fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
     if fb_u8 is None:
         fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
-    mat = ()
-    if materials is not None:
-        entry, mat = _MATERIALS_ENTRY[entry], (_dev_materials(materials, params.num_spheres),)
+    entry, mat = _material_args(entry, params, materials, lights)
     check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
                                 _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat,
                                 ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(fb, "fb", 3 * pixel_count),
@@ -138,12 +153,13 @@ class Context:
                                     _dev_f32(spheres, "spheres"), _dev_f32(colors, "colors"))
         check(lib().apt_last_status(), "apt_context_render_do")
 
-    def render_do_ex(self, params, stream, rays, spheres, colors, materials=None):
-        _render_do_ex("apt_context_render_do_ex", (self._h,), params, stream, rays, spheres, colors, materials)
+    def render_do_ex(self, params, stream, rays, spheres, colors, materials=None, lights=None):
+        _render_do_ex("apt_context_render_do_ex", (self._h,), params, stream, rays, spheres, colors, materials, lights)
 
-    def render_frame(self, params, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None):
+    def render_frame(self, params, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None,
+                     lights=None):
         return _render_frame("apt_context_render_frame", (self._h,), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8,
-                             materials)
+                             materials, lights)
 
 
 def render_host(blockDim, rays, spheres, colors):
@@ -238,29 +254,34 @@ def check_device_status(stream=None):
     check(lib().apt_check(_stream_handle(stream)), "apt_check")
 
 
-def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=None):
+def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=None, lights=None):
     """Run-time-parameter form of render_do: rays [6][N], spheres [10][Ns] padded, colors [3][N] (with APT_FLAG_BAND_BUFFERS: planes of
     path_count floats holding only the range).  materials: contiguous int32 CUDA tensor of num_spheres MAT_* codes -> per-path radiance
     of the material renderer (apt_render_paths_materials); None: the mirror renderer.  With materials, params.accel (a built grid)
     is taken only together with APT_FLAG_GRID_SLOTS (gen_data.grid_flags of that grid): the same colours, found by walking the grid.
     APT_FLAG_NEE in params.flags (materials only): every diffuse hit samples the sphere params.light_index directly -- the same
-    expectation at the same depth, less noise for a small light; it needs light_index >= 0."""
-    _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors, materials)
+    expectation at the same depth, less noise for a small light; it needs light_index >= 0.
+    lights (materials only): a light table on the GPU (gen_data.build_lights, as a contiguous int32 CUDA tensor) -> every diffuse hit
+    samples ONE of the listed spheres (apt_render_paths_lights); APT_FLAG_NEE and light_index are not read then.  A table that is not
+    this scene's renders nothing and check_device_status() raises lights-mismatch."""
+    _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors, materials, lights)
 
 
-def render_paths(params: RenderParams, rays, spheres, stream=None, materials=None):
+def render_paths(params: RenderParams, rays, spheres, stream=None, materials=None, lights=None):
     """Convenience: allocate colours, launch, return the [3][N] tensor (not synchronised)."""
     colors = torch.empty(3 * params.num_paths, dtype=torch.float32, device=rays.device)
-    render_do_ex(params, stream, rays, spheres, colors, materials)
+    render_do_ex(params, stream, rays, spheres, colors, materials, lights)
     return colors.view(3, -1)
 
 
-def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None):
+def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None,
+                 lights=None):
     """Fused ray-generate + trace + decode for pixels [pixel_begin, pixel_begin+pixel_count).
     Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised.  materials: as render_do_ex (apt_render_frame_materials),
     its rule for params.accel included: a grid needs APT_FLAG_GRID_SLOTS, changes which spheres are tested and never the image; a grid
-    that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE: as render_do_ex."""
-    return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials)
+    that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE, lights: as render_do_ex
+    (apt_render_frame_lights)."""
+    return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials, lights)
 
 
 def gen_rays_device(params: RenderParams, stream=None, device="cuda"):

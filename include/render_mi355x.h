@@ -190,7 +190,8 @@ enum {
     APT_DEV_GRID_TURNS = 2u,   /* sample-queue kernel, grid form: the bound on a wave's walk turns ran out                         */
     APT_DEV_LDS_BASE = 4u,     /* sample-queue kernels: the dynamic LDS region does not start at LDS address 0 (a build problem)    */
     APT_DEV_GRID_MISMATCH = 8u, /* APT_FLAG_GRID_SLOTS: the grid at `accel` is not this scene's or has no pair-slot tables          */
-    APT_DEV_BAD_MATERIAL = 16u  /* *_materials entries: a path hit a sphere whose material code is not an APT_MAT_* value            */
+    APT_DEV_BAD_MATERIAL = 16u, /* *_materials entries: a path hit a sphere whose material code is not an APT_MAT_* value            */
+    APT_DEV_LIGHTS_MISMATCH = 32u /* *_lights entries: the light table is not one for this scene (magic, num_spheres, 1 <= n <= Ns)  */
 };
 int  apt_context_check(apt_context *ctx, void *stream);
 int  apt_check(void *stream);
@@ -336,6 +337,64 @@ int apt_render_paths_materials(const apt_render_params *p, void *stream, const f
                                const uint32_t *materials, float *colors);
 int apt_context_render_paths_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays,
                                        const float *spheres, const uint32_t *materials, float *colors);
+/* ---- several lights: a light table for the material renderer (EXTENSION) -------------------------------------------------------------
+ * The *_lights entries are the *_materials entries with one more argument, a DEVICE light table (apt_build_lights_host, uploaded by the
+ * caller): at every diffuse bounce ONE light of the table is chosen and sampled directly.  Their argument checks are the *_materials
+ * entries' in the same order, except that neither APT_FLAG_NEE nor (beyond check_params' range rule) light_index is read, and right
+ * after the materials checks -- before the pixel / path range is looked at -- lights == NULL is APT_ERR_ARG.  accel +
+ * APT_FLAG_GRID_SLOTS, APT_FLAG_RR, APT_FLAG_RETIRE, ranges and APT_FLAG_BAND_BUFFERS are as for the *_materials entries.  The kernel
+ * checks the table's head once (scalar loads) before it reads anything else: a table whose magic or num_spheres is not this launch's,
+ * or whose n is not in [1, num_spheres], is not read further; the kernel writes nothing and ORs APT_DEV_LIGHTS_MISMATCH into the status
+ * word.  A call whose context has no status word for the device (its first launch there is inside a stream capture) is refused on the
+ * host with APT_ERR_DEVICE instead of being launched: a wrong table means wrong sphere indices, which are not tried out.
+ *
+ * The table lists n >= 1 DISTINCT spheres g[0..n) with selection probabilities P[i] > 0, sum P = 1, fixed per table.  The estimator,
+ * in the terms of "Direct light sampling" above (same fp32 rules).  A path carries `sampled` (false at its start) and `kprev`.
+ *   S(j, k, h) = j != k and dot(c_j - h, c_j - h) > r2_j       (w0 = c_j - h per component, d2 = dot(w0, w0), d2 > r2_j; false for NaN)
+ *   light   at a hit on sphere m from segment origin o: L += T * emission(m) is left out iff `sampled`, m is listed, and S(m, kprev, o).
+ *           (o is the previous bounce's h bit for bit, c_m / r2_m the planes' values: the same decision that bounce took for light m.)
+ *           Then sampled = false.
+ *   sample  after the DIFF direction is drawn, when d + 1 < depth (a "sampling bounce" on sphere k at h):
+ *           lkey = splitmix64(seed ^ splitmix64(path) ^ 0x3C6EF372FE94F82B); u = the first of the two uniforms of
+ *           splitmix64(lkey + 0x9E3779B97F4A7C15 * (d + 1)) (its top 24 bits * 2^-24: a fourth stream); i = the first entry with
+ *           u < cdf[i]; j = g[i].  If S(j, k, h): the sample and shadow steps of "Direct light sampling" with Lt = sphere j -- the same
+ *           nkey stream, (v1, v2) and operations --, except wgt = (cosl * (2 * omc)) * invp[i], the light is visible iff the arg-min
+ *           IS j, and visible adds L += (T * e_j) * wgt.  If not S: nothing is added and no segment is traced.
+ *           Either way sampled = true and kprev = k.
+ *   No sample at the last bounce, as above.  Everything else (camera-ray hits, hits after SPEC / REFR or after a last DIFF bounce,
+ *   unlisted emitters) adds emission as the plain renderer does.
+ * Unbiased: at a sampling bounce the listed lights split into those with S true, whose direct light the one-sample estimate
+ * sum_i P[i] * D_i / P[i] has as its expectation, and those with S false (the sphere we stand on, a light we are inside of), which the
+ * next hit gathers as before; both sides decide by the same fp32 predicate on the same values, so no light is counted twice or dropped.
+ * With one light g[0] = Lt (cdf = [1], invp = [1]) every rule reduces to APT_FLAG_NEE with light_index = Lt: the same frame, path
+ * colours and trace counter bit for bit.  At depth 1 the table changes nothing.
+ *
+ * The table, words of 4 bytes: head[16] = (magic 0x4C474854 "LGHT", num_spheres, n, total words, bits[0], zeros), uint32 idx[n] = g,
+ * float cdf[n], float invp[n], uint32 bits[(num_spheres + 31) / 32] with bit (k & 31) of word k >> 5 set iff sphere k is listed;
+ * apt_lights_bytes(num_spheres, n) bytes in all.  Construction (float64 unless said otherwise, every operation on its own, in order):
+ *   w[i] = ((e_x + e_y) + e_z) * r2 of sphere g[i] (emitted power up to a constant), replaced by 0 unless 0 < w[i] < inf;
+ *   W = ((0 + w[0]) + w[1]) + ...;  f = 0.5 / n;  q[i] = (0.5 * w[i]) / W + f  when 0 < W < inf, else f + f   (half by power, half uniform)
+ *   S[i] = ((0 + q[0]) + ...) + q[i];  m[i] = floor(S[i] * 2^24 + 0.5) for i < n - 1, m[n-1] = 2^24;  refused unless 0 < m[0] < m[1] < ...
+ *   cdf[i] = m[i] * 2^-24 and P[i] = (m[i] - m[i-1]) * 2^-24 (m[-1] = 0), both exact in fp32: u is a multiple of 2^-24, so P[i] IS the
+ *   probability of entry i;  invp[i] = 1 / P[i], one IEEE fp32 division.
+ * apt_build_lights_host: spheres = HOST [10][Ns] table; indices = HOST list of num_indices sphere indices (kept in this order), or
+ * NULL (num_indices not read) = every sphere with an emission channel > 0, ascending; lights = HOST buffer of `capacity` bytes;
+ * *out_bytes (optional) receives the table's size.  apt_lights_bytes(num_spheres, num_spheres) bounds every table of a scene.
+ * Nothing is written unless APT_OK.  APT_ERR_ARG: spheres or lights NULL, capacity too small (*out_bytes is set).  APT_ERR_SCENE:
+ * num_spheres == 0, an empty list (or no emitter for NULL), an index >= num_spheres, a sphere listed twice, a P[i] below 2^-24. */
+size_t apt_lights_bytes(uint32_t num_spheres, uint32_t num_lights);
+int apt_build_lights_host(const float *spheres_host, uint32_t num_spheres, const uint32_t *indices, uint32_t num_indices, void *lights,
+                          size_t capacity, size_t *out_bytes);
+int apt_render_frame_lights(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials, const void *lights,
+                            uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8);
+int apt_context_render_frame_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                    const uint32_t *materials, const void *lights, uint64_t pixel_begin, uint64_t pixel_count, float *fb,
+                                    uint8_t *fb_u8);
+int apt_render_paths_lights(const apt_render_params *p, void *stream, const float *rays, const float *spheres, const uint32_t *materials,
+                            const void *lights, float *colors);
+int apt_context_render_paths_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres,
+                                    const uint32_t *materials, const void *lights, float *colors);
+
 /* HOST demo scene: gen_spheres' 8 spheres plus smallpt's glass ball (r 16.5 at (73, 16.5, 78), albedo 0.999) as sphere 8, light 7.
  * spheres = HOST float[128] ([10][9] planes, zero padded like gen_spheres), materials = HOST uint32_t[9]: walls and light DIFF,
  * mirror SPEC, glass REFR. */
