@@ -341,9 +341,12 @@ __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, flo
     return Hit8{tmin, addr, light_mask};
 }
 
-template <int MODE, bool PLANES = false>
+// CAN_BE_LAST and `last` (wave-uniform): the path's last bounce in a full trace.  Nothing traces the ray it would produce, so the
+// whole shading step is skipped (a scalar branch): what is left is the arg-min, alive &= idx != light and the albedo, `n` receives
+// no ray, and the validity chain ends with the discriminants.
+template <int MODE, bool PLANES = false, bool CAN_BE_LAST = false>
 __device__ __forceinline__ uint64_t bounce_ns8_v2(const Scene8 &sc, const Tab8 tab, const PathState &s, PathState &n,
-                                                  const TraceArgs &ta, const KeyConsts &kc, uint64_t &alive, Albedo &albedo) {
+                                                  const TraceArgs &ta, const KeyConsts &kc, uint64_t &alive, Albedo &albedo, bool last = false) {
     float amin = 1.0f;
     const Hit8 hit = intersect_ns8_v2<MODE, PLANES>(sc, s.oxy.x, s.oxy.y, s.oz, s.dxy.x, s.dxy.y, s.dz, ta, kc, amin);
     const float tmin = hit.tmin;
@@ -356,53 +359,55 @@ __device__ __forceinline__ uint64_t bounce_ns8_v2(const Scene8 &sc, const Tab8 t
     // scalar instruction; nothing is contracted): in this kernel every VALU instruction costs about one 4-cycle
     // issue slot whatever its class (measured in place: profiles/history/r02_insitu_costs.md), so the instruction COUNT
     // is what the bounce costs and a packed pair is two operations for one slot.
-    const f2 oxy = s.oxy, dxy = s.dxy;
-    const f2 hxy = oxy + dxy * tmin;                           // :513-518  h = o + d*t (mul, then add)
-    const float hz = s.oz + s.dz * tmin;
-    const f2 nxy = hxy - f2{c.x, c.y};                         // :635-637
-    const float nz = hz - c.z;
-    const f2 sq = nxy * nxy;
-    float len2;
-    if (MODE == kModeOracle) {                                 // np.linalg.norm, gen_data.py:347: float64 accumulation
-        const float p2 = nz * nz;
-        double acc = (double)sq.x;                             // (sdot starts from 0.0: 0 + a square is that square)
-        acc = acc + (double)sq.y;
-        acc = acc + (double)p2;
-        len2 = (float)acc;
-    } else {
-        float acc = sq.x + sq.y;                               // :641-649 (0 + x^2 is x^2: a square is never -0)
-        acc = acc + nz * nz;
-        len2 = acc;
+    if (!(CAN_BE_LAST && last)) {
+        const f2 oxy = s.oxy, dxy = s.dxy;
+        const f2 hxy = oxy + dxy * tmin;                           // :513-518  h = o + d*t (mul, then add)
+        const float hz = s.oz + s.dz * tmin;
+        const f2 nxy = hxy - f2{c.x, c.y};                         // :635-637
+        const float nz = hz - c.z;
+        const f2 sq = nxy * nxy;
+        float len2;
+        if (MODE == kModeOracle) {                                 // np.linalg.norm, gen_data.py:347: float64 accumulation
+            const float p2 = nz * nz;
+            double acc = (double)sq.x;                             // (sdot starts from 0.0: 0 + a square is that square)
+            acc = acc + (double)sq.y;
+            acc = acc + (double)p2;
+            len2 = (float)acc;
+        } else {
+            float acc = sq.x + sq.y;                               // :641-649 (0 + x^2 is x^2: a square is never -0)
+            acc = acc + nz * nz;
+            len2 = acc;
+        }
+        float L;
+        {
+            const float r0 = __builtin_amdgcn_rsqf(len2);
+            amin = minimum3_abs_after_trans(amin, r0, nxy.x); // validity of the fast sqrt / divide sequences: see kFastMin
+            amin = minimum3_abs(amin, nxy.y, nz);
+            const float y = len2 * r0, h = 0.5f * r0;
+            const float r = __builtin_fmaf(-y, y, len2);
+            L = __builtin_fmaf(r, h, y);
+        }
+        f2 uxy;
+        float uz;
+        div3_packed(nxy, nz, L, uxy, uz);           // pt_core.h; validity = the amin / huge tests of this function
+        const f2 pr = dxy * uxy;
+        const float pz = s.dz * uz;
+        float dot;
+        if (MODE == kModeOracle) {                                 // np.dot, gen_data.py:349
+            double acc = (double)pr.x;                             // (sdot's 0.0 start: twice_canonical() below)
+            acc = acc + (double)pr.y;
+            acc = acc + (double)pz;
+            dot = (float)acc;
+        } else {
+            dot = pr.x;                                            // :690 Duplicate(0): twice_canonical() below; :694-696
+            dot = dot + pr.y;
+            dot = dot + pz;
+        }
+        const float k2 = twice_canonical(dot);                    // :697
+        n.dxy = dxy - uxy * k2;                                    // :699-704
+        n.dz = s.dz - uz * k2;
+        n.oxy = hxy; n.oz = hz;                                    // :706-708
     }
-    float L;
-    {
-        const float r0 = __builtin_amdgcn_rsqf(len2);
-        amin = minimum3_abs_after_trans(amin, r0, nxy.x); // validity of the fast sqrt / divide sequences: see kFastMin
-        amin = minimum3_abs(amin, nxy.y, nz);
-        const float y = len2 * r0, h = 0.5f * r0;
-        const float r = __builtin_fmaf(-y, y, len2);
-        L = __builtin_fmaf(r, h, y);
-    }
-    f2 uxy;
-    float uz;
-    div3_packed(nxy, nz, L, uxy, uz);           // pt_core.h; validity = the amin / huge tests of this function
-    const f2 pr = dxy * uxy;
-    const float pz = s.dz * uz;
-    float dot;
-    if (MODE == kModeOracle) {                                 // np.dot, gen_data.py:349
-        double acc = (double)pr.x;                             // (sdot's 0.0 start: twice_canonical() below)
-        acc = acc + (double)pr.y;
-        acc = acc + (double)pz;
-        dot = (float)acc;
-    } else {
-        dot = pr.x;                                            // :690 Duplicate(0): twice_canonical() below; :694-696
-        dot = dot + pr.y;
-        dot = dot + pz;
-    }
-    const float k2 = twice_canonical(dot);                    // :697
-    n.dxy = dxy - uxy * k2;                                    // :699-704
-    n.dz = s.dz - uz * k2;
-    n.oxy = hxy; n.oz = hz;                                    // :706-708
     // AccumulateIntervalColor (rt_helper.h:711-830): alive &= idx != light; ret *= alive ? albedo : 1.  The mask
     // is updated here; the multiplication itself is apply_albedo(), which the caller runs once it knows that this
     // bounce stands (no exact re-run): it can then overwrite the throughput registers in place.
@@ -632,7 +637,9 @@ __device__ __forceinline__ uint32_t trace_ns8(const Scene8 &sc, const Tab8 tab, 
         auto step = [&](PathState &in, PathState &out, uint32_t d) -> bool {
             Albedo albedo;
             uint64_t alive_out = alive;
-            const uint64_t redo = bounce_ns8_v2p<MODE>(sc, tab, in, out, ta, kc, alive_out, albedo, sc.planes);
+            const bool last = d + 1 == ta.depth; // no ray after the last bounce: `out` then receives none (bounce_ns8_v2)
+            const uint64_t redo = sc.planes ? bounce_ns8_v2<MODE, true, true>(sc, tab, in, out, ta, kc, alive_out, albedo, last)
+                                            : bounce_ns8_v2<MODE, false, true>(sc, tab, in, out, ta, kc, alive_out, albedo, last);
             if (__builtin_expect(redo != 0, 0)) {
                 // A lane left the validity range of the fast sequences (|sqrt argument| < 2^-96, divide operands
                 // outside [2^-40, 2^40]).  A lane whose path is already finished (alive bit cleared or throughput
@@ -661,7 +668,7 @@ __device__ __forceinline__ uint32_t trace_ns8(const Scene8 &sc, const Tab8 tab, 
         }
         if (d < ta.depth) {
             if (__builtin_expect(step(s, n, d), 0)) { rest_exact(s, d); return traced; }
-            s = n;
+            // (no s = n: this was the last bounce, n holds no ray, and the callers read the throughput and s.alive only)
         }
         s.rxy = rxy; s.rz = rz;
         if (lane_alive) s.alive = select_const(alive, 1);

@@ -130,8 +130,39 @@ __device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, co
     redoB = __builtin_amdgcn_ballot_w64(!(aminB >= kFastMin));
 }
 
+// The LAST bounce of both paths.  Nothing traces the ray it would produce (the callers read the throughputs only), so of a
+// bounce it keeps what reaches the frame: the arg-min, alive &= idx != light, and the throughput times the hit sphere's
+// albedo (or 1) -- rx / ry / rz receive those products.  No hit point, normal, square root, quotient or reflection; only the
+// albedo entries are read from LDS; the validity chain ends with the discriminants (nothing else here uses a fast sequence).
+template <int MODE, bool PLANES>
+__device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 tab, const PathPair &s, f2 &rx, f2 &ry, f2 &rz,
+                                                 const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
+                                                 uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
+    float aminA = 1.0f, aminB = 1.0f;
+    const Hit8 hA = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+    const Hit8 hB = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    aliveA &= ~hA.light;                    // rt_helper.h:773-787  alive &= idx != light
+    aliveB &= ~hB.light;
+    uint32_t cA, cB; // as in bounce2_ns8
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cA) : "v"(ones_off), "v"(hA.addr), "s"(aliveA));
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cB) : "v"(ones_off), "v"(hB.addr), "s"(aliveB));
+    const char *geo = reinterpret_cast<const char *>(tab.geo);
+    const uint32_t aA = (uint32_t)(uintptr_t)geo + cA, aB = (uint32_t)(uintptr_t)geo + cB; // + 128 below: alb = geo + 8 entries (load_scene8)
+    float axA, ayA, azA, axB, ayB, azB;
+    asm volatile("ds_read_b32 %0, %6 offset:128\n ds_read_b32 %1, %6 offset:132\n ds_read_b32 %2, %6 offset:136\n"
+                 "ds_read_b32 %3, %7 offset:128\n ds_read_b32 %4, %7 offset:132\n ds_read_b32 %5, %7 offset:136\n"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(axA), "=&v"(ayA), "=&v"(azA), "=&v"(axB), "=&v"(ayB), "=&v"(azB)
+                 : "v"(aA), "v"(aB)
+                 : "memory");
+    rx = f2{axA, axB} * s.rx; ry = f2{ayA, ayB} * s.ry; rz = f2{azA, azB} * s.rz;  // :804-810 (albedo or 1)
+    redoA = __builtin_amdgcn_ballot_w64(!(aminA >= kFastMin)); // a discriminant too small, or a NaN
+    redoB = __builtin_amdgcn_ballot_w64(!(aminB >= kFastMin));
+}
+
 // All bounces of both paths (full trace: no retirement, no roulette).  The hot loop has no merge with the exact
-// form and no state copies (two bounces per turn, ping-pong): see trace_ns8.
+// form and no state copies (two bounces per turn, ping-pong): see trace_ns8.  On return only the throughputs of `s` are
+// meaningful: depth - 1 bounces produce a ray, the last one (bounce2_ns8_last) does not.
 template <int MODE, bool PLANES>
 __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta) {
     const KeyConsts kc = make_key_consts(ta.eps);
@@ -144,42 +175,68 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
     // both ping-pong halves alive across the back edge.  (Four bounces per turn -- half as many back-edge copies -- measured in
     // round 3: C2 20.40 against 19.95 ms, the longer body costs the ray-generate part more registers than the copies cost; not kept.)
     const bool fast_ok = eps_allows_rootkey(ta.eps);
+    // the request of a path that is already finished (alive bit cleared or throughput zero) is ignored: it cannot
+    // reach any output any more (deep all-miss paths, |n| ~ 1e20, are of that kind)
+    auto redo_stands = [&](const PathPair &in, uint64_t redoA, uint64_t redoB) __attribute__((always_inline)) {
+        const bool finA = select_const(aliveA, 1) == 0 || (in.rx.x == 0.0f && in.ry.x == 0.0f && in.rz.x == 0.0f);
+        const bool finB = select_const(aliveB, 1) == 0 || (in.rx.y == 0.0f && in.ry.y == 0.0f && in.rz.y == 0.0f);
+        return __builtin_amdgcn_ballot_w64((select_const(redoA, 1) != 0 && !finA) || (select_const(redoB, 1) != 0 && !finB)) != 0;
+    };
+    auto exact_pair = [&](const PathPair &in, PathState &na, PathState &nb) __attribute__((always_inline)) {
+        PathState a = unpack_path(in, 0, aliveA), b = unpack_path(in, 1, aliveB);
+        bounce_ns8_exact<MODE>(sc, tab, a, na, ta);
+        bounce_ns8_exact<MODE>(sc, tab, b, nb, ta);
+        if (ta.traced && (threadIdx.x & 63) == 0) atomicAdd(ta.traced + 3, 1ull); // statistics: exact re-runs of a wave-bounce
+    };
     auto step = [&](const PathPair &in, PathPair &out) __attribute__((always_inline)) {
         uint64_t oa = aliveA, ob = aliveB;
         bool redo_any = !fast_ok;
         if (__builtin_expect(fast_ok, 1)) {
             uint64_t redoA, redoB;
             bounce2_ns8<MODE, PLANES>(sc, tab, in, out, ta, kc, ones_off, oa, ob, redoA, redoB);
-            if (__builtin_expect((redoA | redoB) != 0, 0)) {
-                // the request of a path that is already finished (alive bit cleared or throughput zero) is ignored: it cannot
-                // reach any output any more (deep all-miss paths, |n| ~ 1e20, are of that kind)
-                const bool finA = select_const(aliveA, 1) == 0 || (in.rx.x == 0.0f && in.ry.x == 0.0f && in.rz.x == 0.0f);
-                const bool finB = select_const(aliveB, 1) == 0 || (in.rx.y == 0.0f && in.ry.y == 0.0f && in.rz.y == 0.0f);
-                redo_any = __builtin_amdgcn_ballot_w64((select_const(redoA, 1) != 0 && !finA) || (select_const(redoB, 1) != 0 && !finB)) != 0;
-            }
+            if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB);
         }
         if (__builtin_expect(redo_any, 0)) {
-            PathState a = unpack_path(in, 0, aliveA), b = unpack_path(in, 1, aliveB), na, nb;
-            bounce_ns8_exact<MODE>(sc, tab, a, na, ta);
-            bounce_ns8_exact<MODE>(sc, tab, b, nb, ta);
+            PathState na, nb;
+            exact_pair(in, na, nb);
             out.ox = f2{na.oxy.x, nb.oxy.x}; out.oy = f2{na.oxy.y, nb.oxy.y}; out.oz = f2{na.oz, nb.oz};
             out.dx = f2{na.dxy.x, nb.dxy.x}; out.dy = f2{na.dxy.y, nb.dxy.y}; out.dz = f2{na.dz, nb.dz};
             out.rx = f2{na.rxy.x, nb.rxy.x}; out.ry = f2{na.rxy.y, nb.rxy.y}; out.rz = f2{na.rz, nb.rz};
             oa = __builtin_amdgcn_ballot_w64(na.alive != 0);
             ob = __builtin_amdgcn_ballot_w64(nb.alive != 0);
-            if (ta.traced && (threadIdx.x & 63) == 0) atomicAdd(ta.traced + 3, 1ull); // statistics: exact re-runs of a wave-bounce
         }
         aliveA = oa; aliveB = ob;
     };
+    // The last bounce, state in `in`: throughputs -> s.  Its exact form is the whole exact bounce with the ray ignored.
+    auto last = [&](const PathPair &in) __attribute__((always_inline)) {
+        uint64_t oa = aliveA, ob = aliveB; // (nothing reads the alive masks after this bounce: they are not written back)
+        f2 rx, ry, rz;
+        bool redo_any = !fast_ok;
+        if (__builtin_expect(fast_ok, 1)) {
+            uint64_t redoA, redoB;
+            bounce2_ns8_last<MODE, PLANES>(sc, tab, in, rx, ry, rz, ta, kc, ones_off, oa, ob, redoA, redoB);
+            if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB);
+        }
+        if (__builtin_expect(redo_any, 0)) {
+            PathState na, nb;
+            exact_pair(in, na, nb);
+            rx = f2{na.rxy.x, nb.rxy.x}; ry = f2{na.rxy.y, nb.rxy.y}; rz = f2{na.rz, nb.rz};
+        }
+        s.rx = rx; s.ry = ry; s.rz = rz;
+    };
+    if (ta.depth == 0) return;
+    const uint32_t full = ta.depth - 1; // bounces whose ray is traced on
     PathPair n;
     uint32_t d = 0;
-    for (; d + 2 <= ta.depth; d += 2) { // render.cpp:140-188
+    for (; d + 2 <= full; d += 2) { // render.cpp:140-188
         step(s, n);
         step(n, s);
     }
-    if (d < ta.depth) {
+    if (d < full) {
         step(s, n);
-        s = n;
+        last(n);
+    } else {
+        last(s);
     }
 }
 
