@@ -35,7 +35,9 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_render_frame_materials", "apt_context_render_frame_materials", "apt_render_paths_materials",
                "apt_context_render_paths_materials", "apt_gen_spheres_materials_host", "apt_gen_scene_materials_host",
                "apt_lights_bytes", "apt_build_lights_host", "apt_render_frame_lights", "apt_context_render_frame_lights",
-               "apt_render_paths_lights", "apt_context_render_paths_lights"]
+               "apt_render_paths_lights", "apt_context_render_paths_lights",
+               "apt_camera_default_host", "apt_camera_build_host", "apt_camera_check_host", "apt_context_set_camera", "apt_set_camera",
+               "apt_gen_rays_camera_device"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
 CXX_RENDER_DO = "_Z9render_dojPvS_PhS0_S0_"
 ABI_VERSION = 3
@@ -64,6 +66,21 @@ class RenderParams(ctypes.Structure):
         for k, v in kw.items():
             setattr(p, k, v)
         return p
+
+
+class ApCamera(ctypes.Structure):
+    """apt_camera (include/render_mi355x.h "camera"): the frame pos / g / cx / cy, the segment's start `offset`, and the thin lens.
+    Made by gen_data.default_camera / gen_data.camera; a record filled in by hand goes through apt_camera_check_host when it is set."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("pos", ctypes.c_double * 3), ("g", ctypes.c_double * 3),
+                ("cx", ctypes.c_double * 3), ("cy", ctypes.c_double * 3), ("offset", ctypes.c_double), ("aperture", ctypes.c_double),
+                ("focus", ctypes.c_double), ("lens_u", ctypes.c_double * 3), ("lens_v", ctypes.c_double * 3),
+                ("offset_over_focus", ctypes.c_double)]
+
+    def copy(self, **kw):
+        c = ApCamera.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(c, k, (ctypes.c_double * 3)(*v) if isinstance(v, (tuple, list)) else v)
+        return c
 
 
 _lib = None

@@ -51,12 +51,15 @@ struct apt_context {
         unsigned long long *trace_counter; // optional device statistics block, or null
         uint32_t refill_lanes;             // APT_FLAG_RETIRE refill threshold of render_frame
         apt::Debug debug;
+        bool has_camera = false;           // apt_context_set_camera: the material frame entries render from `camera`, the mirror frame entries refuse
+        apt_camera camera;                 // checked when it was set
     };
     apt_context();
     Values snapshot();                     // consistent copy under the lock
     void set_params(const apt_render_params &p);
     void set_trace_counter(unsigned long long *c);
     void set_refill_lanes(uint32_t lanes);
+    void set_camera(const apt_camera *cam_or_null);   // a checked record, or null: the reference's camera
     int set_debug(const char *key, double value); // APT_OK / APT_ERR_ARG (error record set)
     int get_debug(const char *key, double *value); // the knob's current value (what set_debug last stored, or the environment's initial value)
 

@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/render_mi355x.h"   // apt_camera
+
 namespace apt {
 
 struct MatTrace {                 // the parts of apt_render_params the material kernels read, after the checks
@@ -30,6 +32,7 @@ struct MatFrameCall {             // render_frame with materials: pixels [pixel_
     float *fb;
     uint8_t *fb_u8;
     void *stream;
+    const apt_camera *camera;     // the context's camera (checked when it was set), or null: the reference's
 };
 
 struct MatPathsCall {             // render_do_ex with materials: paths [b, b + c) of buffers whose planes hold n paths (already shifted)
@@ -41,8 +44,21 @@ struct MatPathsCall {             // render_do_ex with materials: paths [b, b + 
     void *stream;
 };
 
+struct CamRaysCall {              // apt_gen_rays_camera_device: paths [b, b + c) of a buffer whose planes hold n paths (already shifted)
+    const apt_camera *camera;     // checked by the entry
+    uint32_t width, height, samples;
+    uint64_t seed;
+    float *rays;
+    uint64_t n, b, c;
+    void *stream;
+};
+
+// Can a frame of `samples` carry a camera?  Its plan must leave the words the camera's tail rides in (materials.hip).
+bool mat_camera_fits(uint32_t samples);
+
 // Enqueue the launch (hipGetLastError() tells the caller whether it was accepted).
 void mat_render_frame(const MatFrameCall &call);
 void mat_render_paths(const MatPathsCall &call);
+void mat_gen_rays_camera(const CamRaysCall &call);
 
 } // namespace apt

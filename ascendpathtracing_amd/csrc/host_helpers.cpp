@@ -18,6 +18,7 @@
 #include "../../include/render_mi355x.h"
 #include "apt_host.h"
 #include "pt_core.h"
+#include "pt_camera.h"
 
 // ---- error record and contexts (apt_host.h) ---------------------------------------------------------
 namespace {
@@ -53,6 +54,8 @@ apt_context::apt_context() {
     apt_default_params(&v_.params);
     v_.trace_counter = nullptr;
     v_.refill_lanes = apt::kDefaultRefillLanes;
+    v_.has_camera = false;
+    memset(&v_.camera, 0, sizeof v_.camera);
     struct { const char *env, *key; } knobs[] = {{"APT_QUEUE_PPW", "queue_ppw"}, {"APT_QUEUE_NBUF", "queue_nbuf"}, {"APT_QUEUE_LDS_PAD", "queue_lds_pad"},
                                                  {"APT_GRID_SPHERES_PER_CELL", "grid_spheres_per_cell"}};
     for (const auto &k : knobs) {
@@ -66,6 +69,11 @@ apt_context::Values apt_context::snapshot() { std::lock_guard<std::mutex> g(m_);
 void apt_context::set_params(const apt_render_params &p) { std::lock_guard<std::mutex> g(m_); v_.params = p; }
 void apt_context::set_trace_counter(unsigned long long *c) { std::lock_guard<std::mutex> g(m_); v_.trace_counter = c; }
 void apt_context::set_refill_lanes(uint32_t lanes) { std::lock_guard<std::mutex> g(m_); v_.refill_lanes = lanes; }
+void apt_context::set_camera(const apt_camera *cam) {
+    std::lock_guard<std::mutex> g(m_);
+    v_.has_camera = cam != nullptr;
+    if (cam) v_.camera = *cam;
+}
 int apt_context::set_debug(const char *key, double value) {
     if (!key) return apt::set_error(APT_ERR_ARG, "apt_context_set_debug: key is null%s");
     const std::string k(key);
@@ -481,5 +489,136 @@ int apt_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8
     }
     return fclose(f) == 0 ? APT_OK : set_error(APT_ERR_IO, "apt_write_ppm: write to %s failed", path);
 }
+
+} // extern "C"
+
+// ---- camera (include/render_mi355x.h "camera"): the record's host helpers.  float64, one operation at a time (-ffp-contract=off), in the
+// manner of camera_init (pt_core.h); tests/camera_ref.py restates them.
+namespace {
+using apt::set_error;
+bool cam_finite3(const double v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+bool cam_within3(const double v[3], double m) { return fabs(v[0]) <= m && fabs(v[1]) <= m && fabs(v[2]) <= m; }
+bool cam_zero3(const double v[3]) { return v[0] == 0 && v[1] == 0 && v[2] == 0; }
+void cam_cross(const double p[3], const double q[3], double out[3]) {   // np.cross
+    out[0] = p[1] * q[2] - p[2] * q[1];
+    out[1] = p[2] * q[0] - p[0] * q[2];
+    out[2] = p[0] * q[1] - p[1] * q[0];
+}
+// The refusals of apt_camera_check_host, struct_size aside.  `what`: the entry's name for the message.
+int cam_check_fields(const apt_camera &c, const char *what) {
+    if (!(cam_finite3(c.pos) && cam_finite3(c.g) && cam_finite3(c.cx) && cam_finite3(c.cy) && cam_finite3(c.lens_u) && cam_finite3(c.lens_v) &&
+          std::isfinite(c.offset) && std::isfinite(c.aperture) && std::isfinite(c.focus) && std::isfinite(c.offset_over_focus)))
+        return set_error(APT_ERR_ARG, "%s: camera: a field is not finite", what);
+    if (!(cam_within3(c.pos, apt::kCamMaxPos) && cam_within3(c.cx, apt::kCamMaxAxis) && cam_within3(c.cy, apt::kCamMaxAxis) &&
+          cam_within3(c.g, apt::kCamMaxUnit) && cam_within3(c.lens_u, apt::kCamMaxUnit) && cam_within3(c.lens_v, apt::kCamMaxUnit) &&
+          c.offset <= apt::kCamMaxPos && c.aperture <= apt::kCamMaxAxis && fabs(c.focus) <= apt::kCamMaxPos))
+        return set_error(APT_ERR_ARG, "%s: camera: a field is outside the magnitude bound (|pos|, offset, focus <= 2^30; |cx|, |cy|, aperture <= 2^20)", what);
+    if (cam_zero3(c.g) || cam_zero3(c.cx) || cam_zero3(c.cy)) return set_error(APT_ERR_ARG, "%s: camera: g, cx and cy must be non-zero", what);
+    if (c.offset < 0) return set_error(APT_ERR_ARG, "%s: camera: offset < 0", what);
+    if (c.aperture < 0) return set_error(APT_ERR_ARG, "%s: camera: aperture < 0", what);
+    if (c.aperture > 0) {
+        if (!(c.focus >= apt::kCamMinFocus)) return set_error(APT_ERR_ARG, "%s: camera: a lens (aperture > 0) needs focus >= 2^-20", what);
+        if (cam_zero3(c.lens_u) || cam_zero3(c.lens_v)) return set_error(APT_ERR_ARG, "%s: camera: a lens needs non-zero lens_u and lens_v", what);
+        if (c.offset_over_focus != c.offset / c.focus) return set_error(APT_ERR_ARG, "%s: camera: offset_over_focus must be offset / focus", what);
+    }
+    return APT_OK;
+}
+int cam_check_out(const apt_camera *out, uint32_t width, uint32_t height, const char *what) {
+    if (!out) return set_error(APT_ERR_ARG, "%s: camera: out is null", what);
+    if (out->struct_size != sizeof(apt_camera)) return set_error(APT_ERR_STRUCT, "%s: apt_camera.struct_size mismatch", what);
+    if (!width || !height) return set_error(APT_ERR_ARG, "%s: camera: width/height must be non-zero", what);
+    return APT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int apt_camera_default_host(uint32_t width, uint32_t height, apt_camera *out) {
+    apt::clear_error();
+    int rc = cam_check_out(out, width, height, "apt_camera_default_host");
+    if (rc) return rc;
+    apt::Camera c;
+    apt::camera_init(c, width, height);
+    apt_camera r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = sizeof r;
+    for (int k = 0; k < 3; ++k) { r.pos[k] = c.pos[k]; r.g[k] = c.g[k]; r.cx[k] = c.cx[k]; r.cy[k] = c.cy[k]; }
+    double cr[3];
+    cam_cross(c.cx, c.g, cr);                                   // camera_init's own cross product, before its * 0.5135
+    const double cn = apt::norm3(cr[0], cr[1], cr[2]);
+    for (int k = 0; k < 3; ++k) r.lens_v[k] = cr[k] / cn;
+    r.lens_u[0] = 1; r.lens_u[1] = 0; r.lens_u[2] = 0;
+    r.offset = 140;
+    if ((rc = cam_check_fields(r, "apt_camera_default_host"))) return rc;   // (an absurd aspect ratio leaves the bound)
+    *out = r;
+    return APT_OK;
+}
+
+int apt_camera_build_host(const double eye[3], const double dir[3], const double up[3], double scale, double offset, double aperture,
+                          double focus, uint32_t width, uint32_t height, apt_camera *out) {
+    apt::clear_error();
+    const char *what = "apt_camera_build_host";
+    if (!eye || !dir || !up) return set_error(APT_ERR_ARG, "%s: eye/dir/up must be non-null", what);
+    int rc = cam_check_out(out, width, height, what);
+    if (rc) return rc;
+    if (!(cam_finite3(eye) && cam_finite3(dir) && cam_finite3(up) && std::isfinite(scale) && std::isfinite(offset) && std::isfinite(aperture) &&
+          std::isfinite(focus))) return set_error(APT_ERR_ARG, "%s: an input is not finite", what);
+    if (!(cam_within3(eye, apt::kCamMaxPos) && cam_within3(dir, apt::kCamMaxPos) && cam_within3(up, apt::kCamMaxPos)))
+        return set_error(APT_ERR_ARG, "%s: |eye|, |dir|, |up| components must be <= 2^30", what);
+    if (!(scale >= apt::kCamMinScale && scale <= apt::kCamMaxScale)) return set_error(APT_ERR_ARG, "%s: scale must lie in [2^-20, 2^20]", what);
+    if (offset < 0) return set_error(APT_ERR_ARG, "%s: offset < 0", what);
+    if (aperture < 0) return set_error(APT_ERR_ARG, "%s: aperture < 0", what);
+    if (aperture > 0 && !(focus > 0)) return set_error(APT_ERR_ARG, "%s: a lens (aperture > 0) needs focus > 0", what);
+    apt_camera r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = sizeof r;
+    const double gn = apt::norm3(dir[0], dir[1], dir[2]), un2 = apt::norm3_sq(up[0], up[1], up[2]);
+    if (!(gn >= apt::kCamMinNorm) || !(un2 >= apt::kCamMinNorm * apt::kCamMinNorm)) return set_error(APT_ERR_ARG, "%s: dir and up must be non-zero (norm >= 2^-30)", what);
+    for (int k = 0; k < 3; ++k) r.g[k] = dir[k] / gn;
+    double c[3];
+    cam_cross(r.g, up, c);
+    const double c2 = apt::norm3_sq(c[0], c[1], c[2]);
+    if (!(c2 >= apt::kCamMinSin2 * un2)) return set_error(APT_ERR_ARG, "%s: up is parallel to dir", what);
+    const double cn = sqrt(c2);
+    double right[3];
+    for (int k = 0; k < 3; ++k) right[k] = c[k] / cn;
+    const double sx = ((double)width * scale) / (double)height;
+    for (int k = 0; k < 3; ++k) r.cx[k] = right[k] * sx;
+    double e[3];
+    cam_cross(r.cx, r.g, e);
+    const double en = apt::norm3(e[0], e[1], e[2]);
+    for (int k = 0; k < 3; ++k) {
+        r.lens_v[k] = e[k] / en;
+        r.cy[k] = r.lens_v[k] * scale;
+        r.lens_u[k] = right[k];
+        r.pos[k] = eye[k];
+    }
+    r.offset = offset; r.aperture = aperture; r.focus = focus;
+    r.offset_over_focus = aperture > 0 ? offset / focus : 0.0;
+    if ((rc = cam_check_fields(r, what))) return rc;
+    *out = r;
+    return APT_OK;
+}
+
+int apt_camera_check_host(const apt_camera *cam) {
+    apt::clear_error();
+    if (!cam) return set_error(APT_ERR_ARG, "%s: camera is null", "apt_camera_check_host");
+    if (cam->struct_size != sizeof(apt_camera)) return set_error(APT_ERR_STRUCT, "%s: apt_camera.struct_size mismatch", "apt_camera_check_host");
+    return cam_check_fields(*cam, "apt_camera_check_host");
+}
+
+int apt_context_set_camera(apt_context *ctx, const apt_camera *cam) {
+    apt::clear_error();
+    if (!ctx) return set_error(APT_ERR_ARG, "%s: context is null", "apt_context_set_camera");
+    if (cam) {
+        if (cam->struct_size != sizeof(apt_camera)) return set_error(APT_ERR_STRUCT, "%s: apt_camera.struct_size mismatch", "apt_context_set_camera");
+        const int rc = cam_check_fields(*cam, "apt_context_set_camera");
+        if (rc) return rc;
+    }
+    ctx->set_camera(cam);
+    return APT_OK;
+}
+
+int apt_set_camera(const apt_camera *cam) { return apt_context_set_camera(&apt::default_context(), cam); }
 
 } // extern "C"

@@ -3,6 +3,7 @@
 // before byte for byte as it was (`make asm` writes this code object to materials.s).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/render_mi355x.h"
 #include "apt_materials.h"
@@ -29,8 +30,23 @@ TraceArgs mat_trace_args(const apt::MatTrace &t) {
 
 // The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.  APT_FLAG_NEE rides on it (kMatNee), or a
 // light table (kMatLights), which stands for the flag: never both.
-constexpr int mat_scene_form(bool ns8, bool grid, bool nee, bool lights) {
-    return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (lights ? kMatLights : (nee ? kMatNee : 0));
+constexpr int mat_scene_form(bool ns8, bool grid, bool nee, bool lights, bool camera = false) {
+    return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (lights ? kMatLights : (nee ? kMatNee : 0)) | (camera ? kMatCamera : 0);
+}
+
+// An apt_camera (checked by the entry that took it) as the kernels read it.
+CameraEx camera_ex(const apt_camera &r, uint32_t width, uint32_t height) {
+    CameraEx c;
+    for (int k = 0; k < 3; ++k) {
+        c.base.pos[k] = r.pos[k]; c.base.g[k] = r.g[k]; c.base.cx[k] = r.cx[k]; c.base.cy[k] = r.cy[k];
+        c.t.lens_u[k] = r.lens_u[k]; c.t.lens_v[k] = r.lens_v[k];
+    }
+    c.base.inv_w = 1.0 / (double)width;   // correctly rounded, as camera_init's
+    c.base.inv_h = 1.0 / (double)height;
+    c.t.offset = r.offset; c.t.focus = r.focus; c.t.oof = r.offset_over_focus;
+    c.t.aperture = (float)r.aperture;
+    c.t.lens = r.aperture > 0.0 ? 1u : 0u;   // the rule: from the float64 value, not from its fp32 rounding
+    return c;
 }
 
 } // namespace
@@ -39,21 +55,24 @@ namespace apt {
 
 void mat_render_frame(const MatFrameCall &c) {
     FrameArgs fa;
-    camera_init(fa.cam, c.width, c.height);
+    CameraEx cx;
+    if (c.camera) { cx = camera_ex(*c.camera, c.width, c.height); fa.cam = cx.base; }
+    else camera_init(fa.cam, c.width, c.height);
     fa.width = c.width; fa.height = c.height; fa.samples = c.samples; fa.seed = c.t.seed;
     fa.pixel_begin = c.pixel_begin; fa.pixel_count = c.pixel_count; fa.fb = c.fb; fa.fb_u8 = c.fb_u8;
     const TraceArgs ta = mat_trace_args(c.t);
     LeafProg lp;
-    (void)make_leaf_plan(c.samples, lp);                   // the caller checked that the plan exists
+    (void)make_leaf_plan(c.samples, lp);                   // the caller checked that the plan exists (with a camera: that it leaves the tail's words)
+    if (c.camera) memcpy(&lp.leaf[kCamTailLeaf], &cx.t, sizeof cx.t);
     const int group = c.samples >= 8 ? 8 : 1;
     const uint64_t blocks = (c.pixel_count * 4u * (uint64_t)group + kBlock - 1) / kBlock;   // <= 2^31 - 1: checked by the caller
     const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
-            hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt), g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds,
+        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.camera != nullptr, [&](auto cam) {
+            hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, cam), g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds,
                                st, c.spheres, c.materials, fa, ta, lp);
-        }); });
+        }); }); });
     }); }); });
 }
 
@@ -67,6 +86,18 @@ void mat_render_paths(const MatPathsCall &c) {
                                c.spheres, c.materials, c.colors, c.n, c.b, c.c, ta);
         }); });
     }); });
+}
+
+bool mat_camera_fits(uint32_t samples) {
+    LeafProg lp;
+    return make_leaf_plan(samples, lp) && lp.nleaves <= kCamTailLeaf;
+}
+
+void mat_gen_rays_camera(const CamRaysCall &c) {
+    const CameraEx cam = camera_ex(*c.camera, c.width, c.height);
+    const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
+    hipLaunchKernelGGL(gen_rays_camera_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)c.stream, cam, c.width, c.height,
+                       c.samples, c.seed, c.n, c.b, c.c, c.rays);
 }
 
 } // namespace apt

@@ -7,6 +7,8 @@
 // (-ffp-contract=off): tests/materials_ref.py restates it and the GPU tests compare bit for bit.
 #pragma once
 #include "pt_frame.h"   // FrameArgs, frame_lane, park_camera, frame_decode; pt_trace.h
+#include "pt_camera.h"  // CameraEx, camera_ray_ex: a context's camera (kMatCamera)
+#include <type_traits>
 
 namespace {
 
@@ -20,7 +22,12 @@ static_assert((kMatLights & (kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0
 // How a kernel samples lights (LM, from the two bits above): not at all, the one sphere light_index, one light of a table per bounce.
 constexpr int kLmNone = 0, kLmNee = 1, kLmTable = 2;
 constexpr int mat_light_mode(int scn) { return (scn & kMatLights) ? kLmTable : ((scn & kMatNee) ? kLmNee : kLmNone); }
-constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights); }
+constexpr int kMatCamera = 16;  // a context's camera (apt_context_set_camera) in the same template argument, frame kernels only: ray-generate in its general form
+static_assert((kMatCamera & (kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatCamera must be a bit of its own");
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera); }
+// Where a camera's CameraTail rides in a frame kernel's LeafProg: its last kCamTailWords leaf words (the launch refuses a plan that
+// reaches them).  FrameArgs is shared with render_kernels.hip's kernels and keeps its layout.
+constexpr uint32_t kCamTailLeaf = kMaxLeaves - kCamTailWords;
 constexpr int kMatTab = 24;     // 8-sphere LDS table: geometry [0, 8), albedo [8, 16), emission [16, 24)
 
 struct MatPath {
@@ -161,6 +168,23 @@ __device__ __forceinline__ void mat_sincos(float u1, float &sn, float &cs) {
     const float a = (q & 1) ? c : s, b = (q & 1) ? s : c;
     sn = (q >= 2) ? -a : a;
     cs = (q == 1 || q == 2) ? -b : b;
+}
+
+// The thin lens's point in lens coordinates (include/render_mi355x.h "camera"): a uniform point of the disc of radius `aperture`, fp32,
+// from the lens's own stream -- one draw per path -- with the DIFF block's sqrt and polynomial.
+__device__ __forceinline__ void cam_lens_point(uint64_t seed, uint64_t path, float aperture, float &lx, float &ly) {
+    float v1, v2;
+    mat_uniforms(splitmix64(seed ^ splitmix64(path) ^ kLensKeySalt), 0u, v1, v2);
+    const float r = sqrtf(v1);
+    float sn, cs;
+    mat_sincos(v2, sn, cs);
+    lx = (cs * r) * aperture;
+    ly = (sn * r) * aperture;
+}
+// The extended camera, parked in LDS like the 14 doubles of park_camera: those from FrameArgs, the tail from the plan's spare words.
+__device__ __forceinline__ void park_camera_ex(CameraEx &cam, const FrameArgs &fa, const LeafProg &lp) {
+    park_camera(cam.base, fa);
+    if (threadIdx.x < kCamTailWords) reinterpret_cast<uint32_t *>(&cam.t)[threadIdx.x] = lp.leaf[kCamTailLeaf + threadIdx.x];
 }
 
 // Duff et al. 2017: the orthonormal basis (t, b) of the unit vector n, branchless.
@@ -580,10 +604,33 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
     count_traced(ta, valid ? traced : 0);
 }
 
+// ---- kernel: rays of a camera into a buffer -----------------------------------------------------------------------------------------
+// gen_rays_kernel (pt_kernels.h) for a CameraEx: the rays the camera instantiations of the frame kernel trace, bit for bit (the same
+// camera_ray_ex on the same uniforms and lens point).
+__global__ __launch_bounds__(kBlock) void gen_rays_camera_kernel(CameraEx cam, uint32_t width, uint32_t height, uint32_t samples,
+                                                                 uint64_t seed, uint64_t n_total, uint64_t begin, uint64_t count,
+                                                                 float *__restrict__ rays) {
+    const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = local < count;                                    // no early return: camera_ray_ex votes over the wave
+    const uint64_t p = begin + (valid ? local : 0);
+    uint32_t i, j, sy, sx;
+    path_coords(p, height, samples, i, j, sy, sx);
+    double u1, u2;
+    path_uniforms(seed, p, u1, u2);
+    float lx = 0.0f, ly = 0.0f;
+    if (cam.t.lens) cam_lens_point(seed, p, cam.t.aperture, lx, ly);
+    float rox, roy, roz, rdx, rdy, rdz;
+    camera_ray_ex(cam, width, height, i, j, sy, sx, u1, u2, lx, ly, rox, roy, roz, rdx, rdy, rdz);
+    if (valid) {
+        rays[p] = rox; rays[n_total + p] = roy; rays[2 * n_total + p] = roz;
+        rays[3 * n_total + p] = rdx; rays[4 * n_total + p] = rdy; rays[5 * n_total + p] = rdz;
+    }
+}
+
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
-// SCN: the scene form and kMatNee / kMatLights, as for the buffer kernel.
+// SCN: the scene form and kMatNee / kMatLights, as for the buffer kernel, and kMatCamera.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, TraceArgs ta, LeafProg lp) {
@@ -593,12 +640,14 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
     float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
-    __shared__ Camera cam;
+    constexpr bool CAM = (SCN & kMatCamera) != 0;                            // a context's camera: CameraEx (its tail from lp), camera_ray_ex
+    __shared__ std::conditional_t<CAM, CameraEx, Camera> cam;
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
     MatTable tb;
     if (!mat_lights_header<LM>(ta, sph, tab, tb)) return;
-    park_camera(cam, fa);
+    if constexpr (CAM) park_camera_ex(cam, fa, lp);
+    else park_camera(cam, fa);
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
     else __syncthreads();
@@ -618,7 +667,13 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         double u1, u2;
         path_uniforms(fa.seed, pbase + k, u1, u2);
         float rox, roy, roz, rdx, rdy, rdz;
-        camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
+        if constexpr (CAM) {
+            float lx = 0.0f, ly = 0.0f;
+            if (cam.t.lens) cam_lens_point(fa.seed, pbase + k, cam.t.aperture, lx, ly);   // launch-uniform branch
+            camera_ray_ex(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, lx, ly, rox, roy, roz, rdx, rdy, rdz);
+        } else {
+            camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
+        }
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
         traced += trace_mat<SC, LM>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k);

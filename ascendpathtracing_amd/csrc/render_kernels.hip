@@ -68,6 +68,12 @@ int check_materials(const apt_render_params *p, const uint32_t *materials, bool 
     return APT_OK;
 }
 
+// A context's camera (include/render_mi355x.h "camera") serves the material frame entries only.  The mirror frame entries have exactly the
+// reference's camera and refuse, after their own checks, rather than render a frame from a viewpoint the caller did not ask for.
+int refuse_camera(const apt_context::Values &cv, const char *entry) {
+    return cv.has_camera ? fail(APT_ERR_ARG, "%s: the context has a camera set (apt_context_set_camera), which the mirror frame entries do not take: unset it, or use apt_gen_rays_camera_device + render_do_ex + apt_decode_color_device", entry) : APT_OK;
+}
+
 // A material entry's own arguments: which entry it is, and what it was given.  lights: with_lights entries only (device light table).
 struct MatArgs {
     const uint32_t *materials = nullptr;
@@ -255,10 +261,12 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     const apt::Debug &dbg = ls.cv.debug;
     if (mat) {   // per-sphere materials: materials.hip
         if ((rc = check_lights_status(ma, ls.status))) return rc;
+        if (ls.cv.has_camera && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera: a frame with a camera set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
         apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
-                                                pixel_count, fb, fb_u8, stream});
+                                                pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr});
         return launched();
     }
+    if ((rc = refuse_camera(ls.cv, "render_frame"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
     TraceArgs ta = make_trace_args(p, ls);
@@ -608,6 +616,7 @@ int apt_multi_create(const int *device_ids, uint32_t num_bands, uint32_t stripes
     int rc = check_params(p);
     if (rc) return rc;
     if (p->accel) return fail(APT_ERR_ARG, "apt_multi_create: accel is a single-device address; not supported here%s");
+    if ((rc = refuse_camera(apt::default_context().snapshot(), "apt_multi_create"))) return rc;   // apt_multi_render renders through the default context
     const int ndev = apt_device_count();
     for (uint32_t b = 0; b < num_bands; ++b)
         if (device_ids[b] < 0 || device_ids[b] >= ndev) return fail(APT_ERR_DEVICE, "apt_multi_create: device id out of range%s");
@@ -648,6 +657,7 @@ int apt_multi_create(const int *device_ids, uint32_t num_bands, uint32_t stripes
 int apt_multi_render(apt_multi *m, float *fb_root, uint8_t *u8_root, float *band_kernel_ms) {
     clear_error();
     if (!m || !fb_root) return fail(APT_ERR_ARG, "apt_multi_render: handle/fb must be non-null%s");
+    if (int crc = refuse_camera(apt::default_context().snapshot(), "apt_multi_render")) return crc;
     const uint64_t npix = (uint64_t)m->params.width * m->params.height;
     const uint64_t nb = m->bands.size(), parts = nb * m->stripes;
     int rc = APT_OK;
@@ -846,6 +856,20 @@ int apt_gen_rays_device(const apt_render_params *p, void *stream, float *rays) {
     return launched();
 }
 
+int apt_gen_rays_camera_device(const apt_render_params *p, const apt_camera *cam, void *stream, float *rays) {
+    clear_error();
+    int rc = check_params(p);
+    if (rc) return rc;
+    if ((rc = apt_camera_check_host(cam))) return rc;      // (clears and sets the error record itself)
+    if (!rays) return fail(APT_ERR_ARG, "rays must be non-null%s");
+    PathRange r;
+    if ((rc = path_range(p, r)) || r.c == 0) return rc;
+    const uint64_t blocks = (r.c + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
+    apt::mat_gen_rays_camera(apt::CamRaysCall{cam, p->width, p->height, p->samples, p->seed, r.base(rays), r.plane(), r.b, r.c, stream});
+    return launched();
+}
+
 int apt_gen_rays_mt_device_ex(const apt_render_params *p, void *stream, const uint32_t *checkpoints, uint32_t stride,
                               uint64_t num_checkpoints, uint64_t first_block, float *rays) {
     clear_error();
@@ -896,6 +920,7 @@ int apt_render_frame_mt(const apt_render_params *p, void *stream, const uint32_t
     const uint64_t g_lo = pixel_begin / kMtGroupPixels, g_hi = (pixel_begin + pixel_count + kMtGroupPixels - 1) / kMtGroupPixels;
     if (g_lo < first_group || g_hi - first_group > num_checkpoints) return fail(APT_ERR_ARG, "apt_render_frame_mt: the checkpoint table does not cover the pixel range%s");
     if (g_hi - g_lo > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    if ((rc = refuse_camera(apt::default_context().snapshot(), "apt_render_frame_mt"))) return rc;
     const TraceArgs ta = make_trace_args(p, launch_state(apt::default_context(), stream));
     const FrameArgs fa = make_frame_args(p, pixel_begin, pixel_count, fb, fb_u8);
     MtFrameArgs ma;

@@ -243,3 +243,51 @@ if __name__ == "__main__":              # gen_data.py:435-446
     gen_rays(width, height, samples, seed=0, out_dir="./input")
     gen_spheres(out_dir="./input")
     print("===========Python Script Done=============")
+
+
+def _new_camera():
+    from ._lib import ApCamera
+    c = ApCamera()
+    c.struct_size = ctypes.sizeof(ApCamera)
+    return c
+
+
+def default_camera(w, h):
+    """The reference's camera for a w x h image as a record (apt_camera_default_host): gen_rays' frame bit for bit, offset 140, no lens.
+    Setting it renders what no camera renders, through the camera kernels."""
+    c = _new_camera()
+    check(lib().apt_camera_default_host(ctypes.c_uint32(w), ctypes.c_uint32(h), ctypes.byref(c)), "apt_camera_default_host")
+    return c
+
+
+def camera(eye, dir=None, target=None, up=(0, 1, 0), vfov_deg=None, scale=0.5135, offset=140.0, aperture=0.0, focus=None, width=None,
+           height=None):
+    """A look-along camera (apt_camera_build_host) for a width x height image: at `eye`, looking along `dir` or at `target` (dir = target
+    - eye), `up` roughly up.  vfov_deg: the vertical field of view in degrees, 0 < vfov < 180 (scale = 2 * tan(vfov / 2)); else `scale`,
+    the full image height at forward depth 1 (the reference's 0.5135), in [2^-20, 2^20].  offset: the segments start this far along the
+    ray in units of forward depth (the reference's 140 steps through its front wall; 0 starts at the eye).  aperture: lens radius, 0 =
+    pinhole; focus: forward depth of the plane in focus (None with a target: the distance to it)."""
+    import math
+    if width is None or height is None:
+        raise AptError("camera: width and height are required")
+    if (dir is None) == (target is None):
+        raise AptError("camera: give exactly one of dir and target")
+    eye = [float(x) for x in eye]
+    if target is not None:
+        dir = [float(t) - e for t, e in zip(target, eye)]
+        if focus is None:
+            focus = math.sqrt(sum(x * x for x in dir))
+    if vfov_deg is not None:
+        if not 0.0 < vfov_deg < 180.0:
+            raise AptError("camera: vfov_deg must lie in (0, 180)")
+        scale = 2.0 * math.tan(math.radians(vfov_deg) / 2.0)
+    if focus is None:
+        if aperture > 0:
+            raise AptError("camera: a lens (aperture > 0) needs focus or target")
+        focus = 0.0
+    d3 = ctypes.c_double * 3
+    c = _new_camera()
+    check(lib().apt_camera_build_host(d3(*eye), d3(*[float(x) for x in dir]), d3(*[float(x) for x in up]), ctypes.c_double(scale),
+                                      ctypes.c_double(offset), ctypes.c_double(aperture), ctypes.c_double(focus), ctypes.c_uint32(width),
+                                      ctypes.c_uint32(height), ctypes.byref(c)), "apt_camera_build_host")
+    return c

@@ -134,6 +134,11 @@ class Context:
         ptr = ctypes.c_void_p(tensor_or_none.data_ptr()) if tensor_or_none is not None else None
         check(lib().apt_context_set_trace_counter(self._h, ptr), "apt_context_set_trace_counter")
 
+    def set_camera(self, cam):
+        """apt_context_set_camera: this context's material frames render from `cam` (gen_data.camera / default_camera; None: the
+        reference's camera again), its mirror frame entries refuse while one is set."""
+        check(lib().apt_context_set_camera(self._h, None if cam is None else ctypes.byref(cam)), "apt_context_set_camera")
+
     def set_debug(self, key, value):
         check(lib().apt_context_set_debug(self._h, key.encode(), ctypes.c_double(value)), "apt_context_set_debug")
 
@@ -217,6 +222,13 @@ def set_default_params(params):
     check(lib().apt_set_default_params(ctypes.byref(params)), "apt_set_default_params")
 
 
+def set_camera(cam):
+    """apt_set_camera: the default context's camera (gen_data.camera / default_camera), or None for the reference's.  render_frame with
+    materials= then renders from it; render_frame without materials refuses while it is set (gen_rays_camera + render_paths +
+    decode_color_device gives the mirror renderer a camera)."""
+    check(lib().apt_set_camera(None if cam is None else ctypes.byref(cam)), "apt_set_camera")
+
+
 def set_debug(key, value):
     """Measurement knob of the default context (include/render_mi355x.h apt_context_set_debug): "queue_ppw", "queue_nbuf",
     "queue_lds_pad", "grid_walk" (1 = nested item walk), "grid_spheres_per_cell"; 0 = the library's own choice."""
@@ -290,6 +302,17 @@ def gen_rays_device(params: RenderParams, stream=None, device="cuda"):
     rays = torch.empty(6 * params.num_paths, dtype=torch.float32, device=device)
     check(lib().apt_gen_rays_device(ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays")),
           "apt_gen_rays_device")
+    return rays.view(6, -1)
+
+
+def gen_rays_camera(params: RenderParams, cam, stream=None, device="cuda"):
+    """apt_gen_rays_camera_device: the rays of camera `cam` (its lens included) -> [6][N] tensor, or [6][path_count] with
+    APT_FLAG_BAND_BUFFERS; only paths [path_begin, path_begin + path_count) are written.  The rays a material frame traces with `cam` set."""
+    require_gpu()
+    n = _buffer_paths(params)
+    rays = torch.empty(6 * n, dtype=torch.float32, device=device)
+    check(lib().apt_gen_rays_camera_device(ctypes.byref(params), ctypes.byref(cam), _stream_handle(stream), _dev_f32(rays, "rays")),
+          "apt_gen_rays_camera_device")
     return rays.view(6, -1)
 
 

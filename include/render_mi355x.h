@@ -405,6 +405,81 @@ int apt_gen_spheres_materials_host(float *spheres, uint32_t *materials);
  * uint64 wrap-around.  num_spheres < 8: APT_ERR_SCENE, like apt_gen_scene_host; materials == NULL: APT_ERR_ARG. */
 int apt_gen_scene_materials_host(uint32_t num_spheres, uint64_t seed, uint32_t *materials);
 
+/* ---- camera (EXTENSION: a movable camera with a thin lens for the material renderer) -------------------------------------------------
+ * The reference has one camera, written into gen_rays (scripts/gen_data.py:24-30): pos (50, 52, 295.6), dir (0, -0.042612, -1), the
+ * factor 0.5135, and ray segments that start 140 units of forward depth along the ray.  An apt_camera holds that frame as data.  A
+ * context carries at most one (apt_context_set_camera; none = the reference's camera, every entry, kernel and image as before).
+ * With a camera set
+ *   - the four material FRAME entries (apt_render_frame_materials, apt_render_frame_lights, their apt_context_* forms) render from it;
+ *   - the mirror frame entries -- render_frame / apt_context_render_frame, apt_render_frame_mt, apt_multi_render (default context) --
+ *     return APT_ERR_ARG after their own checks: they have exactly the reference's camera, and a frame silently taken from another
+ *     viewpoint is worse than a refusal.  apt_gen_rays_camera_device + render_do_ex + apt_decode_color_device gives them any camera;
+ *   - buffer-mode entries take rays and are unaffected;
+ *   - a material frame whose sample count has a pairwise-sum plan of more than 44 leaves (4200 samples is the first; every count
+ *     <= 4199 fits) is refused with APT_ERR_ARG: the record's tail travels in the plan's spare words.
+ *
+ * Ray generation, all float64, every operation rounded on its own (no FMA except where written), then ONE rounding to fp32.  a, b (the
+ * tent-filtered image-plane coordinates in [-0.5, 0.5]), the path layout and the two SplitMix64 uniforms are render_frame's.
+ *   d[k] = (cx[k]*a + cy[k]*b) + g[k]                                                  k = 0, 1, 2
+ *   norm(v) = sqrt(fma(v2, v2, fma(v1, v1, v0*v0)))                                    np.linalg.norm's ddot
+ *   pinhole (aperture == 0; decided by this rule, never by arithmetic on aperture, whatever `focus` holds):
+ *     s[k] = pos[k];  v[k] = d[k];  t = offset
+ *   thin lens (aperture > 0):
+ *     lkey = splitmix64(seed ^ splitmix64(path) ^ 0xA54FF53A5F1D36F1); h = splitmix64(lkey + 0x9E3779B97F4A7C15);
+ *     v1 = (float)(h >> 40) * 2^-24, v2 = (float)((h >> 16) & 0xFFFFFF) * 2^-24      (a stream of its own, the material streams' split)
+ *     r = sqrtf(v1); (sin, cos) of 2*pi*v2 by DIFF's polynomial; lx = (cos*r)*(float)aperture, ly = (sin*r)*(float)aperture (fp32; both
+ *     widen exactly)
+ *     s[k] = pos[k] + (lens_u[k]*lx + lens_v[k]*ly)                                   the point on the lens
+ *     v[k] = (pos[k] + d[k]*focus) - s[k]                                             towards the point in focus (d's forward part is 1)
+ *     t = offset_over_focus                                                            RN(offset / focus), made on the host
+ *   o[k] = (float)(s[k] + v[k]*t);  dir[k] = (float)(v[k] / norm(v))
+ * With apt_camera_default_host's record this is render_frame's ray bit for bit (the terms it drops for the reference frame are exact
+ * identities).  The device evaluates the quotients and the square roots with faster sequences that give the same bits while nothing
+ * is scaled; one test per ray (the tent arguments, |xa|, |xb|, |v[k]| and norm^2 >= 2^-60, norm <= 2^60) sends the whole wave to IEEE
+ * sqrt and division otherwise.  Magnitude bound (the helpers below refuse records outside it, which keeps every float64 intermediate
+ * and every fp32 result finite): |pos[k]|, offset, focus <= 2^30; |cx[k]|, |cy[k]|, aperture <= 2^20; |g[k]|, |lens_u[k]|,
+ * |lens_v[k]| <= 2; focus >= 2^-20 when aperture > 0.  Then |v[k]| < 2^53 and |o[k]| < 2^104. */
+typedef struct apt_camera {
+    uint32_t struct_size;       /* = sizeof(apt_camera)                                                     */
+    uint32_t reserved;          /* 0                                                                        */
+    double pos[3];              /* eye                                                                      */
+    double g[3];                /* unit view direction                                                      */
+    double cx[3], cy[3];        /* image-plane axes: full image width / height at forward depth 1           */
+    double offset;              /* the segment starts this far along the ray, in units of forward depth (reference: 140, through the front wall) */
+    double aperture;            /* lens radius; 0 = pinhole                                                 */
+    double focus;               /* forward depth of the plane in focus (read when aperture > 0)              */
+    double lens_u[3], lens_v[3];/* unit lens axes (right, up)                                               */
+    double offset_over_focus;   /* RN(offset / focus) when aperture > 0, else not read                      */
+} apt_camera;
+
+/* Host helpers: no GPU, nothing written unless APT_OK.
+ * apt_camera_default_host: the reference's frame for a width x height image, bit for bit gen_rays' (cx = (width*0.5135/height, 0, 0),
+ *   cy = cross(cx, g) / norm * 0.5135), offset 140, aperture 0, focus 0, lens_u = (1, 0, 0), lens_v = cross(cx, g) / norm.
+ * apt_camera_build_host: a look-along camera.  `scale` is what 0.5135 is to the reference: the full image height at forward depth 1
+ *   (2 * tan(vfov / 2) for a vertical field of view; no angle is taken here, so that the result does not depend on a libm).  float64,
+ *   one operation at a time, cross(p, q) = (p1*q2 - p2*q1, p2*q0 - p0*q2, p0*q1 - p1*q0):
+ *     g = dir / norm(dir);  c = cross(g, up);  right = c / norm(c);  cx = right * ((width * scale) / height);
+ *     e = cross(cx, g);  lens_v = e / norm(e);  cy = lens_v * scale;  lens_u = right;  pos = eye;
+ *     offset_over_focus = aperture > 0 ? offset / focus : 0.
+ *   APT_ERR_ARG: a NULL pointer, width or height 0, a non-finite input, |eye[k]|, |dir[k]|, |up[k]| > 2^30, norm(dir) or norm(up) <
+ *   2^-30, up parallel to dir (norm(c)^2 < 2^-40 * norm(up)^2), scale outside [2^-20, 2^20], offset < 0, aperture < 0, aperture > 0
+ *   with focus <= 0, or a finished record outside the magnitude bound above.
+ * apt_camera_check_host: the same refusals for a record filled in by hand: APT_ERR_STRUCT for a wrong struct_size; APT_ERR_ARG for a
+ *   NULL pointer, a non-finite field, a field outside the magnitude bound, g, cx or cy zero, offset < 0, aperture < 0, and with
+ *   aperture > 0: focus <= 0, lens_u or lens_v zero, offset_over_focus != offset / focus.
+ * All three return APT_ERR_STRUCT when out->struct_size is not sizeof(apt_camera): the caller sets it, as for apt_render_params. */
+int apt_camera_default_host(uint32_t width, uint32_t height, apt_camera *out);
+int apt_camera_build_host(const double eye[3], const double dir[3], const double up[3], double scale, double offset, double aperture,
+                          double focus, uint32_t width, uint32_t height, apt_camera *out);
+int apt_camera_check_host(const apt_camera *cam);
+/* The context's camera: checked (apt_camera_check_host), copied, part of the snapshot every render call takes.  NULL: back to the
+ * reference's camera.  A refused record leaves the previous one in place.  apt_set_camera = the default context. */
+int apt_context_set_camera(apt_context *ctx, const apt_camera *cam_or_null);
+int apt_set_camera(const apt_camera *cam_or_null);
+/* apt_gen_rays_device for a camera: rays [6][N] for paths [path_begin, path_begin + path_count) (APT_FLAG_BAND_BUFFERS as there), the
+ * rays the material frame entries trace with this camera set, bit for bit.  The record is the argument's, not the context's. */
+int apt_gen_rays_camera_device(const apt_render_params *p, const apt_camera *cam, void *stream, float *rays);
+
 /* ---- one process, several GPUs (the reference's 8-block split, src/render.cpp:9-10,24-27, across devices) ----
  * The frame's x-major pixel range is cut into num_bands*stripes contiguous stripes; band b renders stripes
  * b, b+num_bands, ... (stripes == 1: one contiguous band per device, the reference's split; stripes > 1
