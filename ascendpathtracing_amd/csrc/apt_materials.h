@@ -61,4 +61,7 @@ void mat_render_frame(const MatFrameCall &call);
 void mat_render_paths(const MatPathsCall &call);
 void mat_gen_rays_camera(const CamRaysCall &call);
 
+// apt_selftest_direction's launch (count > 0): the test kernel is kept out of render_kernels.hip's code object as well.
+void selftest_direction(void *stream, const double *d3_dev, uint64_t count, uint64_t *result5_dev, uint8_t *flags_dev);
+
 } // namespace apt

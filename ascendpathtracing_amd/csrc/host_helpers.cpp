@@ -19,6 +19,7 @@
 #include "apt_host.h"
 #include "pt_core.h"
 #include "pt_camera.h"
+#include "pt_leaf.h"
 
 // ---- error record and contexts (apt_host.h) ---------------------------------------------------------
 namespace {
@@ -218,6 +219,72 @@ int apt_gen_rays_host(uint32_t width, uint32_t height, uint32_t samples, uint32_
                         rays[p] = ray.ox; rays[n + p] = ray.oy; rays[2 * n + p] = ray.oz;   // SoA: :65-71
                         rays[3 * n + p] = ray.dx; rays[4 * n + p] = ray.dy; rays[5 * n + p] = ray.dz;
                     }
+    return APT_OK;
+}
+
+// The fast direction of ray-generate and its accept rule (pt_core.h fast_direction) on the host, with y = (1/sqrt(n2)) * (1 + rsq_rel_error)
+// standing in for v_rsq_f64, against the exact form (float)(d_k / sqrt(n2)).
+int apt_selftest_direction_host(const double *d3, uint64_t count, double rsq_rel_error, uint64_t *result5, uint8_t *flags) {
+    apt::clear_error();
+    if (!d3 || !result5 || !(rsq_rel_error >= -0x1p-20 && rsq_rel_error <= 0x1p-20))
+        return set_error(APT_ERR_ARG, "apt_selftest_direction_host: d3 and result5 must be non-null, |rsq_rel_error| <= 2^-20%s");
+    uint64_t max_cert = result5[4];
+    for (uint64_t i = 0; i < count; ++i) {
+        const double d0 = d3[3 * i], d1 = d3[3 * i + 1], d2 = d3[3 * i + 2];
+        const double n2 = apt::norm3_sq(d0, d1, d2), n = sqrt(n2);
+        const double y = (1.0 / n) * (1.0 + rsq_rel_error);
+        double cert;
+        const uint32_t f = apt::dir_probe(d0, d1, d2, y, (float)(d0 / n), (float)(d1 / n), (float)(d2 / n), cert);
+        result5[(f & 71u) == 71u ? 0 : 1] += 1;
+        result5[2] += ((f & (f >> 3)) & 1u) + ((f & (f >> 3)) >> 1 & 1u) + ((f & (f >> 3)) >> 2 & 1u);
+        result5[3] += (f & 64u) ? 0 : 1;
+        if (std::isfinite(cert)) {
+            const double ac = fabs(cert);
+            uint64_t b;
+            memcpy(&b, &ac, sizeof b);
+            max_cert = b > max_cert ? b : max_cert;
+        }
+        if (flags) flags[i] = (uint8_t)f;
+    }
+    result5[4] = max_cert;
+    return APT_OK;
+}
+
+// The generator states render_frame's two-paths-per-lane kernel forms by addition (pt_core.h lane_base_state, chain_state_uniform,
+// kPairStateStep), for every lane of the pixels [pixel_begin, pixel_begin + pixel_count) and every pair of the frame's plan, against the
+// definition: the two outputs of path_uniforms(seed, path) are splitmix64(s) and splitmix64(s + phi), s = splitmix64(seed) + path * kPathStride.
+// The leaf and pair loops below MIRROR render_frame_kernel's (pt_kernels.h, TWO): they are not shared with it and have to be kept in step
+// by hand; what guards the kernel itself are the frame-parity tests on the GPU.
+int apt_selftest_chain_states_host(uint32_t samples, uint64_t seed, uint64_t pixel_begin, uint64_t pixel_count, uint64_t *result3) {
+    apt::clear_error();
+    apt::LeafProg lp;
+    if (!result3 || !samples || !apt::make_leaf_plan(samples, lp))
+        return set_error(APT_ERR_ARG, "apt_selftest_chain_states_host: result3 must be non-null, samples non-zero with a pairwise plan%s");
+    const uint64_t phi = 0x9E3779B97F4A7C15ull;
+    auto differs = [&](uint64_t state, uint64_t path) {
+        const uint64_t s = apt::splitmix64(seed) + path * apt::kPathStride;
+        return apt::splitmix64(state) != apt::splitmix64(s) || apt::splitmix64(state + phi) != apt::splitmix64(s + phi);
+    };
+    for (uint64_t q = pixel_begin; q < pixel_begin + pixel_count; ++q)
+        for (uint32_t sub = 0; sub < 4; ++sub)
+            for (uint32_t j = 0; j < 8; ++j) {                                        // the lane (pt_frame.h frame_lane, GROUP == 8)
+                const uint64_t pbase = (q * 4 + sub) * samples;
+                const uint64_t lane = apt::lane_base_state(seed, pbase, j);
+                uint32_t start = 0;
+                for (uint32_t leaf = 0; leaf < lp.nleaves; ++leaf) {                   // pt_kernels.h render_frame_kernel, TWO
+                    const uint32_t n = lp.len(leaf), nfull = n & ~7u;
+                    uint32_t i8 = 0;
+                    if (samples >= 8 && nfull >= 16)
+                        for (; i8 + 16 <= nfull; i8 += 16) {
+                            const uint64_t a = apt::chain_state_uniform(lane, start + i8);
+                            result3[1] += differs(a, pbase + start + i8 + j) ? 1 : 0;
+                            result3[1] += differs(a + apt::kPairStateStep, pbase + start + i8 + 8 + j) ? 1 : 0;
+                            result3[0] += 2;
+                        }
+                    result3[2] += (nfull - i8) / 8 + (j < n - nfull ? 1 : 0);          // traced one at a time, from path_uniforms itself
+                    start += n;
+                }
+            }
     return APT_OK;
 }
 

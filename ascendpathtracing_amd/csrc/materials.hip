@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "../../include/render_mi355x.h"
 #include "apt_materials.h"
 #include "pt_core.h"
@@ -49,9 +51,41 @@ CameraEx camera_ex(const apt_camera &r, uint32_t width, uint32_t height) {
     return c;
 }
 
+// Self-test of ray-generate's fast direction (pt_core.h fast_direction, dir_probe) with the real v_rsq_f64, against this device's exact
+// form -- sqrt() and '/', what a rejected wave redoes.  A test kernel: it lives in this code object, like everything added after the
+// mirror renderer's kernels.  res: [0] += rays accepted, [1] += rays rejected, [2] += accepted components that differ, [3] += rays the
+// ray-level part rejects, [4] = max over the rays of the bits of |certificate|.
+__global__ __launch_bounds__(kBlock) void selftest_direction_kernel(const double *__restrict__ d3, uint64_t count, unsigned long long *res,
+                                                                    uint8_t *flags) {
+    unsigned long long acc = 0, rej = 0, bad = 0, ray_rej = 0, max_cert = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += (uint64_t)gridDim.x * kBlock) {
+        const double d0 = d3[3 * i], d1 = d3[3 * i + 1], d2 = d3[3 * i + 2];
+        const double n2 = norm3_sq(d0, d1, d2), n = sqrt(n2);
+        double cert;
+        const uint32_t f = dir_probe(d0, d1, d2, __builtin_amdgcn_rsq(n2), (float)(d0 / n), (float)(d1 / n), (float)(d2 / n), cert);
+        if ((f & 71u) == 71u) ++acc; else ++rej;
+        bad += __popc(f & (f >> 3) & 7u);
+        ray_rej += (f & 64u) ? 0u : 1u;
+        const double ac = fabs(cert);
+        if (ac <= 1.7976931348623157e308) max_cert = max(max_cert, (unsigned long long)__double_as_longlong(ac));
+        if (flags) flags[i] = (uint8_t)f;
+    }
+    if (acc) atomicAdd(res, acc);
+    if (rej) atomicAdd(res + 1, rej);
+    if (bad) atomicAdd(res + 2, bad);
+    if (ray_rej) atomicAdd(res + 3, ray_rej);
+    if (max_cert) atomicMax(res + 4, max_cert);
+}
+
 } // namespace
 
 namespace apt {
+
+void selftest_direction(void *stream, const double *d3, uint64_t count, uint64_t *result5, uint8_t *flags) {
+    const uint64_t blocks = std::min<uint64_t>((count + kBlock - 1) / kBlock, 256 * 16);
+    hipLaunchKernelGGL(selftest_direction_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, d3, count,
+                       (unsigned long long *)result5, flags);
+}
 
 void mat_render_frame(const MatFrameCall &c) {
     FrameArgs fa;

@@ -470,20 +470,108 @@ __device__ __forceinline__ double refined_reciprocal(double b) {
     e = fma(-b, y, 1.0);
     return fma(y, e, y);
 }
-// Validity of the fast sequences is checked ONCE per ray: `lo` = min over the two tent arguments, |xa|, |xb|,
-// |d0|, |d1|, |d2| and |d|^2 must be >= 2^-60 (nothing is zero -- its sign would matter --, denormal or absurdly
-// small: a numerator is 0 only for a handful of exact jitter values, probability ~2^-52 per path) and the norm
-// <= 2^60 (also rejects NaN / inf); everything else is bounded by construction (|x| <= w + 1, |d| < 3 with u in
-// [0, 1) and a finite camera).  If any lane of the wave fails, the whole wave recomputes the ray with sqrt() and
+// Validity of the fast sequences is checked ONCE per ray (RayCheck below): `lo` = min over the two tent arguments, |xa|, |xb|,
+// |d0|, |d1|, |d2| and the refined reciprocal square root Z of |d|^2 must be >= 2^-60 (nothing is zero -- its sign would
+// matter --, denormal or absurdly small: a numerator is 0 only for a handful of exact jitter values, probability ~2^-52
+// per path), and the direction's certificate and midpoint key must pass (fast_direction below; the certificate also rejects
+// NaN / inf, which reach |d|^2 from wherever they arise); everything else is bounded by construction (|x| <= w + 1, |d| < 3
+// with u in [0, 1) and a finite camera).  If any lane of the wave fails, the whole wave recomputes the ray with sqrt() and
 // '/'.  (One combined test instead of five wave-level branches with their own compare / select / compare
 // sequences: 17 instructions per ray less.)
 #endif
 
+// ---- the direction d / |d| of a camera ray, rounded to float32 -----------------------------------------------------------------------
+// The reference computes n = RN(sqrt(n2)), q_k = RN(d_k / n) in float64 and rounds q_k to float32 (n2 = norm3_sq(d)).  Only the
+// float32 values leave ray-generate, so the fast path makes each component with ONE multiply by a reciprocal square root and
+// accepts it only where that provably rounds to the same float32:
+//     y = v_rsq_f64(n2);  g = n2*y;  h = 0.5*y;  r = fma(-h, g, 0.5);  Y = fma(y, r, y);          (one Newton step)
+//     c = fma(RN(n2*Y), Y, -1);                                                                   (the certificate: Y^2 n2 - 1)
+//     Z = fma(-0.5*Y, c, Y);                                                                      (a second step, from the certificate)
+//     F_k = d_k * Z
+// (a) Certificate, per ray: |c| <= tau = 2^-40, and Z >= 2^-60 (a term of the ray's `lo` chain).  Write x = Y*sqrt(n2), s = x^2 - 1.
+//     RN(n2*Y) = n2*Y*(1+e1) and the fma rounds once: c = (s + x^2 e1)(1+e2), |e_i| <= 2^-53, so |c| <= tau gives |s| < 2^-39.99 and
+//     c = s + delta with |delta| < 2^-53 (1 + 2^-38).  Z > 0 and |c| < 1 make Y > 0, so x > 0.  With z = Z*sqrt(n2) = x (1 - c/2)(1+e3):
+//     z^2 = (1+s)(1 - c + c^2/4)(1+e3)^2 = (1 - delta - s^2 + c^2/4 - s delta + s c^2/4)(1+e3)^2, hence |z^2 - 1| < 3 * 2^-53 (1 + 2^-25)
+//     and |z - 1| = |z^2 - 1| / (z + 1) < 0.76 * 2^-52 =: eta.  Nothing but IEEE float64 operations on n2 and Y enters: whatever
+//     v_rsq_f64 returned, a Z that passes is that accurate (a NaN fails the comparison).  The instruction is documented to 2^29 float64
+//     ulps, a relative error e <= 2^-23; one Newton step leaves c ~ 3 e^2 <= 3 * 2^-46, and tau admits e up to 2^-20.8.  (The one-step
+//     form alone, F_k = d_k*Y, would need |c| <= 2^-47, e <= 2^-24.3, to stay inside the window of (b): more than is documented.)
+// (b) With v = d_k/sqrt(n2):  q_k = v*(1+e4)/(1+e5) and F_k = v*z*(1+e6), |e_i| <= 2^-53 (every value is a normal float64:
+//     |d_k| >= 2^-60 by `lo`, sqrt(n2) <= 2^60*(1+eta) by Z >= 2^-60, so 2^-120 <= |v| <= 1 + 2^-51).  Then
+//     |q_k - F_k| <= |v| * (2^-52 + eta + 2^-53 + ...) < 2.3 * 2^-52 * |v| < 5 ulp(F_k)             [ulp(F) > 2^-53 |F|, |F| >= |v|(1 - 2^-51)].
+//     Float32 results in this range are normal, so the float32 neighbours of F_k are 2^29 ulp(F_k) apart (half that below a
+//     power of two) and the rounding midpoints inside F_k's binade are where the low 29 bits of F_k equal 2^28; the nearest
+//     midpoint outside the binade is >= 2^27 ulps away.  A component is accepted when its low 29 bits L have |L - 2^28| >
+//     kDirMidD = 256: then no midpoint lies within 256 ulp(F_k) of F_k, q_k (fewer than 5 away) lies on the same side of all
+//     of them, and (float)F_k == (float)q_k.  256 leaves a factor 50 over the bound; 3 * 513 / 2^29 = 2.9e-6 of the rays fail.
+//     The key below is (L - (2^28 - D)) mod 2^29 in the top 29 bits of a dword: one add-and-shift; inside the window <=> key <= 16 D.
+constexpr double kDirCertTau = 0x1p-40;
+constexpr uint32_t kDirMidD = 256;
+APT_HD uint32_t f64_low_dword(double f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__double_as_longlong(f);
+#else
+    uint64_t b;
+    memcpy(&b, &f, sizeof b);
+    return (uint32_t)b;
+#endif
+}
+APT_HD uint32_t dir_mid_key(double f) { return (f64_low_dword(f) + (0xF0000000u + kDirMidD)) << 3; }
+APT_HD uint32_t min3_u32(uint32_t a, uint32_t b, uint32_t c) { const uint32_t m = a < b ? a : b; return m < c ? m : c; }
+// y: an approximation of 1/sqrt(n2) (v_rsq_f64 on the device; the host self-test hands in perturbed values).  cert and mid are
+// what ray_check_ok() tests; Z goes into the ray's `lo` chain.
+APT_HD void fast_direction(double d0, double d1, double d2, double n2, double y, double &f0, double &f1, double &f2, double &Z,
+                           double &cert, uint32_t &mid) {
+    const double g = n2 * y, h = 0.5 * y;
+    const double r = fma(-h, g, 0.5);
+    const double Y = fma(y, r, y);
+    cert = fma(n2 * Y, Y, -1.0);
+    Z = fma(-0.5 * Y, cert, Y);
+    f0 = d0 * Z; f1 = d1 * Z; f2 = d2 * Z;
+    mid = min3_u32(dir_mid_key(f0), dir_mid_key(f1), dir_mid_key(f2));
+}
+// One vector through the fast direction and its accept rule, as the self-tests see it (host: apt_selftest_direction_host with a
+// stand-in for v_rsq_f64; device: apt_selftest_direction with the instruction).  y: the reciprocal square root handed in; e0..e2: the
+// exact form's float32 results.  -> bit k: component k is accepted (the ray-level part -- |d_k|, Z >= 2^-60 and the certificate --
+// and its own midpoint key pass), bit 3 + k: (float)F_k differs from e_k in its bits, bit 6: the ray-level part passes.
+APT_HD uint32_t float_bits(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_uint(f);
+#else
+    uint32_t b;
+    memcpy(&b, &f, sizeof b);
+    return b;
+#endif
+}
+APT_HD uint32_t dir_probe(double d0, double d1, double d2, double y, float e0, float e1, float e2, double &cert) {
+    double q0, q1, q2, Z;
+    uint32_t mid;
+    fast_direction(d0, d1, d2, norm3_sq(d0, d1, d2), y, q0, q1, q2, Z, cert, mid);
+    const bool ray = (fabs(d0) >= 0x1p-60) & (fabs(d1) >= 0x1p-60) & (fabs(d2) >= 0x1p-60) & (Z >= 0x1p-60) & (fabs(cert) <= kDirCertTau);
+    uint32_t r = ray ? 64u : 0u;
+    r |= (ray & (dir_mid_key(q0) > 16u * kDirMidD)) ? 1u : 0u;
+    r |= (ray & (dir_mid_key(q1) > 16u * kDirMidD)) ? 2u : 0u;
+    r |= (ray & (dir_mid_key(q2) > 16u * kDirMidD)) ? 4u : 0u;
+    r |= float_bits((float)q0) != float_bits(e0) ? 8u : 0u;
+    r |= float_bits((float)q1) != float_bits(e1) ? 16u : 0u;
+    r |= float_bits((float)q2) != float_bits(e2) ? 32u : 0u;
+    return r;
+}
+// What a ray's fast sequences hand to the one validity test; two rays combine theirs (ray_check_both) before the test.
+struct RayCheck { double lo, cert; uint32_t mid; };
+// ('&', not '&&': three compares and two scalar ANDs, no branches between them)
+APT_HD bool ray_check_ok(const RayCheck &k) { return (k.lo >= 0x1p-60) & (fabs(k.cert) <= kDirCertTau) & (k.mid > 16u * kDirMidD); }
+// The same for a ray whose direction keeps the correctly rounded sequences (camera_ray_t<true, false>: the sample-queue kernels, whose
+// refill block has no registers to spare for the new form): lo covers |d|^2 as well, `cert` carries the norm, which must be <= 2^60
+// (also rejects NaN / inf).
+APT_HD bool ray_check_ok_rn(const RayCheck &k) { return (k.lo >= 0x1p-60) & (k.cert <= 0x1p60); }
+
 // Outputs are six scalar references on purpose: an aggregate result gets its stores merged into
 // vector stores to a stack slot that SROA can then no longer promote (it ended up in scratch).
-template <bool FAST, class CAM>
-APT_HD bool camera_ray_t(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
-                         double u1, double u2, float &rox, float &roy, float &roz, float &rdx, float &rdy, float &rdz) {
+// RSQDIR (read when FAST): the direction from fast_direction; false: sqrt_f64_core, one refined reciprocal, three Markstein quotients.
+template <bool FAST, bool RSQDIR = true, class CAM>
+APT_HD void camera_ray_t(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
+                         double u1, double u2, float &rox, float &roy, float &roz, float &rdx, float &rdy, float &rdz, RayCheck &chk) {
     double arg1, arg2;
     const double ddx = tent_t<FAST>(u1, arg1), ddy = tent_t<FAST>(u2, arg2);
     const double xa = ((double)sx + 0.5 + ddx) / 2 + (double)i, xb = ((double)sy + 0.5 + ddy) / 2 + (double)j;
@@ -510,37 +598,49 @@ APT_HD bool camera_ray_t(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint3
     roy = (float)(c.pos[1] + d1 * 140);
     roz = (float)(c.pos[2] + d2 * 140);
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (FAST) {
+    if (FAST && !RSQDIR) {
         const double n = sqrt_f64_core(n2);
         const double y = refined_reciprocal(n);
         rdx = (float)div_by_rn_reciprocal(d0, n, y);                         // :46
         rdy = (float)div_by_rn_reciprocal(d1, n, y);
         rdz = (float)div_by_rn_reciprocal(d2, n, y);
-        double lo = min3_abs_f64(arg1, arg2, xa); // everything the fast sequences need bounded away from zero
+        double lo = min3_abs_f64(arg1, arg2, xa);
         lo = min3_abs_f64(lo, xb, d0);
         lo = min3_abs_f64(lo, d1, d2);
         asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(n2));
-        return lo >= 0x1p-60 && n <= 0x1p60;
+        chk.lo = lo; chk.cert = n;
+        return;
+    }
+    if (FAST) {
+        double q0, q1, q2, Z;
+        fast_direction(d0, d1, d2, n2, __builtin_amdgcn_rsq(n2), q0, q1, q2, Z, chk.cert, chk.mid);
+        rdx = (float)q0; rdy = (float)q1; rdz = (float)q2;                   // :46, where the ray's check passes
+        double lo = min3_abs_f64(arg1, arg2, xa); // everything the fast sequences need bounded away from zero
+        lo = min3_abs_f64(lo, xb, d0);
+        lo = min3_abs_f64(lo, d1, d2);
+        asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(Z));
+        chk.lo = lo;
+        return;
     }
 #endif
     const double n = sqrt(n2);
     rdx = (float)(d0 / n);                                                   // :46
     rdy = (float)(d1 / n);
     rdz = (float)(d2 / n);
-    return true;
 }
 
 // Outputs are six scalar references on purpose: an aggregate result gets its stores merged into
 // vector stores to a stack slot that SROA can then no longer promote (it ended up in scratch).
-template <class CAM>
+template <bool RSQDIR = true, class CAM>
 APT_HD void camera_ray(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
                        double u1, double u2, float &rox, float &roy, float &roz, float &rdx, float &rdy, float &rdz) {
+    RayCheck chk;
 #if defined(__HIP_DEVICE_COMPILE__)
-    const bool ok = camera_ray_t<true>(c, w, h, i, j, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) == 0, 1)) return;
+    camera_ray_t<true, RSQDIR>(c, w, h, i, j, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz, chk);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(RSQDIR ? ray_check_ok(chk) : ray_check_ok_rn(chk))) == 0, 1)) return;
     asm volatile("" ::: "memory"); // keeps the exact form out of the hot path's schedule
 #endif
-    (void)camera_ray_t<false>(c, w, h, i, j, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
+    camera_ray_t<false>(c, w, h, i, j, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz, chk);
 }
 APT_HD Ray camera_ray(const Camera &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
                       double u1, double u2) {
@@ -586,6 +686,53 @@ APT_HD void path_uniforms_at(uint64_t state, double &u1, double &u2) {   // stat
 APT_HD void path_uniforms(uint64_t seed, uint64_t path, double &u1, double &u2) {
     path_uniforms_at(splitmix64(seed) + path * kPathStride, u1, u2);
 }
+
+// The generator states of a frame lane's chain, by addition.  Lane j of a sub-pixel traces samples j, 8 + j, 16 + j, ... of the paths
+// pbase, pbase + 1, ...: sample u + j, u the same for every lane of a wave, has the state
+//     splitmix64(seed) + (pbase + u + j) * kPathStride = lane_base_state(seed, pbase, j) + u * kPathStride        (mod 2^64)
+// -- one 64-bit multiply per lane and frame, then one 64-bit add of a product the scalar unit makes; the second sample of a pair
+// (u + 8 + j) is kPairStateStep further.  Same integers as path_uniforms(seed, pbase + u + j): the arithmetic is exact mod 2^64.
+constexpr uint64_t kPairStateStep = 8ull * kPathStride;
+APT_HD uint64_t lane_base_state(uint64_t seed, uint64_t pbase, uint32_t j) { return splitmix64(seed) + (pbase + j) * kPathStride; }
+// PRECONDITION on the device: u is the same in every lane of the wave.  The product is pinned to scalar registers, so a u that differs
+// between lanes would silently give every lane the first active lane's offset.
+APT_HD uint64_t chain_state_uniform(uint64_t lane_base, uint32_t u) {
+    uint64_t off = (uint64_t)u * kPathStride;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(off)); // the product stays on the scalar unit instead of becoming a vector multiply-add with the base
+#endif
+    return lane_base + off;
+}
+
+#if defined(__HIPCC__)
+// Both rays of a lane's path pair (pt_trace2.h PathPair: .x = the sample whose generator state is state_a, .y = the one
+// kPairStateStep further) with ONE validity test and one cold block for the two; results go straight into the pair's halves.
+template <class CAM>
+__device__ __forceinline__ void camera_ray_pair(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
+                                                uint64_t state_a, f2 &ox, f2 &oy, f2 &oz, f2 &dx, f2 &dy, f2 &dz) {
+#if defined(__HIP_DEVICE_COMPILE__)   // (the host pass of a kernel's translation unit only needs the declaration)
+    double u1a, u2a, u1b, u2b;
+    path_uniforms_at(state_a, u1a, u2a);
+    path_uniforms_at(state_a + kPairStateStep, u1b, u2b);
+    float ax, ay, az, adx, ady, adz, bx, by, bz, bdx, bdy, bdz;
+    RayCheck ka, kb;
+    camera_ray_t<true>(c, w, h, i, j, sy, sx, u1a, u2a, ax, ay, az, adx, ady, adz, ka);
+    camera_ray_t<true>(c, w, h, i, j, sy, sx, u1b, u2b, bx, by, bz, bdx, bdy, bdz, kb);
+    double lo;
+    asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(ka.lo), "v"(kb.lo));
+    // (the certificates are compared one by one: a maximum would drop a NaN)
+    const bool ok = (lo >= 0x1p-60) & (fabs(ka.cert) <= kDirCertTau) & (fabs(kb.cert) <= kDirCertTau) &
+                    ((ka.mid < kb.mid ? ka.mid : kb.mid) > 16u * kDirMidD);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {
+        asm volatile("" ::: "memory"); // keeps the exact form out of the hot path's schedule
+        camera_ray_t<false>(c, w, h, i, j, sy, sx, u1a, u2a, ax, ay, az, adx, ady, adz, ka);
+        camera_ray_t<false>(c, w, h, i, j, sy, sx, u1b, u2b, bx, by, bz, bdx, bdy, bdz, kb);
+    }
+    ox = f2{ax, bx}; oy = f2{ay, by}; oz = f2{az, bz};
+    dx = f2{adx, bdx}; dy = f2{ady, bdy}; dz = f2{adz, bdz};
+#endif
+}
+#endif
 
 // ---- uniform grid over the small spheres of a large scene ----------------------------------------
 // One flat buffer of 32-bit words, built on the host (host_helpers.cpp) or on the device (pt_grid_build.h), traversed on the device:

@@ -41,9 +41,9 @@ struct FrameLane {
     uint64_t pbase;     // path index of the sub-pixel's sample 0
 };
 template <int GROUP>
-__device__ __forceinline__ FrameLane<GROUP> frame_lane(const FrameArgs &fa) {
+__device__ __forceinline__ FrameLane<GROUP> frame_lane(const FrameArgs &fa, uint32_t tid = threadIdx.x) {
     FrameLane<GROUP> f;
-    const uint64_t L = (uint64_t)xcd_chunked_block<16>(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
+    const uint64_t L = (uint64_t)xcd_chunked_block<16>(blockIdx.x, gridDim.x) * kBlock + tid;
     f.j = (GROUP == 8) ? (uint32_t)(L & 7) : 0u;
     f.sub = (uint32_t)(L / GROUP) & 3u;
     f.pl = L / (4 * GROUP);

@@ -223,31 +223,35 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
     const Gain3 gain = load_gain(sph, ta);
     struct Col { float r, g, b; };
     auto sample = [&](uint32_t k) __attribute__((always_inline)) -> Col {
+        uint64_t pb = pbase;
+        if (TWO) { // one path at a time is the rare case there (a chain's odd member, the n % 8 tail): the lane's first path index is made again
+                   // here, from a thread index the compiler cannot see through, instead of staying in two registers across the pair loop
+            uint32_t tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            pb = frame_lane<GROUP>(fa, tid).pbase;
+        }
         double u1, u2;
-        path_uniforms(fa.seed, pbase + k, u1, u2);
+        path_uniforms(fa.seed, pb + k, u1, u2);
         float rox, roy, roz, rdx, rdy, rdz;
         camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
         PathState s;
         path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        if (SC == kScene8) traced += trace_ns8<MODE, RETIRE>(sc, tab8, s, valid, ta, pbase + k);
-        else if (SC == kSceneGrid) traced += trace_grid<MODE, RETIRE>(sph, ta.grid, s, valid, ta, pbase + k);
-        else traced += trace_dyn<MODE, RETIRE>(sph, tile, s, valid, ta, pbase + k);
+        if (SC == kScene8) traced += trace_ns8<MODE, RETIRE>(sc, tab8, s, valid, ta, pb + k);
+        else if (SC == kSceneGrid) traced += trace_grid<MODE, RETIRE>(sph, ta.grid, s, valid, ta, pb + k);
+        else traced += trace_dyn<MODE, RETIRE>(sph, tile, s, valid, ta, pb + k);
         return Col{s.rxy.x * gain.r, s.rxy.y * gain.g, s.rz * gain.b};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };
     struct Col2 { Col a, b; };
-    auto sample2 = [&](uint32_t ka, uint32_t kb) __attribute__((always_inline)) -> Col2 { // samples ka and kb of this lane's sub-pixel, traced together
+    // the generator state of this lane's sample j (pt_core.h lane_base_state): sample u + j, u wave-uniform, is u * kPathStride further
+    const uint64_t lane_state = TWO ? lane_base_state(fa.seed, pbase, j) : 0;
+    auto sample2 = [&](uint32_t u) __attribute__((always_inline)) -> Col2 { // samples u + j and u + 8 + j of this lane's sub-pixel (u wave-uniform), traced together
         PathPair pp;
-        {
-            double u1, u2;
-            float rox, roy, roz, rdx, rdy, rdz;
-            path_uniforms(fa.seed, pbase + ka, u1, u2);
-            camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
-            pp.ox.x = rox; pp.oy.x = roy; pp.oz.x = roz; pp.dx.x = rdx; pp.dy.x = rdy; pp.dz.x = rdz;
-            path_uniforms(fa.seed, pbase + kb, u1, u2);
-            camera_ray(cam, fa.width, fa.height, pi, pj, sy, sx, u1, u2, rox, roy, roz, rdx, rdy, rdz);
-            pp.ox.y = rox; pp.oy.y = roy; pp.oz.y = roz; pp.dx.y = rdx; pp.dy.y = rdy; pp.dz.y = rdz;
-        }
+        // u = start (+ i8): kernel arguments and loop counters only, the same in every lane (chain_state_uniform's precondition)
+        camera_ray_pair(cam, fa.width, fa.height, pi, pj, sy, sx, chain_state_uniform(lane_state, u), pp.ox, pp.oy, pp.oz, pp.dx, pp.dy, pp.dz);
+        // (no instruction: the six pairs are pinned to registers here.  Without it the allocator carries them through the bounce loop in
+        // the registers the conversions wrote and pays with 6 v_mov_b32 in the loop's first pair-bounce, every turn.)
+        asm("" : "+v"(pp.ox), "+v"(pp.oy), "+v"(pp.oz), "+v"(pp.dx), "+v"(pp.dy), "+v"(pp.dz));
         pp.rx = pp.ry = pp.rz = f2{1.0f, 1.0f};
         trace2_ns8<MODE>(sc, tab8, pp, ta, planes);
         traced += 2 * ta.depth;
@@ -383,10 +387,10 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
                 Col a;
                 uint32_t i8;
                 if (TWO && nfull >= 16) { // numpy's chain r[j] += a[j + 8m], two members at a time, added in order
-                    Col2 c = sample2(start + j, start + 8 + j);
+                    Col2 c = sample2(start);
                     a = add(c.a, c.b);
                     for (i8 = 16; i8 + 16 <= nfull; i8 += 16) {
-                        c = sample2(start + i8 + j, start + i8 + 8 + j);
+                        c = sample2(start + i8);
                         a = add(a, c.a);
                         a = add(a, c.b);
                     }

@@ -188,7 +188,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SC == kScene
         // (splitmix64(seed) is recomputed here, on the scalar unit, rather than kept in two scalar registers across the hot loop)
         path_uniforms_at(splitmix64(fa.seed) + base * kPathStride + (uint64_t)off * kPathStride, u1, u2);
         float rox, roy, roz, rdx, rdy, rdz;
-        camera_ray(cam, fa.width, fa.height, g_pi, g_pj, sub >> 1, sub & 1u, u1, u2, rox, roy, roz, rdx, rdy, rdz);
+        // <false>: the correctly rounded direction, as before -- the reciprocal-square-root form costs this block a float64 spill
+        camera_ray<false>(cam, fa.width, fa.height, g_pi, g_pj, sub >> 1, sub & 1u, u1, u2, rox, roy, roz, rdx, rdy, rdz);
         // (a batch is generated only into an EMPTY pool -- kPoolBatch == kPool --, so it always starts at entry 0 and the FIFO never wraps)
         static_assert(kPoolBatch == kPool, "gen_batch restarts the pool at entry 0");
         pool_head = 0;

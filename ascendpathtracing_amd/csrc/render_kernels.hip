@@ -827,6 +827,14 @@ int apt_selftest_div3(void *stream, uint64_t first, uint64_t count, uint64_t *de
     return launched();
 }
 
+int apt_selftest_direction(void *stream, const double *d3, uint64_t count, uint64_t *device_result5, uint8_t *device_flags) {
+    clear_error();
+    if (!d3 || !device_result5) return fail(APT_ERR_ARG, "apt_selftest_direction: bad arguments%s");
+    if (count == 0) return APT_OK;
+    apt::selftest_direction(stream, d3, count, device_result5, device_flags);
+    return launched();
+}
+
 int apt_test_scene(const apt_render_params *p, void *stream, const float *rays, const float *spheres, float *out) {
     clear_error();
     int rc = check_params(p);

@@ -382,6 +382,23 @@ def selftest_div3(first=0, count=1 << 32, stream=None):
     return tuple(res.tolist())
 
 
+def selftest_direction(d3, flags=False, stream=None):
+    """Ray-generate's fast direction with the device's own v_rsq_f64 against its exact form, on the float64 vectors d3 [n, 3] (a CUDA
+    tensor): -> dict(accepted, rejected, bad, ray_rejected, max_cert), with flags=True also the per-vector flag bytes (numpy).
+    `bad` counts accepted components that differ from the exact form: it must be 0."""
+    require_gpu()
+    assert d3.is_cuda and d3.dtype == torch.float64 and d3.dim() == 2 and d3.shape[1] == 3 and d3.is_contiguous()
+    res = torch.zeros(5, dtype=torch.int64, device="cuda")
+    fl = torch.zeros(d3.shape[0], dtype=torch.uint8, device="cuda") if flags else None
+    check(lib().apt_selftest_direction(_stream_handle(stream), ctypes.c_void_p(d3.data_ptr()), ctypes.c_uint64(d3.shape[0]),
+                                       ctypes.c_void_p(res.data_ptr()), ctypes.c_void_p(fl.data_ptr()) if flags else None),
+          "apt_selftest_direction")
+    torch.cuda.synchronize()
+    r = res.cpu()
+    out = dict(accepted=int(r[0]), rejected=int(r[1]), bad=int(r[2]), ray_rejected=int(r[3]), max_cert=float(r[4:5].view(torch.float64)[0]))
+    return (out, fl.cpu().numpy()) if flags else out
+
+
 def set_refill_lanes(lanes):
     """Compaction batch threshold (1..64, default 32); speed only, results do not depend on it."""
     check(lib().apt_set_refill_lanes(ctypes.c_uint32(lanes)), "apt_set_refill_lanes")

@@ -627,6 +627,26 @@ int apt_selftest_sqrt(int variant, void *stream, uint64_t first_bits, uint64_t c
  * Initialise to 0, ~0, 0. */
 int apt_selftest_div3(void *stream, uint64_t first, uint64_t count, uint64_t *device_result3);
 
+/* Self-test of ray-generate's direction: the device makes d / |d| in float32 from one refined reciprocal square root and accepts a
+ * component only where that provably rounds like the reference's float64 sqrt and divisions (csrc/pt_core.h fast_direction); a ray
+ * with a rejected component is redone in the exact form.  d3 = `count` vectors (d0, d1, d2), float64.  result5: [0] += vectors
+ * accepted, [1] += vectors rejected, [2] += accepted components whose float32 differs from the exact form's (must stay 0),
+ * [3] += vectors rejected by the ray-level part of the rule (operand range, certificate), [4] = max(bits of |certificate|) -- the
+ * caller zeroes all five.  flags (or NULL): per vector, bit k = component k accepted, bit 3 + k = component k differs, bit 6 = the
+ * ray-level part passes.
+ * apt_selftest_direction: DEVICE buffers, the real v_rsq_f64, against the device's sqrt() and `/`.
+ * apt_selftest_direction_host: HOST buffers, no GPU; (1/sqrt(n2)) * (1 + rsq_rel_error), |rsq_rel_error| <= 2^-20, stands in for the
+ * instruction. */
+int apt_selftest_direction(void *stream, const double *d3, uint64_t count, uint64_t *device_result5, uint8_t *device_flags);
+int apt_selftest_direction_host(const double *d3, uint64_t count, double rsq_rel_error, uint64_t *result5, uint8_t *flags);
+
+/* Self-test (host, no GPU) of the generator states render_frame's two-paths-per-lane kernel forms by addition -- one base state per
+ * lane, plus a multiple of the per-path stride that is the same for a whole wave -- for every lane of pixels [pixel_begin,
+ * pixel_begin + pixel_count) and every pair of samples of the frame's summation plan, against the counter generator's definition
+ * (the two 64-bit outputs of path (pixel * 4 + sub-pixel) * samples + k).  result3: [0] += samples checked, [1] += samples whose
+ * outputs differ (must stay 0), [2] += samples the kernel traces one at a time, from the definition itself; the caller zeroes them. */
+int apt_selftest_chain_states_host(uint32_t samples, uint64_t seed, uint64_t pixel_begin, uint64_t pixel_count, uint64_t *result3);
+
 /* Tuning knob of the APT_FLAG_RETIRE compaction in render_frame: a wave runs its (expensive,
  * float64) ray-generate when at least `lanes` of its 64 lanes have an empty ray slot (default
  * 32).  Speed only: results are bit-identical for every value.  Default context. */
