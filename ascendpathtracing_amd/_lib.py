@@ -15,10 +15,12 @@ APT_FLAG_EMISSION = 4
 APT_FLAG_BAND_BUFFERS = 8
 APT_FLAG_GRID_SLOTS = 16
 APT_FLAG_NEE = 32
+APT_FLAG_GLOSS = 64
 APT_ERR_DEVICE = 4
 APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH = 1, 2, 4, 8      # bits of the device status word (apt_context_check)
 APT_DEV_BAD_MATERIAL = 16
 APT_DEV_LIGHTS_MISMATCH = 32
+MAT_GLOSS = 3                           # with APT_FLAG_GLOSS: gen_data.gloss(alpha) makes the word (APT_MAT_GLOSS_WORD)
 MAT_SPEC, MAT_DIFF, MAT_REFR = 0, 1, 2  # material codes of the *_materials entries (include/render_mi355x.h APT_MAT_*)
 
 # every symbol include/render_mi355x.h declares
@@ -34,6 +36,7 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_context_check", "apt_check", "apt_context_set_debug", "apt_set_debug", "apt_context_get_debug", "apt_get_debug", "apt_grid_flags",
                "apt_render_frame_materials", "apt_context_render_frame_materials", "apt_render_paths_materials",
                "apt_context_render_paths_materials", "apt_gen_spheres_materials_host", "apt_gen_scene_materials_host",
+               "apt_materials_flags_host",
                "apt_lights_bytes", "apt_build_lights_host", "apt_render_frame_lights", "apt_context_render_frame_lights",
                "apt_render_paths_lights", "apt_context_render_paths_lights",
                "apt_camera_default_host", "apt_camera_build_host", "apt_camera_check_host", "apt_context_set_camera", "apt_set_camera",
@@ -116,6 +119,7 @@ def lib():
         h.apt_render_do.restype = None
         h.apt_multi_destroy.restype = None
         h.apt_lights_bytes.restype = ctypes.c_size_t
+        h.apt_materials_flags_host.restype = ctypes.c_uint32
         getattr(h, CXX_RENDER_DO).restype = None
         if h.apt_abi_version() != ABI_VERSION:
             raise AptError("librender_mi355x.so ABI version mismatch")

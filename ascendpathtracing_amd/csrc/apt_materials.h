@@ -21,6 +21,7 @@ struct MatTrace {                 // the parts of apt_render_params the material
     unsigned long long *traced;   // apt_set_trace_counter block, or null
     const uint32_t *lights;       // the *_lights entries: the light table (device), which then stands for `light` / `nee`; else null.
                                   // Never set without a status word: a table that is not this scene's is reported through it.
+    bool gloss;                   // APT_FLAG_GLOSS: the material table may hold APT_MAT_GLOSS words (the gloss instantiations)
 };
 
 struct MatFrameCall {             // render_frame with materials: pixels [pixel_begin, pixel_begin + pixel_count), pixel_count > 0

@@ -470,6 +470,15 @@ int apt_build_lights_host(const float *sph, uint32_t ns, const uint32_t *indices
 // so that any ray the fp32 intersection formula can possibly accept passes through the interior of a
 // cell that lists the sphere (the formula's absolute error on disc is ~1e-3 at these coordinates; the
 // margin is 0.05 + 1e-4 * coordinate scale).  Cells are sized for kGridSpheresPerCell = 0.5 sphere centres each (apt_set_debug("grid_spheres_per_cell", v) overrides: tuning knob).
+uint32_t apt_materials_flags_host(const uint32_t *materials_host, uint32_t num_spheres) {
+    if (!materials_host) return 0u;
+    for (uint32_t k = 0; k < num_spheres; ++k) {
+        const uint32_t w = materials_host[k], q = (w >> 8) & 0xFFFFu;
+        if ((w & 0xFFu) == (uint32_t)APT_MAT_GLOSS && q != 0u && (w >> 24) == 0u) return APT_FLAG_GLOSS;
+    }
+    return 0u;
+}
+
 uint32_t apt_grid_flags(const void *grid_head_host, uint32_t num_spheres) {
     apt::clear_error();
     if (!grid_head_host) return 0u;

@@ -32,8 +32,10 @@ TraceArgs mat_trace_args(const apt::MatTrace &t) {
 
 // The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.  APT_FLAG_NEE rides on it (kMatNee), or a
 // light table (kMatLights), which stands for the flag: never both.
-constexpr int mat_scene_form(bool ns8, bool grid, bool nee, bool lights, bool camera = false) {
-    return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (lights ? kMatLights : (nee ? kMatNee : 0)) | (camera ? kMatCamera : 0);
+// APT_FLAG_GLOSS rides on it as well (kMatGloss): without the flag a launch runs the instantiations it ran before the flag existed.
+constexpr int mat_scene_form(bool ns8, bool grid, bool nee, bool lights, bool gloss, bool camera = false) {
+    return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (lights ? kMatLights : (nee ? kMatNee : 0)) | (gloss ? kMatGloss : 0) |
+           (camera ? kMatCamera : 0);
 }
 
 // An apt_camera (checked by the entry that took it) as the kernels read it.
@@ -104,8 +106,10 @@ void mat_render_frame(const MatFrameCall &c) {
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) {
         with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.camera != nullptr, [&](auto cam) {
-            hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, cam), g8 ? 8 : 1>), dim3((unsigned)blocks), dim3(kBlock), lds,
-                               st, c.spheres, c.materials, fa, ta, lp);
+            with_flag(c.t.gloss, [&](auto gl) {
+                hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam), g8 ? 8 : 1>), dim3((unsigned)blocks),
+                                   dim3(kBlock), lds, st, c.spheres, c.materials, fa, ta, lp);
+            });
         }); }); });
     }); }); });
 }
@@ -115,10 +119,10 @@ void mat_render_paths(const MatPathsCall &c) {
     const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
-            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt)>), dim3((unsigned)blocks), dim3(kBlock), 0, st, c.rays,
-                               c.spheres, c.materials, c.colors, c.n, c.b, c.c, ta);
-        }); });
+        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.t.gloss, [&](auto gl) {
+            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl)>), dim3((unsigned)blocks), dim3(kBlock), 0, st,
+                               c.rays, c.spheres, c.materials, c.colors, c.n, c.b, c.c, ta);
+        }); }); });
     }); });
 }
 

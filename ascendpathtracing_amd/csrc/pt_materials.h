@@ -24,11 +24,22 @@ constexpr int kLmNone = 0, kLmNee = 1, kLmTable = 2;
 constexpr int mat_light_mode(int scn) { return (scn & kMatLights) ? kLmTable : ((scn & kMatNee) ? kLmNee : kLmNone); }
 constexpr int kMatCamera = 16;  // a context's camera (apt_context_set_camera) in the same template argument, frame kernels only: ray-generate in its general form
 static_assert((kMatCamera & (kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatCamera must be a bit of its own");
-constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera); }
+constexpr int kMatGloss = 32;   // APT_FLAG_GLOSS in the same template argument: the table may hold APT_MAT_GLOSS words (the caller's statement)
+static_assert((kMatGloss & (kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatGloss must be a bit of its own");
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss); }
 // Where a camera's CameraTail rides in a frame kernel's LeafProg: its last kCamTailWords leaf words (the launch refuses a plan that
 // reaches them).  FrameArgs is shared with render_kernels.hip's kernels and keeps its layout.
 constexpr uint32_t kCamTailLeaf = kMaxLeaves - kCamTailWords;
 constexpr int kMatTab = 24;     // 8-sphere LDS table: geometry [0, 8), albedo [8, 16), emission [16, 24)
+constexpr int kMatTabGloss = 32; // with kMatGloss: .x of [24, 32) is alpha (0 for a sphere that is not gloss).  Both sizes are one 1280-byte LDS granule
+constexpr int mat_tab_entries(int scn) { return (scn & kMatGloss) ? kMatTabGloss : kMatTab; }
+// A material word as the kernels read it with APT_FLAG_GLOSS: -> the code (0..2 as they are, 3 for a well-formed gloss word, 15 = bad
+// for everything else) and q (bits 8..23; alpha = q * 2^-16, exact).
+__device__ __forceinline__ uint32_t mat_gloss_code(uint32_t w, uint32_t &q) {
+    q = (w >> 8) & 0xFFFFu;
+    const bool gloss = (w & 0xFFu) == (uint32_t)APT_MAT_GLOSS && q != 0u && (w >> 24) == 0u;
+    return w <= (uint32_t)APT_MAT_REFR ? w : (gloss ? (uint32_t)APT_MAT_GLOSS : 15u);
+}
 
 struct MatPath {
     float ox, oy, oz, dx, dy, dz;
@@ -205,10 +216,13 @@ __device__ __forceinline__ void mat_basis(float nx, float ny, float nz, float &t
 // way and remembers its sphere (kprev >= 0 is this mode's `sampled`; -1 otherwise).  The light step then leaves out the emission of a LISTED sphere for which S held at the
 // previous bounce: the same fp32 chain on the same values (s.o is that bounce's h, geo the record the sample gathered).
 // With LM == kLmNone the arguments from `lt` on are not read and nothing of this remains in the code.
-template <int LM, int SC>
+// GL (APT_FLAG_GLOSS): `code` may be APT_MAT_GLOSS, a rough conductor of roughness `alpha` (the header's GLOSS block: visible normals of
+// the GGX distribution in their spherical-cap form, weight G1(l)); one more per-lane branch.  A direction drawn below the horizon ends
+// the path (s.live).  For the light modes it is a bounce that does not sample, like SPEC.  Without GL `alpha` is not read.
+template <int LM, int SC, bool GL>
 __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 geo, float4 alb, float4 em, uint32_t code,
                                           uint64_t mkey, uint32_t d, const MatLight &lt, uint64_t nkey, bool may, bool &sampled,
-                                          MatShadow &sh, const MatTable &tb, uint64_t lkey, int &kprev) {
+                                          MatShadow &sh, const MatTable &tb, uint64_t lkey, int &kprev, float alpha) {
     float hx = s.dx * tmin, hy = s.dy * tmin, hz = s.dz * tmin;
     hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
     const float nx0 = hx - geo.x, ny0 = hy - geo.y, nz0 = hz - geo.z;
@@ -300,6 +314,54 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
                 if (LM == kLmNee) sampled = true;
             }
         }
+    } else if (GL && code == (uint32_t)APT_MAT_GLOSS) {
+        const float nlx = into ? nx : -nx, nly = into ? ny : -ny, nlz = into ? nz : -nz;
+        float tx, ty, tz, bx, by, bz;
+        mat_basis(nlx, nly, nlz, tx, ty, tz, bx, by, bz);
+        const float wx = -s.dx, wy = -s.dy, wz = -s.dz;       // v = -d, in the frame (t, bt, nl)
+        float vx = 0.0f + wx * tx;
+        vx = vx + wy * ty;
+        vx = vx + wz * tz;
+        float vy = 0.0f + wx * bx;
+        vy = vy + wy * by;
+        vy = vy + wz * bz;
+        float vz = 0.0f + wx * nlx;
+        vz = vz + wy * nly;
+        vz = vz + wz * nlz;
+        const float sx0 = alpha * vx, sy0 = alpha * vy;       // the view direction of the stretched (alpha = 1) configuration
+        float s2 = 0.0f + sx0 * sx0;
+        s2 = s2 + sy0 * sy0;
+        s2 = s2 + vz * vz;
+        const float sl = sqrtf(s2);
+        const float sx = sx0 / sl, sy = sy0 / sl, sz = vz / sl;
+        float u1, u2;
+        mat_uniforms(mkey, d, u1, u2);
+        float sn, cs;
+        mat_sincos(u1, sn, cs);
+        const float z = (1.0f - u2) * (1.0f + sz) - sz;       // a uniform point of the spherical cap z > -s.z
+        const float r2 = 1.0f - z * z;
+        const float r = sqrtf(r2 > 0.0f ? r2 : 0.0f);
+        const float mx0 = alpha * (r * cs + sx), my0 = alpha * (r * sn + sy), mz0 = z + sz;   // the half vector, stretched back
+        float m2 = 0.0f + mx0 * mx0;
+        m2 = m2 + my0 * my0;
+        m2 = m2 + mz0 * mz0;
+        const float ml = sqrtf(m2);
+        const float mx = mx0 / ml, my = my0 / ml, mz = mz0 / ml;
+        float vm = 0.0f + vx * mx;
+        vm = vm + vy * my;
+        vm = vm + vz * mz;
+        const float vm2 = 2.0f * vm;
+        const float lx = mx * vm2 - vx, ly = my * vm2 - vy, lz = mz * vm2 - vz;
+        if (!(lz > 0.0f)) s.live = false;                     // below the horizon: the path ends here, L keeps its value
+        const float a2 = alpha * alpha;
+        const float g = (2.0f * lz) / (lz + sqrtf(a2 + (1.0f - a2) * (lz * lz)));   // G1(l), separable Smith
+        s.tx = s.tx * g; s.ty = s.ty * g; s.tz = s.tz * g;
+        const float qx = (tx * lx + bx * ly) + nlx * lz, qy = (ty * lx + by * ly) + nly * lz, qz = (tz * lx + bz * ly) + nlz * lz;
+        float q2 = 0.0f + qx * qx;
+        q2 = q2 + qy * qy;
+        q2 = q2 + qz * qz;
+        const float ql = sqrtf(q2);
+        ndx = qx / ql; ndy = qy / ql; ndz = qz / ql;
     } else {
         const float k2 = ddn * 2.0f;                          // SPEC, and the reflection of REFR
         ndx = s.dx - nx * k2; ndy = s.dy - ny * k2; ndz = s.dz - nz * k2;
@@ -449,17 +511,27 @@ struct MatScene8 {
     const float4 *tab;
     uint32_t codes;
 };
+// GL: the codes are mat_gloss_code's (3 = gloss, still 4 bits each), and alpha goes into the table's fourth block.
+template <bool GL>
 __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ sph, const uint32_t *__restrict__ mat, float4 *tab) {
     MatScene8 m;
     if (threadIdx.x < 8) {
         const int k = threadIdx.x;
         tab[16 + k] = make_float4(sph[32 + k], sph[40 + k], sph[48 + k], 0.0f);
+        if (GL) {
+            uint32_t q;
+            const bool gloss = mat_gloss_code(mat[k], q) == (uint32_t)APT_MAT_GLOSS;
+            tab[24 + k] = make_float4(gloss ? (float)q * 0x1p-16f : 0.0f, 0.0f, 0.0f, 0.0f);
+        }
     }
     (void)load_scene8<false>(sph, m.sc, tab);   // geometry and albedo entries; its barrier covers the emission entries too
     m.tab = tab;
     uint32_t codes = 0;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) codes |= min(mat[k], 15u) << (4 * k);
+    for (int k = 0; k < 8; ++k) {
+        uint32_t q;
+        codes |= (GL ? mat_gloss_code(mat[k], q) : min(mat[k], 15u)) << (4 * k);
+    }
     m.codes = codes;
     return m;
 }
@@ -469,7 +541,7 @@ __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ s
 // LM != kLmNone: after a bounce that drew a shadow segment, that segment goes through the form's own hit routine -- so it sees the scene the bounce
 // ray will see -- whenever some lane of the wave (of the workgroup for the tile form, whose scan has barriers) has one; the light is
 // visible iff the arg-min is the light (the lane's own chosen light with a table).  A traced shadow segment counts as a traced segment.
-template <int SC, int LM>
+template <int SC, int LM, bool GL>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
                                               const GridHeader &gh, const MatLight &lt, const MatTable &tb, float4 *tile, MatPath &s,
                                               const TraceArgs &ta, uint64_t path) {
@@ -485,6 +557,7 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
         int k;
         float4 geo, alb, em;
         uint32_t code;
+        float alpha = 0.0f;                                   // GL only
         if (SC == kScene8) {
             if (__all(!s.live)) break;
             if (d == 0) mat_hit8<false>(m8.sc, s, ta.eps, tmin, k);
@@ -492,6 +565,7 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
             const int g = k < 0 ? 0 : k;
             geo = m8.tab[g]; alb = m8.tab[8 + g]; em = m8.tab[16 + g];
             code = (m8.codes >> (4 * g)) & 15u;
+            if (GL) alpha = m8.tab[24 + g].x;
         } else {
             if (SC == kSceneGrid) {
                 if (__all(!s.live)) break;
@@ -505,16 +579,21 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
             alb = make_float4(sph[7 * ns + g], sph[8 * ns + g], sph[9 * ns + g], 0.0f);
             em = make_float4(sph[4 * ns + g], sph[5 * ns + g], sph[6 * ns + g], 0.0f);
             code = mat[g];
+            if (GL) {
+                uint32_t q;
+                code = mat_gloss_code(code, q);
+                alpha = (float)q * 0x1p-16f;
+            }
         }
         const bool hit = s.live && k >= 0;
-        const bool bad = hit && code > (uint32_t)APT_MAT_REFR;
+        const bool bad = hit && code > (uint32_t)(GL ? APT_MAT_GLOSS : APT_MAT_REFR);
         if (__any(bad)) report_status(ta, APT_DEV_BAD_MATERIAL);
         s.live = hit && !bad;
         const bool may = LM && d + 1 < ta.depth;              // no sample at the last bounce: the header says why
         MatShadow sh;
         sh.want = false;
         if (s.live) {
-            mat_shade<LM, SC>(s, tmin, k, geo, alb, em, code, mkey, d, lt, nkey, may, sampled, sh, tb, lkey, kprev);
+            mat_shade<LM, SC, GL>(s, tmin, k, geo, alb, em, code, mkey, d, lt, nkey, may, sampled, sh, tb, lkey, kprev, alpha);
             ++traced;
         }
         if (may && (SC == kSceneTiles ? __syncthreads_or(sh.want) : __any(sh.want))) {
@@ -572,7 +651,7 @@ __device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, fl
 }
 
 // ---- kernel: rays from a buffer -----------------------------------------------------------------------------------------------
-// SCN: the scene form, with kMatNee set for APT_FLAG_NEE or kMatLights for a light table.  Both travel in the first template argument so
+// SCN: the scene form, with kMatNee set for APT_FLAG_NEE or kMatLights for a light table, and kMatGloss.  All travel in the first template argument so
 // that the instantiations a launch without them runs keep the symbol names (and, the sampling code being dead there, the instructions)
 // they had before these existed.
 template <int SCN>
@@ -581,21 +660,22 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
                                                                   uint64_t n_total, uint64_t begin, uint64_t count, TraceArgs ta) {
     constexpr int SC = mat_scene_of(SCN);
     constexpr int LM = mat_light_mode(SCN);
-    __shared__ float4 tab[kMatTab];
+    constexpr bool GL = (SCN & kMatGloss) != 0;
+    __shared__ float4 tab[mat_tab_entries(SCN)];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
     MatTable tb;
     if (!mat_lights_header<LM>(ta, sph, tab, tb)) return;
     MatScene8 m8;
-    if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
+    if (SC == kScene8) m8 = load_mat_scene8<GL>(sph, mat, tab);
     const MatLight lt = load_mat_light<LM>(sph, ta);      // here, not after the ray loads: there it reorders the registers of the flag-off kernels
     const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = local < count;
     const uint64_t p = begin + (valid ? local : 0);
     MatPath s;
     mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
-    const uint32_t traced = trace_mat<SC, LM>(sph, mat, m8, gh, lt, tb, tile, s, ta, p);
+    const uint32_t traced = trace_mat<SC, LM, GL>(sph, mat, m8, gh, lt, tb, tile, s, ta, p);
     if (valid) {
         colors[p] = s.lx;
         colors[n_total + p] = s.ly;
@@ -630,13 +710,14 @@ __global__ __launch_bounds__(kBlock) void gen_rays_camera_kernel(CameraEx cam, u
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
-// SCN: the scene form and kMatNee / kMatLights, as for the buffer kernel, and kMatCamera.
+// SCN: the scene form and kMatNee / kMatLights / kMatGloss, as for the buffer kernel, and kMatCamera.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, TraceArgs ta, LeafProg lp) {
     constexpr int SC = mat_scene_of(SCN);
     constexpr int LM = mat_light_mode(SCN);
-    __shared__ float4 tab[kMatTab];
+    constexpr bool GL = (SCN & kMatGloss) != 0;
+    __shared__ float4 tab[mat_tab_entries(SCN)];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
     float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
@@ -649,7 +730,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     if constexpr (CAM) park_camera_ex(cam, fa, lp);
     else park_camera(cam, fa);
     MatScene8 m8;
-    if (SC == kScene8) m8 = load_mat_scene8(sph, mat, tab);
+    if (SC == kScene8) m8 = load_mat_scene8<GL>(sph, mat, tab);
     else __syncthreads();
     const MatLight lt = load_mat_light<LM>(sph, ta);
 
@@ -676,7 +757,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         }
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        traced += trace_mat<SC, LM>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k);
+        traced += trace_mat<SC, LM, GL>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k);
         return Col{s.lx, s.ly, s.lz};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };

@@ -142,7 +142,8 @@ apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls, const
     // form, which needs no promise, renders the same image then.  (ta.grid is null for the 8-sphere scene: make_trace_args.)
     // A light table stands for APT_FLAG_NEE and light_index, which its entries do not read.
     const uint32_t *lights = m.with_lights ? static_cast<const uint32_t *>(m.lights) : nullptr;
-    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, !lights && (p->flags & APT_FLAG_NEE) != 0, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced, lights};
+    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, !lights && (p->flags & APT_FLAG_NEE) != 0, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced, lights,
+                         (p->flags & APT_FLAG_GLOSS) != 0};
 }
 
 // The path range [b, b + c) of a buffer-mode call (path_count 0: to the end of the image) among the image's n_image paths.  With

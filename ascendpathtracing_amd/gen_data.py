@@ -84,13 +84,36 @@ def gen_spheres(out_dir=None):
     return sph
 
 
-def gen_spheres_materials():
+def gloss(alpha):
+    """The material word of a rough-metal sphere (APT_MAT_GLOSS_WORD; needs APT_FLAG_GLOSS in the launch's flags): GGX roughness alpha
+    in steps of 2^-16, q = round(alpha * 65536) clamped to [1, 65535].  alpha -> 0 tends to MAT_SPEC, alpha 0.5 is satin.  Pure Python."""
+    from ._lib import MAT_GLOSS
+    q = min(65535, max(1, int(round(float(alpha) * 65536.0))))
+    return MAT_GLOSS | (q << 8)
+
+
+_gloss_word = gloss     # (gen_spheres_materials has an argument of that name)
+
+
+def materials_flags(table):
+    """apt_materials_flags_host: the flags a material table earns -- APT_FLAG_GLOSS when it holds a well-formed gloss word, else 0.
+    `table`: the host array of codes (gen_spheres_materials / gen_scene_materials).  OR the result into make_params(flags=)."""
+    t = np.ascontiguousarray(np.asarray(table).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32).ravel()
+    f = lib().apt_materials_flags_host
+    f.restype = ctypes.c_uint32
+    return int(f(t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.c_uint32(t.size)))
+
+
+def gen_spheres_materials(gloss=None):
     """The material entries' demo scene (apt_gen_spheres_materials_host): gen_spheres' eight spheres plus smallpt's glass ball as
-    sphere 8 -> (spheres float32 [128] = [10][9] planes zero padded, materials int32 [9] of MAT_* codes; light index 7)."""
+    sphere 8 -> (spheres float32 [128] = [10][9] planes zero padded, materials int32 [9] of MAT_* codes; light index 7).
+    gloss=alpha: the mirror ball (sphere 6) is a rough-metal ball of that roughness instead (render with APT_FLAG_GLOSS)."""
     sph = np.zeros(128, dtype=np.float32)
     mat = np.zeros(9, dtype=np.uint32)
     check(lib().apt_gen_spheres_materials_host(_fptr(sph), mat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
           "apt_gen_spheres_materials_host")
+    if gloss is not None:
+        mat[6] = _gloss_word(gloss)
     return sph, mat.view(np.int32)
 
 

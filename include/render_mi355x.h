@@ -92,6 +92,9 @@ enum {
     APT_FLAG_NEE = 32u,    /* EXTENSION, *_materials entries only (every other entry ignores the bit): direct light sampling of  */
                            /* the sphere light_index at every diffuse hit, "direct light sampling" below.  Needs light_index >= 0  */
                            /* (APT_ERR_SCENE otherwise).  Unbiased; changes the image by noise only, at any depth.                 */
+    APT_FLAG_GLOSS = 64u,  /* EXTENSION, *_materials and *_lights entries only (every other entry ignores the bit): the CALLER states  */
+                           /* that the material table may hold APT_MAT_GLOSS words ("GLOSS" below; apt_materials_flags_host() says so */
+                           /* for a table).  Without it such a word is a bad code as before and every launch is the one it was.       */
     APT_FLAG_RR = 2u       /* EXTENSION (not in the reference; BASELINE config 5): Russian */
                            /* roulette.  After shading bounce d (0-based) with d+1 >=       */
                            /* rr_start, a path that is alive with q = max(r,g,b) > 0        */
@@ -235,7 +238,7 @@ int render_do_ex(const apt_render_params *p, void *stream,
 int render_frame(const apt_render_params *p, void *stream, const float *spheres,
                  uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8);
 
-/* ---- per-sphere materials (EXTENSION: smallpt's DIFF / SPEC / REFR, scripts/gen_data.py:77-102) ----------------------------------
+/* ---- per-sphere materials (EXTENSION: smallpt's DIFF / SPEC / REFR, scripts/gen_data.py:77-102, and a rough metal, GLOSS) ----------
  * Opt-in: the entries below take a DEVICE uint32_t materials[num_spheres]; every other entry point renders mirrors as before.  Callers
  * detect the feature by its symbols (APT_ABI_VERSION is unchanged).  Arguments are checked before any HIP call: check_params' rules
  * (except that a light_index of -1 is accepted with APT_FLAG_EMISSION, which is not read here), then APT_ERR_ARG for materials == NULL,
@@ -256,6 +259,9 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  *     hit     the K-mode test of render_do_ex for every sphere but `skip` (t = t0 > eps ? t0 : t1, accepted when t > eps, strict '<'
  *             arg-min, lowest index on ties, kMissT = 1e20 never wins).  No sphere: the path ends (L keeps its value).
  *     code    m = materials[k] of the hit sphere k; m > 2: the kernel ORs APT_DEV_BAD_MATERIAL into the status word and the path ends.
+ *             With APT_FLAG_GLOSS a word APT_MAT_GLOSS_WORD(q) -- low byte 3, q in bits 8..23 with 1 <= q <= 65535, bits 24..31 zero --
+ *             is a GLOSS sphere of roughness alpha = q * 2^-16 (exact in fp32); every other word above 2 (q == 0, a set bit 24..31, a
+ *             low byte above 3) is bad as before.  Words 0..2 mean what they mean without the flag.
  *     point   h = o + d*t (mul, then add); n = (h - c) / sqrt(dot(h - c, h - c)) (three divisions), as render_do_ex's K-mode.
  *     light   L += T * emission(k) per channel (planes 4..6), then T *= albedo(k) (planes 7..9).
  *     orient  ddn = dot(d, n); into = ddn < 0; nl = into ? n : -n.
@@ -276,9 +282,23 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  *             g = dn * nnt + sqrt(cos2t), g = into ? g : -g; v = d * nnt - n * g per component; tdir = v / sqrt(dot(v, v));
  *             c = 1 - (into ? -ddn : dot(tdir, n)); Re = APT_MAT_R0 + APT_MAT_1MR0 * ((((c * c) * c) * c) * c); Tr = 1 - Re;
  *             P = 0.25 + 0.5 * Re; u1 < P: reflect, weight Re / P; otherwise d = tdir, weight Tr / (1 - P); T *= weight per channel.
+ *     GLOSS   (APT_FLAG_GLOSS) a rough conductor: the GGX (Trowbridge-Reitz) distribution of roughness alpha, the separable Smith
+ *             shadowing term, reflectance = albedo at every angle (no Fresnel term, as SPEC has none: alpha -> 0 tends to SPEC); the
+ *             half vector is drawn from the distribution of visible normals in its spherical-cap form (Dupuy & Benyoub 2023), which
+ *             leaves the weight albedo * G1(l) <= 1.  (t, bt) = the Duff basis of nl, as DIFF's.
+ *             v = (dot(-d, t), dot(-d, bt), dot(-d, nl))                  the view direction in the frame (negation is exact)
+ *             s0 = (alpha * v.x, alpha * v.y, v.z); s = s0 / sqrt(dot(s0, s0))                       (three divisions)
+ *             (sin, cos) of 2*pi*u1 by DIFF's polynomial; z = (1 - u2) * (1 + s.z) - s.z; w = 1 - z * z; r = sqrt(w > 0 ? w : 0)
+ *             m0 = (alpha * (r * cos + s.x), alpha * (r * sin + s.y), z + s.z); m = m0 / sqrt(dot(m0, m0))
+ *             l = m * (2 * dot(v, m)) - v per component (mul, then sub).  !(l.z > 0): the path ends here; L keeps its value (this
+ *             hit's emission included), no status bit is set.  Otherwise
+ *             a2 = alpha * alpha; g = (2 * l.z) / (l.z + sqrt(a2 + (1 - a2) * (l.z * l.z))); T *= g per channel     (G1(l))
+ *             q = (t * l.x + bt * l.y) + nl * l.z per component; d = q / sqrt(dot(q, q)).
+ *             For direct light sampling and the light tables below a GLOSS hit is a bounce that does not sample, like SPEC: it draws
+ *             no shadow segment, leaves `sampled` false, and whatever the path hits next adds its emission in full.
  *     skip    o = h.  A branch that leaves on the sphere's OUTER side does not test sphere k on the next segment (skip = k; a convex
  *             sphere cannot be re-hit going outward, while the near root of a wall of radius 1e5 is fp32 noise of ~5e-3 >> eps):
- *             DIFF, SPEC and the REFR reflection leave outward iff `into`, the REFR refraction iff `!into`; otherwise skip = none.
+ *             DIFF, SPEC, GLOSS and the REFR reflection leave outward iff `into`, the REFR refraction iff `!into`; otherwise skip = none.
  *     roulette  APT_FLAG_RR as specified above, on T (the path counts as alive until it ends).
  *   colour  L.  render_frame's decode (numpy's pairwise mean, float64 sum of the 4 sub-pixels, clip, x255 truncation) is unchanged.
  *
@@ -310,7 +330,8 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  *   statistics).  Roulette, APT_DEV_BAD_MATERIAL, the grid rules and APT_FLAG_RETIRE are as above.  d2 > r2 is an fp32 decision for
  *   points near the light's surface: either answer is unbiased because `sampled` follows it.  A light of any material code or albedo
  *   needs no special case. */
-enum { APT_MAT_SPEC = 0, APT_MAT_DIFF = 1, APT_MAT_REFR = 2 };   /* a zero-filled table = all mirrors */
+enum { APT_MAT_SPEC = 0, APT_MAT_DIFF = 1, APT_MAT_REFR = 2, APT_MAT_GLOSS = 3 };   /* a zero-filled table = all mirrors */
+#define APT_MAT_GLOSS_WORD(q) ((uint32_t)APT_MAT_GLOSS | ((uint32_t)(q) << 8))   /* with APT_FLAG_GLOSS: alpha = q * 2^-16, 1 <= q <= 65535 */
 #define APT_MAT_S1  0x1.921fb6p+0f
 #define APT_MAT_S3  -0x1.4abbcep-1f
 #define APT_MAT_S5  0x1.466bc2p-4f
@@ -404,6 +425,10 @@ int apt_gen_spheres_materials_host(float *spheres, uint32_t *materials);
  * SplitMix64 (x += 0x9E3779B97F4A7C15; x = (x ^ x>>30) * 0xBF58476D1CE4E5B9; x = (x ^ x>>27) * 0x94D049BB133111EB; x ^ x>>31) and
  * uint64 wrap-around.  num_spheres < 8: APT_ERR_SCENE, like apt_gen_scene_host; materials == NULL: APT_ERR_ARG. */
 int apt_gen_scene_materials_host(uint32_t num_spheres, uint64_t seed, uint32_t *materials);
+/* HOST: the flags a material table earns, the counterpart of apt_grid_flags: APT_FLAG_GLOSS when some materials_host[k], k < num_spheres,
+ * is a well-formed APT_MAT_GLOSS_WORD (low byte 3, 1 <= q <= 65535, bits 24..31 zero), else 0 (also for NULL or an empty table).  OR the
+ * result into apt_render_params.flags.  A table without such a word renders the same image with and without the flag. */
+uint32_t apt_materials_flags_host(const uint32_t *materials_host, uint32_t num_spheres);
 
 /* ---- camera (EXTENSION: a movable camera with a thin lens for the material renderer) -------------------------------------------------
  * The reference has one camera, written into gen_rays (scripts/gen_data.py:24-30): pos (50, 52, 295.6), dir (0, -0.042612, -1), the
