@@ -148,9 +148,11 @@ __device__ __forceinline__ void div3_shared(float nx, float ny, float nz, float 
     // 2^-96; +-0 is flagged too, which only costs an exact re-run); the second is the sign bit of
     // bits(2^60) - bits(len2) (len2 >= 0 or NaN), OR-ed into `hiflag` with 2-cycle integer ops.
     // len2 itself must not have underflowed (d would be 0 or unrelated to the numerators).
-    // The seed must be v_rcp_f32(d) itself: seeding from the sqrt's v_rsq_f32(len2) (error ~1.5 ulp of
+    // With ONE Newton step the seed must be v_rcp_f32(d) itself: seeding from the sqrt's v_rsq_f32(len2) (error ~1.5 ulp of
     // 1/d) passes 2^30 random operand sets but fails 0.6 % of the self-test's structured ones (divisor
-    // mantissa all ones, where 1/d sits 2^-48 from a rounding midpoint) -- measured, rejected.
+    // mantissa all ones, where 1/d sits 2^-48 from a rounding midpoint) -- measured, rejected.  TWO Newton steps from that seed
+    // give RN(1/d) for every divisor but the all-ones mantissas, and there the failure announces itself (the second residual is
+    // exactly 2^-24): div3_seeded_packed2 below, the form of the two-path bounce.
     amin = fminf(fminf(amin, fabsf(nx)), fminf(fabsf(ny), fabsf(nz)));
     amin = fminf(amin, len2);
     hiflag |= 0x5d800000u - __float_as_uint(len2);
@@ -198,6 +200,36 @@ __device__ __forceinline__ bool div3_operands_ok(float len2, float nx, float ny,
     const float lo = fminf(fminf(fabsf(nx), fabsf(ny)), fminf(fabsf(nz), r0));
     return lo >= 0x1p-29f && r0 == r0 && nx == nx && ny == ny && nz == nz;
 }
+// The three quotients of TWO paths (one path per half of every pair) without a v_rcp_f32: the reciprocal is refined from a seed
+// the caller already has -- r0 = v_rsq_f32(len2), an approximation of 1/d to ~1.5 ulp, d = RN(sqrt(len2)) -- by two Newton
+// steps, and each quotient then takes ONE residual round (Markstein: with y = RN(1/d), q = RN(n*y), fma(fma(-d, q, n), y, q)
+// is RN(n/d)).  13 packed operations instead of 17 and two transcendentals.
+// Two Newton steps from any seed within 6 ulps give RN(1/d) for every divisor mantissa but one: all ones, d = 2^k (2 - 2^-23).
+// There 1/d = 2^-k-1 (1 + 2^-24 + 2^-48 + ...) lies 2^-48 above a rounding midpoint; the first step lands on 2^-k-1 whatever
+// the seed (unless the seed was RN(1/d) itself), the second step's exact sum r1 + e1*r1 is the midpoint, rounds to even and
+// stays there.  One quotient round does not repair a reciprocal that is 1/2 ulp off (it fails for numerators that are powers
+// of two).  But the case gives itself away: e1 = fma(-d, r1, 1) is EXACTLY 2^-24 there and nowhere else -- a reciprocal
+// that is RN(1/d) has |1 - d*r| <= d*ulp(r)/2 < 2^-24, the residual is exact, and d*r1 = 1 - 2^-24 with r1 next to 1/d has no
+// other solution in 24-bit mantissas (all 2^23 divisor mantissas x seeds of -6..+6 ulps enumerated on the host).  `e1` is
+// handed back; the caller sends the lanes with e1 == 2^-24 to the exact form (two compares per pair-bounce).
+// Validity otherwise as div3_packed's: div3_operands_ok().  apt_selftest_div3_seeded checks this function against '/'.
+__device__ __forceinline__ f2_t refine_seed_packed2(f2_t d, f2_t r0, f2_t &e1) { // -> RN(1/d) per half, unless e1 == kDiv3SeededStuck
+    const f2_t one = {1.0f, 1.0f};
+    const f2_t e0 = __builtin_elementwise_fma(-d, r0, one);
+    const f2_t r1 = __builtin_elementwise_fma(e0, r0, r0);
+    e1 = __builtin_elementwise_fma(-d, r1, one);
+    return __builtin_elementwise_fma(e1, r1, r1);
+}
+__device__ __forceinline__ void div3_seeded_packed2(f2_t nx, f2_t ny, f2_t nz, f2_t d, f2_t r0, f2_t &ux, f2_t &uy, f2_t &uz, f2_t &e1) {
+    const f2_t r = refine_seed_packed2(d, r0, e1);
+    f2_t q = nx * r;
+    ux = __builtin_elementwise_fma(__builtin_elementwise_fma(-d, q, nx), r, q);
+    q = ny * r;
+    uy = __builtin_elementwise_fma(__builtin_elementwise_fma(-d, q, ny), r, q);
+    q = nz * r;
+    uz = __builtin_elementwise_fma(__builtin_elementwise_fma(-d, q, nz), r, q);
+}
+constexpr float kDiv3SeededStuck = 0x1p-24f; // e1 of a lane whose reciprocal stayed on the wrong side of its midpoint
 #endif
 
 // The two roots b -/+ q of one ray/sphere pair in the reference's own form (rt_helper.h:263-331), sqrtf() for the square root.

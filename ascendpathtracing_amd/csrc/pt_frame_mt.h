@@ -120,7 +120,6 @@ __global__ __launch_bounds__(kBlock, APT_TWO_WAVES) void render_frame_mt_kernel(
             if (half == 0) { pp.ox.x = rox; pp.oy.x = roy; pp.oz.x = roz; pp.dx.x = rdx; pp.dy.x = rdy; pp.dz.x = rdz; }
             else { pp.ox.y = rox; pp.oy.y = roy; pp.oz.y = roz; pp.dx.y = rdx; pp.dy.y = rdy; pp.dz.y = rdz; }
         }
-        pp.rx = pp.ry = pp.rz = f2{1.0f, 1.0f};
         trace2_ns8<MODE>(sc, tab8, pp, ta, planes);            // full trace of both paths (lanes past the range compute garbage)
         traced += (valid[0] ? ta.depth : 0u) + (valid[1] ? ta.depth : 0u);
         cbuf[t] = pp.rx.x * gain.r; cbuf[kMtRound + t] = pp.ry.x * gain.g; cbuf[2 * kMtRound + t] = pp.rz.x * gain.b; // render.cpp:194-196
@@ -249,7 +248,6 @@ __global__ __launch_bounds__(kBlock, APT_TWO_WAVES) void render_frame_mt_any_ker
             if (half == 0) { pp.ox.x = rox; pp.oy.x = roy; pp.oz.x = roz; pp.dx.x = rdx; pp.dy.x = rdy; pp.dz.x = rdz; }
             else { pp.ox.y = rox; pp.oy.y = roy; pp.oz.y = roz; pp.dx.y = rdx; pp.dy.y = rdy; pp.dz.y = rdz; }
         }
-        pp.rx = pp.ry = pp.rz = f2{1.0f, 1.0f};
         trace2_ns8<MODE>(sc, tab8, pp, ta, planes);
         traced += (valid[0] ? ta.depth : 0u) + (valid[1] ? ta.depth : 0u);
         {

@@ -65,7 +65,6 @@ __global__ __launch_bounds__(kBlock, APT_TWO_WAVES) void render_paths2_kernel(co
         pp.ox = f2{rays[pa], rays[pb]}; pp.oy = f2{rays[n_total + pa], rays[n_total + pb]}; pp.oz = f2{rays[2 * n_total + pa], rays[2 * n_total + pb]};
         pp.dx = f2{rays[3 * n_total + pa], rays[3 * n_total + pb]}; pp.dy = f2{rays[4 * n_total + pa], rays[4 * n_total + pb]};
         pp.dz = f2{rays[5 * n_total + pa], rays[5 * n_total + pb]};
-        pp.rx = pp.ry = pp.rz = f2{1.0f, 1.0f};            // render.cpp:116-121
         trace2_ns8<MODE>(sc, tab8, pp, ta, sc.planes);
         if (va) { colors[pa] = pp.rx.x * gain.r; colors[n_total + pa] = pp.ry.x * gain.g; colors[2 * n_total + pa] = pp.rz.x * gain.b; }   // CopyOut :210-223
         if (vb) { colors[pb] = pp.rx.y * gain.r; colors[n_total + pb] = pp.ry.y * gain.g; colors[2 * n_total + pb] = pp.rz.y * gain.b; }
@@ -252,7 +251,6 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
         // (no instruction: the six pairs are pinned to registers here.  Without it the allocator carries them through the bounce loop in
         // the registers the conversions wrote and pays with 6 v_mov_b32 in the loop's first pair-bounce, every turn.)
         asm("" : "+v"(pp.ox), "+v"(pp.oy), "+v"(pp.oz), "+v"(pp.dx), "+v"(pp.dy), "+v"(pp.dz));
-        pp.rx = pp.ry = pp.rz = f2{1.0f, 1.0f};
         trace2_ns8<MODE>(sc, tab8, pp, ta, planes);
         traced += 2 * ta.depth;
         return Col2{Col{pp.rx.x * gain.r, pp.ry.x * gain.g, pp.rz.x * gain.b}, Col{pp.rx.y * gain.r, pp.ry.y * gain.g, pp.rz.y * gain.b}};

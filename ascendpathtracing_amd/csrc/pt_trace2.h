@@ -12,6 +12,8 @@
 // Same arithmetic as bounce_ns8_v2 (pt_trace.h), operation for operation: v_pk_{add,mul,fma}_f32 round each half
 // like the scalar instruction.  Used for the frame kernel without APT_FLAG_RETIRE and APT_FLAG_RR only.
 #pragma once
+#include <type_traits>
+
 #include "pt_trace.h"
 
 namespace {
@@ -21,10 +23,12 @@ struct PathPair { // .x = path A, .y = path B
     f2 rx, ry, rz;             // throughputs
 };
 
-__device__ __forceinline__ PathState unpack_path(const PathPair &p, int which, uint64_t alive) {
+// first: the pair has no throughputs yet -- path_init's (1, 1, 1) and alive = 1 stand
+__device__ __forceinline__ PathState unpack_path(const PathPair &p, int which, uint64_t alive, bool first) {
     PathState s;
     if (which == 0) path_init(s, p.ox.x, p.oy.x, p.oz.x, p.dx.x, p.dy.x, p.dz.x);
     else path_init(s, p.ox.y, p.oy.y, p.oz.y, p.dx.y, p.dy.y, p.dz.y);
+    if (first) return s;
     s.rxy = which == 0 ? f2{p.rx.x, p.ry.x} : f2{p.rx.y, p.ry.y};
     s.rz = which == 0 ? p.rz.x : p.rz.y;
     s.alive = select_const(alive, 1);
@@ -43,15 +47,23 @@ __device__ __forceinline__ float sum3_f64(float p0, float p1, float p2) {
 // One bounce of both paths.  aliveA / aliveB: wave masks (in: before, out: after).  redoA / redoB: wave masks of
 // the lanes whose path A / B left the validity range of the fast sequences.  `ones_off`: byte offset, relative to the albedo
 // table, of an entry (1, 1, 1) -- a path that is no longer alive multiplies its throughput by it (x1 is exact).
-template <int MODE, bool PLANES>
-__device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, const PathPair &s, PathPair &n,
-                                            const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
-                                            uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
+// FIRST: the first bounce of a pair.  Both paths are alive and their throughput is (1, 1, 1) by definition: s.rx / ry / rz and
+// the incoming masks are not read, the new masks are ~light, and the new throughput IS the albedo entry (or the (1, 1, 1) entry
+// for a path that hit the light) -- no products.
+template <int MODE, bool PLANES, bool FIRST>
+__device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, const PathPair &s, PathPair &n,
+                                              const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
+                                              uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f; // per path: a finished path's request for the exact form can be ignored (trace2_ns8)
     const Hit8 hA = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
     const Hit8 hB = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
-    aliveA &= ~hA.light;                    // rt_helper.h:773-787  alive &= idx != light
-    aliveB &= ~hB.light;
+    if (FIRST) {
+        aliveA = ~hA.light;
+        aliveB = ~hB.light;
+    } else {
+        aliveA &= ~hA.light;                // rt_helper.h:773-787  alive &= idx != light
+        aliveB &= ~hB.light;
+    }
     // centre and albedo of the two hit spheres: dword reads from the LDS table straight into (A, B) pairs
     const char *geo = reinterpret_cast<const char *>(tab.geo);
     uint32_t cA, cB; // albedo entry, or the (1,1,1) entry once the path is not alive (rt_helper.h:799-810: ret *= alive ? albedo : 1)
@@ -88,8 +100,8 @@ __device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, co
         len2 = len2 + nz * nz;
     }
     f2 L;
+    const f2 r0 = {__builtin_amdgcn_rsqf(len2.x), __builtin_amdgcn_rsqf(len2.y)};
     {   // sqrt_rn_rsq1 on both paths
-        const f2 r0 = {__builtin_amdgcn_rsqf(len2.x), __builtin_amdgcn_rsqf(len2.y)};
         aminA = minimum3_abs_after_trans(aminA, r0.x, nx.x);    // validity of the fast sqrt / divide sequences: see kFastMin (pt_trace.h)
         aminA = minimum3_abs(aminA, ny.x, nz.x);
         aminB = minimum3_abs_after_trans(aminB, r0.y, nx.y);
@@ -98,21 +110,10 @@ __device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, co
         const f2 r = __builtin_elementwise_fma(-y, y, len2);
         L = __builtin_elementwise_fma(r, h, y);
     }
-    f2 ux, uy, uz;
-    {   // div3_packed's sequence (pt_core.h) with (A, B) in the halves: one refined reciprocal per path, three quotients
-        const f2 r0 = {__builtin_amdgcn_rcpf(L.x), __builtin_amdgcn_rcpf(L.y)};
-        const f2 one = {1.0f, 1.0f};
-        const f2 e0 = __builtin_elementwise_fma(-L, r0, one);
-        const f2 r = __builtin_elementwise_fma(e0, r0, r0);
-        auto quot = [&](const f2 num) __attribute__((always_inline)) {
-            f2 q = num * r;
-            f2 e = __builtin_elementwise_fma(-L, q, num);
-            q = __builtin_elementwise_fma(e, r, q);
-            e = __builtin_elementwise_fma(-L, q, num);
-            return __builtin_elementwise_fma(e, r, q);
-        };
-        ux = quot(nx); uy = quot(ny); uz = quot(nz);
-    }
+    // the three quotients of both paths, the reciprocal refined from the square root's own seed (pt_core.h): no v_rcp_f32.  A lane
+    // whose divisor has an all-ones mantissa can come out with e1 == 2^-24 and then joins the exact re-run below.
+    f2 ux, uy, uz, e1;
+    div3_seeded_packed2(nx, ny, nz, L, r0, ux, uy, uz, e1);
     f2 dot;
     if (MODE == kModeOracle) {
         const f2 p0 = s.dx * ux, p1 = s.dy * uy, p2 = s.dz * uz;
@@ -125,24 +126,44 @@ __device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, co
     const f2 k2 = twice_canonical(dot);                                            // :697
     n.dx = s.dx - ux * k2; n.dy = s.dy - uy * k2; n.dz = s.dz - uz * k2;           // :699-704
     n.ox = hx; n.oy = hy; n.oz = hz;                                               // :706-708
-    n.rx = ax * s.rx; n.ry = ay * s.ry; n.rz = az * s.rz;                          // :804-810 (albedo or 1)
-    redoA = __builtin_amdgcn_ballot_w64(!(aminA >= kFastMin)); // something too small, len2 > 2^60, or a NaN
-    redoB = __builtin_amdgcn_ballot_w64(!(aminB >= kFastMin));
+    if (FIRST) { n.rx = ax; n.ry = ay; n.rz = az; }
+    else { n.rx = ax * s.rx; n.ry = ay * s.ry; n.rz = az * s.rz; }                 // :804-810 (albedo or 1)
+    // something too small, len2 > 2^60, or a NaN; or the reciprocal of an all-ones divisor that did not converge
+    redoA = __builtin_amdgcn_ballot_w64(!(aminA >= kFastMin)) | __builtin_amdgcn_ballot_w64(e1.x == kDiv3SeededStuck);
+    redoB = __builtin_amdgcn_ballot_w64(!(aminB >= kFastMin)) | __builtin_amdgcn_ballot_w64(e1.y == kDiv3SeededStuck);
+}
+template <int MODE, bool PLANES>
+__device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, const PathPair &s, PathPair &n,
+                                            const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
+                                            uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
+    bounce2_ns8_t<MODE, PLANES, false>(sc, tab, s, n, ta, kc, ones_off, aliveA, aliveB, redoA, redoB);
+}
+template <int MODE, bool PLANES>
+__device__ __forceinline__ void bounce2_ns8_first(const Scene8 &sc, const Tab8 tab, const PathPair &s, PathPair &n,
+                                                  const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
+                                                  uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
+    bounce2_ns8_t<MODE, PLANES, true>(sc, tab, s, n, ta, kc, ones_off, aliveA, aliveB, redoA, redoB);
 }
 
 // The LAST bounce of both paths.  Nothing traces the ray it would produce (the callers read the throughputs only), so of a
 // bounce it keeps what reaches the frame: the arg-min, alive &= idx != light, and the throughput times the hit sphere's
 // albedo (or 1) -- rx / ry / rz receive those products.  No hit point, normal, square root, quotient or reflection; only the
 // albedo entries are read from LDS; the validity chain ends with the discriminants (nothing else here uses a fast sequence).
-template <int MODE, bool PLANES>
+// FIRST (depth 1: the last bounce is also the first): as in bounce2_ns8_t.
+template <int MODE, bool PLANES, bool FIRST = false>
 __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 tab, const PathPair &s, f2 &rx, f2 &ry, f2 &rz,
                                                  const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                                  uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f;
     const Hit8 hA = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
     const Hit8 hB = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
-    aliveA &= ~hA.light;                    // rt_helper.h:773-787  alive &= idx != light
-    aliveB &= ~hB.light;
+    if (FIRST) {
+        aliveA = ~hA.light;
+        aliveB = ~hB.light;
+    } else {
+        aliveA &= ~hA.light;                // rt_helper.h:773-787  alive &= idx != light
+        aliveB &= ~hB.light;
+    }
     uint32_t cA, cB; // as in bounce2_ns8
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cA) : "v"(ones_off), "v"(hA.addr), "s"(aliveA));
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(cB) : "v"(ones_off), "v"(hB.addr), "s"(aliveB));
@@ -155,14 +176,18 @@ __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 ta
                  : "=&v"(axA), "=&v"(ayA), "=&v"(azA), "=&v"(axB), "=&v"(ayB), "=&v"(azB)
                  : "v"(aA), "v"(aB)
                  : "memory");
-    rx = f2{axA, axB} * s.rx; ry = f2{ayA, ayB} * s.ry; rz = f2{azA, azB} * s.rz;  // :804-810 (albedo or 1)
+    if (FIRST) { rx = f2{axA, axB}; ry = f2{ayA, ayB}; rz = f2{azA, azB}; }
+    else { rx = f2{axA, axB} * s.rx; ry = f2{ayA, ayB} * s.ry; rz = f2{azA, azB} * s.rz; } // :804-810 (albedo or 1)
     redoA = __builtin_amdgcn_ballot_w64(!(aminA >= kFastMin)); // a discriminant too small, or a NaN
     redoB = __builtin_amdgcn_ballot_w64(!(aminB >= kFastMin));
 }
 
 // All bounces of both paths (full trace: no retirement, no roulette).  The hot loop has no merge with the exact
-// form and no state copies (two bounces per turn, ping-pong): see trace_ns8.  On return only the throughputs of `s` are
-// meaningful: depth - 1 bounces produce a ray, the last one (bounce2_ns8_last) does not.
+// form and no state copies (two bounces per turn, ping-pong): see trace_ns8.  On entry `s` holds the two rays; its throughputs
+// are not read (a fresh path's is (1, 1, 1), and the first bounce is a form of its own that knows it).  On return only the
+// throughputs of `s` are meaningful: depth - 1 bounces produce a ray, the last one (bounce2_ns8_last) does not.
+//   depth 0: throughput 1.   depth 1: last<first>(s).   depth >= 2: first(s -> n), ping-pong steps from n, last from whichever
+//   half holds the state.
 template <int MODE, bool PLANES>
 __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta) {
     const KeyConsts kc = make_key_consts(ta.eps);
@@ -176,29 +201,31 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
     // round 3: C2 20.40 against 19.95 ms, the longer body costs the ray-generate part more registers than the copies cost; not kept.)
     const bool fast_ok = eps_allows_rootkey(ta.eps);
     // the request of a path that is already finished (alive bit cleared or throughput zero) is ignored: it cannot
-    // reach any output any more (deep all-miss paths, |n| ~ 1e20, are of that kind)
-    auto redo_stands = [&](const PathPair &in, uint64_t redoA, uint64_t redoB) __attribute__((always_inline)) {
+    // reach any output any more (deep all-miss paths, |n| ~ 1e20, are of that kind).  A path at its first bounce is never finished.
+    auto redo_stands = [&](const PathPair &in, uint64_t redoA, uint64_t redoB, bool first) __attribute__((always_inline)) {
+        if (first) return (redoA | redoB) != 0;
         const bool finA = select_const(aliveA, 1) == 0 || (in.rx.x == 0.0f && in.ry.x == 0.0f && in.rz.x == 0.0f);
         const bool finB = select_const(aliveB, 1) == 0 || (in.rx.y == 0.0f && in.ry.y == 0.0f && in.rz.y == 0.0f);
         return __builtin_amdgcn_ballot_w64((select_const(redoA, 1) != 0 && !finA) || (select_const(redoB, 1) != 0 && !finB)) != 0;
     };
-    auto exact_pair = [&](const PathPair &in, PathState &na, PathState &nb) __attribute__((always_inline)) {
-        PathState a = unpack_path(in, 0, aliveA), b = unpack_path(in, 1, aliveB);
+    auto exact_pair = [&](const PathPair &in, PathState &na, PathState &nb, bool first) __attribute__((always_inline)) {
+        PathState a = unpack_path(in, 0, aliveA, first), b = unpack_path(in, 1, aliveB, first);
         bounce_ns8_exact<MODE>(sc, tab, a, na, ta);
         bounce_ns8_exact<MODE>(sc, tab, b, nb, ta);
         if (ta.traced && (threadIdx.x & 63) == 0) atomicAdd(ta.traced + 3, 1ull); // statistics: exact re-runs of a wave-bounce
     };
-    auto step = [&](const PathPair &in, PathPair &out) __attribute__((always_inline)) {
+    auto step = [&](const PathPair &in, PathPair &out, auto first_tag) __attribute__((always_inline)) {
+        constexpr bool first = decltype(first_tag)::value;
         uint64_t oa = aliveA, ob = aliveB;
         bool redo_any = !fast_ok;
         if (__builtin_expect(fast_ok, 1)) {
             uint64_t redoA, redoB;
-            bounce2_ns8<MODE, PLANES>(sc, tab, in, out, ta, kc, ones_off, oa, ob, redoA, redoB);
-            if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB);
+            bounce2_ns8_t<MODE, PLANES, first>(sc, tab, in, out, ta, kc, ones_off, oa, ob, redoA, redoB);
+            if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB, first);
         }
         if (__builtin_expect(redo_any, 0)) {
             PathState na, nb;
-            exact_pair(in, na, nb);
+            exact_pair(in, na, nb, first);
             out.ox = f2{na.oxy.x, nb.oxy.x}; out.oy = f2{na.oxy.y, nb.oxy.y}; out.oz = f2{na.oz, nb.oz};
             out.dx = f2{na.dxy.x, nb.dxy.x}; out.dy = f2{na.dxy.y, nb.dxy.y}; out.dz = f2{na.dz, nb.dz};
             out.rx = f2{na.rxy.x, nb.rxy.x}; out.ry = f2{na.rxy.y, nb.rxy.y}; out.rz = f2{na.rz, nb.rz};
@@ -208,35 +235,47 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
         aliveA = oa; aliveB = ob;
     };
     // The last bounce, state in `in`: throughputs -> s.  Its exact form is the whole exact bounce with the ray ignored.
-    auto last = [&](const PathPair &in) __attribute__((always_inline)) {
+    auto last = [&](const PathPair &in, auto first_tag) __attribute__((always_inline)) {
+        constexpr bool first = decltype(first_tag)::value;
         uint64_t oa = aliveA, ob = aliveB; // (nothing reads the alive masks after this bounce: they are not written back)
         f2 rx, ry, rz;
         bool redo_any = !fast_ok;
         if (__builtin_expect(fast_ok, 1)) {
             uint64_t redoA, redoB;
-            bounce2_ns8_last<MODE, PLANES>(sc, tab, in, rx, ry, rz, ta, kc, ones_off, oa, ob, redoA, redoB);
-            if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB);
+            bounce2_ns8_last<MODE, PLANES, first>(sc, tab, in, rx, ry, rz, ta, kc, ones_off, oa, ob, redoA, redoB);
+            if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB, first);
         }
         if (__builtin_expect(redo_any, 0)) {
             PathState na, nb;
-            exact_pair(in, na, nb);
+            exact_pair(in, na, nb, first);
             rx = f2{na.rxy.x, nb.rxy.x}; ry = f2{na.rxy.y, nb.rxy.y}; rz = f2{na.rz, nb.rz};
         }
         s.rx = rx; s.ry = ry; s.rz = rz;
     };
-    if (ta.depth == 0) return;
-    const uint32_t full = ta.depth - 1; // bounces whose ray is traced on
+    using Yes = std::true_type;   // "this is the pair's first bounce", as a type: the lambdas pick their bounce form by it
+    using No = std::false_type;
+    if (ta.depth == 0) {
+        const f2 one = {1.0f, 1.0f};
+        s.rx = one; s.ry = one; s.rz = one;                    // render.cpp:116-121
+        return;
+    }
+    if (ta.depth == 1) {
+        last(s, Yes{});
+        return;
+    }
+    const uint32_t full = ta.depth - 1; // bounces whose ray is traced on (>= 1)
     PathPair n;
-    uint32_t d = 0;
+    step(s, n, Yes{});
+    uint32_t d = 1;
     for (; d + 2 <= full; d += 2) { // render.cpp:140-188
-        step(s, n);
-        step(n, s);
+        step(n, s, No{});
+        step(s, n, No{});
     }
     if (d < full) {
-        step(s, n);
-        last(n);
+        step(n, s, No{});
+        last(s, No{});
     } else {
-        last(s);
+        last(n, No{});
     }
 }
 

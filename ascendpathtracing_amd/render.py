@@ -382,6 +382,18 @@ def selftest_div3(first=0, count=1 << 32, stream=None):
     return tuple(res.tolist())
 
 
+def selftest_div3_seeded(part=0, first=0, count=1 << 32, stream=None):
+    """The two-path bounce's seeded divide vs `/` (include/render_mi355x.h apt_selftest_div3_seeded; part 0: apt_selftest_div3's operand
+    sets, 1: every len2 bit pattern, 2: one divisor against every numerator mantissa): -> dict(bad, first, accepted, flagged,
+    flagged_other, in_range, shared_ok, recip_off)."""
+    require_gpu()
+    res = torch.tensor([0, -1, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device="cuda")
+    check(lib().apt_selftest_div3_seeded(_stream_handle(stream), ctypes.c_int(part), ctypes.c_uint64(first), ctypes.c_uint64(count),
+                                         ctypes.c_void_p(res.data_ptr())), "apt_selftest_div3_seeded")
+    torch.cuda.synchronize()
+    return dict(zip(("bad", "first", "accepted", "flagged", "flagged_other", "in_range", "shared_ok", "recip_off"), res.tolist()))
+
+
 def selftest_direction(d3, flags=False, stream=None):
     """Ray-generate's fast direction with the device's own v_rsq_f64 against its exact form, on the float64 vectors d3 [n, 3] (a CUDA
     tensor): -> dict(accepted, rejected, bad, ray_rejected, max_cert), with flags=True also the per-vector flag bytes (numpy).

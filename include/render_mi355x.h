@@ -652,6 +652,21 @@ int apt_selftest_sqrt(int variant, void *stream, uint64_t first_bits, uint64_t c
  * Initialise to 0, ~0, 0. */
 int apt_selftest_div3(void *stream, uint64_t first, uint64_t count, uint64_t *device_result3);
 
+/* Self-test of the two-path bounce's divide (csrc/pt_core.h div3_seeded_packed2: the reciprocal refined from the square
+ * root's v_rsq_f32 seed by two Newton steps, one residual round per quotient, a flag for the one divisor family whose
+ * reciprocal may not converge) against the plain `/`.
+ *   part 0: the operand sets [first, first + count) of apt_selftest_div3's generator;
+ *   part 1: every len2 whose bit pattern lies in [first, first + count), d = sqrtf(len2), four numerator triples each;
+ *   part 2: the divisor with bit pattern `first`, numerator mantissa i & 0x7fffff at exponent class i >> 23 for
+ *           i in [0, count), count <= 3 * 2^23, from the v_rsq_f32 seed of every len2 next to d * d whose sqrtf() is d and from
+ *           RN(1/d) - 1, + 0, + 1 ulp.
+ * device_result8: [0] += accepted sets with a wrong quotient (must stay 0), [1] = min(first such index), [2] += accepted
+ * sets, [3] += sets in range whose flag is raised (they take the exact form in the renderer), [4] += of those, the ones whose
+ * divisor mantissa is NOT all ones (must stay 0), [5] += sets inside the operand range of the bounce's validity chain,
+ * [6] += (part 0) sets the scalar form's own flags accept -- [5] + [6] is what apt_selftest_div3 reports as accepted on the
+ * same range --, [7] += accepted sets whose refined reciprocal is not RN(1/d).  Initialise to 0, ~0, 0, 0, 0, 0, 0, 0. */
+int apt_selftest_div3_seeded(void *stream, int part, uint64_t first, uint64_t count, uint64_t *device_result8);
+
 /* Self-test of ray-generate's direction: the device makes d / |d| in float32 from one refined reciprocal square root and accepts a
  * component only where that provably rounds like the reference's float64 sqrt and divisions (csrc/pt_core.h fast_direction); a ray
  * with a rejected component is redone in the exact form.  d3 = `count` vectors (d0, d1, d2), float64.  result5: [0] += vectors
