@@ -41,7 +41,8 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_render_paths_lights", "apt_context_render_paths_lights",
                "apt_camera_default_host", "apt_camera_build_host", "apt_camera_check_host", "apt_context_set_camera", "apt_set_camera",
                "apt_gen_rays_camera_device",
-               "apt_selftest_direction", "apt_selftest_direction_host", "apt_selftest_chain_states_host", "apt_selftest_div3_seeded"]
+               "apt_selftest_direction", "apt_selftest_direction_host", "apt_selftest_chain_states_host", "apt_selftest_div3_seeded",
+               "apt_selftest_tent_bits_host"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
 CXX_RENDER_DO = "_Z9render_dojPvS_PhS0_S0_"
 ABI_VERSION = 3

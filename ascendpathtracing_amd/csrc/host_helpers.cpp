@@ -288,6 +288,22 @@ int apt_selftest_chain_states_host(uint32_t samples, uint64_t seed, uint64_t pix
     return APT_OK;
 }
 
+// The tent filter from the generator's bits (pt_core.h tent_e_from_bits, tent_e: what the two-paths-per-lane kernel's ray-generate
+// uses) against the form every other caller keeps, tent_t(unit_from_bits(z)), on the 64-bit generator outputs z[0 .. count).
+int apt_selftest_tent_bits_host(const uint64_t *z, uint64_t count, uint64_t *result2) {
+    apt::clear_error();
+    if (!result2 || (!z && count)) return set_error(APT_ERR_ARG, "apt_selftest_tent_bits_host: z and result2 must be non-null%s");
+    auto bits = [](double d) { uint64_t b; memcpy(&b, &d, sizeof b); return b; };
+    for (uint64_t i = 0; i < count; ++i) {
+        double xe, xt;
+        const double te = apt::tent_e<false>(apt::tent_e_from_bits(z[i]), xe);
+        const double tt = apt::tent_t<false>(apt::unit_from_bits(z[i]), xt);
+        result2[0] += bits(xe) != bits(xt) ? 1 : 0;
+        result2[1] += (bits(te) != bits(tt) && !(te == 0.0 && tt == 0.0)) ? 1 : 0;
+    }
+    return APT_OK;
+}
+
 // Checkpoints of the MT19937 stream for the device generator (apt_gen_rays_mt_device).  Output
 // block b (624 words = the 4 words of 156 consecutive paths) is the tempering of the state after
 // b+1 twists; checkpoint i is that raw state for block i*stride.  Sequential by nature; done once

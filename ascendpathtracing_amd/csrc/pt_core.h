@@ -472,6 +472,24 @@ APT_HD double tent_t(double u, double &arg) {
     return lower ? t : -t;
 }
 
+// The same from e = 2u - 1 = r - 1 (tent_e_from_bits below makes it straight from the generator's bits, exactly): x = 1 - |e| is r where
+// r < 1 and 2 - r otherwise, both subtractions exact (r is a multiple of 2^-51 in [0, 2)), and e < 0 is `lower`, so the result is
+// t = q - 1 <= 0 under e's sign: one add with a source modifier and one v_bfi_b32 in place of a compare, four selects, an xor and two
+// adds.  x and the result are tent_t's bit for bit, except the result at r == 1 exactly: +0 here, -0 there, which the one consumer
+// cannot see (tent_t's comment).
+template <bool FAST>
+APT_HD double tent_e(double e, double &arg) {
+    const double x = 1.0 - __builtin_fabs(e);
+    arg = x;
+    double q;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (FAST) q = sqrt_f64_core(x);
+    else
+#endif
+        q = sqrt(x);
+    return __builtin_copysign(q - 1, e);
+}
+
 struct Ray { float ox, oy, oz, dx, dy, dz; };
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -601,11 +619,12 @@ APT_HD bool ray_check_ok_rn(const RayCheck &k) { return (k.lo >= 0x1p-60) & (k.c
 // Outputs are six scalar references on purpose: an aggregate result gets its stores merged into
 // vector stores to a stack slot that SROA can then no longer promote (it ended up in scratch).
 // RSQDIR (read when FAST): the direction from fast_direction; false: sqrt_f64_core, one refined reciprocal, three Markstein quotients.
-template <bool FAST, bool RSQDIR = true, class CAM>
+// TENT_E: u1, u2 carry e = 2u - 1 (tent_e_from_bits) instead of u, and the jitter comes from tent_e.
+template <bool FAST, bool RSQDIR = true, bool TENT_E = false, class CAM>
 APT_HD void camera_ray_t(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
                          double u1, double u2, float &rox, float &roy, float &roz, float &rdx, float &rdy, float &rdz, RayCheck &chk) {
     double arg1, arg2;
-    const double ddx = tent_t<FAST>(u1, arg1), ddy = tent_t<FAST>(u2, arg2);
+    const double ddx = TENT_E ? tent_e<FAST>(u1, arg1) : tent_t<FAST>(u1, arg1), ddy = TENT_E ? tent_e<FAST>(u2, arg2) : tent_t<FAST>(u2, arg2);
     const double xa = ((double)sx + 0.5 + ddx) / 2 + (double)i, xb = ((double)sy + 0.5 + ddy) / 2 + (double)j;
     double a, b;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -707,6 +726,21 @@ APT_HD double unit_from_bits(uint64_t z) {
     return d - 1.0;
 #endif
 }
+// The tent filter's e = 2u - 1 of the same uniform, straight from the bits: the 52 high bits under exponent 0x400 are v = 2 + 2u in
+// [2, 4), and v - 3 is exact (2u is a multiple of 2^-51 in [0, 2)).  On the device the high dword (z >> 12 | exponent) is ONE
+// v_alignbit_b32 with the exponent as its high source, instead of a shift and an or.
+APT_HD double tent_e_from_bits(uint64_t z) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t zl = (uint32_t)z, zh = (uint32_t)(z >> 32);
+    const uint32_t hi = __builtin_amdgcn_alignbit(0x400u, zh, 12u), lo = __builtin_amdgcn_alignbit(zh, zl, 12u);
+    return __hiloint2double((int)hi, (int)lo) - 3.0;
+#else
+    const uint64_t b = (z >> 12) | 0x4000000000000000ull;
+    double d;
+    memcpy(&d, &b, sizeof d);
+    return d - 3.0;
+#endif
+}
 // The two uniforms of path p are outputs 2p+1 and 2p+2 of ONE SplitMix64 generator (state += phi; output =
 // mix(state)) whose state starts at splitmix64(seed): every path reads its own two consecutive outputs of the
 // same well-tested stream by random access, state(p) = splitmix64(seed) + 2p*phi.  52 high bits each.
@@ -717,6 +751,11 @@ APT_HD void path_uniforms_at(uint64_t state, double &u1, double &u2) {   // stat
 }
 APT_HD void path_uniforms(uint64_t seed, uint64_t path, double &u1, double &u2) {
     path_uniforms_at(splitmix64(seed) + path * kPathStride, u1, u2);
+}
+// The same two outputs as tent_e's arguments (e = 2u - 1).
+APT_HD void path_tent_e_at(uint64_t state, double &e1, double &e2) {
+    e1 = tent_e_from_bits(splitmix64(state));
+    e2 = tent_e_from_bits(splitmix64(state + 0x9E3779B97F4A7C15ull));
 }
 
 // The generator states of a frame lane's chain, by addition.  Lane j of a sub-pixel traces samples j, 8 + j, 16 + j, ... of the paths
@@ -743,13 +782,13 @@ template <class CAM>
 __device__ __forceinline__ void camera_ray_pair(const CAM &c, uint32_t w, uint32_t h, uint32_t i, uint32_t j, uint32_t sy, uint32_t sx,
                                                 uint64_t state_a, f2 &ox, f2 &oy, f2 &oz, f2 &dx, f2 &dy, f2 &dz) {
 #if defined(__HIP_DEVICE_COMPILE__)   // (the host pass of a kernel's translation unit only needs the declaration)
-    double u1a, u2a, u1b, u2b;
-    path_uniforms_at(state_a, u1a, u2a);
-    path_uniforms_at(state_a + kPairStateStep, u1b, u2b);
+    double u1a, u2a, u1b, u2b;   // (as e = 2u - 1: tent_e)
+    path_tent_e_at(state_a, u1a, u2a);
+    path_tent_e_at(state_a + kPairStateStep, u1b, u2b);
     float ax, ay, az, adx, ady, adz, bx, by, bz, bdx, bdy, bdz;
     RayCheck ka, kb;
-    camera_ray_t<true>(c, w, h, i, j, sy, sx, u1a, u2a, ax, ay, az, adx, ady, adz, ka);
-    camera_ray_t<true>(c, w, h, i, j, sy, sx, u1b, u2b, bx, by, bz, bdx, bdy, bdz, kb);
+    camera_ray_t<true, true, true>(c, w, h, i, j, sy, sx, u1a, u2a, ax, ay, az, adx, ady, adz, ka);
+    camera_ray_t<true, true, true>(c, w, h, i, j, sy, sx, u1b, u2b, bx, by, bz, bdx, bdy, bdz, kb);
     double lo;
     asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(ka.lo), "v"(kb.lo));
     // (the certificates are compared one by one: a maximum would drop a NaN)
@@ -757,8 +796,8 @@ __device__ __forceinline__ void camera_ray_pair(const CAM &c, uint32_t w, uint32
                     ((ka.mid < kb.mid ? ka.mid : kb.mid) > 16u * kDirMidD);
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {
         asm volatile("" ::: "memory"); // keeps the exact form out of the hot path's schedule
-        camera_ray_t<false>(c, w, h, i, j, sy, sx, u1a, u2a, ax, ay, az, adx, ady, adz, ka);
-        camera_ray_t<false>(c, w, h, i, j, sy, sx, u1b, u2b, bx, by, bz, bdx, bdy, bdz, kb);
+        camera_ray_t<false, true, true>(c, w, h, i, j, sy, sx, u1a, u2a, ax, ay, az, adx, ady, adz, ka);
+        camera_ray_t<false, true, true>(c, w, h, i, j, sy, sx, u1b, u2b, bx, by, bz, bdx, bdy, bdz, kb);
     }
     ox = f2{ax, bx}; oy = f2{ay, by}; oz = f2{az, bz};
     dx = f2{adx, bdx}; dy = f2{ady, bdy}; dz = f2{adz, bdz};

@@ -61,7 +61,9 @@ __device__ __forceinline__ FrameLane<GROUP> frame_lane(const FrameArgs &fa, uint
 // different waves: no partial dwords for the L2 to merge.  (Measured: what brought the frame's write traffic to exactly its size was the
 // XCD-aware block mapping, pt_trace.h; this took the launch's fetched bytes from 0.88 to 0.83 MB.  Kept: it costs one barrier per workgroup.)
 constexpr uint32_t frame_u8_words(int group) { return kBlock / (4 * group) * 3 / 4; }
-template <int GROUP>
+// CHANNEL_LANES (GROUP == 8 only): one division and one set of gathers per wave half, see below.  The one-path frame kernels of
+// pt_kernels.h keep the per-channel form: with the other one they spill more VGPRs.
+template <int GROUP, bool CHANNEL_LANES = (GROUP == 8)>
 __device__ __forceinline__ void frame_decode(const FrameArgs fa, uint64_t pl, bool valid, const float (&res)[3],
                                              uint32_t (&u8pack_kernel)[frame_u8_words(GROUP)]) {
     constexpr uint32_t kPixPerBlock = kBlock / (4 * GROUP), kU8Words = frame_u8_words(GROUP);
@@ -75,19 +77,47 @@ __device__ __forceinline__ void frame_decode(const FrameArgs fa, uint64_t pl, bo
     const bool pack = fa.fb_u8 && pl0 + kPixPerBlock <= fa.pixel_count && (((uintptr_t)fa.fb_u8 + pl0 * 3) & 3u) == 0;   // workgroup-uniform
     const float fs = (float)fa.samples;
     const int gbase = (int)(lane & ~(uint32_t)(4 * GROUP - 1));
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float mean = res[ch] / fs;            // np.mean: float32 sum / count
+    if (GROUP == 8 && CHANNEL_LANES) {
+        // After the butterfly the 8 lanes of a sub-pixel hold the same three sums, so lane c = lane & 7 of every sub-pixel carries channel c
+        // (c < 3) through ONE division and one set of gathers -- the source lane gbase + sq * 8 + c has the same c, so it holds the channel
+        // its reader wants -- and lanes 0..2 of a pixel finish and store one channel each: the operations of the per-channel form below
+        // on the same values, once per wave half instead of three times.
+        const uint32_t c = lane & 7u;
+        const float sum = c == 0 ? res[0] : (c == 1 ? res[1] : res[2]);
+        float mean;                                 // np.mean: float32 sum / count
+        if ((fa.samples & (fa.samples - 1)) == 0) { // (wave-uniform) a power of two: 1 / count is exact, and sum * (1 / count) is the correctly rounded
+                                                    // quotient just as sum / count is, denormal results included.  Its bits come from the scalar unit.
+            const uint32_t inv = (127u - (uint32_t)__builtin_ctz(fa.samples)) << 23;
+            mean = sum * __uint_as_float(inv);
+        } else {
+            mean = sum / fs;
+        }
         double acc = 0.0;                           // :38 sum_color = zeros (float64)
 #pragma unroll
-        for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP, 64); // :41-45
+        for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP + (int)c, 64); // :41-45
         const double v = acc / 4;                   // :46
         const double cl = v < 0 ? 0 : (v > 1 ? 1 : v); // :54
-        if (valid && (lane & (4 * GROUP - 1)) == 0) {
-            fa.fb[(uint64_t)ch * fa.pixel_count + pl] = (float)cl;
+        if (valid && (lane & (4 * GROUP - 1)) < 3) {
+            fa.fb[(uint64_t)c * fa.pixel_count + pl] = (float)cl;
             const uint8_t b8 = (uint8_t)(cl * 255);                               // :55-57 truncation
-            if (pack) ((lds_uint8 *)u8pack)[(threadIdx.x / (4 * GROUP)) * 3 + ch] = b8;
-            else if (fa.fb_u8) fa.fb_u8[pl * 3 + ch] = b8;
+            if (pack) ((lds_uint8 *)u8pack)[(threadIdx.x / (4 * GROUP)) * 3 + c] = b8;
+            else if (fa.fb_u8) fa.fb_u8[pl * 3 + c] = b8;
+        }
+    } else {   // (GROUP == 1 has no other form: the four lanes of a pixel hold different sums, so a source lane cannot pre-select its reader's channel)
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float mean = res[ch] / fs;            // np.mean: float32 sum / count
+            double acc = 0.0;                           // :38 sum_color = zeros (float64)
+#pragma unroll
+            for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP, 64); // :41-45
+            const double v = acc / 4;                   // :46
+            const double cl = v < 0 ? 0 : (v > 1 ? 1 : v); // :54
+            if (valid && (lane & (4 * GROUP - 1)) == 0) {
+                fa.fb[(uint64_t)ch * fa.pixel_count + pl] = (float)cl;
+                const uint8_t b8 = (uint8_t)(cl * 255);                               // :55-57 truncation
+                if (pack) ((lds_uint8 *)u8pack)[(threadIdx.x / (4 * GROUP)) * 3 + ch] = b8;
+                else if (fa.fb_u8) fa.fb_u8[pl * 3 + ch] = b8;
+            }
         }
     }
     if (pack) {                                     // (workgroup-uniform: every thread reaches the barrier)

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
     }
 
     __shared__ uint32_t u8pack[frame_u8_words(GROUP)];
-    frame_decode<GROUP>(fa, pl, valid, res, u8pack);
+    frame_decode<GROUP, TWO>(fa, pl, valid, res, u8pack);
     count_traced(ta, (valid ? traced : 0) + queue_traced);
 }
 

@@ -687,6 +687,12 @@ int apt_selftest_direction_host(const double *d3, uint64_t count, double rsq_rel
  * outputs differ (must stay 0), [2] += samples the kernel traces one at a time, from the definition itself; the caller zeroes them. */
 int apt_selftest_chain_states_host(uint32_t samples, uint64_t seed, uint64_t pixel_begin, uint64_t pixel_count, uint64_t *result3);
 
+/* Self-test (host, no GPU) of the tent filter made straight from the generator's bits (csrc/pt_core.h tent_e_from_bits, tent_e: the
+ * ray-generate of render_frame's two-paths-per-lane kernel) against the form from the uniform itself (tent_t(unit_from_bits(z))), for
+ * the 64-bit generator outputs z[0 .. count).  result2: [0] += outputs whose square-root arguments differ in their bits, [1] += outputs
+ * whose results differ other than in the sign of a zero (both must stay 0); the caller zeroes them. */
+int apt_selftest_tent_bits_host(const uint64_t *z, uint64_t count, uint64_t *result2);
+
 /* Tuning knob of the APT_FLAG_RETIRE compaction in render_frame: a wave runs its (expensive,
  * float64) ray-generate when at least `lanes` of its 64 lanes have an empty ray slot (default
  * 32).  Speed only: results are bit-identical for every value.  Default context. */
