@@ -54,7 +54,7 @@ struct CamRaysCall {              // apt_gen_rays_camera_device: paths [b, b + c
     void *stream;
 };
 
-// Can a frame of `samples` carry a camera?  Its plan must leave the words the camera's tail rides in (materials.hip).
+// Can a frame of `samples` carry a camera?  The contract's limit (include/render_mi355x.h "camera"): a plan of at most 44 leaves.
 bool mat_camera_fits(uint32_t samples);
 
 // Enqueue the launch (hipGetLastError() tells the caller whether it was accepted).

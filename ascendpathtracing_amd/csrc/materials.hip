@@ -3,7 +3,6 @@
 // before byte for byte as it was (`make asm` writes this code object to materials.s).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
 
 #include <algorithm>
 
@@ -15,24 +14,25 @@
 
 namespace {
 
-TraceArgs mat_trace_args(const apt::MatTrace &t) {
-    TraceArgs ta;
+MatKernelArgs mat_trace_args(const apt::MatTrace &t) {
+    MatKernelArgs ka;
+    TraceArgs &ta = ka.ta;
     ta.ns = t.ns; ta.depth = t.depth; ta.light = t.light;   // read with APT_FLAG_NEE only
     ta.eps = t.eps; ta.gain = 0.0f; ta.traced = t.traced;
     ta.status = t.status;
-    // the light table's address: TraceArgs has no field for it and keeps its layout (pt_materials.h mat_lights_ptr); null without a table
-    ta.refill_lanes = (uint32_t)(uintptr_t)t.lights;
+    ta.refill_lanes = 0;
     ta.grid = t.grid;
     ta.grid_walk = 0;
-    ta.emission = (uint32_t)((uint64_t)(uintptr_t)t.lights >> 32);
+    ta.emission = 0;
     ta.rr_start = t.rr_start;
     ta.seed = t.seed;
-    return ta;
+    ka.lights = t.lights;   // null without a table
+    return ka;
 }
 
-// The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.  APT_FLAG_NEE rides on it (kMatNee), or a
+// The scene form of a launch: the 8-sphere scene ignores a grid, as the mirror entries do.  APT_FLAG_NEE is a bit of it (kMatNee), or a
 // light table (kMatLights), which stands for the flag: never both.
-// APT_FLAG_GLOSS rides on it as well (kMatGloss): without the flag a launch runs the instantiations it ran before the flag existed.
+// APT_FLAG_GLOSS is another (kMatGloss): without the flag a launch runs the instantiations it ran before the flag existed.
 constexpr int mat_scene_form(bool ns8, bool grid, bool nee, bool lights, bool gloss, bool camera = false) {
     return (ns8 ? kScene8 : (grid ? kSceneGrid : kSceneTiles)) | (lights ? kMatLights : (nee ? kMatNee : 0)) | (gloss ? kMatGloss : 0) |
            (camera ? kMatCamera : 0);
@@ -91,15 +91,14 @@ void selftest_direction(void *stream, const double *d3, uint64_t count, uint64_t
 
 void mat_render_frame(const MatFrameCall &c) {
     FrameArgs fa;
-    CameraEx cx;
+    CameraEx cx = {};                                       // without a camera the kernels do not read the tail
     if (c.camera) { cx = camera_ex(*c.camera, c.width, c.height); fa.cam = cx.base; }
     else camera_init(fa.cam, c.width, c.height);
     fa.width = c.width; fa.height = c.height; fa.samples = c.samples; fa.seed = c.t.seed;
     fa.pixel_begin = c.pixel_begin; fa.pixel_count = c.pixel_count; fa.fb = c.fb; fa.fb_u8 = c.fb_u8;
-    const TraceArgs ta = mat_trace_args(c.t);
+    const MatKernelArgs ka = mat_trace_args(c.t);
     LeafProg lp;
-    (void)make_leaf_plan(c.samples, lp);                   // the caller checked that the plan exists (with a camera: that it leaves the tail's words)
-    if (c.camera) memcpy(&lp.leaf[kCamTailLeaf], &cx.t, sizeof cx.t);
+    (void)make_leaf_plan(c.samples, lp);                   // the caller checked that the plan exists (with a camera: mat_camera_fits)
     const int group = c.samples >= 8 ? 8 : 1;
     const uint64_t blocks = (c.pixel_count * 4u * (uint64_t)group + kBlock - 1) / kBlock;   // <= 2^31 - 1: checked by the caller
     const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
@@ -108,27 +107,27 @@ void mat_render_frame(const MatFrameCall &c) {
         with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.camera != nullptr, [&](auto cam) {
             with_flag(c.t.gloss, [&](auto gl) {
                 hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam), g8 ? 8 : 1>), dim3((unsigned)blocks),
-                                   dim3(kBlock), lds, st, c.spheres, c.materials, fa, ta, lp);
+                                   dim3(kBlock), lds, st, c.spheres, c.materials, fa, ka, lp, cx.t);
             });
         }); }); });
     }); }); });
 }
 
 void mat_render_paths(const MatPathsCall &c) {
-    const TraceArgs ta = mat_trace_args(c.t);
+    const MatKernelArgs ka = mat_trace_args(c.t);
     const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
         with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.t.gloss, [&](auto gl) {
             hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl)>), dim3((unsigned)blocks), dim3(kBlock), 0, st,
-                               c.rays, c.spheres, c.materials, c.colors, c.n, c.b, c.c, ta);
+                               c.rays, c.spheres, c.materials, c.colors, c.n, c.b, c.c, ka);
         }); }); });
     }); });
 }
 
 bool mat_camera_fits(uint32_t samples) {
     LeafProg lp;
-    return make_leaf_plan(samples, lp) && lp.nleaves <= kCamTailLeaf;
+    return make_leaf_plan(samples, lp) && lp.nleaves <= kCamMaxLeaves;
 }
 
 void mat_gen_rays_camera(const CamRaysCall &c) {

@@ -18,9 +18,8 @@ constexpr uint64_t kLensKeySalt = 0xA54FF53A5F1D36F1ull;
 constexpr double kCamMaxPos = 0x1p30, kCamMaxAxis = 0x1p20, kCamMaxUnit = 2.0, kCamMinFocus = 0x1p-20;
 constexpr double kCamMinScale = 0x1p-20, kCamMaxScale = 0x1p20, kCamMinNorm = 0x1p-30, kCamMinSin2 = 0x1p-40;
 
-// What a camera instantiation reads beyond the Camera of FrameArgs: 20 dwords.  The frame kernels get it in the spare words of their
-// LeafProg (kCamTailLeaf: FrameArgs and the kernels' signatures keep their layout, so every kernel without a camera keeps its symbol
-// and its code), the ray-buffer generator as part of its own argument.
+// What a camera instantiation reads beyond the Camera of FrameArgs: 20 dwords.  The frame kernels get it as an argument of its own
+// (FrameArgs is shared with the mirror renderer's kernels and keeps its layout), the ray-buffer generator as part of its CameraEx.
 struct CameraTail {
     double offset, focus, oof;      // oof = RN(offset / focus), host-made
     double lens_u[3], lens_v[3];

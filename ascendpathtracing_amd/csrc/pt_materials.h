@@ -27,9 +27,9 @@ static_assert((kMatCamera & (kMatLights | kMatNee | kScene8 | kSceneTiles | kSce
 constexpr int kMatGloss = 32;   // APT_FLAG_GLOSS in the same template argument: the table may hold APT_MAT_GLOSS words (the caller's statement)
 static_assert((kMatGloss & (kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatGloss must be a bit of its own");
 constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss); }
-// Where a camera's CameraTail rides in a frame kernel's LeafProg: its last kCamTailWords leaf words (the launch refuses a plan that
-// reaches them).  FrameArgs is shared with render_kernels.hip's kernels and keeps its layout.
-constexpr uint32_t kCamTailLeaf = kMaxLeaves - kCamTailWords;
+// The contract's limit (include/render_mi355x.h "camera"): a frame with a camera takes a plan of at most this many leaves.  Nothing in
+// the kernels needs it any more; lifting it is a feature with its own tests above 4199 samples, not part of any clean-up.
+constexpr uint32_t kCamMaxLeaves = 44;
 constexpr int kMatTab = 24;     // 8-sphere LDS table: geometry [0, 8), albedo [8, 16), emission [16, 24)
 constexpr int kMatTabGloss = 32; // with kMatGloss: .x of [24, 32) is alpha (0 for a sphere that is not gloss).  Both sizes are one 1280-byte LDS granule
 constexpr int mat_tab_entries(int scn) { return (scn & kMatGloss) ? kMatTabGloss : kMatTab; }
@@ -62,6 +62,14 @@ struct MatShadow {
     bool want;                  // cosl > 0: the shadow segment is traced
     int g;                      // light table: the sphere that was sampled (set with `want`)
 };
+// The material kernels' own argument: TraceArgs as every helper of pt_trace.h reads it (report_status, count_traced, grid_stats,
+// russian_roulette, load_grid_header take `ta`), and next to it what only these kernels read.
+struct MatKernelArgs {
+    TraceArgs ta;               // refill_lanes, emission, gain, grid_walk: 0, not read here
+    const uint32_t *lights;     // the light table of the *_lights entries (device), or null
+};
+static_assert(std::is_trivially_copyable<MatKernelArgs>::value && std::is_trivially_copyable<CameraTail>::value, "kernel arguments are copied as bytes");
+static_assert(offsetof(MatKernelArgs, ta) == 0, "the helpers that take TraceArgs see the layout they always saw");
 template <int LM>
 __device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph, const TraceArgs &ta) {
     MatLight lt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1};
@@ -74,9 +82,7 @@ __device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph
     return lt;
 }
 
-// The light table of the *_lights entries ("several lights" in the header; the layout: pt_core.h kLightsMagic).  Its
-// device address has no field of its own in TraceArgs, whose layout every kernel of render_kernels.hip shares: it travels in two words the
-// material kernels never read, refill_lanes (low half) and emission (high half); mat_trace_args (materials.hip) puts it there.
+// The light table of the *_lights entries ("several lights" in the header; the layout: pt_core.h kLightsMagic; MatKernelArgs::lights).
 // The head is read once per kernel by a scalar load and checked before anything else of the table is (mat_lights_header); what the
 // struct keeps is wave-uniform and lives in SGPRs.  cdf / idx / invp are searched and gathered per lane: the lanes of a wave choose
 // different lights.
@@ -91,15 +97,13 @@ struct MatTable {
     const float4 *tab8;
     uint32_t ns;
 };
-__device__ __forceinline__ const uint32_t *mat_lights_ptr(const TraceArgs &ta) {
-    return reinterpret_cast<const uint32_t *>(((uint64_t)ta.emission << 32) | (uint64_t)ta.refill_lanes);
-}
 // -> false: the table is not one for this scene (magic, num_spheres, 1 <= n <= num_spheres).  It is not read further, the kernel writes
 // nothing and says APT_DEV_LIGHTS_MISMATCH.  Uniform over the launch, like mat_grid_header.
 template <int LM>
-__device__ __forceinline__ bool mat_lights_header(const TraceArgs &ta, const float *__restrict__ sph, const float4 *tab8, MatTable &tb) {
+__device__ __forceinline__ bool mat_lights_header(const MatKernelArgs &ka, const float *__restrict__ sph, const float4 *tab8, MatTable &tb) {
     if (LM != kLmTable) return true;
-    const uint32_t *p = mat_lights_ptr(ta);
+    const TraceArgs &ta = ka.ta;
+    const uint32_t *p = ka.lights;
     uint32_t hw[kLightsHead];
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
@@ -192,12 +196,23 @@ __device__ __forceinline__ void cam_lens_point(uint64_t seed, uint64_t path, flo
     lx = (cs * r) * aperture;
     ly = (sn * r) * aperture;
 }
-// The extended camera, parked in LDS like the 14 doubles of park_camera: those from FrameArgs, the tail from the plan's spare words.
-__device__ __forceinline__ void park_camera_ex(CameraEx &cam, const FrameArgs &fa, const LeafProg &lp) {
+// The extended camera, parked in LDS like the 14 doubles of park_camera: those from FrameArgs, the tail from the kernel's own argument.
+__device__ __forceinline__ void park_camera_ex(CameraEx &cam, const FrameArgs &fa, const CameraTail &ct) {
     park_camera(cam.base, fa);
-    if (threadIdx.x < kCamTailWords) reinterpret_cast<uint32_t *>(&cam.t)[threadIdx.x] = lp.leaf[kCamTailLeaf + threadIdx.x];
+    if (threadIdx.x < kCamTailWords) reinterpret_cast<uint32_t *>(&cam.t)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&ct)[threadIdx.x];
 }
 
+// The written-out fp32 forms of the blocks below (-ffp-contract=off: every product and sum rounds on its own): the dot product as
+// ((0 + ax*bx) + ay*by) + az*bz, and v / |v| as that dot of v with itself, an IEEE sqrtf and three divides.
+__device__ __forceinline__ float mat_dot(float ax, float ay, float az, float bx, float by, float bz) {
+    float s = 0.0f + ax * bx;
+    s = s + ay * by;
+    return s + az * bz;
+}
+__device__ __forceinline__ void mat_normalise(float x, float y, float z, float &nx, float &ny, float &nz) {
+    const float l = sqrtf(mat_dot(x, y, z, x, y, z));
+    nx = x / l; ny = y / l; nz = z / l;
+}
 // Duff et al. 2017: the orthonormal basis (t, b) of the unit vector n, branchless.
 __device__ __forceinline__ void mat_basis(float nx, float ny, float nz, float &tx, float &ty, float &tz, float &bx, float &by, float &bz) {
     const float sg = copysignf(1.0f, nz);
@@ -207,55 +222,73 @@ __device__ __forceinline__ void mat_basis(float nx, float ny, float nz, float &t
     bx = b; by = sg + (ny * ny) * a; bz = -ny;
 }
 
-// The bounce after the hit: light, throughput, new direction, skip.  `code` is APT_MAT_SPEC / DIFF / REFR (checked by the caller).
-// The DIFF and REFR blocks are per-lane branches: exec-masked, skipped by a wave with none of its lanes in them.
-// LM == kLmNee (APT_FLAG_NEE): the light step leaves out the emission of a light that the previous bounce sampled, and a DIFF hit that
-// may sample (`may`: not the last bounce; wave-uniform) draws the direction of its shadow segment -> sh, sampled.
-// LM == kLmTable (a light table): such a hit first picks ONE listed light per lane (the fourth stream, lkey) and samples that one if the
-// predicate S holds for it -- it is not the sphere we stand on and h is strictly outside it --; the bounce counts as sampled either
-// way and remembers its sphere (kprev >= 0 is this mode's `sampled`; -1 otherwise).  The light step then leaves out the emission of a LISTED sphere for which S held at the
-// previous bounce: the same fp32 chain on the same values (s.o is that bounce's h, geo the record the sample gathered).
-// With LM == kLmNone the arguments from `lt` on are not read and nothing of this remains in the code.
-// GL (APT_FLAG_GLOSS): `code` may be APT_MAT_GLOSS, a rough conductor of roughness `alpha` (the header's GLOSS block: visible normals of
-// the GGX distribution in their spherical-cap form, weight G1(l)); one more per-lane branch.  A direction drawn below the horizon ends
-// the path (s.live).  For the light modes it is a bounce that does not sample, like SPEC.  Without GL `alpha` is not read.
+// A path's stream keys, made once per path: the bounce's, APT_FLAG_NEE's direction (LM != kLmNone), the table's selection (kLmTable).
+struct MatKeys {
+    uint64_t bounce, nee, pick;
+};
+template <int LM>
+__device__ __forceinline__ MatKeys mat_path_keys(uint64_t seed, uint64_t path) {
+    return MatKeys{mat_path_key(seed, path), LM ? nee_path_key(seed, path) : 0, LM == kLmTable ? light_path_key(seed, path) : 0};
+}
+// What a segment found: the nearest root and its sphere (k < 0: none; the record is then sphere 0's and is not shaded), that sphere's
+// record, its material code (with GL: mat_gloss_code's) and, for a gloss sphere, its roughness.  The colours are three floats: a float4
+// member makes the 8-sphere form read the unused fourth word of its LDS entries.
+struct MatRgb {
+    float x, y, z;
+};
+__device__ __forceinline__ MatRgb mat_rgb(float4 v) { return MatRgb{v.x, v.y, v.z}; }
+struct MatHit {
+    float t;
+    int k;
+    float4 geo;                 // geo.w: r2 in the 8-sphere form only
+    MatRgb alb, em;
+    uint32_t code;
+    float alpha;                // GL only
+};
+// The bounce after the hit `h` (h.code is APT_MAT_SPEC / DIFF / REFR, with GL also GLOSS: checked by the caller): the light step, the
+// throughput, the new direction and origin, the skip sphere.  The DIFF, GLOSS and REFR blocks are per-lane branches: exec-masked, skipped
+// by a wave with none of its lanes in them.  They stay in this one function, and the light state stays two variables: as functions of
+// their own the blocks cost four instantiations a wave of occupancy (profiles/mat_record_isa.txt), as one variable the state made the
+// 8-sphere APT_FLAG_NEE frame slower than the parent's by more than the parent's spread (profiles/mat_record_ab_state_merged.json).
+// A bounce samples a light only at a DIFF hit that may (`may`: a light mode and not the last bounce; wave-uniform); it then draws the
+// direction and weight of its shadow segment -> sh.  The light step leaves out the emission of a light the previous bounce sampled: that
+// bounce's shadow segment has counted it.
+//   kLmNee    the one light lt.  `sampled`: the previous bounce drew a direction towards it (h was strictly outside it).
+//   kLmTable  the hit first picks ONE listed light per lane (key.pick) and samples that one if the predicate S holds for it -- it is not
+//             the sphere we stand on and h is strictly outside it --; the bounce counts as sampling either way and remembers its sphere
+//             (kprev; -1: the previous bounce did not sample).  The light step leaves out a LISTED sphere for which S held at the
+//             previous bounce: the same fp32 chain on the same values (s.o is that bounce's h, h.geo the record the sample gathered).
+// With LM == kLmNone lt, tb, sampled, kprev and sh are not read and nothing of this remains in the code.
+// GLOSS: a rough conductor of roughness h.alpha (the header's GLOSS block: visible normals of the GGX distribution in their
+// spherical-cap form, weight G1(l)).  A direction drawn below the horizon ends the path (s.live).  It does not sample, like SPEC.
 template <int LM, int SC, bool GL>
-__device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 geo, float4 alb, float4 em, uint32_t code,
-                                          uint64_t mkey, uint32_t d, const MatLight &lt, uint64_t nkey, bool may, bool &sampled,
-                                          MatShadow &sh, const MatTable &tb, uint64_t lkey, int &kprev, float alpha) {
-    float hx = s.dx * tmin, hy = s.dy * tmin, hz = s.dz * tmin;
+__device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys key, uint32_t d, const MatLight &lt, bool may, bool &sampled,
+                                          MatShadow &sh, const MatTable &tb, int &kprev) {
+    const int k = h.k;
+    float hx = s.dx * h.t, hy = s.dy * h.t, hz = s.dz * h.t;
     hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
-    const float nx0 = hx - geo.x, ny0 = hy - geo.y, nz0 = hz - geo.z;
-    float len2 = 0.0f + nx0 * nx0;
-    len2 = len2 + ny0 * ny0;
-    len2 = len2 + nz0 * nz0;
-    const float ln = sqrtf(len2);
-    const float nx = nx0 / ln, ny = ny0 / ln, nz = nz0 / ln;
+    float nx, ny, nz;
+    mat_normalise(hx - h.geo.x, hy - h.geo.y, hz - h.geo.z, nx, ny, nz);
     bool counted = LM == kLmNee && sampled && k == lt.idx;
     if (LM == kLmTable && kprev >= 0) {                       // the previous bounce was a sampling bounce (that IS `sampled` here)
         if (k != kprev && mat_light_listed<SC>(tb, k)) {
-            const float r2k = SC == kScene8 ? geo.w : tb.sph[(size_t)k];
-            const float wx0 = geo.x - s.ox, wy0 = geo.y - s.oy, wz0 = geo.z - s.oz;
-            float d2 = 0.0f + wx0 * wx0;
-            d2 = d2 + wy0 * wy0;
-            d2 = d2 + wz0 * wz0;
-            counted = d2 > r2k;
+            const float r2k = SC == kScene8 ? h.geo.w : tb.sph[(size_t)k];
+            const float wx0 = h.geo.x - s.ox, wy0 = h.geo.y - s.oy, wz0 = h.geo.z - s.oz;
+            counted = mat_dot(wx0, wy0, wz0, wx0, wy0, wz0) > r2k;
         }
     }
-    if (!counted) { s.lx = s.lx + s.tx * em.x; s.ly = s.ly + s.ty * em.y; s.lz = s.lz + s.tz * em.z; }
+    if (!counted) { s.lx = s.lx + s.tx * h.em.x; s.ly = s.ly + s.ty * h.em.y; s.lz = s.lz + s.tz * h.em.z; }
     if (LM == kLmNee) sampled = false;
     if (LM == kLmTable) kprev = -1;
-    s.tx = s.tx * alb.x; s.ty = s.ty * alb.y; s.tz = s.tz * alb.z;
-    float ddn = 0.0f + s.dx * nx;
-    ddn = ddn + s.dy * ny;
-    ddn = ddn + s.dz * nz;
+    s.tx = s.tx * h.alb.x; s.ty = s.ty * h.alb.y; s.tz = s.tz * h.alb.z;
+    const float ddn = mat_dot(s.dx, s.dy, s.dz, nx, ny, nz);
     const bool into = ddn < 0.0f;
     bool outward = into;
     float ndx, ndy, ndz;
-    if (code == APT_MAT_DIFF) {
+    if (h.code == APT_MAT_DIFF) {
         const float nlx = into ? nx : -nx, nly = into ? ny : -ny, nlz = into ? nz : -nz;
         float u1, u2;
-        mat_uniforms(mkey, d, u1, u2);
+        mat_uniforms(key.bounce, d, u1, u2);
         float sn, cs;
         mat_sincos(u1, sn, cs);
         const float r = sqrtf(u2);
@@ -263,17 +296,13 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
         mat_basis(nlx, nly, nlz, tx, ty, tz, bx, by, bz);
         const float cr = cs * r, sr = sn * r, w = sqrtf(1.0f - u2);
         const float vx = (tx * cr + bx * sr) + nlx * w, vy = (ty * cr + by * sr) + nly * w, vz = (tz * cr + bz * sr) + nlz * w;
-        float v2 = 0.0f + vx * vx;
-        v2 = v2 + vy * vy;
-        v2 = v2 + vz * vz;
-        const float vl = sqrtf(v2);
-        ndx = vx / vl; ndy = vy / vl; ndz = vz / vl;
+        mat_normalise(vx, vy, vz, ndx, ndy, ndz);
         MatLight chosen;                                      // kLmTable: the lane's light; kLmNee: lt itself
         const MatLight &cur = LM == kLmTable ? chosen : lt;
         float invp = 1.0f;
         if (LM == kLmTable && may) {
             float u, unused;
-            mat_uniforms(lkey, d, u, unused);
+            mat_uniforms(key.pick, d, u, unused);
             const uint32_t i = mat_light_pick(tb, u);
             invp = tb.invp()[i];
             mat_light_geometry<SC>(tb, (int)min(tb.idx()[i], tb.ns - 1u), chosen);   // (the clamp: a table is trusted, an address is not)
@@ -281,15 +310,13 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
         }
         if (LM && may && k != cur.idx) {
             const float wx0 = cur.cx - hx, wy0 = cur.cy - hy, wz0 = cur.cz - hz;
-            float d2 = 0.0f + wx0 * wx0;
-            d2 = d2 + wy0 * wy0;
-            d2 = d2 + wz0 * wz0;
+            const float d2 = mat_dot(wx0, wy0, wz0, wx0, wy0, wz0);
             if (d2 > cur.r2) {                                // h strictly outside the light (false for NaN)
                 const float x = cur.r2 / d2;
                 const float cmax = sqrtf(1.0f - x);
                 const float omc = x / (1.0f + cmax);          // 1 - cos_max
                 float v1, v2;
-                mat_uniforms(nkey, d, v1, v2);
+                mat_uniforms(key.nee, d, v1, v2);
                 const float cos_a = 1.0f - v1 * omc;
                 const float sin_a = sqrtf(1.0f - cos_a * cos_a);
                 float sp, cp;
@@ -300,72 +327,43 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
                 mat_basis(wx, wy, wz, ax, ay, az, ex, ey, ez);
                 const float ca = cp * sin_a, sa = sp * sin_a;
                 const float qx = (ax * ca + ex * sa) + wx * cos_a, qy = (ay * ca + ey * sa) + wy * cos_a, qz = (az * ca + ez * sa) + wz * cos_a;
-                float q2 = 0.0f + qx * qx;
-                q2 = q2 + qy * qy;
-                q2 = q2 + qz * qz;
-                const float ql = sqrtf(q2);
-                sh.dx = qx / ql; sh.dy = qy / ql; sh.dz = qz / ql;
-                float cosl = 0.0f + sh.dx * nlx;
-                cosl = cosl + sh.dy * nly;
-                cosl = cosl + sh.dz * nlz;
+                mat_normalise(qx, qy, qz, sh.dx, sh.dy, sh.dz);
+                const float cosl = mat_dot(sh.dx, sh.dy, sh.dz, nlx, nly, nlz);
                 sh.w = cosl * (2.0f * omc);
                 if (LM == kLmTable) { sh.w = sh.w * invp; sh.g = cur.idx; }
                 sh.want = cosl > 0.0f;
                 if (LM == kLmNee) sampled = true;
             }
         }
-    } else if (GL && code == (uint32_t)APT_MAT_GLOSS) {
+    } else if (GL && h.code == (uint32_t)APT_MAT_GLOSS) {
         const float nlx = into ? nx : -nx, nly = into ? ny : -ny, nlz = into ? nz : -nz;
         float tx, ty, tz, bx, by, bz;
         mat_basis(nlx, nly, nlz, tx, ty, tz, bx, by, bz);
         const float wx = -s.dx, wy = -s.dy, wz = -s.dz;       // v = -d, in the frame (t, bt, nl)
-        float vx = 0.0f + wx * tx;
-        vx = vx + wy * ty;
-        vx = vx + wz * tz;
-        float vy = 0.0f + wx * bx;
-        vy = vy + wy * by;
-        vy = vy + wz * bz;
-        float vz = 0.0f + wx * nlx;
-        vz = vz + wy * nly;
-        vz = vz + wz * nlz;
-        const float sx0 = alpha * vx, sy0 = alpha * vy;       // the view direction of the stretched (alpha = 1) configuration
-        float s2 = 0.0f + sx0 * sx0;
-        s2 = s2 + sy0 * sy0;
-        s2 = s2 + vz * vz;
-        const float sl = sqrtf(s2);
-        const float sx = sx0 / sl, sy = sy0 / sl, sz = vz / sl;
+        const float vx = mat_dot(wx, wy, wz, tx, ty, tz), vy = mat_dot(wx, wy, wz, bx, by, bz), vz = mat_dot(wx, wy, wz, nlx, nly, nlz);
+        float sx, sy, sz;
+        mat_normalise(h.alpha * vx, h.alpha * vy, vz, sx, sy, sz);   // the view direction of the stretched (alpha = 1) configuration
         float u1, u2;
-        mat_uniforms(mkey, d, u1, u2);
+        mat_uniforms(key.bounce, d, u1, u2);
         float sn, cs;
         mat_sincos(u1, sn, cs);
         const float z = (1.0f - u2) * (1.0f + sz) - sz;       // a uniform point of the spherical cap z > -s.z
         const float r2 = 1.0f - z * z;
         const float r = sqrtf(r2 > 0.0f ? r2 : 0.0f);
-        const float mx0 = alpha * (r * cs + sx), my0 = alpha * (r * sn + sy), mz0 = z + sz;   // the half vector, stretched back
-        float m2 = 0.0f + mx0 * mx0;
-        m2 = m2 + my0 * my0;
-        m2 = m2 + mz0 * mz0;
-        const float ml = sqrtf(m2);
-        const float mx = mx0 / ml, my = my0 / ml, mz = mz0 / ml;
-        float vm = 0.0f + vx * mx;
-        vm = vm + vy * my;
-        vm = vm + vz * mz;
-        const float vm2 = 2.0f * vm;
+        float mx, my, mz;
+        mat_normalise(h.alpha * (r * cs + sx), h.alpha * (r * sn + sy), z + sz, mx, my, mz);   // the half vector, stretched back
+        const float vm2 = 2.0f * mat_dot(vx, vy, vz, mx, my, mz);
         const float lx = mx * vm2 - vx, ly = my * vm2 - vy, lz = mz * vm2 - vz;
         if (!(lz > 0.0f)) s.live = false;                     // below the horizon: the path ends here, L keeps its value
-        const float a2 = alpha * alpha;
+        const float a2 = h.alpha * h.alpha;
         const float g = (2.0f * lz) / (lz + sqrtf(a2 + (1.0f - a2) * (lz * lz)));   // G1(l), separable Smith
         s.tx = s.tx * g; s.ty = s.ty * g; s.tz = s.tz * g;
         const float qx = (tx * lx + bx * ly) + nlx * lz, qy = (ty * lx + by * ly) + nly * lz, qz = (tz * lx + bz * ly) + nlz * lz;
-        float q2 = 0.0f + qx * qx;
-        q2 = q2 + qy * qy;
-        q2 = q2 + qz * qz;
-        const float ql = sqrtf(q2);
-        ndx = qx / ql; ndy = qy / ql; ndz = qz / ql;
+        mat_normalise(qx, qy, qz, ndx, ndy, ndz);
     } else {
         const float k2 = ddn * 2.0f;                          // SPEC, and the reflection of REFR
         ndx = s.dx - nx * k2; ndy = s.dy - ny * k2; ndz = s.dz - nz * k2;
-        if (code == APT_MAT_REFR) {
+        if (h.code == APT_MAT_REFR) {
             const float dn = into ? ddn : -ddn;
             const float nnt = into ? APT_MAT_NNT_IN : 1.5f;
             const float cos2t = 1.0f - (nnt * nnt) * (1.0f - dn * dn);
@@ -373,21 +371,16 @@ __device__ __forceinline__ void mat_shade(MatPath &s, float tmin, int k, float4 
                 float g = dn * nnt + sqrtf(cos2t);
                 g = into ? g : -g;
                 const float vx = s.dx * nnt - nx * g, vy = s.dy * nnt - ny * g, vz = s.dz * nnt - nz * g;
-                float v2 = 0.0f + vx * vx;
-                v2 = v2 + vy * vy;
-                v2 = v2 + vz * vz;
-                const float vl = sqrtf(v2);
-                const float tdx = vx / vl, tdy = vy / vl, tdz = vz / vl;
-                float dt = 0.0f + tdx * nx;
-                dt = dt + tdy * ny;
-                dt = dt + tdz * nz;
+                float tdx, tdy, tdz;
+                mat_normalise(vx, vy, vz, tdx, tdy, tdz);
+                const float dt = mat_dot(tdx, tdy, tdz, nx, ny, nz);
                 const float c = 1.0f - (into ? -ddn : dt);
                 const float c5 = (((c * c) * c) * c) * c;
                 const float re = APT_MAT_R0 + APT_MAT_1MR0 * c5;
                 const float tr = 1.0f - re;
                 const float P = 0.25f + 0.5f * re;
                 float u1, u2;
-                mat_uniforms(mkey, d, u1, u2);
+                mat_uniforms(key.bounce, d, u1, u2);
                 float wt;
                 if (u1 < P) {
                     wt = re / P;
@@ -545,55 +538,50 @@ template <int SC, int LM, bool GL>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
                                               const GridHeader &gh, const MatLight &lt, const MatTable &tb, float4 *tile, MatPath &s,
                                               const TraceArgs &ta, uint64_t path) {
-    const uint64_t mkey = mat_path_key(ta.seed, path);
+    const MatKeys key = mat_path_keys<LM>(ta.seed, path);
     const uint64_t rr_key = ta.rr_start ? rr_path_key(ta.seed, path) : 0;
     uint32_t traced = 0, n_cells = 0, n_tests = 0;           // the last two: walk statistics of the grid form
-    const uint64_t nkey = LM ? nee_path_key(ta.seed, path) : 0;
-    const uint64_t lkey = LM == kLmTable ? light_path_key(ta.seed, path) : 0;
     bool sampled = false;                                    // kLmNee: the previous bounce sampled the light
     int kprev = -1;                                          // kLmTable: the sphere of the previous bounce if it was a sampling bounce, else -1
     for (uint32_t d = 0; d < ta.depth; ++d) {
-        float tmin;
-        int k;
-        float4 geo, alb, em;
-        uint32_t code;
-        float alpha = 0.0f;                                   // GL only
+        MatHit h;
+        h.alpha = 0.0f;
         if (SC == kScene8) {
             if (__all(!s.live)) break;
-            if (d == 0) mat_hit8<false>(m8.sc, s, ta.eps, tmin, k);
-            else mat_hit8<true>(m8.sc, s, ta.eps, tmin, k);
-            const int g = k < 0 ? 0 : k;
-            geo = m8.tab[g]; alb = m8.tab[8 + g]; em = m8.tab[16 + g];
-            code = (m8.codes >> (4 * g)) & 15u;
-            if (GL) alpha = m8.tab[24 + g].x;
+            if (d == 0) mat_hit8<false>(m8.sc, s, ta.eps, h.t, h.k);
+            else mat_hit8<true>(m8.sc, s, ta.eps, h.t, h.k);
+            const int g = h.k < 0 ? 0 : h.k;
+            h.geo = m8.tab[g]; h.alb = mat_rgb(m8.tab[8 + g]); h.em = mat_rgb(m8.tab[16 + g]);
+            h.code = (m8.codes >> (4 * g)) & 15u;
+            if (GL) h.alpha = m8.tab[24 + g].x;
         } else {
             if (SC == kSceneGrid) {
                 if (__all(!s.live)) break;
-                mat_hit_grid(gh, ta.grid, s, ta.eps, tmin, k, n_cells, n_tests);
+                mat_hit_grid(gh, ta.grid, s, ta.eps, h.t, h.k, n_cells, n_tests);
             } else {
                 if (__syncthreads_and(!s.live)) break;
-                mat_hit_tiles(sph, tile, s, ta.ns, ta.eps, tmin, k);
+                mat_hit_tiles(sph, tile, s, ta.ns, ta.eps, h.t, h.k);
             }
-            const size_t ns = ta.ns, g = k < 0 ? 0 : (size_t)k;
-            geo = make_float4(sph[ns + g], sph[2 * ns + g], sph[3 * ns + g], 0.0f);
-            alb = make_float4(sph[7 * ns + g], sph[8 * ns + g], sph[9 * ns + g], 0.0f);
-            em = make_float4(sph[4 * ns + g], sph[5 * ns + g], sph[6 * ns + g], 0.0f);
-            code = mat[g];
+            const size_t ns = ta.ns, g = h.k < 0 ? 0 : (size_t)h.k;
+            h.geo = make_float4(sph[ns + g], sph[2 * ns + g], sph[3 * ns + g], 0.0f);
+            h.alb = MatRgb{sph[7 * ns + g], sph[8 * ns + g], sph[9 * ns + g]};
+            h.em = MatRgb{sph[4 * ns + g], sph[5 * ns + g], sph[6 * ns + g]};
+            h.code = mat[g];
             if (GL) {
                 uint32_t q;
-                code = mat_gloss_code(code, q);
-                alpha = (float)q * 0x1p-16f;
+                h.code = mat_gloss_code(h.code, q);
+                h.alpha = (float)q * 0x1p-16f;
             }
         }
-        const bool hit = s.live && k >= 0;
-        const bool bad = hit && code > (uint32_t)(GL ? APT_MAT_GLOSS : APT_MAT_REFR);
+        const bool hit = s.live && h.k >= 0;
+        const bool bad = hit && h.code > (uint32_t)(GL ? APT_MAT_GLOSS : APT_MAT_REFR);
         if (__any(bad)) report_status(ta, APT_DEV_BAD_MATERIAL);
         s.live = hit && !bad;
         const bool may = LM && d + 1 < ta.depth;              // no sample at the last bounce: the header says why
         MatShadow sh;
         sh.want = false;
         if (s.live) {
-            mat_shade<LM, SC, GL>(s, tmin, k, geo, alb, em, code, mkey, d, lt, nkey, may, sampled, sh, tb, lkey, kprev, alpha);
+            mat_shade<LM, SC, GL>(s, h, key, d, lt, may, sampled, sh, tb, kprev);
             ++traced;
         }
         if (may && (SC == kSceneTiles ? __syncthreads_or(sh.want) : __any(sh.want))) {
@@ -657,7 +645,8 @@ __device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, fl
 template <int SCN>
 __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *__restrict__ rays, const float *__restrict__ sph,
                                                                   const uint32_t *__restrict__ mat, float *__restrict__ colors,
-                                                                  uint64_t n_total, uint64_t begin, uint64_t count, TraceArgs ta) {
+                                                                  uint64_t n_total, uint64_t begin, uint64_t count, MatKernelArgs ka) {
+    const TraceArgs &ta = ka.ta;
     constexpr int SC = mat_scene_of(SCN);
     constexpr int LM = mat_light_mode(SCN);
     constexpr bool GL = (SCN & kMatGloss) != 0;
@@ -666,7 +655,7 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
     MatTable tb;
-    if (!mat_lights_header<LM>(ta, sph, tab, tb)) return;
+    if (!mat_lights_header<LM>(ka, sph, tab, tb)) return;
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8<GL>(sph, mat, tab);
     const MatLight lt = load_mat_light<LM>(sph, ta);      // here, not after the ray loads: there it reorders the registers of the flag-off kernels
@@ -710,10 +699,11 @@ __global__ __launch_bounds__(kBlock) void gen_rays_camera_kernel(CameraEx cam, u
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
-// SCN: the scene form and kMatNee / kMatLights / kMatGloss, as for the buffer kernel, and kMatCamera.
+// SCN: the scene form and kMatNee / kMatLights / kMatGloss, as for the buffer kernel, and kMatCamera: only then is `ct` read.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
-                                                                  FrameArgs fa, TraceArgs ta, LeafProg lp) {
+                                                                  FrameArgs fa, MatKernelArgs ka, LeafProg lp, CameraTail ct) {
+    const TraceArgs &ta = ka.ta;
     constexpr int SC = mat_scene_of(SCN);
     constexpr int LM = mat_light_mode(SCN);
     constexpr bool GL = (SCN & kMatGloss) != 0;
@@ -721,13 +711,13 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
     float *stack_lds = dyn_lds;                                            // [kMaxStack][3][kStackSlots] when lp.nleaves > 1
-    constexpr bool CAM = (SCN & kMatCamera) != 0;                            // a context's camera: CameraEx (its tail from lp), camera_ray_ex
+    constexpr bool CAM = (SCN & kMatCamera) != 0;                            // a context's camera: CameraEx (its tail from ct), camera_ray_ex
     __shared__ std::conditional_t<CAM, CameraEx, Camera> cam;
     GridHeader gh;
     if (!mat_grid_header<SC>(ta, gh)) return;
     MatTable tb;
-    if (!mat_lights_header<LM>(ta, sph, tab, tb)) return;
-    if constexpr (CAM) park_camera_ex(cam, fa, lp);
+    if (!mat_lights_header<LM>(ka, sph, tab, tb)) return;
+    if constexpr (CAM) park_camera_ex(cam, fa, ct);
     else park_camera(cam, fa);
     MatScene8 m8;
     if (SC == kScene8) m8 = load_mat_scene8<GL>(sph, mat, tab);

@@ -4,8 +4,11 @@
 Runs `make -B asm` in both directories.  For every kernel of render_kernels.s and materials.s it compares the instruction lines
 between the symbol and its .Lfunc_end (labels, directives and comments dropped; block labels renumbered per function, since a
 function's index in the file moves them; differences counted by a sequence diff) and the kernel-resource-usage remarks (registers,
-spills, scratch, LDS, occupancy).
-Prints one line per kernel that differs and a summary; exit status 1 when any kernel or resource row differs."""
+spills, scratch, LDS, occupancy).  Kernels of render_kernels.s are matched by symbol; those of materials.s by demangled name without the
+argument list, so that a kernel whose signature changed is compared with its predecessor.
+Prints one line per kernel that differs and a summary per file.  For materials.s it also prints whether every kernel keeps scratch 0,
+no VGPR spills and at least the old occupancy (`conditions`).  Exit status 1 when a kernel of render_kernels.s differs at all, when a
+kernel of materials.s exists on one side only, or when one breaks those conditions."""
 import difflib, os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 
@@ -64,22 +67,39 @@ def main():
     for s in ("render_kernels.s", "materials.s"):
         ko, kn = kernels(os.path.join(old, s)), kernels(os.path.join(new, s))
         dm = demangle(sorted(set(ko) | set(kn)))
+        by_name, broken = s == "materials.s", []
+        if by_name:               # symbol -> demangled name: a changed argument list still finds its predecessor
+            assert len(set(dm[n] for n in ko)) == len(ko) and len(set(dm[n] for n in kn)) == len(kn), "demangled names are not unique"
+            ko, kn = {dm[n]: b for n, b in ko.items()}, {dm[n]: b for n, b in kn.items()}
+            so, sn = {dm.get(n, n): r for n, r in ro.items()}, {dm.get(n, n): r for n, r in rn.items()}
+            dm = {n: n for n in set(ko) | set(kn)}
+        else:
+            so, sn = ro, rn
         same = 0
         for n in sorted(set(ko) | set(kn), key=lambda n: dm[n]):
             if n not in ko or n not in kn:
                 print(f"{s}: {dm[n]}: only in {'new' if n in kn else 'old'}")
                 differ += 1
                 continue
-            res = "" if ro.get(n) == rn.get(n) else f"  resources {ro.get(n)} -> {rn.get(n)}"
+            a, b = so.get(n, {}), sn.get(n, {})
+            changed = [f"{k} {a.get(k)} -> {b.get(k)}" for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
+            res = "  resources " + ", ".join(changed) if changed else ""
+            if by_name and (b.get("ScratchSize [bytes/lane]") != "0" or b.get("VGPRs Spill") != "0"
+                            or int(b.get("Occupancy [waves/SIMD]", 0)) < int(a.get("Occupancy [waves/SIMD]", 0))):
+                broken.append(n)
             if ko[n] == kn[n] and not res:
                 same += 1
                 continue
-            differ += 1
+            differ += not by_name
             ops = [o for o in difflib.SequenceMatcher(None, ko[n], kn[n]).get_opcodes() if o[0] != "equal"]
             lines = sum(max(i2 - i1, j2 - j1) for _, i1, i2, j1, j2 in ops)
             print(f"{s}: {dm[n]}: {len(ko[n])} -> {len(kn[n])} instructions, {lines} lines in {len(ops)} hunks differ "
                   f"(first at instruction {ops[0][1] if ops else '-'}){res}")
         print(f"{s}: {same} of {len(set(ko) | set(kn))} kernels identical (instructions and resources)")
+        if by_name:
+            print(f"{s}: conditions (scratch 0, no VGPR spills, occupancy not below the old build's): "
+                  + ("kept by every kernel" if not broken else "BROKEN by " + ", ".join(broken)))
+            differ += len(broken)
     sys.exit(1 if differ else 0)
 
 

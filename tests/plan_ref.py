@@ -224,7 +224,7 @@ def mt_colours(oracle, s):
 # Material renderer: depth 5, seed 20 (measured: seeds 11 and 12 miss the conditions at 257 samples with direct light sampling).
 MAT_SAMPLES = (257, 4199, 7688)
 MAT_DEPTH, MAT_SEED = 5, 20
-CAMERA_SAMPLES = 4199                        # 44 leaves: the last leaf word is leaf[43], the camera's words begin at leaf[44]
+CAMERA_SAMPLES = 4199                        # 44 leaves: the contract's 44-leaf limit with a camera
 # (scene, light mode): diff8 plain and with APT_FLAG_NEE, demo9 with the lamp and a light table (by tiles and through its grid: one restatement)
 MAT_CASES = (("diff8", "plain"), ("diff8", "nee"), ("demo9lamp", "table"))
 

@@ -250,7 +250,7 @@ def test_material_frame_light_table_by_tiles_and_through_the_grid(apt, s):
 
 
 def test_material_frame_with_a_lens_camera_at_the_44_leaf_limit(apt):
-    """4199 samples: the plan's last leaf word is leaf[43] and the camera's words begin at leaf[44].  A thin-lens camera, the light
+    """4199 samples, 44 leaves: the contract's 44-leaf limit with a camera.  A thin-lens camera, the light
     table, by tiles and through the grid."""
     s = pr.CAMERA_SAMPLES
     assert pr.stats(s)["leaves"] == 44 and pr.stats(s + 1)["leaves"] == 45
