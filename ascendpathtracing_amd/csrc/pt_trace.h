@@ -286,7 +286,19 @@ __device__ __forceinline__ void apply_albedo(f2 &rxy, float &rz, const Albedo &a
 // The intersection half of a bounce: all 8 spheres against one ray, integer-key arg-min, -> nearest accepted root,
 // byte offset of the hit sphere's LDS table entry (index * 16) and the wave mask of the lanes that hit the light.
 struct Hit8 { float tmin; uint32_t addr; uint64_t light; };
-template <int MODE, bool PLANES = false>
+// "No lane of the wave can hit either sphere of this pair": both discriminants negative or NaN in every lane.  Two VALU instructions
+// (v_max_f32, where a NaN operand drops out and two NaNs stay NaN -- the discriminants are results of arithmetic, so their NaNs are
+// quiet --, and one ordered compare into a wave mask: -0 >= 0 holds, a -0 discriminant is the real double root t = b) and a scalar test.
+__device__ __forceinline__ bool pair_misses_wave(f2 disc) {
+    return __builtin_amdgcn_ballot_w64(__builtin_fmaxf(disc.x, disc.y) >= 0.0f) == 0;
+}
+// SKIP, bit j: the root stage of sphere pair (2j, 2j+1) is branched round (a SCALAR branch) when pair_misses_wave().  The frame is the
+// same bit for bit: in such a wave v_rsq_f32 returns NaN for both discriminants of every lane, q and both (-t0, t1) register pairs are
+// NaN, their keys are >= key(kMissT) (the argument above update64 below) and never win v_min3_u32 -- `best`, b0 / b1 / b2 and `any` keep
+// their values whether the stage runs or not.  The stage's only other product is `amin`, which can only ask for the exact re-run of the
+// bounce, and that computes the same bounce (a negative discriminant is a miss there as well: sqrtf gives NaN, select_root kMissT).
+// Off by default: only the two-path bounce (pt_trace2.h) turns it on, every other caller's code is what it was.
+template <int MODE, bool PLANES = false, int SKIP = 0>
 __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                                  const TraceArgs &ta, const KeyConsts &kc, float &amin) {
     uint32_t best = kc.init;
@@ -308,6 +320,9 @@ __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, flo
         const HitPre2 h = PLANES ? hp[k / 2]
                                  : intersect_pre2(f2{sc.cx[k], sc.cx[k + 1]}, f2{sc.cy[k], sc.cy[k + 1]}, f2{sc.cz[k], sc.cz[k + 1]},
                                                   f2{sc.r2[k], sc.r2[k + 1]}, ox, oy, oz, dx, dy, dz);
+        if ((SKIP >> (k / 2)) & 1) {
+            if (pair_misses_wave(h.disc)) continue; // nothing below can change best, b0 / b1 / b2 or any (see SKIP above)
+        }
         amin = minimum3_abs(amin, h.disc.x, h.disc.y);
         // sqrt_rn_rsq1 on both lanes of the pair (pt_core.h): y = x*r, hh = r/2, q = fma(fma(-y,y,x), hh, y)
         const f2 r0 = {__builtin_amdgcn_rsqf(h.disc.x), __builtin_amdgcn_rsqf(h.disc.y)};

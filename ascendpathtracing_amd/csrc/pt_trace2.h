@@ -18,6 +18,16 @@
 
 namespace {
 
+// The sphere pairs whose root stage a wave of the two-path bounce branches round when none of its lanes can hit either sphere
+// (intersect_ns8_v2's SKIP; bit j = pair (2j, 2j+1)).  Decided by counting (profiles/pair_skip_counts.json):
+//   * pair (6,7) of a table that shares planes -- the reference scene's mirror ball and light: a whole wave misses both in 81 % of its
+//     first bounces and 45 % of all eight, where the test (2 VALU) pays from 10 % on;
+//   * no wall pair: a ray inside the room always has one of two opposite walls in front of it (0 of 4.1 million waves);
+//   * nothing in the general form: its pairing is whatever the table's order makes it (bench.py's general scene: 0 for every pair);
+//   * not path B of the LAST bounce: with that one the headline kernel keeps two VGPRs in scratch (at 12 % there it would pay nothing).
+template <bool PLANES> constexpr int kPairSkip = PLANES ? 0x8 : 0;
+constexpr int kPairSkipLastB = 0;
+
 struct PathPair { // .x = path A, .y = path B
     f2 ox, oy, oz, dx, dy, dz; // rays
     f2 rx, ry, rz;             // throughputs
@@ -55,8 +65,8 @@ __device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, 
                                               const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                               uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f; // per path: a finished path's request for the exact form can be ignored (trace2_ns8)
-    const Hit8 hA = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
-    const Hit8 hB = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES>>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
     if (FIRST) {
         aliveA = ~hA.light;
         aliveB = ~hB.light;
@@ -155,8 +165,8 @@ __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 ta
                                                  const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                                  uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f;
-    const Hit8 hA = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
-    const Hit8 hB = intersect_ns8_v2<MODE, PLANES>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkipLastB>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
     if (FIRST) {
         aliveA = ~hA.light;
         aliveB = ~hB.light;
@@ -214,8 +224,35 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
         bounce_ns8_exact<MODE>(sc, tab, b, nb, ta);
         if (ta.traced && (threadIdx.x & 63) == 0) atomicAdd(ta.traced + 3, 1ull); // statistics: exact re-runs of a wave-bounce
     };
+#ifdef APT_COUNT_PAIR_SKIP   // measurement build only (make variant ... EXTRA=-DAPT_COUNT_PAIR_SKIP, profiles/pair_skip_count.py): how often
+    // pair_misses_wave() holds, per path half, bounce and sphere pair.  The statistics block must then have 4 + 8 * 8 + 1 entries:
+    // [4 + (half * 8 + min(bounce, 7)) * 4 + pair] += 1 per wave where it holds, [68] += 1 per wave and path pair it traces.
+    uint32_t count_bounce = 0;
+    auto count_pairs = [&](const PathPair &in) __attribute__((always_inline)) {
+        if (!ta.traced) return;
+        const bool lane0 = (threadIdx.x & 63) == 0;
+        for (int half = 0; half < 2; ++half) {
+            const float ox = half ? in.ox.y : in.ox.x, oy = half ? in.oy.y : in.oy.x, oz = half ? in.oz.y : in.oz.x;
+            const float dx = half ? in.dx.y : in.dx.x, dy = half ? in.dy.y : in.dy.x, dz = half ? in.dz.y : in.dz.x;
+            HitPre2 hp[4];
+            if (PLANES) intersect_pre_planes(sc, ox, oy, oz, dx, dy, dz, hp);
+            for (int k = 0; k < 8; k += 2) {
+                const HitPre2 h = PLANES ? hp[k / 2]
+                                         : intersect_pre2(f2{sc.cx[k], sc.cx[k + 1]}, f2{sc.cy[k], sc.cy[k + 1]}, f2{sc.cz[k], sc.cz[k + 1]},
+                                                          f2{sc.r2[k], sc.r2[k + 1]}, ox, oy, oz, dx, dy, dz);
+                const uint32_t slot = 4u + (uint32_t)(half * 8 + (count_bounce < 7u ? count_bounce : 7u)) * 4u + (uint32_t)(k / 2);
+                if (pair_misses_wave(h.disc) && lane0) atomicAdd(ta.traced + slot, 1ull);
+            }
+        }
+        if (count_bounce == 0 && lane0) atomicAdd(ta.traced + 68, 1ull);
+        ++count_bounce;
+    };
+#endif
     auto step = [&](const PathPair &in, PathPair &out, auto first_tag) __attribute__((always_inline)) {
         constexpr bool first = decltype(first_tag)::value;
+#ifdef APT_COUNT_PAIR_SKIP
+        count_pairs(in);
+#endif
         uint64_t oa = aliveA, ob = aliveB;
         bool redo_any = !fast_ok;
         if (__builtin_expect(fast_ok, 1)) {
@@ -237,6 +274,9 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
     // The last bounce, state in `in`: throughputs -> s.  Its exact form is the whole exact bounce with the ray ignored.
     auto last = [&](const PathPair &in, auto first_tag) __attribute__((always_inline)) {
         constexpr bool first = decltype(first_tag)::value;
+#ifdef APT_COUNT_PAIR_SKIP
+        count_pairs(in);
+#endif
         uint64_t oa = aliveA, ob = aliveB; // (nothing reads the alive masks after this bounce: they are not written back)
         f2 rx, ry, rz;
         bool redo_any = !fast_ok;
