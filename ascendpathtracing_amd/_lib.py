@@ -20,6 +20,7 @@ APT_ERR_DEVICE = 4
 APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH = 1, 2, 4, 8      # bits of the device status word (apt_context_check)
 APT_DEV_BAD_MATERIAL = 16
 APT_DEV_LIGHTS_MISMATCH = 32
+APT_ENV_SAMPLE_SUN = 1                  # apt_environment.flags: DIFF hits sample the sun directly
 MAT_GLOSS = 3                           # with APT_FLAG_GLOSS: gen_data.gloss(alpha) makes the word (APT_MAT_GLOSS_WORD)
 MAT_SPEC, MAT_DIFF, MAT_REFR = 0, 1, 2  # material codes of the *_materials entries (include/render_mi355x.h APT_MAT_*)
 
@@ -41,6 +42,7 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_render_paths_lights", "apt_context_render_paths_lights",
                "apt_camera_default_host", "apt_camera_build_host", "apt_camera_check_host", "apt_context_set_camera", "apt_set_camera",
                "apt_gen_rays_camera_device",
+               "apt_environment_build_host", "apt_environment_check_host", "apt_context_set_environment", "apt_set_environment",
                "apt_selftest_direction", "apt_selftest_direction_host", "apt_selftest_chain_states_host", "apt_selftest_div3_seeded",
                "apt_selftest_tent_bits_host"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
@@ -86,6 +88,20 @@ class ApCamera(ctypes.Structure):
         for k, v in kw.items():
             setattr(c, k, (ctypes.c_double * 3)(*v) if isinstance(v, (tuple, list)) else v)
         return c
+
+
+class ApEnvironment(ctypes.Structure):
+    """apt_environment (include/render_mi355x.h "environment"): the sky's two radiances, the sun's direction, radiance and cone
+    (sun_omc = 1 - cos(half angle), 0 = no sun), APT_ENV_* flags.  Made by gen_data.environment; a record filled in by hand goes
+    through apt_environment_check_host when it is set."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("horizon", ctypes.c_float * 3), ("zenith", ctypes.c_float * 3),
+                ("sun_dir", ctypes.c_float * 3), ("sun_radiance", ctypes.c_float * 3), ("sun_omc", ctypes.c_float)]
+
+    def copy(self, **kw):
+        e = ApEnvironment.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(e, k, (ctypes.c_float * 3)(*v) if isinstance(v, (tuple, list)) else v)
+        return e
 
 
 _lib = None

@@ -53,6 +53,8 @@ struct apt_context {
         apt::Debug debug;
         bool has_camera = false;           // apt_context_set_camera: the material frame entries render from `camera`, the mirror frame entries refuse
         apt_camera camera;                 // checked when it was set
+        bool has_env = false;              // apt_context_set_environment: the material entries read `env`, the mirror frame entries refuse
+        apt_environment env;               // checked when it was set
     };
     apt_context();
     Values snapshot();                     // consistent copy under the lock
@@ -60,6 +62,7 @@ struct apt_context {
     void set_trace_counter(unsigned long long *c);
     void set_refill_lanes(uint32_t lanes);
     void set_camera(const apt_camera *cam_or_null);   // a checked record, or null: the reference's camera
+    void set_environment(const apt_environment *env_or_null);   // a checked record, or null: no environment
     int set_debug(const char *key, double value); // APT_OK / APT_ERR_ARG (error record set)
     int get_debug(const char *key, double *value); // the knob's current value (what set_debug last stored, or the environment's initial value)
 

@@ -62,6 +62,13 @@ void mat_render_frame(const MatFrameCall &call);
 void mat_render_paths(const MatPathsCall &call);
 void mat_gen_rays_camera(const CamRaysCall &call);
 
+// The same two launches with the context's environment (include/render_mi355x.h "environment"; checked when it was set): the kMatEnv
+// kernels, which live in environment.hip -- a third code object, so that a launch without an environment runs the very kernels it ran
+// before there was one.  They are always the general-camera and gloss instantiations: call.camera must be non-null (without a camera
+// set the caller hands in apt_camera_default_host's record, the reference's camera bit for bit), and call.t.gloss travels as data.
+void env_render_frame(const MatFrameCall &call, const apt_environment &env);
+void env_render_paths(const MatPathsCall &call, const apt_environment &env);
+
 // apt_selftest_direction's launch (count > 0): the test kernel is kept out of render_kernels.hip's code object as well.
 void selftest_direction(void *stream, const double *d3_dev, uint64_t count, uint64_t *result5_dev, uint8_t *flags_dev);
 

@@ -57,6 +57,8 @@ apt_context::apt_context() {
     v_.refill_lanes = apt::kDefaultRefillLanes;
     v_.has_camera = false;
     memset(&v_.camera, 0, sizeof v_.camera);
+    v_.has_env = false;
+    memset(&v_.env, 0, sizeof v_.env);
     struct { const char *env, *key; } knobs[] = {{"APT_QUEUE_PPW", "queue_ppw"}, {"APT_QUEUE_NBUF", "queue_nbuf"}, {"APT_QUEUE_LDS_PAD", "queue_lds_pad"},
                                                  {"APT_GRID_SPHERES_PER_CELL", "grid_spheres_per_cell"}};
     for (const auto &k : knobs) {
@@ -74,6 +76,11 @@ void apt_context::set_camera(const apt_camera *cam) {
     std::lock_guard<std::mutex> g(m_);
     v_.has_camera = cam != nullptr;
     if (cam) v_.camera = *cam;
+}
+void apt_context::set_environment(const apt_environment *env) {
+    std::lock_guard<std::mutex> g(m_);
+    v_.has_env = env != nullptr;
+    if (env) v_.env = *env;
 }
 int apt_context::set_debug(const char *key, double value) {
     if (!key) return apt::set_error(APT_ERR_ARG, "apt_context_set_debug: key is null%s");
@@ -712,5 +719,82 @@ int apt_context_set_camera(apt_context *ctx, const apt_camera *cam) {
 }
 
 int apt_set_camera(const apt_camera *cam) { return apt_context_set_camera(&apt::default_context(), cam); }
+
+} // extern "C"
+
+// ---- environment (include/render_mi355x.h "environment"): the record's host helpers, in the manner of the camera's.
+namespace {
+// The refusals of apt_environment_check_host, struct_size aside.
+int env_check_fields(const apt_environment &e, const char *what) {
+    if (e.flags & ~(uint32_t)APT_ENV_SAMPLE_SUN) return set_error(APT_ERR_ARG, "%s: environment: unknown flag bits", what);
+    const float *rad[3] = {e.horizon, e.zenith, e.sun_radiance};
+    for (const float *r : rad)
+        for (int k = 0; k < 3; ++k)
+            if (!(std::isfinite(r[k]) && r[k] >= 0.0f)) return set_error(APT_ERR_ARG, "%s: environment: a radiance is negative or not finite", what);
+    if (!(e.sun_omc >= 0.0f && e.sun_omc <= 1.0f)) return set_error(APT_ERR_ARG, "%s: environment: sun_omc must lie in [0, 1]", what);
+    if (!(std::isfinite(e.sun_dir[0]) && std::isfinite(e.sun_dir[1]) && std::isfinite(e.sun_dir[2])))
+        return set_error(APT_ERR_ARG, "%s: environment: sun_dir is not finite", what);
+    if (e.sun_omc > 0.0f) {
+        const double x = e.sun_dir[0], y = e.sun_dir[1], z = e.sun_dir[2];
+        double l2 = x * x;
+        l2 = l2 + y * y;
+        l2 = l2 + z * z;
+        if (!(fabs(l2 - 1.0) <= 0x1p-20)) return set_error(APT_ERR_ARG, "%s: environment: sun_dir must have unit length (squared length within 2^-20 of 1)", what);
+    }
+    return APT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int apt_environment_build_host(const double horizon[3], const double zenith[3], const double sun_dir[3], const double sun_radiance[3],
+                               double sun_omc, uint32_t flags, apt_environment *out) {
+    apt::clear_error();
+    const char *what = "apt_environment_build_host";
+    if (!horizon || !zenith || !sun_dir || !sun_radiance || !out) return set_error(APT_ERR_ARG, "%s: horizon/zenith/sun_dir/sun_radiance/out must be non-null", what);
+    if (out->struct_size != sizeof(apt_environment)) return set_error(APT_ERR_STRUCT, "%s: apt_environment.struct_size mismatch", what);
+    if (!(cam_finite3(horizon) && cam_finite3(zenith) && cam_finite3(sun_dir) && cam_finite3(sun_radiance) && std::isfinite(sun_omc)))
+        return set_error(APT_ERR_ARG, "%s: an input is not finite", what);
+    apt_environment r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = sizeof r;
+    r.flags = flags;
+    double w[3] = {sun_dir[0], sun_dir[1], sun_dir[2]};
+    if (sun_omc > 0) {
+        const double n = apt::norm3(sun_dir[0], sun_dir[1], sun_dir[2]);
+        if (!(n >= apt::kCamMinNorm)) return set_error(APT_ERR_ARG, "%s: sun_dir must be non-zero (norm >= 2^-30) when sun_omc > 0", what);
+        for (int k = 0; k < 3; ++k) w[k] = sun_dir[k] / n;
+    }
+    for (int k = 0; k < 3; ++k) {
+        r.horizon[k] = (float)horizon[k]; r.zenith[k] = (float)zenith[k];
+        r.sun_dir[k] = (float)w[k]; r.sun_radiance[k] = (float)sun_radiance[k];
+    }
+    r.sun_omc = (float)sun_omc;
+    const int rc = env_check_fields(r, what);
+    if (rc) return rc;
+    *out = r;
+    return APT_OK;
+}
+
+int apt_environment_check_host(const apt_environment *env) {
+    apt::clear_error();
+    if (!env) return set_error(APT_ERR_ARG, "%s: environment is null", "apt_environment_check_host");
+    if (env->struct_size != sizeof(apt_environment)) return set_error(APT_ERR_STRUCT, "%s: apt_environment.struct_size mismatch", "apt_environment_check_host");
+    return env_check_fields(*env, "apt_environment_check_host");
+}
+
+int apt_context_set_environment(apt_context *ctx, const apt_environment *env) {
+    apt::clear_error();
+    if (!ctx) return set_error(APT_ERR_ARG, "%s: context is null", "apt_context_set_environment");
+    if (env) {
+        if (env->struct_size != sizeof(apt_environment)) return set_error(APT_ERR_STRUCT, "%s: apt_environment.struct_size mismatch", "apt_context_set_environment");
+        const int rc = env_check_fields(*env, "apt_context_set_environment");
+        if (rc) return rc;
+    }
+    ctx->set_environment(env);
+    return APT_OK;
+}
+
+int apt_set_environment(const apt_environment *env) { return apt_context_set_environment(&apt::default_context(), env); }
 
 } // extern "C"

@@ -17,6 +17,7 @@ constexpr uint64_t kNeeKeySalt = 0xBB67AE8584CAA73Bull;   // APT_FLAG_NEE's stre
 constexpr int kMatNee = 4;      // APT_FLAG_NEE in the kernels' scene-form template argument (kScene8 / kSceneTiles / kSceneGrid are 0 / 1 / 2)
 static_assert((kMatNee & (kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatNee must be a bit of its own");
 constexpr uint64_t kLightKeySalt = 0x3C6EF372FE94F82Bull; // the light table's selection draw: a fourth stream
+constexpr uint64_t kSunKeySalt = APT_ENV_SUN_SALT;        // the environment's sun sample: one more
 constexpr int kMatLights = 8;   // a light table (the *_lights entries) in the same template argument; never together with kMatNee
 static_assert((kMatLights & (kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatLights must be a bit of its own");
 // How a kernel samples lights (LM, from the two bits above): not at all, the one sphere light_index, one light of a table per bounce.
@@ -26,7 +27,9 @@ constexpr int kMatCamera = 16;  // a context's camera (apt_context_set_camera) i
 static_assert((kMatCamera & (kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatCamera must be a bit of its own");
 constexpr int kMatGloss = 32;   // APT_FLAG_GLOSS in the same template argument: the table may hold APT_MAT_GLOSS words (the caller's statement)
 static_assert((kMatGloss & (kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatGloss must be a bit of its own");
-constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss); }
+constexpr int kMatEnv = 64;     // a context's environment (apt_context_set_environment) in the same template argument: only then is the kernels' MatEnv read
+static_assert((kMatEnv & (kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatEnv must be a bit of its own");
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv); }
 // The contract's limit (include/render_mi355x.h "camera"): a frame with a camera takes a plan of at most this many leaves.  Nothing in
 // the kernels needs it any more; lifting it is a feature with its own tests above 4199 samples, not part of any clean-up.
 constexpr uint32_t kCamMaxLeaves = 44;
@@ -70,6 +73,26 @@ struct MatKernelArgs {
 };
 static_assert(std::is_trivially_copyable<MatKernelArgs>::value && std::is_trivially_copyable<CameraTail>::value, "kernel arguments are copied as bytes");
 static_assert(offsetof(MatKernelArgs, ta) == 0, "the helpers that take TraceArgs see the layout they always saw");
+// The environment ("environment" in the header) as the kMatEnv kernels read it: a kernel argument of its own, so wave-uniform and
+// fetched by scalar loads where it is used.  gloss: the launch carries APT_FLAG_GLOSS -- the environment kernels are always the gloss
+// instantiations, and without the flag a well-formed gloss word is the bad code it is in the kernels without kMatGloss.
+struct MatEnv {
+    float horizon[3], zenith[3];
+    float sun[3], sun_rad[3];   // sun_dir, sun_radiance
+    float omc;                  // sun_omc; 0: no sun
+    uint32_t sample;            // APT_ENV_SAMPLE_SUN and omc > 0: DIFF hits sample the sun
+    uint32_t gloss;
+};
+struct MatNoEnv {};             // what the kernels without kMatEnv take in its place: nothing
+template <int SCN> using MatEnvArg = std::conditional_t<(SCN & kMatEnv) != 0, MatEnv, MatNoEnv>;
+static_assert(std::is_trivially_copyable<MatEnv>::value, "kernel arguments are copied as bytes");
+// The sun's part of a bounce's state (kMatEnv only): the stream key, `sampled_sun`, and what a DIFF hit hands to the sun's shadow test.
+struct MatSun {
+    uint64_t key;
+    bool sampled;
+    bool may;                   // this bounce may sample: E samples and d + 1 < depth (wave-uniform)
+    MatShadow sh;               // g is not read
+};
 template <int LM>
 __device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph, const TraceArgs &ta) {
     MatLight lt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1};
@@ -162,6 +185,7 @@ __device__ __forceinline__ float4 mat_light_emission(const MatTable &tb, int g) 
 __device__ __forceinline__ uint64_t light_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kLightKeySalt); }
 __device__ __forceinline__ uint64_t nee_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kNeeKeySalt); }
 __device__ __forceinline__ uint64_t mat_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kMatKeySalt); }
+__device__ __forceinline__ uint64_t sun_path_key(uint64_t seed, uint64_t path) { return splitmix64(seed ^ splitmix64(path) ^ kSunKeySalt); }
 __device__ __forceinline__ void mat_uniforms(uint64_t mkey, uint32_t d, float &u1, float &u2) {
     const uint64_t h = splitmix64(mkey + 0x9E3779B97F4A7C15ull * (uint64_t)(d + 1u));
     u1 = (float)(uint32_t)(h >> 40) * 0x1p-24f;
@@ -261,9 +285,11 @@ struct MatHit {
 // With LM == kLmNone lt, tb, sampled, kprev and sh are not read and nothing of this remains in the code.
 // GLOSS: a rough conductor of roughness h.alpha (the header's GLOSS block: visible normals of the GGX distribution in their
 // spherical-cap form, weight G1(l)).  A direction drawn below the horizon ends the path (s.live).  It does not sample, like SPEC.
-template <int LM, int SC, bool GL>
+// EV (kMatEnv): every hit clears su.sampled, and a DIFF hit that may (su.may) draws the sun's shadow segment -> su.sh, "Direct light
+// sampling"'s arithmetic with w = sun_dir and omc = sun_omc; without EV env and su are not read.
+template <int LM, int SC, bool GL, bool EV = false, class ENV = MatNoEnv>
 __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys key, uint32_t d, const MatLight &lt, bool may, bool &sampled,
-                                          MatShadow &sh, const MatTable &tb, int &kprev) {
+                                          MatShadow &sh, const MatTable &tb, int &kprev, const ENV &env, MatSun &su) {
     const int k = h.k;
     float hx = s.dx * h.t, hy = s.dy * h.t, hz = s.dz * h.t;
     hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
@@ -280,6 +306,7 @@ __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys k
     if (!counted) { s.lx = s.lx + s.tx * h.em.x; s.ly = s.ly + s.ty * h.em.y; s.lz = s.lz + s.tz * h.em.z; }
     if (LM == kLmNee) sampled = false;
     if (LM == kLmTable) kprev = -1;
+    if constexpr (EV) su.sampled = false;
     s.tx = s.tx * h.alb.x; s.ty = s.ty * h.alb.y; s.tz = s.tz * h.alb.z;
     const float ddn = mat_dot(s.dx, s.dy, s.dz, nx, ny, nz);
     const bool into = ddn < 0.0f;
@@ -333,6 +360,26 @@ __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys k
                 if (LM == kLmTable) { sh.w = sh.w * invp; sh.g = cur.idx; }
                 sh.want = cosl > 0.0f;
                 if (LM == kLmNee) sampled = true;
+            }
+        }
+        if constexpr (EV) {
+            if (su.may) {
+                const float omc = env.omc, wx = env.sun[0], wy = env.sun[1], wz = env.sun[2];
+                float v1, v2;
+                mat_uniforms(su.key, d, v1, v2);
+                const float cos_a = 1.0f - v1 * omc;
+                const float sin_a = sqrtf(1.0f - cos_a * cos_a);
+                float sp, cp;
+                mat_sincos(v2, sp, cp);
+                float ax, ay, az, ex, ey, ez;
+                mat_basis(wx, wy, wz, ax, ay, az, ex, ey, ez);
+                const float ca = cp * sin_a, sa = sp * sin_a;
+                const float qx = (ax * ca + ex * sa) + wx * cos_a, qy = (ay * ca + ey * sa) + wy * cos_a, qz = (az * ca + ez * sa) + wz * cos_a;
+                mat_normalise(qx, qy, qz, su.sh.dx, su.sh.dy, su.sh.dz);
+                const float cosl = mat_dot(su.sh.dx, su.sh.dy, su.sh.dz, nlx, nly, nlz);
+                su.sh.w = cosl * (2.0f * omc);
+                su.sh.want = cosl > 0.0f;
+                su.sampled = true;                            // whatever follows
             }
         }
     } else if (GL && h.code == (uint32_t)APT_MAT_GLOSS) {
@@ -534,11 +581,17 @@ __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ s
 // LM != kLmNone: after a bounce that drew a shadow segment, that segment goes through the form's own hit routine -- so it sees the scene the bounce
 // ray will see -- whenever some lane of the wave (of the workgroup for the tile form, whose scan has barriers) has one; the light is
 // visible iff the arg-min is the light (the lane's own chosen light with a table).  A traced shadow segment counts as a traced segment.
-template <int SC, int LM, bool GL>
+// EV (kMatEnv; env: the environment, else not read): a live path that finds no sphere gathers the sky and -- unless the bounce before
+// sampled it -- the sun before it ends, and after a DIFF bounce that drew one (mat_shade) the sun's shadow segment goes through the
+// same hit routine under the same vote, after the light's: the sun is visible iff it finds no sphere.
+template <int SC, int LM, bool GL, bool EV = false, class ENV = MatNoEnv>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
                                               const GridHeader &gh, const MatLight &lt, const MatTable &tb, float4 *tile, MatPath &s,
-                                              const TraceArgs &ta, uint64_t path) {
+                                              const TraceArgs &ta, uint64_t path, const ENV &env = ENV()) {
     const MatKeys key = mat_path_keys<LM>(ta.seed, path);
+    MatSun su;
+    su.sampled = false;
+    if constexpr (EV) su.key = env.sample ? sun_path_key(ta.seed, path) : 0;
     const uint64_t rr_key = ta.rr_start ? rr_path_key(ta.seed, path) : 0;
     uint32_t traced = 0, n_cells = 0, n_tests = 0;           // the last two: walk statistics of the grid form
     bool sampled = false;                                    // kLmNee: the previous bounce sampled the light
@@ -573,6 +626,21 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
                 h.alpha = (float)q * 0x1p-16f;
             }
         }
+        if constexpr (EV) {
+            if (GL && !env.gloss && h.code == (uint32_t)APT_MAT_GLOSS) h.code = 15u;   // no APT_FLAG_GLOSS: a gloss word is a bad code
+            if (s.live && h.k < 0) {                          // miss: the sky, and the sun unless the bounce before sampled it
+                float t = s.dy * 0.5f + 0.5f;
+                t = t > 0.0f ? t : 0.0f;
+                t = t < 1.0f ? t : 1.0f;
+                const float kx = env.horizon[0] + (env.zenith[0] - env.horizon[0]) * t;
+                const float ky = env.horizon[1] + (env.zenith[1] - env.horizon[1]) * t;
+                const float kz = env.horizon[2] + (env.zenith[2] - env.horizon[2]) * t;
+                s.lx = s.lx + s.tx * kx; s.ly = s.ly + s.ty * ky; s.lz = s.lz + s.tz * kz;
+                if (env.omc > 0.0f && mat_dot(s.dx, s.dy, s.dz, env.sun[0], env.sun[1], env.sun[2]) >= 1.0f - env.omc && !su.sampled) {
+                    s.lx = s.lx + s.tx * env.sun_rad[0]; s.ly = s.ly + s.ty * env.sun_rad[1]; s.lz = s.lz + s.tz * env.sun_rad[2];
+                }
+            }
+        }
         const bool hit = s.live && h.k >= 0;
         const bool bad = hit && h.code > (uint32_t)(GL ? APT_MAT_GLOSS : APT_MAT_REFR);
         if (__any(bad)) report_status(ta, APT_DEV_BAD_MATERIAL);
@@ -580,8 +648,11 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
         const bool may = LM && d + 1 < ta.depth;              // no sample at the last bounce: the header says why
         MatShadow sh;
         sh.want = false;
+        su.sh.want = false;
+        su.may = false;
+        if constexpr (EV) su.may = env.sample && d + 1 < ta.depth;   // no sample at the last bounce, as for the lights
         if (s.live) {
-            mat_shade<LM, SC, GL>(s, h, key, d, lt, may, sampled, sh, tb, kprev);
+            mat_shade<LM, SC, GL, EV>(s, h, key, d, lt, may, sampled, sh, tb, kprev, env, su);
             ++traced;
         }
         if (may && (SC == kSceneTiles ? __syncthreads_or(sh.want) : __any(sh.want))) {
@@ -604,6 +675,28 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
                     }
                 } else if (ks == lt.idx) {
                     s.lx = s.lx + (s.tx * lt.ex) * sh.w; s.ly = s.ly + (s.ty * lt.ey) * sh.w; s.lz = s.lz + (s.tz * lt.ez) * sh.w;
+                }
+            }
+        }
+        if constexpr (EV) {
+            if (su.may && (SC == kSceneTiles ? __syncthreads_or(su.sh.want) : __any(su.sh.want))) {
+                const bool want = su.sh.want;
+                MatPath q;                                    // from h along l with this bounce's skip, as the light's segment
+                q.ox = s.ox; q.oy = s.oy; q.oz = s.oz;
+                q.dx = want ? su.sh.dx : s.dx; q.dy = want ? su.sh.dy : s.dy; q.dz = want ? su.sh.dz : s.dz;
+                q.skip = s.skip;
+                q.live = want;
+                float ts;
+                int ks;
+                if (SC == kScene8) mat_hit8<true>(m8.sc, q, ta.eps, ts, ks);
+                else if (SC == kSceneGrid) mat_hit_grid(gh, ta.grid, q, ta.eps, ts, ks, n_cells, n_tests);
+                else mat_hit_tiles(sph, tile, q, ta.ns, ta.eps, ts, ks);
+                if (want) {
+                    ++traced;
+                    if (ks < 0) {                             // nothing in the way: the sun is visible
+                        s.lx = s.lx + (s.tx * env.sun_rad[0]) * su.sh.w; s.ly = s.ly + (s.ty * env.sun_rad[1]) * su.sh.w;
+                        s.lz = s.lz + (s.tz * env.sun_rad[2]) * su.sh.w;
+                    }
                 }
             }
         }
@@ -642,14 +735,18 @@ __device__ __forceinline__ void mat_path_init(MatPath &s, float ox, float oy, fl
 // SCN: the scene form, with kMatNee set for APT_FLAG_NEE or kMatLights for a light table, and kMatGloss.  All travel in the first template argument so
 // that the instantiations a launch without them runs keep the symbol names (and, the sampling code being dead there, the instructions)
 // they had before these existed.
+// ev: the environment with kMatEnv, else an empty argument (which moves the hidden kernel arguments by 8 bytes: the only thing that
+// differs in the instructions of the kernels without kMatEnv from what they were before there was an environment).
 template <int SCN>
 __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *__restrict__ rays, const float *__restrict__ sph,
                                                                   const uint32_t *__restrict__ mat, float *__restrict__ colors,
-                                                                  uint64_t n_total, uint64_t begin, uint64_t count, MatKernelArgs ka) {
+                                                                  uint64_t n_total, uint64_t begin, uint64_t count, MatKernelArgs ka,
+                                                                  MatEnvArg<SCN> ev) {
     const TraceArgs &ta = ka.ta;
     constexpr int SC = mat_scene_of(SCN);
     constexpr int LM = mat_light_mode(SCN);
     constexpr bool GL = (SCN & kMatGloss) != 0;
+    constexpr bool EV = (SCN & kMatEnv) != 0;
     __shared__ float4 tab[mat_tab_entries(SCN)];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     GridHeader gh;
@@ -664,7 +761,7 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
     const uint64_t p = begin + (valid ? local : 0);
     MatPath s;
     mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
-    const uint32_t traced = trace_mat<SC, LM, GL>(sph, mat, m8, gh, lt, tb, tile, s, ta, p);
+    const uint32_t traced = trace_mat<SC, LM, GL, EV>(sph, mat, m8, gh, lt, tb, tile, s, ta, p, ev);
     if (valid) {
         colors[p] = s.lx;
         colors[n_total + p] = s.ly;
@@ -700,13 +797,16 @@ __global__ __launch_bounds__(kBlock) void gen_rays_camera_kernel(CameraEx cam, u
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
 // SCN: the scene form and kMatNee / kMatLights / kMatGloss, as for the buffer kernel, and kMatCamera: only then is `ct` read.
+// kMatEnv (both kernels): only then does `ev` hold anything -- the environment.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
-                                                                  FrameArgs fa, MatKernelArgs ka, LeafProg lp, CameraTail ct) {
+                                                                  FrameArgs fa, MatKernelArgs ka, LeafProg lp, CameraTail ct,
+                                                                  MatEnvArg<SCN> ev) {
     const TraceArgs &ta = ka.ta;
     constexpr int SC = mat_scene_of(SCN);
     constexpr int LM = mat_light_mode(SCN);
     constexpr bool GL = (SCN & kMatGloss) != 0;
+    constexpr bool EV = (SCN & kMatEnv) != 0;
     __shared__ float4 tab[mat_tab_entries(SCN)];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
@@ -747,7 +847,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         }
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        traced += trace_mat<SC, LM, GL>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k);
+        traced += trace_mat<SC, LM, GL, EV>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k, ev);
         return Col{s.lx, s.ly, s.lz};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };

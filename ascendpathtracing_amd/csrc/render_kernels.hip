@@ -70,7 +70,9 @@ int check_materials(const apt_render_params *p, const uint32_t *materials, bool 
 
 // A context's camera (include/render_mi355x.h "camera") serves the material frame entries only.  The mirror frame entries have exactly the
 // reference's camera and refuse, after their own checks, rather than render a frame from a viewpoint the caller did not ask for.
+// The same holds for a context's environment ("environment"): the mirror renderer has none, and refuses with the same status.
 int refuse_camera(const apt_context::Values &cv, const char *entry) {
+    if (cv.has_env) return fail(APT_ERR_ARG, "%s: the context has an environment set (apt_context_set_environment), which the mirror frame entries do not take: unset it, or use the material entries", entry);
     return cv.has_camera ? fail(APT_ERR_ARG, "%s: the context has a camera set (apt_context_set_camera), which the mirror frame entries do not take: unset it, or use apt_gen_rays_camera_device + render_do_ex + apt_decode_color_device", entry) : APT_OK;
 }
 
@@ -196,7 +198,9 @@ int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, 
     if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
     if (mat) {   // per-sphere materials: materials.hip
         if ((rc = check_lights_status(ma, ls.status))) return rc;
-        apt::mat_render_paths(apt::MatPathsCall{make_mat_trace(p, ls, ma), r.base(rays), spheres, ma.materials, r.base(colors), n, b, c, stream});
+        const apt::MatPathsCall call{make_mat_trace(p, ls, ma), r.base(rays), spheres, ma.materials, r.base(colors), n, b, c, stream};
+        if (ls.cv.has_env) apt::env_render_paths(call, ls.cv.env);   // the context's environment: environment.hip
+        else apt::mat_render_paths(call);
         return launched();
     }
     hipStream_t st = (hipStream_t)stream;
@@ -262,9 +266,20 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     const apt::Debug &dbg = ls.cv.debug;
     if (mat) {   // per-sphere materials: materials.hip
         if ((rc = check_lights_status(ma, ls.status))) return rc;
-        if (ls.cv.has_camera && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera: a frame with a camera set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
-        apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
-                                                pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr});
+        if ((ls.cv.has_camera || ls.cv.has_env) && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera / environment: a frame with a camera or an environment set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
+        apt::MatFrameCall call{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
+                               pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr};
+        if (ls.cv.has_env) {   // the context's environment: environment.hip, whose frame kernels all take a camera record
+            apt_camera reference;
+            reference.struct_size = sizeof reference;
+            if (!call.camera) {
+                if ((rc = apt_camera_default_host(p->width, p->height, &reference))) return rc;   // (its own error record)
+                call.camera = &reference;
+            }
+            apt::env_render_frame(call, ls.cv.env);
+            return launched();
+        }
+        apt::mat_render_frame(call);
         return launched();
     }
     if ((rc = refuse_camera(ls.cv, "render_frame"))) return rc;

@@ -17,6 +17,9 @@ stripe, so that all ranks send equal bytes whatever the split:
     per stripe:  float32 region of 3*max_stripe floats holding the dense [3][count] planes at its start,
                  uint8   region of 3*max_stripe bytes  holding the dense [count][3] pixels at its start.
 The kernels write straight into these regions (no pack step); the root unpacks with the true counts.
+
+Mirrors only.  The bands are rendered by the mirror frame entry: this module takes neither materials nor a camera nor an environment
+(render.set_camera / render.set_environment), and that entry refuses while the default context carries one of the two.
 """
 import json
 import os

@@ -314,3 +314,80 @@ def camera(eye, dir=None, target=None, up=(0, 1, 0), vfov_deg=None, scale=0.5135
                                       ctypes.c_double(offset), ctypes.c_double(aperture), ctypes.c_double(focus), ctypes.c_uint32(width),
                                       ctypes.c_uint32(height), ctypes.byref(c)), "apt_camera_build_host")
     return c
+
+
+def environment(horizon=(0.0, 0.0, 0.0), zenith=None, sun_dir=(0.0, 1.0, 0.0), sun_radiance=(0.0, 0.0, 0.0), sun_angle_deg=0.0,
+                sample_sun=True):
+    """An environment record (apt_environment_build_host) for render.set_environment / Context.set_environment: a sky that blends from
+    `horizon` (straight down) to `zenith` (straight up, +y; None: the horizon's value, a uniform sky) and a sun of radiance
+    `sun_radiance` in the cone of half angle sun_angle_deg (0 = no sun, at most 90) around `sun_dir` (any length).  Radiances are one
+    number or an (r, g, b) triple.  sample_sun: DIFF hits sample the sun directly (APT_ENV_SAMPLE_SUN: the same expectation, far less
+    noise for a small sun).  sun_omc = 1 - cos(angle) is made here with numpy as 2 * sin(angle / 2)^2, which does not cancel for a
+    small angle; the real sun's 0.2666 degrees give 1.08e-5."""
+    from ._lib import APT_ENV_SAMPLE_SUN, ApEnvironment
+    rgb = lambda v: [float(v)] * 3 if np.isscalar(v) else [float(x) for x in v]
+    if not 0.0 <= float(sun_angle_deg) <= 90.0:
+        raise AptError("environment: sun_angle_deg must lie in [0, 90]")
+    half = np.sin(np.radians(np.float64(sun_angle_deg)) * 0.5)
+    omc = float(2.0 * half * half)
+    d3 = ctypes.c_double * 3
+    e = ApEnvironment()
+    e.struct_size = ctypes.sizeof(ApEnvironment)
+    check(lib().apt_environment_build_host(d3(*rgb(horizon)), d3(*rgb(horizon if zenith is None else zenith)), d3(*[float(x) for x in sun_dir]),
+                                           d3(*rgb(sun_radiance)), ctypes.c_double(omc),
+                                           ctypes.c_uint32(APT_ENV_SAMPLE_SUN if sample_sun and omc > 0.0 else 0), ctypes.byref(e)),
+          "apt_environment_build_host")
+    return e
+
+
+def _table_of(rows):
+    """rows of (radius, x, y, z, emission rgb, albedo rgb) -> the zero-padded [10][Ns] table; r -> r^2 in float64, one rounding."""
+    rows = np.array(rows, dtype=np.float64)
+    rows[:, 0] = rows[:, 0] ** 2
+    ns = rows.shape[0]
+    out = np.zeros((ns * 10 + 127) // 128 * 128, dtype=np.float32)
+    out[:10 * ns] = rows.T.astype(np.float32).ravel()
+    return out
+
+
+def gen_spheres_open():
+    """An open 8-sphere scene for an environment (render.set_environment): a ground sphere of radius 1e5 whose top is y = 0 and seven
+    balls standing on it around (50, ., 60), in front of the reference camera -- three DIFF, a mirror, a glass ball, and two rough-metal
+    balls (render with materials_flags(materials), APT_FLAG_GLOSS).  No walls and no emitter: without an environment every image of
+    it is black -> (spheres float32 [128] = [10][8] planes zero padded, materials int32 [8]).  Pure Python."""
+    from ._lib import MAT_DIFF, MAT_REFR, MAT_SPEC
+    rows = [[1e5, 50.0, -1e5, 60.0, 0, 0, 0, 0.55, 0.5, 0.45],        # the ground
+            [16.5, 27.0, 16.5, 47.0, 0, 0, 0, 0.999, 0.999, 0.999],   # mirror
+            [16.5, 73.0, 16.5, 78.0, 0, 0, 0, 0.999, 0.999, 0.999],   # glass
+            [12.0, 50.0, 12.0, 30.0, 0, 0, 0, 0.75, 0.25, 0.25],      # DIFF, red
+            [8.0, 10.0, 8.0, 90.0, 0, 0, 0, 0.25, 0.75, 0.25],        # DIFF, green
+            [8.0, 92.0, 8.0, 40.0, 0, 0, 0, 0.25, 0.25, 0.75],        # DIFF, blue
+            [10.0, 52.0, 10.0, 100.0, 0, 0, 0, 0.9, 0.7, 0.3],        # rough metal, satin
+            [6.0, 30.0, 6.0, 105.0, 0, 0, 0, 0.8, 0.8, 0.85]]         # rough metal, nearly a mirror
+    mat = np.array([MAT_DIFF, MAT_SPEC, MAT_REFR, MAT_DIFF, MAT_DIFF, MAT_DIFF, gloss(0.35), gloss(0.05)], dtype=np.int32)
+    return _table_of(rows), mat
+
+
+def gen_scene_open(num_spheres, seed=0):
+    """An open many-sphere scene for an environment: sphere 0 is gen_spheres_open's ground (radius 1e5, top at y = 0, DIFF) and spheres
+    1 .. num_spheres - 1 are the small spheres of gen_scene_materials(num_spheres + 6, seed) -- its spheres 6 .. num_spheres + 4, radius
+    0.5 .. 2 in the box [1, 99] x [0, 81.6] x [0, 170], with their material codes -- without its six walls and its light.  The walls
+    of gen_scene are spheres that ENCLOSE the room, so taking away the ceiling alone opens nothing: every upward ray still ends on
+    the inside of another wall; hence this scene instead of a variant of that one.  apt_build_grid_host accepts it (checked on the
+    CPU, tests/test_environment_cpu.py: the ground goes to the always-tested list, the small spheres into cells), and
+    num_spheres <= 64 runs through LDS tiles -> (spheres float32 zero-padded [10][Ns], materials int32 [Ns]).  No emitter: light it
+    with an environment, or turn small spheres into lamps with with_lamps.  Pure Python on top of gen_scene_materials."""
+    ns = int(num_spheres)
+    if ns < 2:
+        raise AptError("gen_scene_open: needs num_spheres >= 2 (the ground and a sphere)")
+    from ._lib import MAT_DIFF
+    src, smat = gen_scene_materials(ns + 6, seed)
+    small = src[:10 * (ns + 6)].reshape(10, ns + 6)[:, 6:ns + 5]
+    out = np.zeros((ns * 10 + 127) // 128 * 128, dtype=np.float32)
+    planes = out[:10 * ns].reshape(10, ns)
+    planes[:, 0] = _table_of([[1e5, 50.0, -1e5, 60.0, 0, 0, 0, 0.55, 0.5, 0.45]])[:10]
+    planes[:, 1:] = small
+    mat = np.empty(ns, dtype=np.int32)
+    mat[0] = MAT_DIFF
+    mat[1:] = smat[6:ns + 5]
+    return out, mat

@@ -139,6 +139,12 @@ class Context:
         reference's camera again), its mirror frame entries refuse while one is set."""
         check(lib().apt_context_set_camera(self._h, None if cam is None else ctypes.byref(cam)), "apt_context_set_camera")
 
+    def set_environment(self, env):
+        """apt_context_set_environment: this context's material and light-table entries, frame and buffer mode, gather `env`'s sky and
+        sun where a path leaves the scene (gen_data.environment; None: no environment, every image as before); its mirror frame
+        entries refuse while one is set."""
+        check(lib().apt_context_set_environment(self._h, None if env is None else ctypes.byref(env)), "apt_context_set_environment")
+
     def set_debug(self, key, value):
         check(lib().apt_context_set_debug(self._h, key.encode(), ctypes.c_double(value)), "apt_context_set_debug")
 
@@ -227,6 +233,13 @@ def set_camera(cam):
     materials= then renders from it; render_frame without materials refuses while it is set (gen_rays_camera + render_paths +
     decode_color_device gives the mirror renderer a camera)."""
     check(lib().apt_set_camera(None if cam is None else ctypes.byref(cam)), "apt_set_camera")
+
+
+def set_environment(env):
+    """apt_set_environment: the default context's environment (gen_data.environment), or None for none.  render_frame / render_do_ex
+    with materials= (and lights=) then light every path that leaves the scene with its sky and sun; render_frame without materials
+    refuses while it is set.  dist.py and MultiGpu render mirrors only: they take neither materials nor an environment."""
+    check(lib().apt_set_environment(None if env is None else ctypes.byref(env)), "apt_set_environment")
 
 
 def set_debug(key, value):

@@ -257,7 +257,8 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  *   state   o, d = the camera ray (render_frame) or the ray buffer (render_paths); L = (0,0,0), T = (1,1,1); skip = none.
  *   bounce d = 0 .. depth-1:
  *     hit     the K-mode test of render_do_ex for every sphere but `skip` (t = t0 > eps ? t0 : t1, accepted when t > eps, strict '<'
- *             arg-min, lowest index on ties, kMissT = 1e20 never wins).  No sphere: the path ends (L keeps its value).
+ *             arg-min, lowest index on ties, kMissT = 1e20 never wins).  No sphere: the path ends (L keeps its value; with an environment set it first gathers the sky
+ *             and the sun, "environment" below).
  *     code    m = materials[k] of the hit sphere k; m > 2: the kernel ORs APT_DEV_BAD_MATERIAL into the status word and the path ends.
  *             With APT_FLAG_GLOSS a word APT_MAT_GLOSS_WORD(q) -- low byte 3, q in bits 8..23 with 1 <= q <= 65535, bits 24..31 zero --
  *             is a GLOSS sphere of roughness alpha = q * 2^-16 (exact in fp32); every other word above 2 (q == 0, a set bit 24..31, a
@@ -504,6 +505,81 @@ int apt_set_camera(const apt_camera *cam_or_null);
 /* apt_gen_rays_device for a camera: rays [6][N] for paths [path_begin, path_begin + path_count) (APT_FLAG_BAND_BUFFERS as there), the
  * rays the material frame entries trace with this camera set, bit for bit.  The record is the argument's, not the context's. */
 int apt_gen_rays_camera_device(const apt_render_params *p, const apt_camera *cam, void *stream, float *rays);
+
+/* ---- environment (EXTENSION: light from the directions where there is no geometry -- a sky and a sun -- for the material renderer) ------
+ * Above, a path whose hit test finds no sphere ends and L keeps its value: every ray that leaves the scene is black.  An apt_environment
+ * gives those directions a radiance: a sky that blends from `horizon` (d.y = -1) to `zenith` (d.y = +1; the scene's up is +y) and a sun,
+ * "a sphere light at infinity": a cone of half angle a around the unit vector sun_dir, sun_omc = 1 - cos(a), of radiance sun_radiance.
+ * A context carries at most one (apt_context_set_environment; none = every entry, kernel and image as before).  With one set
+ *   - the material and light-table entries -- apt_render_frame_materials, apt_render_paths_materials, apt_render_frame_lights,
+ *     apt_render_paths_lights and their apt_context_* forms, frame and buffer mode alike -- read it;
+ *   - the mirror frame entries that refuse while a camera is set (render_frame / apt_context_render_frame, apt_render_frame_mt,
+ *     apt_multi_create / apt_multi_render) refuse in the same way, APT_ERR_ARG after their own checks: they have no environment;
+ *   - a material frame takes a pairwise-sum plan of at most 44 leaves, as with a camera set (APT_ERR_ARG otherwise), and with no camera
+ *     set it is rendered from apt_camera_default_host's record, which is the reference's camera bit for bit (APT_ERR_ARG for an image
+ *     shape that record refuses);
+ *   - the mirror buffer-mode entries (render_do, render_do_ex) take no environment and are unaffected.
+ * APT_ABI_VERSION is unchanged: callers detect the feature by its symbols.
+ *
+ * The arithmetic, in the terms of "per-sphere materials" and "Direct light sampling" above (fp32, every operation rounded on its own:
+ * no FMA).  With an environment E a path carries one more flag, `sampled_sun`, false at its start, and the bounce changes in three
+ * places:
+ *     miss    a live path whose arg-min finds no sphere, along its direction d:
+ *             t = d.y * 0.5f + 0.5f (mul, then add); t = t > 0 ? t : 0; t = t < 1 ? t : 1            (a NaN gives 0)
+ *             sky_c = horizon_c + (zenith_c - horizon_c) * t;  L_c = L_c + T_c * sky_c                 per channel c
+ *             then, if sun_omc > 0 and dot(d, sun_dir) >= 1.0f - sun_omc and not `sampled_sun`: L_c = L_c + T_c * sun_radiance_c.
+ *             The path ends.
+ *     light   at every hit sampled_sun = false, next to sampled = false.
+ *     sun sample  at a DIFF hit when d + 1 < depth, E.flags & APT_ENV_SAMPLE_SUN and sun_omc > 0, after the DIFF direction is drawn and
+ *             after the APT_FLAG_NEE / light-table sample if there is one.  "Direct light sampling"'s own arithmetic with w = sun_dir
+ *             and omc = sun_omc (no d2, x, cmax or dl: the record holds both):
+ *             skey = splitmix64(seed ^ splitmix64(path) ^ APT_ENV_SUN_SALT); (v1, v2) from skey exactly as (u1, u2) from mkey
+ *             (one more stream: h = splitmix64(skey + 0x9E3779B97F4A7C15 * (d + 1)), the same 24-bit split)
+ *             cos_a = 1 - v1 * omc; sin_a = sqrt(1 - cos_a * cos_a); (sin, cos) of 2*pi*v2 by DIFF's polynomial
+ *             (t, bt) = the Duff basis of w; q = (t * (cos * sin_a) + bt * (sin * sin_a)) + w * cos_a per component
+ *             l = q / sqrt(dot(q, q)); cosl = dot(l, nl); wgt = cosl * (2 * omc)
+ *             sampled_sun = true, whatever follows.
+ *             if cosl > 0: a shadow segment from h along l through the hit test, every sphere but this bounce's skip sphere.  The sun
+ *             is visible iff that test finds NO sphere.  Visible: L_c = L_c + (T_c * sun_radiance_c) * wgt, T being the throughput
+ *             after `T *= albedo` and before this bounce's roulette; it is added after the light's own contribution.
+ *   There is NO sample at the last bounce (d + 1 == depth), for the reason given for APT_FLAG_NEE: the sample at bounce d stands for the
+ *   sun a miss of segment d + 1 would add.  With this rule APT_ENV_SAMPLE_SUN changes the image by noise only, and at depth 1 by
+ *   nothing.  The sun's shadow segment counts as a traced segment in the trace counter (and its cells / candidates in the grid
+ *   statistics).  GLOSS, SPEC and REFR hits do not sample: a miss after them adds the sun in full.  The sun sample is independent of
+ *   APT_FLAG_NEE and of a light table: it works with neither of them and with either (a launch has at most one of the two).  The cone test
+ *   dot(d, sun_dir) >= 1.0f - sun_omc is an fp32 decision: the sampled cone (cos_a >= 1 - omc before q is normalised) and the tested
+ *   cone differ by rounding at the rim, a relative solid angle of the order of 2^-23 / sun_omc.  A miss on the camera ray adds sky and
+ *   sun like any other.  Roulette, APT_DEV_BAD_MATERIAL, the grid rules (a grid that is not the scene's: nothing written,
+ *   APT_DEV_GRID_MISMATCH), APT_FLAG_GLOSS and the light rules are as above.
+ * An environment whose radiances are all 0 and that has no sun (sun_omc = 0) adds exactly +0 at a miss: every image is the one without
+ * an environment, bit for bit. */
+enum { APT_ENV_SAMPLE_SUN = 1u };  /* apt_environment.flags: sample the sun directly at every diffuse hit */
+#define APT_ENV_SUN_SALT 0x510E527FADE682D1ull   /* the sun sample's stream; differs from the bounce's, APT_FLAG_NEE's, the light table's, the lens's and roulette's (none) */
+typedef struct apt_environment {
+    uint32_t struct_size;       /* = sizeof(apt_environment)                                                */
+    uint32_t flags;             /* APT_ENV_*                                                                */
+    float horizon[3], zenith[3];/* sky radiance at d.y = -1 and d.y = +1                                    */
+    float sun_dir[3];           /* unit, towards the sun                                                    */
+    float sun_radiance[3];
+    float sun_omc;              /* 1 - cos(half angle); 0 = no sun; <= 1                                    */
+} apt_environment;
+
+/* Host helpers: no GPU, nothing written unless APT_OK.
+ * apt_environment_build_host: sun_dir of any length is normalised in float64, one operation at a time as apt_camera_build_host does
+ *   (n = sqrt(fma(d2, d2, fma(d1, d1, d0*d0))), d[k] / n), then every field is rounded ONCE to fp32.  With sun_omc == 0 sun_dir may be
+ *   anything finite (a zero vector is stored as it is).  APT_ERR_ARG: a NULL pointer, a non-finite input, a sun_dir shorter than 2^-30
+ *   with sun_omc > 0, or a finished record apt_environment_check_host refuses.  APT_ERR_STRUCT when out->struct_size is not
+ *   sizeof(apt_environment): the caller sets it.
+ * apt_environment_check_host: APT_ERR_STRUCT for a wrong struct_size; APT_ERR_ARG for a NULL pointer, unknown flag bits, a radiance
+ *   (horizon, zenith, sun_radiance) that is not finite or is negative, sun_omc outside [0, 1] or NaN, a non-finite sun_dir, and with
+ *   sun_omc > 0 a sun_dir whose squared length (float64 from the fp32 fields) is further than 2^-20 from 1.
+ * apt_context_set_environment: checked (the same refusals), copied, part of the snapshot every render call takes.  NULL removes it.  A
+ *   refused record leaves the previous one in place.  apt_set_environment = the default context. */
+int apt_environment_build_host(const double horizon[3], const double zenith[3], const double sun_dir[3] /* any length */,
+                               const double sun_radiance[3], double sun_omc, uint32_t flags, apt_environment *out);
+int apt_environment_check_host(const apt_environment *env);
+int apt_context_set_environment(apt_context *ctx, const apt_environment *env_or_null);
+int apt_set_environment(const apt_environment *env_or_null);
 
 /* ---- one process, several GPUs (the reference's 8-block split, src/render.cpp:9-10,24-27, across devices) ----
  * The frame's x-major pixel range is cut into num_bands*stripes contiguous stripes; band b renders stripes
