@@ -21,6 +21,9 @@ APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH
 APT_DEV_BAD_MATERIAL = 16
 APT_DEV_LIGHTS_MISMATCH = 32
 APT_ENV_SAMPLE_SUN = 1                  # apt_environment.flags: DIFF hits sample the sun directly
+APT_TONEMAP_CLIP, APT_TONEMAP_REINHARD = 0, 1   # apt_film_resolve.tonemap
+APT_CURVE_LINEAR, APT_CURVE_SRGB = 0, 1         # apt_film_curve_host
+APT_FILM_PASS_SALT = 0x9B05688C2B3E6C1F
 MAT_GLOSS = 3                           # with APT_FLAG_GLOSS: gen_data.gloss(alpha) makes the word (APT_MAT_GLOSS_WORD)
 MAT_SPEC, MAT_DIFF, MAT_REFR = 0, 1, 2  # material codes of the *_materials entries (include/render_mi355x.h APT_MAT_*)
 
@@ -43,6 +46,8 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_camera_default_host", "apt_camera_build_host", "apt_camera_check_host", "apt_context_set_camera", "apt_set_camera",
                "apt_gen_rays_camera_device",
                "apt_environment_build_host", "apt_environment_check_host", "apt_context_set_environment", "apt_set_environment",
+               "apt_film_pass_seed", "apt_render_frame_film", "apt_context_render_frame_film", "apt_film_curve_host",
+               "apt_film_resolve_device", "apt_film_resolve_host", "apt_write_pfm",
                "apt_selftest_direction", "apt_selftest_direction_host", "apt_selftest_chain_states_host", "apt_selftest_div3_seeded",
                "apt_selftest_tent_bits_host"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
@@ -104,6 +109,16 @@ class ApEnvironment(ctypes.Structure):
         return e
 
 
+class ApFilmResolve(ctypes.Structure):
+    """apt_film_resolve (include/render_mi355x.h "film"): passes in the film, the tone operator, exposure and 1 / white^2."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("tonemap", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("exposure", ctypes.c_float), ("inv_white2", ctypes.c_float)]
+
+
+def film_resolve_record(passes, exposure=1.0, tonemap=APT_TONEMAP_CLIP, inv_white2=0.0):
+    return ApFilmResolve(ctypes.sizeof(ApFilmResolve), passes, tonemap, 0, exposure, inv_white2)
+
+
 _lib = None
 
 
@@ -137,6 +152,8 @@ def lib():
         h.apt_multi_destroy.restype = None
         h.apt_lights_bytes.restype = ctypes.c_size_t
         h.apt_materials_flags_host.restype = ctypes.c_uint32
+        h.apt_film_pass_seed.restype = ctypes.c_uint64
+        h.apt_film_pass_seed.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
         getattr(h, CXX_RENDER_DO).restype = None
         if h.apt_abi_version() != ABI_VERSION:
             raise AptError("librender_mi355x.so ABI version mismatch")

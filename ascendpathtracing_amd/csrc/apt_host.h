@@ -82,4 +82,6 @@ struct apt_context {
 
 namespace apt {
 apt_context &default_context(); // process-wide, constructed on first use (thread-safe static)
+// What both forms of the film resolve refuse (host_helpers.cpp; include/render_mi355x.h "film"): APT_OK or the error record set.
+int film_resolve_check(const apt_film_resolve *r, const void *film, const void *table, const void *out, const void *u8, const char *what);
 }

@@ -69,6 +69,13 @@ void mat_gen_rays_camera(const CamRaysCall &call);
 void env_render_frame(const MatFrameCall &call, const apt_environment &env);
 void env_render_paths(const MatPathsCall &call, const apt_environment &env);
 
+// The film launches (include/render_mi355x.h "film"), film.hip: a fourth code object.  film_render_frame is env_render_frame with a film
+// tail: call.fb is the film, call.fb_u8 null, `add` false for pass 0 (a store).  Always the kMatEnv kernels: without an environment the
+// caller hands in the all-zero record.  film_resolve: the checked arguments of apt_film_resolve_device, pixel_count > 0.
+void film_render_frame(const MatFrameCall &call, const apt_environment &env, bool add);
+void film_resolve(const apt_film_resolve &r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev, float *out_or_null,
+                  uint8_t *u8_or_null);
+
 // apt_selftest_direction's launch (count > 0): the test kernel is kept out of render_kernels.hip's code object as well.
 void selftest_direction(void *stream, const double *d3_dev, uint64_t count, uint64_t *result5_dev, uint8_t *flags_dev);
 

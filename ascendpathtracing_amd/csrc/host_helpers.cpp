@@ -798,3 +798,96 @@ int apt_context_set_environment(apt_context *ctx, const apt_environment *env) {
 int apt_set_environment(const apt_environment *env) { return apt_context_set_environment(&apt::default_context(), env); }
 
 } // extern "C"
+
+// ---- film (include/render_mi355x.h "film"): the pass seed, the curve table, the resolve's CPU twin and the PFM writer.
+namespace apt {
+// What both resolve forms refuse, in the header's order; the pointers are the entry's own.
+int film_resolve_check(const apt_film_resolve *r, const void *film, const void *table, const void *out, const void *u8, const char *what) {
+    if (!r || !film || !table) return set_error(APT_ERR_ARG, "%s: r/film/table must be non-null", what);
+    if (r->struct_size != sizeof(apt_film_resolve)) return set_error(APT_ERR_STRUCT, "%s: apt_film_resolve.struct_size mismatch", what);
+    if (!out && !u8) return set_error(APT_ERR_ARG, "%s: out and u8 are both null: nothing to write", what);
+    if (r->passes == 0 || r->passes > (1u << 24)) return set_error(APT_ERR_ARG, "%s: passes must lie in [1, 2^24]", what);
+    if (r->tonemap > (uint32_t)APT_TONEMAP_REINHARD) return set_error(APT_ERR_ARG, "%s: unknown tone operator", what);
+    if (!(std::isfinite(r->exposure) && r->exposure >= 0.0f && std::isfinite(r->inv_white2) && r->inv_white2 >= 0.0f))
+        return set_error(APT_ERR_ARG, "%s: exposure / inv_white2 must be finite and not negative", what);
+    return APT_OK;
+}
+} // namespace apt
+
+extern "C" {
+
+uint64_t apt_film_pass_seed(uint64_t seed, uint32_t pass) {
+    return pass == 0 ? seed : apt::splitmix64(seed ^ apt::splitmix64((uint64_t)pass ^ APT_FILM_PASS_SALT));
+}
+
+int apt_film_curve_host(uint32_t curve, float table[256]) {
+    apt::clear_error();
+    if (!table) return set_error(APT_ERR_ARG, "%s: table must be non-null", "apt_film_curve_host");
+    if (curve > (uint32_t)APT_CURVE_SRGB) return set_error(APT_ERR_ARG, "%s: unknown curve", "apt_film_curve_host");
+    table[0] = 0.0f;
+    for (int k = 1; k < 256; ++k) {
+        const double e = ((double)k - 0.5) / 255.0;
+        const double v = curve == (uint32_t)APT_CURVE_LINEAR ? e : (e <= 0.04045 ? e / 12.92 : pow((e + 0.055) / 1.055, 2.4));
+        table[k] = (float)v;
+    }
+    return APT_OK;
+}
+
+// One value of the film -> y ("film" in the header, operation by operation; film.hip's kernel is the same text).
+static inline float film_tone(float s, float fpasses, float exposure, float inv_white2, bool reinhard) {
+    const float m = s / fpasses;
+    float x = m * exposure;
+    x = x > 0.0f ? x : 0.0f;
+    float y = x;
+    if (reinhard) {
+        float t = x * inv_white2;
+        t = 1.0f + t;
+        const float num = x * t;
+        const float den = 1.0f + x;
+        y = x == INFINITY ? 1.0f : num / den;
+    }
+    return y < 1.0f ? y : 1.0f;
+}
+static inline uint8_t film_code(const float *table, float y) {
+    uint32_t code = 0;
+    for (uint32_t b = 128; b; b >>= 1) code += table[code + b] <= y ? b : 0u;
+    return (uint8_t)code;
+}
+
+int apt_film_resolve_host(const apt_film_resolve *r, const float *film, uint64_t pixel_count, const float *table, float *out, uint8_t *u8) {
+    apt::clear_error();
+    const int rc = apt::film_resolve_check(r, film, table, out, u8, "apt_film_resolve_host");
+    if (rc) return rc;
+    const float fp = (float)r->passes;
+    const bool reinhard = r->tonemap == (uint32_t)APT_TONEMAP_REINHARD;
+    for (uint64_t c = 0; c < 3; ++c)
+        for (uint64_t i = 0; i < pixel_count; ++i) {
+            const float y = film_tone(film[c * pixel_count + i], fp, r->exposure, r->inv_white2, reinhard);
+            if (out) out[c * pixel_count + i] = y;
+            if (u8) u8[i * 3 + c] = film_code(table, y);
+        }
+    return APT_OK;
+}
+
+int apt_write_pfm(const char *path, uint32_t width, uint32_t height, const float *planes) {
+    apt::clear_error();
+    if (!path || !planes || !width || !height) return set_error(APT_ERR_ARG, "apt_write_pfm: path/planes must be non-null, width/height non-zero%s");
+    FILE *f = fopen(path, "wb");
+    if (!f) return set_error(APT_ERR_IO, "apt_write_pfm: cannot open %s", path);
+    fprintf(f, "PF\n%u %u\n-1.0\n", width, height);
+    const uint64_t np = (uint64_t)width * height;
+    std::vector<uint8_t> row((size_t)width * 12);
+    for (uint32_t y = 0; y < height; ++y) {            // PFM rows run bottom to top, and so does y: no flip
+        for (uint32_t x = 0; x < width; ++x)
+            for (uint64_t c = 0; c < 3; ++c) {
+                uint32_t bits;
+                memcpy(&bits, &planes[c * np + (uint64_t)x * height + y], 4);
+                uint8_t *o = &row[((size_t)x * 3 + c) * 4];   // little-endian whatever the host is
+                o[0] = (uint8_t)bits; o[1] = (uint8_t)(bits >> 8); o[2] = (uint8_t)(bits >> 16); o[3] = (uint8_t)(bits >> 24);
+            }
+        fwrite(row.data(), 1, row.size(), f);
+    }
+    return fclose(f) == 0 ? APT_OK : set_error(APT_ERR_IO, "apt_write_pfm: write to %s failed", path);
+}
+
+} // extern "C"

@@ -126,4 +126,46 @@ __device__ __forceinline__ void frame_decode(const FrameArgs fa, uint64_t pl, bo
     }
 }
 
+// The film tail (include/render_mi355x.h "film"): frame_decode's gathers and float64 sum / 4 without :54's clip and without an 8-bit
+// image -- so no u8pack and no barrier.  r = (float)v is stored (pass 0: whatever the film held is gone) or added to the film word in
+// one fp32 add.  fa.fb is the film, [3][pixel_count]; every word has exactly one owner lane in the launch, hence no atomics.
+template <int GROUP>
+__device__ __forceinline__ void frame_film(const FrameArgs fa, uint64_t pl, bool valid, const float (&res)[3], bool add) {
+    const uint32_t lane = threadIdx.x & 63;
+    const float fs = (float)fa.samples;
+    const int gbase = (int)(lane & ~(uint32_t)(4 * GROUP - 1));
+    if (GROUP == 8) {   // channel c = lane & 7 through one division and one set of gathers per wave half, as in frame_decode
+        const uint32_t c = lane & 7u;
+        const float sum = c == 0 ? res[0] : (c == 1 ? res[1] : res[2]);
+        float mean;                                 // np.mean: float32 sum / count
+        if ((fa.samples & (fa.samples - 1)) == 0) { // (wave-uniform) a power of two: sum * (1 / count) is the correctly rounded quotient
+            const uint32_t inv = (127u - (uint32_t)__builtin_ctz(fa.samples)) << 23;
+            mean = sum * __uint_as_float(inv);
+        } else {
+            mean = sum / fs;
+        }
+        double acc = 0.0;                           // :38 sum_color = zeros (float64)
+#pragma unroll
+        for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP + (int)c, 64); // :41-45
+        const float r = (float)(acc / 4);           // :46, `pre` of the oracle's decode_color
+        if (valid && (lane & (4 * GROUP - 1)) < 3) {
+            float *const w = fa.fb + ((uint64_t)c * fa.pixel_count + pl);
+            *w = add ? *w + r : r;
+        }
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float mean = res[ch] / fs;            // np.mean: float32 sum / count
+            double acc = 0.0;
+#pragma unroll
+            for (int sq = 0; sq < 4; ++sq) acc = acc + (double)__shfl(mean, gbase + sq * GROUP, 64);
+            const float r = (float)(acc / 4);
+            if (valid && (lane & (4 * GROUP - 1)) == 0) {
+                float *const w = fa.fb + ((uint64_t)ch * fa.pixel_count + pl);
+                *w = add ? *w + r : r;
+            }
+        }
+    }
+}
+
 } // namespace

@@ -29,7 +29,10 @@ constexpr int kMatGloss = 32;   // APT_FLAG_GLOSS in the same template argument:
 static_assert((kMatGloss & (kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatGloss must be a bit of its own");
 constexpr int kMatEnv = 64;     // a context's environment (apt_context_set_environment) in the same template argument: only then is the kernels' MatEnv read
 static_assert((kMatEnv & (kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatEnv must be a bit of its own");
-constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv); }
+constexpr int kMatFilm = 128;   // the film entries (include/render_mi355x.h "film") in the same template argument, frame kernels with kMatEnv only: the tail is frame_film
+static_assert((kMatFilm & (kMatEnv | kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatFilm must be a bit of its own");
+constexpr uint32_t kMatEnvFilmAdd = 2u;   // MatEnv::gloss of a kMatFilm launch, next to bit 0: pass > 0, the tail adds to the film instead of storing
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv | kMatFilm); }
 // The contract's limit (include/render_mi355x.h "camera"): a frame with a camera takes a plan of at most this many leaves.  Nothing in
 // the kernels needs it any more; lifting it is a feature with its own tests above 4199 samples, not part of any clean-up.
 constexpr uint32_t kCamMaxLeaves = 44;
@@ -798,6 +801,7 @@ __global__ __launch_bounds__(kBlock) void gen_rays_camera_kernel(CameraEx cam, u
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
 // SCN: the scene form and kMatNee / kMatLights / kMatGloss, as for the buffer kernel, and kMatCamera: only then is `ct` read.
 // kMatEnv (both kernels): only then does `ev` hold anything -- the environment.
+// kMatFilm (with kMatEnv): fa.fb is a film and the tail is frame_film, not frame_decode; fa.fb_u8 is not read.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, MatKernelArgs ka, LeafProg lp, CameraTail ct,
@@ -807,6 +811,13 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     constexpr int LM = mat_light_mode(SCN);
     constexpr bool GL = (SCN & kMatGloss) != 0;
     constexpr bool EV = (SCN & kMatEnv) != 0;
+    constexpr bool FILM = (SCN & kMatFilm) != 0;
+    static_assert(!FILM || EV, "the film kernels are environment kernels: store-or-add travels in MatEnv::gloss");
+    bool film_add = false;
+    if constexpr (FILM) {   // (launch-uniform) the word's bit 0 is what every other reader of ev.gloss takes it for
+        film_add = (ev.gloss & kMatEnvFilmAdd) != 0;
+        ev.gloss = ev.gloss & 1u;
+    }
     __shared__ float4 tab[mat_tab_entries(SCN)];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     extern __shared__ float dyn_lds[];
@@ -911,8 +922,12 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         for (int ch = 0; ch < 3; ++ch) res[ch] = stack_lds[ch * kStackSlots + (threadIdx.x >> 3)];
     }
 
-    __shared__ uint32_t u8pack[frame_u8_words(GROUP)];
-    frame_decode<GROUP>(fa, pl, valid, res, u8pack);
+    if constexpr (FILM) {
+        frame_film<GROUP>(fa, pl, valid, res, film_add);
+    } else {
+        __shared__ uint32_t u8pack[frame_u8_words(GROUP)];
+        frame_decode<GROUP>(fa, pl, valid, res, u8pack);
+    }
     count_traced(ta, valid ? traced : 0);
 }
 

@@ -81,6 +81,8 @@ struct MatArgs {
     const uint32_t *materials = nullptr;
     bool with_lights = false;
     const void *lights = nullptr;
+    bool film = false;       // the film entries ("film" in the header): fb is a film, fb_u8 null
+    uint32_t pass = 0;       // film: pass 0 stores, a later pass adds
 };
 // check_materials, then what the *_lights entries refuse on top of it.
 int check_mat_args(const apt_render_params *p, const MatArgs &m) {
@@ -253,7 +255,7 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     int rc = check_params(p, mat);
     if (rc) return rc;
     if (mat && (rc = check_mat_args(p, ma))) return rc;
-    if (!spheres || !fb) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");
+    if (!spheres || (!fb && !ma.film)) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");   // (a film entry refuses a null film last)
     const uint64_t npix = (uint64_t)p->width * p->height;
     if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
     if (pixel_count == 0) return APT_OK;
@@ -266,15 +268,23 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     const apt::Debug &dbg = ls.cv.debug;
     if (mat) {   // per-sphere materials: materials.hip
         if ((rc = check_lights_status(ma, ls.status))) return rc;
-        if ((ls.cv.has_camera || ls.cv.has_env) && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera / environment: a frame with a camera or an environment set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
+        if ((ls.cv.has_camera || ls.cv.has_env || ma.film) && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera / environment: a frame with a camera or an environment set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
         apt::MatFrameCall call{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
                                pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr};
-        if (ls.cv.has_env) {   // the context's environment: environment.hip, whose frame kernels all take a camera record
+        if (ls.cv.has_env || ma.film) {   // the context's environment: environment.hip, whose frame kernels all take a camera record
             apt_camera reference;
             reference.struct_size = sizeof reference;
             if (!call.camera) {
                 if ((rc = apt_camera_default_host(p->width, p->height, &reference))) return rc;   // (its own error record)
                 call.camera = &reference;
+            }
+            if (ma.film) {   // film.hip: environment kernels with a film tail; no environment = the all-zero record, the same image bit for bit
+                if (!fb) return fail(APT_ERR_ARG, "film must be non-null%s");
+                apt_environment black;
+                memset(&black, 0, sizeof black);
+                black.struct_size = sizeof black;
+                apt::film_render_frame(call, ls.cv.has_env ? ls.cv.env : black, ma.pass != 0);
+                return launched();
             }
             apt::env_render_frame(call, ls.cv.env);
             return launched();
@@ -541,6 +551,37 @@ int apt_context_render_frame_lights(apt_context *ctx, const apt_render_params *p
 int apt_context_render_paths_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres,
                                     const uint32_t *materials, const void *lights, float *colors) {
     return mat_paths_entry(ctx, p, stream, rays, spheres, mat_args_lights(materials, lights), colors);
+}
+
+// The film entries ("film" in the header): the frame entry the caller's `lights` selects, rendered with the pass's seed into a film.
+int apt_context_render_frame_film(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                  const uint32_t *materials, const void *lights, uint64_t pixel_begin, uint64_t pixel_count, float *film,
+                                  uint32_t pass) {
+    MatArgs ma = lights ? mat_args_lights(materials, lights) : mat_args(materials);
+    ma.film = true;
+    ma.pass = pass;
+    apt_render_params q;
+    if (p && p->struct_size == sizeof q) {   // (anything else is check_params' to refuse)
+        q = *p;
+        q.seed = apt_film_pass_seed(p->seed, pass);
+        p = &q;
+    }
+    return mat_frame_entry(ctx, p, stream, spheres, ma, pixel_begin, pixel_count, film, nullptr);
+}
+
+int apt_render_frame_film(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials, const void *lights,
+                          uint64_t pixel_begin, uint64_t pixel_count, float *film, uint32_t pass) {
+    return apt_context_render_frame_film(&apt::default_context(), p, stream, spheres, materials, lights, pixel_begin, pixel_count, film, pass);
+}
+
+int apt_film_resolve_device(const apt_film_resolve *r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev,
+                            float *out, uint8_t *u8) {
+    clear_error();
+    const int rc = apt::film_resolve_check(r, film, table_dev, out, u8, "apt_film_resolve_device");
+    if (rc || pixel_count == 0) return rc;
+    if ((pixel_count + kBlock - 1) / kBlock > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    apt::film_resolve(*r, stream, film, pixel_count, table_dev, out, u8);
+    return launched();
 }
 
 int apt_render_frame_lights(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials, const void *lights,

@@ -350,6 +350,18 @@ def _table_of(rows):
     return out
 
 
+def film_curve(curve="srgb"):
+    """The 256-entry table of render.Film.resolve / apt_film_resolve_* (apt_film_curve_host): table[0] = 0, table[k] the linear value
+    at which the 8-bit code k begins, for curve "srgb" or "linear" (or APT_CURVE_*) -> float32 [256]."""
+    from ._lib import APT_CURVE_LINEAR, APT_CURVE_SRGB
+    code = {"linear": APT_CURVE_LINEAR, "srgb": APT_CURVE_SRGB}.get(curve, curve)
+    if not isinstance(code, int):
+        raise AptError(f"film_curve: unknown curve {curve!r}")
+    table = np.zeros(256, dtype=np.float32)
+    check(lib().apt_film_curve_host(ctypes.c_uint32(code), _fptr(table)), "apt_film_curve_host")
+    return table
+
+
 def gen_spheres_open():
     """An open 8-sphere scene for an environment (render.set_environment): a ground sphere of radius 1e5 whose top is y = 0 and seven
     balls standing on it around (50, ., 60), in front of the reference camera -- three DIFF, a mirror, a glass ball, and two rough-metal

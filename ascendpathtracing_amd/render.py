@@ -97,6 +97,20 @@ def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stre
     return fb, fb_u8
 
 
+def _render_frame_film(entry, handle, params, spheres, materials, lights, pixel_begin, pixel_count, film, pass_index, stream):
+    require_gpu()
+    if pixel_count is None:
+        pixel_count = params.width * params.height - pixel_begin
+    if film is None:
+        film = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
+    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
+                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                                _dev_materials(materials, params.num_spheres), None if lights is None else _dev_lights(lights),
+                                ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(film, "film", 3 * pixel_count),
+                                ctypes.c_uint32(pass_index)), entry)
+    return film
+
+
 def render_do(blockDim, l2ctrl, stream, rays, spheres, colors):
     """void render_do(blockDim, l2ctrl, stream, rays, spheres, colors) -- src/main.cpp:9-10,74.
     Asynchronous on `stream`; uses the process-wide defaults (apt_set_default_params)."""
@@ -171,6 +185,11 @@ class Context:
                      lights=None):
         return _render_frame("apt_context_render_frame", (self._h,), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8,
                              materials, lights)
+
+    def render_frame_film(self, params, spheres, materials, film=None, pass_index=0, lights=None, pixel_begin=0, pixel_count=None,
+                          stream=None):
+        return _render_frame_film("apt_context_render_frame_film", (self._h,), params, spheres, materials, lights, pixel_begin,
+                                  pixel_count, film, pass_index, stream)
 
 
 def render_host(blockDim, rays, spheres, colors):
@@ -307,6 +326,76 @@ def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None,
     that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE, lights: as render_do_ex
     (apt_render_frame_lights)."""
     return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials, lights)
+
+
+def render_frame_film(params: RenderParams, spheres, materials, film=None, pass_index=0, lights=None, pixel_begin=0, pixel_count=None,
+                      stream=None):
+    """apt_render_frame_film: one pass of a film.  The pixel range rendered as render_frame(materials=, lights=) would with the seed
+    apt_film_pass_seed(params.seed, pass_index), unclipped, stored in `film` (float32 [3][count]; None: a new tensor) for pass 0 and
+    added to it for a later pass.  Returns the film; not synchronised."""
+    return _render_frame_film("apt_render_frame_film", (), params, spheres, materials, lights, pixel_begin, pixel_count, film,
+                              pass_index, stream)
+
+
+class Film:
+    """An unclipped float32 accumulation buffer for the pixels [pixel_begin, pixel_begin + pixel_count) of a width x height image
+    (include/render_mi355x.h "film"): add_pass renders one more independent frame into it, resolve turns the mean into a displayable
+    image.  `buffer` is the [3][count] tensor of sums, `passes` how many frames it holds."""
+
+    def __init__(self, width, height, pixel_begin=0, pixel_count=None, device="cuda"):
+        self.width, self.height, self.pixel_begin = width, height, pixel_begin
+        self.pixel_count = width * height - pixel_begin if pixel_count is None else pixel_count
+        self.buffer = torch.zeros((3, self.pixel_count), dtype=torch.float32, device=device)
+        self.passes = 0
+        self._tables = {}
+
+    def reset(self):
+        """Forget the passes: the next one stores."""
+        self.passes = 0
+
+    def add_pass(self, params, spheres, materials, lights=None, stream=None, context=None):
+        """One more frame of `params` (its width and height must be the film's), with pass index self.passes."""
+        if (params.width, params.height) != (self.width, self.height):
+            raise _lib.AptError("Film.add_pass: params.width / height are not the film's")
+        entry, handle = ("apt_render_frame_film", ()) if context is None else ("apt_context_render_frame_film", (context._h,))
+        _render_frame_film(entry, handle, params, spheres, materials, lights, self.pixel_begin, self.pixel_count, self.buffer,
+                           self.passes, stream)
+        self.passes += 1
+        return self
+
+    def mean(self):
+        """The film divided by its passes (fp32, as the resolve's first step) -> float32 [3][count]."""
+        if self.passes == 0:
+            raise _lib.AptError("Film.mean: the film holds no pass")
+        return self.buffer / torch.tensor(self.passes, dtype=torch.float32, device=self.buffer.device)
+
+    def resolve(self, exposure=1.0, tonemap="clip", white=None, curve="srgb", want_float=False, stream=None):
+        """apt_film_resolve_device: mean, exposure, tone operator ("clip" or "reinhard"; white: the radiance that maps to 1, None:
+        plain Reinhard) and the 8-bit encoding by `curve` ("srgb" or "linear") -> u8 [count][3], or (u8, float32 [3][count])."""
+        from . import gen_data
+        if self.passes == 0:
+            raise _lib.AptError("Film.resolve: the film holds no pass")
+        tm = {"clip": _lib.APT_TONEMAP_CLIP, "reinhard": _lib.APT_TONEMAP_REINHARD}.get(tonemap)
+        if tm is None:
+            raise _lib.AptError(f"Film.resolve: unknown tone operator {tonemap!r}")
+        if curve not in self._tables:
+            self._tables[curve] = torch.from_numpy(gen_data.film_curve(curve)).to(self.buffer.device)
+        rec = _lib.film_resolve_record(self.passes, exposure, tm, 0.0 if white is None else 1.0 / (float(white) * float(white)))
+        u8 = torch.empty((self.pixel_count, 3), dtype=torch.uint8, device=self.buffer.device)
+        out = torch.empty((3, self.pixel_count), dtype=torch.float32, device=self.buffer.device) if want_float else None
+        check(lib().apt_film_resolve_device(ctypes.byref(rec), _stream_handle(stream), _dev_f32(self.buffer, "film"),
+                                            ctypes.c_uint64(self.pixel_count), _dev_f32(self._tables[curve], "table", 256),
+                                            None if out is None else ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(u8.data_ptr())),
+              "apt_film_resolve_device")
+        return (u8, out) if want_float else u8
+
+    def write_pfm(self, path):
+        """apt_write_pfm of the mean; the film must cover the whole image."""
+        if self.pixel_begin != 0 or self.pixel_count != self.width * self.height:
+            raise _lib.AptError("Film.write_pfm: the film is a band of the image")
+        planes = self.mean().cpu().numpy()
+        check(lib().apt_write_pfm(str(path).encode(), ctypes.c_uint32(self.width), ctypes.c_uint32(self.height),
+                                  planes.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), "apt_write_pfm")
 
 
 def gen_rays_device(params: RenderParams, stream=None, device="cuda"):

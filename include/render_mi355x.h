@@ -581,6 +581,77 @@ int apt_environment_check_host(const apt_environment *env);
 int apt_context_set_environment(apt_context *ctx, const apt_environment *env_or_null);
 int apt_set_environment(const apt_environment *env_or_null);
 
+/* ---- film (EXTENSION: an unclipped float32 accumulation buffer for the material renderer, filled pass by pass, and its resolve) -------
+ * The frame entries return the mean of ONE launch's samples, clipped to [0, 1] (data_visualization.py:54) and truncated to 8 bits.  A
+ * film keeps what they clip: frame launches add to it pass by pass, and a resolve kernel turns it into a displayable image with an
+ * exposure, a tone operator and a transfer curve.  APT_ABI_VERSION is unchanged: callers detect the feature by its symbols.
+ *
+ * Accumulate.  apt_render_frame_film / apt_context_render_frame_film:
+ *   - film is a DEVICE buffer [3][pixel_count] float32, band-relative exactly as fb is.
+ *   - The launch renders the pixel range exactly as apt_render_frame_lights would (lights_or_null == NULL: as apt_render_frame_materials
+ *     would) with p->seed replaced by apt_film_pass_seed(p->seed, pass): flags, the context's camera and environment, the grid form
+ *     behind `accel`, roulette, the status word, the trace counter, every refusal and the order of refusals are those entries' (a NULL
+ *     `materials` is refused there already: there is no mirror film).  A film launch takes a pairwise-sum plan of at most 44 leaves
+ *     whether or not a camera or an environment is set (every samples <= 4199 has one; APT_ERR_ARG otherwise), and without a camera set
+ *     it renders from apt_camera_default_host's record (APT_ERR_ARG for an image shape that record refuses).  After those refusals the
+ *     entry refuses a NULL `film` (APT_ERR_ARG), with nothing written.  An empty pixel range is APT_OK and launches nothing.
+ *   - Per pixel and channel the kernel forms the same float64 v as the frame entries: the four sub-pixel np.means summed in float64,
+ *     divided by 4 -- the value BEFORE :54's clip.  It does not clip.  r = (float)v.  pass == 0: film[c][pl] = r (a store: whatever the
+ *     buffer held, NaN included, is gone).  pass > 0: film[c][pl] = film[c][pl] + r, one fp32 add.  No 8-bit image is written.
+ *   - So after pass 0 alone clip(film, 0, 1) is the fb of the corresponding frame entry bit for bit (rounding to fp32 is monotone and 0
+ *     and 1 are representable: clipping before or after it is the same), and after passes 0..K-1 the film is the sequential fp32 sum of
+ *     K independent frames' (float)v.
+ *   - apt_film_pass_seed(seed, 0) = seed; for pass > 0 it is splitmix64(seed ^ splitmix64((uint64_t)pass ^ APT_FILM_PASS_SALT)).  The
+ *     salt keeps a pass seed from being the roulette key of path `pass` (splitmix64(seed ^ splitmix64(path))).  The seed is computed
+ *     on the host: the kernel receives a seed as it always has.
+ *   - Passes are the caller's loop; the entry keeps no state.  A caller may run bands, or resume a film another process wrote.
+ *
+ * Resolve.  apt_film_resolve_device (DEVICE pointers, asynchronous on `stream`) and apt_film_resolve_host (HOST pointers, the CPU twin:
+ * the same operations, the same bits).  Every step is one IEEE fp32 operation (no FMA).  Per value s of the film:
+ *     m = s / (float)passes                      (1 <= passes <= 2^24: the conversion is exact)
+ *     x = m * exposure;  x = x > 0 ? x : 0       (a NaN and a negative value become 0)
+ *     APT_TONEMAP_CLIP:      y = x < 1 ? x : 1
+ *     APT_TONEMAP_REINHARD:  y = (x * (1 + x * inv_white2)) / (1 + x), with x == +inf giving 1 by a select before the divide (as does
+ *                            an intermediate that overflows: a NaN quotient gives 1); then y = y < 1 ? y : 1.  inv_white2 = 0 is plain
+ *                            Reinhard; inv_white2 = 1 / white^2 maps the radiance `white` to 1.
+ *     out[c][i] = y                              (out_or_null: [3][pixel_count] float32)
+ *     u8[i][c] = #{ k in 1..255 : table[k] <= y }  (u8_or_null: [pixel_count][3]; any byte alignment)
+ *   The code is a search in a 256-entry table (table[0] is not read), numpy's searchsorted(table[1:], y, side="right") for an increasing
+ *   table, done as 8 branch-free steps: code = 0; for b = 128, 64, ..., 1: if (table[code + b] <= y) code += b.  There is no pow on the
+ *   device: the code is reproducible bit for bit.  For a table that is not increasing the code is what those 8 steps give.
+ *   apt_film_curve_host fills table[0] = 0 and table[k] = (float)EOTF((k - 0.5) / 255) (float64, rounded once) for k = 1..255: the level
+ *   boundaries of an encoding that is ROUNDED to the nearest of 256 levels, unlike the reference decode's truncation, which stays what it
+ *   is in the frame entries.  APT_CURVE_LINEAR: EOTF(e) = e.  APT_CURVE_SRGB: e <= 0.04045 ? e / 12.92 : pow((e + 0.055) / 1.055, 2.4).
+ *   APT_ERR_ARG for a NULL table or an unknown curve.
+ *   Refusals of both resolve forms, nothing written: APT_ERR_ARG for a NULL r, film or table, both outputs NULL, passes == 0 or
+ *   > 2^24, an unknown operator, an exposure or inv_white2 that is not finite or is negative; APT_ERR_STRUCT for a wrong struct_size.
+ *   pixel_count == 0 is APT_OK.  The device form does not read the table on the host.
+ * apt_write_pfm: a colour PFM ("PF\n<w> <h>\n-1.0\n", then little-endian float32 RGB, rows bottom to top) of HOST planes [3][W*H],
+ *   x-major as fb (pixel (x, y) at x * H + y).  y counts upwards here, so file row r is y = r: apt_write_ppm flips, this does not. */
+#define APT_FILM_PASS_SALT 0x9B05688C2B3E6C1Full   /* differs from every stream salt above */
+enum { APT_TONEMAP_CLIP = 0, APT_TONEMAP_REINHARD = 1 };
+enum { APT_CURVE_LINEAR = 0, APT_CURVE_SRGB = 1 };
+typedef struct apt_film_resolve {
+    uint32_t struct_size;       /* = sizeof(apt_film_resolve)                                               */
+    uint32_t passes;            /* passes accumulated in the film, 1 .. 2^24                                */
+    uint32_t tonemap;           /* APT_TONEMAP_*                                                            */
+    uint32_t reserved;          /* not read                                                                 */
+    float exposure;             /* finite, >= 0                                                             */
+    float inv_white2;           /* APT_TONEMAP_REINHARD: 1 / white^2, finite, >= 0; 0 = plain Reinhard      */
+} apt_film_resolve;
+uint64_t apt_film_pass_seed(uint64_t seed, uint32_t pass);   /* host; pass 0 -> seed itself */
+int apt_render_frame_film(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials,
+                          const void *lights_or_null, uint64_t pixel_begin, uint64_t pixel_count, float *film, uint32_t pass);
+int apt_context_render_frame_film(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                  const uint32_t *materials, const void *lights_or_null, uint64_t pixel_begin, uint64_t pixel_count,
+                                  float *film, uint32_t pass);
+int apt_film_curve_host(uint32_t curve, float table[256]);
+int apt_film_resolve_device(const apt_film_resolve *r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev,
+                            float *out_or_null, uint8_t *u8_or_null);
+int apt_film_resolve_host(const apt_film_resolve *r, const float *film, uint64_t pixel_count, const float *table, float *out_or_null,
+                          uint8_t *u8_or_null);
+int apt_write_pfm(const char *path, uint32_t width, uint32_t height, const float *planes_host);
+
 /* ---- one process, several GPUs (the reference's 8-block split, src/render.cpp:9-10,24-27, across devices) ----
  * The frame's x-major pixel range is cut into num_bands*stripes contiguous stripes; band b renders stripes
  * b, b+num_bands, ... (stripes == 1: one contiguous band per device, the reference's split; stripes > 1
