@@ -1,6 +1,7 @@
-// apt_materials.h -- what render_kernels.hip (argument checks, C-ABI) hands to materials.hip (the material kernels and their
-// launches; include/render_mi355x.h "per-sphere materials").  The material kernels live in a translation unit of their own, so
-// that the code object of render_kernels.hip -- every kernel the mirror renderer had before -- is built exactly as before.
+// apt_materials.h -- what render_kernels.hip (argument checks, C-ABI) hands to the material kernels' launches (include/render_mi355x.h
+// "per-sphere materials").  The material kernels live in translation units of their own (materials.hip, environment.hip, film.hip), so
+// that the code object of render_kernels.hip -- every kernel the mirror renderer had before -- is built exactly as before.  Which of
+// them serves a call is decided behind mat_render_frame / mat_render_paths (materials.hip).
 // Plain data only: the kernels' own argument types are internal to each translation unit.
 #pragma once
 #include <stdint.h>
@@ -24,6 +25,8 @@ struct MatTrace {                 // the parts of apt_render_params the material
     bool gloss;                   // APT_FLAG_GLOSS: the material table may hold APT_MAT_GLOSS words (the gloss instantiations)
 };
 
+enum class MatFilm { None, Store, Add };   // Store: pass 0; Add: a later pass
+
 struct MatFrameCall {             // render_frame with materials: pixels [pixel_begin, pixel_begin + pixel_count), pixel_count > 0
     MatTrace t;
     const float *spheres;
@@ -34,6 +37,8 @@ struct MatFrameCall {             // render_frame with materials: pixels [pixel_
     uint8_t *fb_u8;
     void *stream;
     const apt_camera *camera;     // the context's camera (checked when it was set), or null: the reference's
+    const apt_environment *env;   // the context's environment ("environment" in the header; checked when it was set), or null
+    MatFilm film;                 // the film entries ("film" in the header): fb is the film and fb_u8 null
 };
 
 struct MatPathsCall {             // render_do_ex with materials: paths [b, b + c) of buffers whose planes hold n paths (already shifted)
@@ -43,6 +48,7 @@ struct MatPathsCall {             // render_do_ex with materials: paths [b, b + 
     float *colors;
     uint64_t n, b, c;
     void *stream;
+    const apt_environment *env;   // as MatFrameCall's
 };
 
 struct CamRaysCall {              // apt_gen_rays_camera_device: paths [b, b + c) of a buffer whose planes hold n paths (already shifted)
@@ -57,22 +63,14 @@ struct CamRaysCall {              // apt_gen_rays_camera_device: paths [b, b + c
 // Can a frame of `samples` carry a camera?  The contract's limit (include/render_mi355x.h "camera"): a plan of at most 44 leaves.
 bool mat_camera_fits(uint32_t samples);
 
-// Enqueue the launch (hipGetLastError() tells the caller whether it was accepted).
-void mat_render_frame(const MatFrameCall &call);
+// Enqueue the launch (hipGetLastError() tells the caller whether it was accepted).  mat_render_frame -> APT_OK, or, with the error
+// record set and nothing launched, what a call that needs the reference's camera as a record is refused with last: the status of
+// apt_camera_default_host for an image shape that has none, then APT_ERR_ARG for a film entry's null fb (the contract's order).
+int mat_render_frame(const MatFrameCall &call);
 void mat_render_paths(const MatPathsCall &call);
 void mat_gen_rays_camera(const CamRaysCall &call);
 
-// The same two launches with the context's environment (include/render_mi355x.h "environment"; checked when it was set): the kMatEnv
-// kernels, which live in environment.hip -- a third code object, so that a launch without an environment runs the very kernels it ran
-// before there was one.  They are always the general-camera and gloss instantiations: call.camera must be non-null (without a camera
-// set the caller hands in apt_camera_default_host's record, the reference's camera bit for bit), and call.t.gloss travels as data.
-void env_render_frame(const MatFrameCall &call, const apt_environment &env);
-void env_render_paths(const MatPathsCall &call, const apt_environment &env);
-
-// The film launches (include/render_mi355x.h "film"), film.hip: a fourth code object.  film_render_frame is env_render_frame with a film
-// tail: call.fb is the film, call.fb_u8 null, `add` false for pass 0 (a store).  Always the kMatEnv kernels: without an environment the
-// caller hands in the all-zero record.  film_resolve: the checked arguments of apt_film_resolve_device, pixel_count > 0.
-void film_render_frame(const MatFrameCall &call, const apt_environment &env, bool add);
+// film.hip's resolve: the checked arguments of apt_film_resolve_device, pixel_count > 0.
 void film_resolve(const apt_film_resolve &r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev, float *out_or_null,
                   uint8_t *u8_or_null);
 

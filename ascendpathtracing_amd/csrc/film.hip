@@ -2,33 +2,20 @@
 // pt_frame.h frame_film) and the resolve kernel, with their launches: a fourth material code object (`make asm` writes it to film.s), so
 // that render_kernels.hip, materials.hip and environment.hip are built from the instantiations they always held.  As in environment.hip
 // the frame kernels are the general-camera, gloss, environment instantiations only: 3 scene forms x 3 light modes x 2 groups.  A launch
-// without a camera gets the default record, one without an environment the all-zero record (render_kernels.hip), which
-// tests/test_gpu_environment.py shows to be the image without one bit for bit.
+// without a camera gets the default record, one without an environment the all-zero record (materials.hip mat_render_frame).  The
+// launch itself: pt_mat_launch.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/render_mi355x.h"
 #include "apt_materials.h"
 #include "pt_core.h"
-#include "pt_dispatch.h"
 #include "pt_materials.h"
 #include "pt_mat_launch.h"
 
 namespace {
 
-// environment.hip's record, with "store or add" in bit 1 of the gloss word (kMatEnvFilmAdd): no kernel argument of its own
-MatEnv film_env(const apt_environment &e, bool gloss, bool add) {
-    MatEnv m;
-    for (int k = 0; k < 3; ++k) { m.horizon[k] = e.horizon[k]; m.zenith[k] = e.zenith[k]; m.sun[k] = e.sun_dir[k]; m.sun_rad[k] = e.sun_radiance[k]; }
-    m.omc = e.sun_omc;
-    m.sample = ((e.flags & APT_ENV_SAMPLE_SUN) && e.sun_omc > 0.0f) ? 1u : 0u;
-    m.gloss = (gloss ? 1u : 0u) | (add ? kMatEnvFilmAdd : 0u);
-    return m;
-}
-
-constexpr int film_scene_form(bool ns8, bool grid, bool nee, bool lights) {
-    return mat_scene_form(ns8, grid, nee, lights, true, true) | kMatEnv | kMatFilm;
-}
+constexpr int kPins = kMatEnv | kMatGloss | kMatCamera | kMatFilm;
 
 // ---- resolve ----------------------------------------------------------------------------------------------------------------
 // One lane = one pixel: three coalesced plane reads, the header's operations one at a time, an 8-step search in the table (LDS), and
@@ -98,27 +85,7 @@ __global__ __launch_bounds__(kBlock) void film_resolve_kernel(ResolveArgs a) {
 
 namespace apt {
 
-void film_render_frame(const MatFrameCall &c, const apt_environment &env, bool add) {
-    FrameArgs fa;
-    const CameraEx cx = camera_ex(*c.camera, c.width, c.height);
-    fa.cam = cx.base;
-    fa.width = c.width; fa.height = c.height; fa.samples = c.samples; fa.seed = c.t.seed;
-    fa.pixel_begin = c.pixel_begin; fa.pixel_count = c.pixel_count; fa.fb = c.fb; fa.fb_u8 = nullptr;
-    const MatKernelArgs ka = mat_trace_args(c.t);
-    const MatEnv ev = film_env(env, c.t.gloss, add);
-    LeafProg lp;
-    (void)make_leaf_plan(c.samples, lp);                   // the caller checked mat_camera_fits
-    const int group = c.samples >= 8 ? 8 : 1;
-    const uint64_t blocks = (c.pixel_count * 4u * (uint64_t)group + kBlock - 1) / kBlock;   // <= 2^31 - 1: checked by the caller
-    const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
-    hipStream_t st = (hipStream_t)c.stream;
-    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
-            hipLaunchKernelGGL((render_frame_mat_kernel<film_scene_form(ns8, gr, nee, lt), g8 ? 8 : 1>), dim3((unsigned)blocks),
-                               dim3(kBlock), lds, st, c.spheres, c.materials, fa, ka, lp, cx.t, ev);
-        }); });
-    }); }); });
-}
+void film_launch_frame(const MatFrameCall &c) { launch_mat_frame<kPins>(c); }
 
 void film_resolve(const apt_film_resolve &r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev, float *out,
                   uint8_t *u8) {

@@ -1,15 +1,16 @@
-// materials.hip -- the material kernels' translation unit (pt_materials.h) and their launches.  render_kernels.hip checks the
-// arguments and calls in through apt_materials.h; keeping these kernels out of its code object leaves every kernel that was there
-// before byte for byte as it was (`make asm` writes this code object to materials.s).
+// materials.hip -- the material kernels' translation unit (pt_materials.h): the kernels a launch without an environment or a film
+// runs, and the one place that routes a material launch to its code object (this one, environment.hip's or film.hip's).
+// render_kernels.hip checks the arguments and calls in through apt_materials.h; keeping these kernels out of its code object leaves
+// every kernel that was there before byte for byte as it was (`make asm` writes this code object to materials.s).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "../../include/render_mi355x.h"
+#include "apt_host.h"
 #include "apt_materials.h"
 #include "pt_core.h"
-#include "pt_dispatch.h"
 #include "pt_materials.h"
 #include "pt_mat_launch.h"
 
@@ -51,40 +52,32 @@ void selftest_direction(void *stream, const double *d3, uint64_t count, uint64_t
                        (unsigned long long *)result5, flags);
 }
 
-void mat_render_frame(const MatFrameCall &c) {
-    FrameArgs fa;
-    CameraEx cx = {};                                       // without a camera the kernels do not read the tail
-    if (c.camera) { cx = camera_ex(*c.camera, c.width, c.height); fa.cam = cx.base; }
-    else camera_init(fa.cam, c.width, c.height);
-    fa.width = c.width; fa.height = c.height; fa.samples = c.samples; fa.seed = c.t.seed;
-    fa.pixel_begin = c.pixel_begin; fa.pixel_count = c.pixel_count; fa.fb = c.fb; fa.fb_u8 = c.fb_u8;
-    const MatKernelArgs ka = mat_trace_args(c.t);
-    LeafProg lp;
-    (void)make_leaf_plan(c.samples, lp);                   // the caller checked that the plan exists (with a camera: mat_camera_fits)
-    const int group = c.samples >= 8 ? 8 : 1;
-    const uint64_t blocks = (c.pixel_count * 4u * (uint64_t)group + kBlock - 1) / kBlock;   // <= 2^31 - 1: checked by the caller
-    const size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
-    hipStream_t st = (hipStream_t)c.stream;
-    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(group == 8, [&](auto g8) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.camera != nullptr, [&](auto cam) {
-            with_flag(c.t.gloss, [&](auto gl) {
-                hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam), g8 ? 8 : 1>), dim3((unsigned)blocks),
-                                   dim3(kBlock), lds, st, c.spheres, c.materials, fa, ka, lp, cx.t, MatNoEnv{});
-            });
-        }); }); });
-    }); }); });
+// This code object pins nothing: 3 scene forms x 3 light modes x 2 groups x camera x gloss frame kernels, 18 buffer kernels.
+// The kernels with an environment (environment.hip) and with a film (film.hip) exist as the general-camera, gloss instantiations only,
+// and the film's with an environment only.  A frame without a camera set gets apt_camera_default_host's record there, the reference's
+// camera bit for bit; a film without an environment the all-zero record, the same image bit for bit; and APT_FLAG_GLOSS travels as
+// data (tests/test_gpu_environment.py holds all three against the launches without an environment).
+int mat_render_frame(const MatFrameCall &call) {
+    if (!call.env && call.film == MatFilm::None) { launch_mat_frame<0>(call); return APT_OK; }
+    MatFrameCall c = call;
+    apt_camera reference;
+    reference.struct_size = sizeof reference;
+    if (!c.camera) {
+        if (int rc = apt_camera_default_host(c.width, c.height, &reference)) return rc;   // (its own error record)
+        c.camera = &reference;
+    }
+    apt_environment black = {};
+    black.struct_size = sizeof black;
+    if (!c.env) c.env = &black;
+    if (!c.fb) return set_error(APT_ERR_ARG, "film must be non-null%s");   // a film entry's last refusal: after the camera record's
+    if (c.film != MatFilm::None) film_launch_frame(c);
+    else env_launch_frame(c);
+    return APT_OK;
 }
 
-void mat_render_paths(const MatPathsCall &c) {
-    const MatKernelArgs ka = mat_trace_args(c.t);
-    const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
-    hipStream_t st = (hipStream_t)c.stream;
-    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_flag(c.t.gloss, [&](auto gl) {
-            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl)>), dim3((unsigned)blocks), dim3(kBlock), 0, st,
-                               c.rays, c.spheres, c.materials, c.colors, c.n, c.b, c.c, ka, MatNoEnv{});
-        }); }); });
-    }); });
+void mat_render_paths(const MatPathsCall &call) {
+    if (call.env) env_launch_paths(call);
+    else launch_mat_paths<0>(call);
 }
 
 bool mat_camera_fits(uint32_t samples) {

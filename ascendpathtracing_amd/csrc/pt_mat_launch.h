@@ -1,8 +1,17 @@
-// pt_mat_launch.h -- what the translation units that launch the material kernels share (materials.hip, environment.hip): a call's
-// plain data (apt_materials.h) as the kernels' own argument types (pt_materials.h).  Host code only.
+// pt_mat_launch.h -- the launch path of the material kernels, shared by the translation units that hold them (materials.hip,
+// environment.hip, film.hip): a call's plain data (apt_materials.h) as the kernels' own argument types (pt_materials.h), and one frame
+// and one buffer launcher.  Each translation unit instantiates a launcher with the scene-form bits it pins -- the instantiations its
+// code object holds -- and wraps it in a function of its own; materials.hip routes a call to one of them.  Host code only.
 #pragma once
 #include "apt_materials.h"
+#include "pt_dispatch.h"
 #include "pt_materials.h"
+
+namespace apt {   // the wrappers of the code objects behind mat_render_frame / mat_render_paths: call.camera and call.env non-null
+void env_launch_frame(const MatFrameCall &call);    // environment.hip
+void env_launch_paths(const MatPathsCall &call);
+void film_launch_frame(const MatFrameCall &call);   // film.hip: call.film is not None
+} // namespace apt
 
 namespace {
 
@@ -43,6 +52,77 @@ CameraEx camera_ex(const apt_camera &r, uint32_t width, uint32_t height) {
     c.t.aperture = (float)r.aperture;
     c.t.lens = r.aperture > 0.0 ? 1u : 0u;   // the rule: from the float64 value, not from its fp32 rounding
     return c;
+}
+
+// An apt_environment (checked when it was set) as the kMatEnv kernels read it.  film_add: "store or add" of a kMatFilm launch travels
+// in bit 1 of the gloss word (kMatEnvFilmAdd): no kernel argument of its own.
+MatEnv mat_env(const apt_environment &e, bool gloss, bool film_add) {
+    MatEnv m;
+    for (int k = 0; k < 3; ++k) { m.horizon[k] = e.horizon[k]; m.zenith[k] = e.zenith[k]; m.sun[k] = e.sun_dir[k]; m.sun_rad[k] = e.sun_radiance[k]; }
+    m.omc = e.sun_omc;
+    m.sample = ((e.flags & APT_ENV_SAMPLE_SUN) && e.sun_omc > 0.0f) ? 1u : 0u;
+    m.gloss = (gloss ? 1u : 0u) | (film_add ? kMatEnvFilmAdd : 0u);
+    return m;
+}
+
+// PIN: the scene-form bits a translation unit pins (kMatGloss, kMatCamera, kMatEnv, kMatFilm).  A pinned bit is set in every kernel
+// the launcher names, whatever the call says -- what the call says then travels as data (MatEnv::gloss, the camera record) -- and is
+// resolved here, at compile time: with_flag would instantiate the kernels without it as well.
+template <int PIN, int BIT, class F> void with_pinned(bool b, F &&f) {
+    if constexpr ((PIN & BIT) != 0) f(std::true_type{});
+    else with_flag(b, f);
+}
+template <int PIN> MatEnvArg<PIN> mat_env_arg(const apt_environment *e, bool gloss, bool film_add) {
+    if constexpr ((PIN & kMatEnv) != 0) return mat_env(*e, gloss, film_add);
+    else return MatNoEnv{};
+}
+// The camera of a frame call.  Without one, which only a launcher that does not pin kMatCamera takes: the reference's, and a zero
+// tail that the kernels do not read.
+template <int PIN> CameraEx mat_camera(const apt::MatFrameCall &c) {
+    if constexpr ((PIN & kMatCamera) == 0)
+        if (!c.camera) { CameraEx cx = {}; camera_init(cx.base, c.width, c.height); return cx; }
+    return camera_ex(*c.camera, c.width, c.height);
+}
+
+// What every frame launch makes of its call besides the records above.  The caller checked that the plan exists (with a camera, an
+// environment or a film: mat_camera_fits) and that there are at most 2^31 - 1 workgroups.
+struct MatFrame { FrameArgs fa; FrameShape s; };
+MatFrame mat_frame(const apt::MatFrameCall &c, const Camera &cam) {
+    MatFrame f;
+    f.fa.cam = cam;
+    f.fa.width = c.width; f.fa.height = c.height; f.fa.samples = c.samples; f.fa.seed = c.t.seed;
+    f.fa.pixel_begin = c.pixel_begin; f.fa.pixel_count = c.pixel_count; f.fa.fb = c.fb; f.fa.fb_u8 = c.fb_u8;
+    (void)frame_shape(c.samples, c.pixel_count, f.s);
+    return f;
+}
+
+template <int PIN> void launch_mat_frame(const apt::MatFrameCall &c) {
+    const CameraEx cx = mat_camera<PIN>(c);
+    const MatFrame f = mat_frame(c, cx.base);
+    const MatKernelArgs ka = mat_trace_args(c.t);
+    const MatEnvArg<PIN> ev = mat_env_arg<PIN>(c.env, c.t.gloss, c.film == apt::MatFilm::Add);
+    hipStream_t st = (hipStream_t)c.stream;
+    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(f.s.group == 8, [&](auto g8) {
+        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
+            with_pinned<PIN, kMatCamera>(c.camera != nullptr, [&](auto cam) { with_pinned<PIN, kMatGloss>(c.t.gloss, [&](auto gl) {
+                hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam) | (PIN & (kMatEnv | kMatFilm)), g8 ? 8 : 1>),
+                                   dim3((unsigned)f.s.blocks), dim3(kBlock), f.s.lds, st, c.spheres, c.materials, f.fa, ka, f.s.lp, cx.t, ev);
+            }); });
+        }); });
+    }); }); });
+}
+
+template <int PIN> void launch_mat_paths(const apt::MatPathsCall &c) {
+    const MatKernelArgs ka = mat_trace_args(c.t);
+    const MatEnvArg<PIN> ev = mat_env_arg<PIN>(c.env, c.t.gloss, false);
+    const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
+    hipStream_t st = (hipStream_t)c.stream;
+    with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
+        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_pinned<PIN, kMatGloss>(c.t.gloss, [&](auto gl) {
+            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl) | (PIN & kMatEnv)>), dim3((unsigned)blocks),
+                               dim3(kBlock), 0, st, c.rays, c.spheres, c.materials, c.colors, c.n, c.b, c.c, ka, ev);
+        }); }); });
+    }); });
 }
 
 } // namespace

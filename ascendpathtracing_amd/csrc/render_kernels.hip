@@ -41,9 +41,8 @@ int launched() {
 
 // Run-time settings -> template arguments: with_mode / with_flag, pt_dispatch.h.
 
-int make_leaf_prog(uint32_t samples, LeafProg &lp) {   // the plan itself: pt_leaf.h
-    return make_leaf_plan(samples, lp) ? APT_OK : fail(APT_ERR_ARG, "samples too large: its pairwise-sum plan needs more than 64 leaves (every count <= 7688 fits, and 8192)%s");
-}
+int no_leaf_plan() { return fail(APT_ERR_ARG, "samples too large: its pairwise-sum plan needs more than 64 leaves (every count <= 7688 fits, and 8192)%s"); }
+int make_leaf_prog(uint32_t samples, LeafProg &lp) { return make_leaf_plan(samples, lp) ? APT_OK : no_leaf_plan(); }   // the plan itself: pt_leaf.h
 
 // materials: the *_materials entries, which do not read light_index with APT_FLAG_EMISSION (include/render_mi355x.h)
 int check_params(const apt_render_params *p, bool materials = false) {
@@ -81,8 +80,7 @@ struct MatArgs {
     const uint32_t *materials = nullptr;
     bool with_lights = false;
     const void *lights = nullptr;
-    bool film = false;       // the film entries ("film" in the header): fb is a film, fb_u8 null
-    uint32_t pass = 0;       // film: pass 0 stores, a later pass adds
+    apt::MatFilm film = apt::MatFilm::None;   // the film entries ("film" in the header): fb is a film, fb_u8 null
 };
 // check_materials, then what the *_lights entries refuse on top of it.
 int check_mat_args(const apt_render_params *p, const MatArgs &m) {
@@ -157,6 +155,7 @@ struct PathRange {
     uint64_t n_image, b, c;
     bool band;
     uint64_t plane() const { return band ? c : n_image; }
+    uint64_t blocks() const { return (c + kBlock - 1) / kBlock; }   // of one lane per path
     template <class T> T *base(T *buf) const { return band ? buf - b : buf; }
 };
 // -> APT_OK with r.c == 0 for an empty range: the call is a no-op, the caller returns APT_OK without launching anything
@@ -185,31 +184,41 @@ size_t sphere_table_bytes(uint32_t num_spheres) { return ((size_t)num_spheres * 
 // chip better (C1, the reference's own CPU-runnable configuration, is 262 144 paths = 1024 workgroups of it: launch-bound either way).
 constexpr uint64_t kTwoPathBufferMin = 1ull << 20;
 
-// ---- the two render launches, on an explicit snapshot of a context's values -----------------
-// mat: a material entry (include/render_mi355x.h "per-sphere materials"; a null `materials` is refused).
-int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, const float *rays,
-                    const float *spheres, float *colors, bool mat = false, const MatArgs &ma = MatArgs()) {
-    int rc = check_params(p, mat);
-    if (rc) return rc;
-    if (mat && (rc = check_mat_args(p, ma))) return rc;
+// What a buffer-mode launch, mirror or material, checks after its params: pointers, the path range, the size of one launch.
+// -> APT_OK with r.c == 0 for an empty range, as path_range.
+int paths_launch_range(const apt_render_params *p, const float *rays, const float *spheres, const float *colors, PathRange &r) {
     if (!rays || !spheres || !colors) return fail(APT_ERR_ARG, "rays/spheres/colors must be non-null%s");
+    if (int rc = path_range(p, r); rc || r.c == 0) return rc;
+    if (r.blocks() > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
+    return APT_OK;
+}
+
+// The same for a frame launch: pointers (`pointers`: the entry's are non-null), the pixel range, the plan, the size of one launch.
+// -> APT_OK with an all-zero fs (fs.blocks == 0) for an empty range: the call is a no-op, the caller returns APT_OK without launching
+int frame_launch_shape(const apt_render_params *p, bool pointers, uint64_t pixel_begin, uint64_t pixel_count, FrameShape &fs) {
+    if (!pointers) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");
+    const uint64_t npix = (uint64_t)p->width * p->height;
+    if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
+    fs = FrameShape{};
+    if (pixel_count == 0) return APT_OK;
+    if (!frame_shape(p->samples, pixel_count, fs)) return no_leaf_plan();
+    if (fs.blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    return APT_OK;
+}
+
+// ---- the two mirror render launches, on an explicit snapshot of a context's values ---------
+int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, const float *rays,
+                    const float *spheres, float *colors) {
+    int rc = check_params(p);
+    if (rc) return rc;
     PathRange r;
-    if ((rc = path_range(p, r)) || r.c == 0) return rc;
+    if ((rc = paths_launch_range(p, rays, spheres, colors, r)) || r.c == 0) return rc;
     const uint64_t n = r.plane(), b = r.b, c = r.c;
-    const uint64_t blocks = (c + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
-    if (mat) {   // per-sphere materials: materials.hip
-        if ((rc = check_lights_status(ma, ls.status))) return rc;
-        const apt::MatPathsCall call{make_mat_trace(p, ls, ma), r.base(rays), spheres, ma.materials, r.base(colors), n, b, c, stream};
-        if (ls.cv.has_env) apt::env_render_paths(call, ls.cv.env);   // the context's environment: environment.hip
-        else apt::mat_render_paths(call);
-        return launched();
-    }
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
     const TraceArgs ta = make_trace_args(p, ls);
     const bool retire = p->flags & APT_FLAG_RETIRE;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid((unsigned)r.blocks());
     rays = r.base(rays);
     colors = r.base(colors);
     with_mode(p->mode, [&](auto m) {
@@ -250,48 +259,14 @@ bool queue_launch_shape(const apt::Debug &dbg, const LeafProg &lp, bool rr, bool
 }
 
 int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, const float *spheres,
-                    uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8, bool mat = false,
-                    const MatArgs &ma = MatArgs()) {
-    int rc = check_params(p, mat);
+                    uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+    int rc = check_params(p);
     if (rc) return rc;
-    if (mat && (rc = check_mat_args(p, ma))) return rc;
-    if (!spheres || (!fb && !ma.film)) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");   // (a film entry refuses a null film last)
-    const uint64_t npix = (uint64_t)p->width * p->height;
-    if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
-    if (pixel_count == 0) return APT_OK;
-    LeafProg lp;
-    if ((rc = make_leaf_prog(p->samples, lp))) return rc;
-    const int group = p->samples >= 8 ? 8 : 1;
-    const uint64_t lanes = pixel_count * 4u * (uint64_t)group;
-    const uint64_t blocks = (lanes + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    FrameShape fs;
+    if ((rc = frame_launch_shape(p, spheres && fb, pixel_begin, pixel_count, fs)) || fs.blocks == 0) return rc;
+    const LeafProg &lp = fs.lp;
+    const int group = fs.group;
     const apt::Debug &dbg = ls.cv.debug;
-    if (mat) {   // per-sphere materials: materials.hip
-        if ((rc = check_lights_status(ma, ls.status))) return rc;
-        if ((ls.cv.has_camera || ls.cv.has_env || ma.film) && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera / environment: a frame with a camera or an environment set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
-        apt::MatFrameCall call{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
-                               pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr};
-        if (ls.cv.has_env || ma.film) {   // the context's environment: environment.hip, whose frame kernels all take a camera record
-            apt_camera reference;
-            reference.struct_size = sizeof reference;
-            if (!call.camera) {
-                if ((rc = apt_camera_default_host(p->width, p->height, &reference))) return rc;   // (its own error record)
-                call.camera = &reference;
-            }
-            if (ma.film) {   // film.hip: environment kernels with a film tail; no environment = the all-zero record, the same image bit for bit
-                if (!fb) return fail(APT_ERR_ARG, "film must be non-null%s");
-                apt_environment black;
-                memset(&black, 0, sizeof black);
-                black.struct_size = sizeof black;
-                apt::film_render_frame(call, ls.cv.has_env ? ls.cv.env : black, ma.pass != 0);
-                return launched();
-            }
-            apt::env_render_frame(call, ls.cv.env);
-            return launched();
-        }
-        apt::mat_render_frame(call);
-        return launched();
-    }
     if ((rc = refuse_camera(ls.cv, "render_frame"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
@@ -332,9 +307,9 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
         if ((rc = launched()) || vouched) return rc;
         ta.grid_walk = 2;
     }
-    size_t lds = lp.nleaves > 1 ? (size_t)kMaxStack * 3 * kStackSlots * sizeof(float) : 0;
+    size_t lds = fs.lds;
     if (retire && !ns8 && !ta.grid && group == 8) lds += (size_t)(kBlock / 64) * 3 * 8 * lp.maxleaf * sizeof(float); // colour queue of the LDS-tile form
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid((unsigned)fs.blocks);
     with_mode(p->mode, [&](auto m) {
         if (ns8 && group == 8) {
             // With APT_FLAG_RETIRE these frames belong to the sample-queue kernel (above); what arrives here with the flag set is depth 0,
@@ -363,26 +338,41 @@ void split_range(uint64_t total, uint64_t r, uint64_t parts, uint64_t &begin, ui
     count = base + (r < extra ? 1 : 0);
 }
 
-// ---- the material entries: their checks run before the context's launch state is taken (the one place the other entries touch HIP
-// before their checks); do_render_* repeat them and check the rest.
-int mat_frame_entry(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres, const MatArgs &ma,
-                    uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
+// ---- the material entries (include/render_mi355x.h "per-sphere materials"): which kernels serve a call is apt_materials.h's to decide.
+// check_params and check_mat_args run before the context's launch state is taken: the one place the other entries touch HIP before
+// their checks.
+int do_mat_paths(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres, const MatArgs &ma,
+                 float *colors) {
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
     int rc = check_params(p, true);
     if (rc || (rc = check_mat_args(p, ma))) return rc;
-    return do_render_frame(launch_state(*ctx, stream), p, stream, spheres, pixel_begin, pixel_count, fb, fb_u8, true, ma);
+    const Launch ls = launch_state(*ctx, stream);
+    PathRange r;
+    if ((rc = paths_launch_range(p, rays, spheres, colors, r)) || r.c == 0) return rc;
+    if ((rc = check_lights_status(ma, ls.status))) return rc;
+    apt::mat_render_paths(apt::MatPathsCall{make_mat_trace(p, ls, ma), r.base(rays), spheres, ma.materials, r.base(colors), r.plane(), r.b, r.c,
+                                            stream, ls.cv.has_env ? &ls.cv.env : nullptr});
+    return launched();
 }
-int mat_paths_entry(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres, const MatArgs &ma,
-                    float *colors) {
+int do_mat_frame(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres, const MatArgs &ma, uint64_t pixel_begin,
+                 uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
     int rc = check_params(p, true);
     if (rc || (rc = check_mat_args(p, ma))) return rc;
-    return do_render_paths(launch_state(*ctx, stream), p, stream, rays, spheres, colors, true, ma);
+    const Launch ls = launch_state(*ctx, stream);
+    const bool film = ma.film != apt::MatFilm::None;   // (its null film is refused last: by mat_render_frame)
+    FrameShape fs;
+    if ((rc = frame_launch_shape(p, spheres && (fb || film), pixel_begin, pixel_count, fs)) || fs.blocks == 0) return rc;
+    if ((rc = check_lights_status(ma, ls.status))) return rc;
+    if ((ls.cv.has_camera || ls.cv.has_env || film) && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera / environment: a frame with a camera or an environment set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
+    if ((rc = apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
+                                                      pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr,
+                                                      ls.cv.has_env ? &ls.cv.env : nullptr, ma.film})))
+        return rc;
+    return launched();
 }
-MatArgs mat_args(const uint32_t *materials) { MatArgs m; m.materials = materials; return m; }
-MatArgs mat_args_lights(const uint32_t *materials, const void *lights) { MatArgs m; m.materials = materials; m.with_lights = true; m.lights = lights; return m; }
 
 } // namespace
 
@@ -519,16 +509,15 @@ int apt_context_render_frame(apt_context *ctx, const apt_render_params *p, void 
     return do_render_frame(launch_state(*ctx, stream), p, stream, spheres, pixel_begin, pixel_count, fb, fb_u8);
 }
 
-// Per-sphere materials.  check_params and check_materials run before the context's launch state is taken (the one place the other
-// entries touch HIP before their checks); do_render_* repeat them and check the rest.
+// Per-sphere materials: do_mat_frame, do_mat_paths.
 int apt_context_render_frame_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
                                        const uint32_t *materials, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
-    return mat_frame_entry(ctx, p, stream, spheres, mat_args(materials), pixel_begin, pixel_count, fb, fb_u8);
+    return do_mat_frame(ctx, p, stream, spheres, MatArgs{materials}, pixel_begin, pixel_count, fb, fb_u8);
 }
 
 int apt_context_render_paths_materials(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays,
                                        const float *spheres, const uint32_t *materials, float *colors) {
-    return mat_paths_entry(ctx, p, stream, rays, spheres, mat_args(materials), colors);
+    return do_mat_paths(ctx, p, stream, rays, spheres, MatArgs{materials}, colors);
 }
 
 int apt_render_frame_materials(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials,
@@ -545,28 +534,26 @@ int apt_render_paths_materials(const apt_render_params *p, void *stream, const f
 int apt_context_render_frame_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
                                     const uint32_t *materials, const void *lights, uint64_t pixel_begin, uint64_t pixel_count, float *fb,
                                     uint8_t *fb_u8) {
-    return mat_frame_entry(ctx, p, stream, spheres, mat_args_lights(materials, lights), pixel_begin, pixel_count, fb, fb_u8);
+    return do_mat_frame(ctx, p, stream, spheres, MatArgs{materials, true, lights}, pixel_begin, pixel_count, fb, fb_u8);
 }
 
 int apt_context_render_paths_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres,
                                     const uint32_t *materials, const void *lights, float *colors) {
-    return mat_paths_entry(ctx, p, stream, rays, spheres, mat_args_lights(materials, lights), colors);
+    return do_mat_paths(ctx, p, stream, rays, spheres, MatArgs{materials, true, lights}, colors);
 }
 
 // The film entries ("film" in the header): the frame entry the caller's `lights` selects, rendered with the pass's seed into a film.
 int apt_context_render_frame_film(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
                                   const uint32_t *materials, const void *lights, uint64_t pixel_begin, uint64_t pixel_count, float *film,
                                   uint32_t pass) {
-    MatArgs ma = lights ? mat_args_lights(materials, lights) : mat_args(materials);
-    ma.film = true;
-    ma.pass = pass;
+    const MatArgs ma{materials, lights != nullptr, lights, pass ? apt::MatFilm::Add : apt::MatFilm::Store};
     apt_render_params q;
     if (p && p->struct_size == sizeof q) {   // (anything else is check_params' to refuse)
         q = *p;
         q.seed = apt_film_pass_seed(p->seed, pass);
         p = &q;
     }
-    return mat_frame_entry(ctx, p, stream, spheres, ma, pixel_begin, pixel_count, film, nullptr);
+    return do_mat_frame(ctx, p, stream, spheres, ma, pixel_begin, pixel_count, film, nullptr);
 }
 
 int apt_render_frame_film(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials, const void *lights,

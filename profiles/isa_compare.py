@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of two builds' `make asm` output:
    python profiles/isa_compare.py OLD_CSRC [NEW_CSRC]     (NEW_CSRC: this tree's ascendpathtracing_amd/csrc)
-Runs `make -B asm` in both directories.  For every kernel of render_kernels.s, materials.s and environment.s it compares the instruction lines
+Runs `make -B asm` in both directories.  For every kernel of render_kernels.s, materials.s, environment.s and film.s it compares the instruction lines
 between the symbol and its .Lfunc_end (labels, directives and comments dropped; block labels renumbered per function, since a
 function's index in the file moves them; differences counted by a sequence diff) and the kernel-resource-usage remarks (registers,
-spills, scratch, LDS, occupancy).  Kernels of render_kernels.s are matched by symbol; those of materials.s and environment.s by demangled name without the
-argument list, so that a kernel whose signature changed is compared with its predecessor.
+spills, scratch, LDS, occupancy).  Kernels of render_kernels.s are matched by symbol; those of materials.s, environment.s and film.s by demangled name
+without the argument list, so that a kernel whose signature changed is compared with its predecessor.  environment.s and film.s are skipped
+when the old build has none.
 Prints one line per kernel that differs and a summary per file.  For materials.s it also prints whether every kernel keeps scratch 0,
 no VGPR spills and at least the old occupancy (`conditions`).  Exit status 1 when a kernel of render_kernels.s differs at all, when a
 kernel of materials.s exists on one side only, or when one breaks those conditions."""
@@ -64,8 +65,8 @@ def main():
     with ThreadPoolExecutor(2) as ex:
         ro, rn = ex.map(build, (old, new))
     differ = 0
-    for s in ("render_kernels.s", "materials.s", "environment.s"):
-        if s == "environment.s" and not os.path.exists(os.path.join(old, s)):   # an old build from before there was one
+    for s in ("render_kernels.s", "materials.s", "environment.s", "film.s"):
+        if s in ("environment.s", "film.s") and not os.path.exists(os.path.join(old, s)):   # an old build from before there was one
             continue
         ko, kn = kernels(os.path.join(old, s)), kernels(os.path.join(new, s))
         dm = demangle(sorted(set(ko) | set(kn)))
