@@ -4,7 +4,7 @@
 Every operation is one separately rounded float64 NumPy operation in the header's order; the norms are np.linalg.norm's FMA chain
 (norm3_sq of pt_core.h) with fma() taken from libm through ctypes (Python 3.10 has no math.fma).  The two path uniforms come from the
 oracle's counter generator (existing, exact), the lens's fp32 part from materials_ref (uniforms, sincos).  rays() gives [6][N] float32,
-which go through materials_ref / nee_ref / lights_ref.trace and oracle.decode_color for frames.
+which go through materials_ref.trace and oracle.decode_color for frames.
 """
 import ctypes
 import ctypes.util

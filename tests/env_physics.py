@@ -1,6 +1,6 @@
 """The environment's physics checks (include/render_mi355x.h "environment"): scenes, hand-made rays and their expectations, written in
 float64 from geometry alone.  This module imports no restatement and none of the library: tests/test_environment_cpu.py runs
-tests/env_ref.py on these rays, tests/test_gpu_environment.py the kernels, and both meet the same numbers.
+tests/materials_ref.py on these rays, tests/test_gpu_environment.py the kernels, and both meet the same numbers.
 
 Every case is a handful of rays in buffer mode, COPIES copies of each (each copy another path index, so another random sequence),
 seed 1.  The rule is the project's: |mean - expectation| <= Z_CAP * sigma / sqrt(COPIES) per ray and channel, sigma the copies' own

@@ -1,7 +1,7 @@
 """NumPy restatement of the film (include/render_mi355x.h "film": an unclipped float32 accumulation buffer filled pass by pass, and its
 resolve), for the tests only.
 
-A pass is tests/env_ref.py's trace with the pass's seed and the oracle's decode_color, whose `pre` -- the float64 mean before the clip --
+A pass is tests/materials_ref.py's trace with the pass's seed and the oracle's decode_color, whose `pre` -- the float64 mean before the clip --
 is rounded once to float32.  The film is the sequential float32 sum of the passes.  The resolve is float32 NumPy, one separately
 rounded operation per step in the header's order, and np.searchsorted in the curve table.  As in the other restatements f32() fails on
 a float64 intermediate."""
@@ -9,7 +9,7 @@ import re
 
 import numpy as np
 
-import env_ref as er
+import materials_ref as mr
 from materials_ref import F, ROOT, U, f32, splitmix64
 
 TONEMAP_CLIP, TONEMAP_REINHARD = 0, 1
@@ -24,7 +24,7 @@ def _pass_salt():
 
 PASS_SALT = _pass_salt()
 # every stream salt of the header: the bounce's, APT_FLAG_NEE's, the light table's, the lens's, the sun's; roulette has none
-assert PASS_SALT not in (0, 0x6A09E667F3BCC909, 0xBB67AE8584CAA73B, 0x3C6EF372FE94F82B, 0xA54FF53A5F1D36F1, int(er.SUN_SALT))
+assert PASS_SALT not in (0, 0x6A09E667F3BCC909, 0xBB67AE8584CAA73B, 0x3C6EF372FE94F82B, 0xA54FF53A5F1D36F1, int(mr.SUN_SALT))
 
 
 def pass_seed(seed, k):
@@ -44,9 +44,9 @@ def render_pass(params, spheres, materials, env=None, table=None, pass_index=0, 
     w, h, s = q.width, q.height, q.samples
     r = oracle.gen_rays_counter(q) if rays is None else rays(q.seed)
     n = r.shape[1]
-    rr = (q.rr_start or 3) if q.flags & er.FLAG_RR else 0
-    L, bad, seg = er.trace(r, spheres, materials, q.num_spheres, q.depth, q.eps, q.seed, np.arange(n, dtype=U), env, rr,
-                           light=q.light_index, nee=bool(q.flags & er.FLAG_NEE), table=table, gloss=bool(q.flags & er.FLAG_GLOSS))
+    rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
+    L, bad, seg = mr.trace(r, spheres, materials, q.num_spheres, q.depth, q.eps, q.seed, np.arange(n, dtype=U), env, rr,
+                           light=q.light_index, nee=bool(q.flags & mr.FLAG_NEE), table=table, gloss=bool(q.flags & mr.FLAG_GLOSS))
     assert not bad.any()
     pre = oracle.decode_color(L, w, h, s)[0]                   # float64 [W*H][3]: the mean before the clip
     assert pre.dtype == np.float64

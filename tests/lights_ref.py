@@ -1,25 +1,11 @@
-"""NumPy restatement of the material renderer with a light table (include/render_mi355x.h "several lights": the *_lights entries) and
-of the table's construction (apt_build_lights_host), for the tests only.
-
-Same discipline as tests/nee_ref.py and tests/materials_ref.py, whose pieces it uses: float32 arrays vectorised over paths, every
-constant an np.float32, one separately rounded operation per step in the header's order, f32() on the intermediates.  The bounce is
-nee_ref's; what differs is which light a bounce samples (one per path, by a fourth stream), the weight's invp factor, and the rule that
-leaves an emission out at the next hit.  With a one-light table it equals nee_ref.trace(nee=True) bit for bit
-(tests/test_lights_cpu.py asserts that)."""
+"""NumPy restatement of the light table's construction (include/render_mi355x.h "several lights": apt_build_lights_host), its
+invariants, and the scenes with several lights that the tests share, for the tests only.  The renderer that reads the table is
+tests/materials_ref.py's (trace(table=...)), and so is the table as the kernels read it (Table)."""
 import numpy as np
 
-import materials_ref as mr
-import nee_ref as nr
-from materials_ref import C, DIFF, F, REFR, U, basis, dot, f32, fresnel, sincos, splitmix64, uniforms
+from materials_ref import DIFF, F, LIGHTS_HEAD as HEAD, LIGHTS_MAGIC as MAGIC, Table
 
-LIGHT_SALT = U(0x3C6EF372FE94F82B)
-MAGIC = 0x4C474854
-HEAD = 16
 DEV_LIGHTS_MISMATCH = 32
-
-
-def light_key(seed, path):
-    return splitmix64(U(seed) ^ splitmix64(path) ^ LIGHT_SALT)
 
 
 # ---- the table ------------------------------------------------------------------------------------------------------------------
@@ -77,24 +63,6 @@ def build_table(spheres, ns, indices=None):
     return out
 
 
-class Table:
-    """A light table as the kernels read it."""
-
-    def __init__(self, words):
-        t = np.ascontiguousarray(words).view(np.uint32).ravel()
-        assert t[0] == MAGIC and t.size == t[3]
-        self.ns, self.n = int(t[1]), int(t[2])
-        n = self.n
-        self.idx = t[HEAD:HEAD + n].astype(np.int64)
-        self.cdf = t[HEAD + n:HEAD + 2 * n].view(F).copy()
-        self.invp = t[HEAD + 2 * n:HEAD + 3 * n].view(F).copy()
-        bits = t[HEAD + 3 * n:]
-        self.listed = ((bits[np.arange(self.ns) >> 5] >> (np.arange(self.ns) & 31).astype(np.uint32)) & 1).astype(bool)
-
-    def prob(self):
-        return np.diff(self.cdf.astype(np.float64), prepend=0.0)
-
-
 def check_table_invariants(words):
     t = Table(words)
     m = t.cdf.astype(np.float64) * 2.0 ** 24
@@ -103,154 +71,6 @@ def check_table_invariants(words):
     assert np.array_equal((F(1) / P).view(np.uint32), t.invp.view(np.uint32))
     assert t.listed.sum() == t.n and t.listed[t.idx].all() and len(set(t.idx.tolist())) == t.n
     return t
-
-
-# ---- the renderer ---------------------------------------------------------------------------------------------------------------
-def trace(rays, spheres, materials, ns, depth, eps, seed, paths, table, rr_start=0, chunk=1 << 16):
-    """The *_lights entries' paths -> (L float32 [3][n], bad bool [n], segments int: shadow segments included).  table: the words."""
-    rays = np.asarray(rays, dtype=F).reshape(6, -1)
-    n = rays.shape[1]
-    tb = table if isinstance(table, Table) else Table(table)
-    assert tb.ns == ns
-    L = np.zeros((3, n), dtype=F)
-    bad_all = np.zeros(n, dtype=bool)
-    segments = 0
-    step = max(1, (1 << 20) // ns) if ns > 64 else chunk
-    for lo in range(0, n, step):
-        hi = min(n, lo + step)
-        L[:, lo:hi], bad_all[lo:hi], seg = _trace_chunk(rays[:, lo:hi], spheres, materials, ns, depth, eps, seed,
-                                                         np.asarray(paths, dtype=U)[lo:hi], rr_start, tb)
-        segments += seg
-    return L, bad_all, segments
-
-
-def _S(c, r2, same, h):
-    """The predicate S for lights with centres c and r2 seen from h; `same`: the light is the sphere we stand on."""
-    w0 = [c[i] - h[i] for i in range(3)]
-    d2 = dot(*w0, *w0)
-    f32(d2)
-    return ~same & (d2 > r2)
-
-
-def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start, tb):
-    sph = np.asarray(spheres, dtype=F).ravel()[:10 * ns].reshape(10, ns)
-    codes = np.asarray(materials).astype(np.int64).view(np.int64) & 0xFFFFFFFF
-    eps = F(eps)
-    o = [rays[k].copy() for k in range(3)]
-    d = [rays[k].copy() for k in range(3, 6)]
-    n = o[0].size
-    T = [np.ones(n, F) for _ in range(3)]
-    L = [np.zeros(n, F) for _ in range(3)]
-    skip = np.full(n, -1, dtype=np.int64)
-    live = np.ones(n, dtype=bool)
-    sampled = np.zeros(n, dtype=bool)
-    kprev = np.full(n, -1, dtype=np.int64)
-    bad_any = np.zeros(n, dtype=bool)
-    segments = 0
-    mkey, rkey, nkey, lkey = mr.mat_key(seed, paths), mr.rr_key(seed, paths), nr.nee_key(seed, paths), light_key(seed, paths)
-    geo = (sph[1], sph[2], sph[3], sph[0])
-    with np.errstate(all="ignore"):
-        for dd in range(depth):
-            tmin, k = mr._intersect(o, d, geo, eps, skip)
-            g = np.where(k < 0, 0, k)
-            code = codes[g]
-            hit = live & (k >= 0)
-            bad = hit & (code > 2)
-            bad_any |= bad
-            live = hit & ~bad
-            segments += int(live.sum())
-            h = [o[i] + d[i] * tmin for i in range(3)]
-            nr_ = [h[i] - sph[1 + i][g] for i in range(3)]
-            ln = np.sqrt(dot(*nr_, *nr_))
-            nu = [nr_[i] / ln for i in range(3)]
-            # light: the emission of a listed sphere is left out when the previous bounce was a sampling bounce and S held for it there
-            noem = sampled & tb.listed[g] & _S([sph[1 + i][g] for i in range(3)], sph[0][g], g == kprev, o)
-            Ln = [np.where(noem, L[i], L[i] + T[i] * sph[4 + i][g]) for i in range(3)]
-            Tn = [T[i] * sph[7 + i][g] for i in range(3)]
-            ddn = dot(*d, *nu)
-            into = ddn < F(0)
-            nl = [np.where(into, nu[i], -nu[i]) for i in range(3)]
-            u1, u2 = uniforms(mkey, dd)
-            k2 = ddn * F(2)
-            refl = [d[i] - nu[i] * k2 for i in range(3)]
-            sn, cs = sincos(u1)
-            r = np.sqrt(u2)
-            (tx, ty, tz), (bx, by, bz) = basis(*nl)
-            cr, sr, w = cs * r, sn * r, np.sqrt(F(1) - u2)
-            v = [(tx * cr + bx * sr) + nl[0] * w, (ty * cr + by * sr) + nl[1] * w, (tz * cr + bz * sr) + nl[2] * w]
-            vl = np.sqrt(dot(*v, *v))
-            diff = [v[i] / vl for i in range(3)]
-            dn = np.where(into, ddn, -ddn)
-            nnt = np.where(into, C["APT_MAT_NNT_IN"], F(1.5))
-            cos2t = F(1) - (nnt * nnt) * (F(1) - dn * dn)
-            tir = cos2t < F(0)
-            gg = dn * nnt + np.sqrt(cos2t)
-            gg = np.where(into, gg, -gg)
-            v = [d[i] * nnt - nu[i] * gg for i in range(3)]
-            vl = np.sqrt(dot(*v, *v))
-            tdir = [v[i] / vl for i in range(3)]
-            cc = F(1) - np.where(into, -ddn, dot(*tdir, *nu))
-            re, tr = fresnel(cc)
-            P = F(0.25) + F(0.5) * re
-            take_r = u1 < P
-            wt = np.where(take_r, re / P, tr / (F(1) - P))
-            is_d, is_r = code == DIFF, (code == REFR) & ~tir
-            refract = is_r & ~take_r
-            newd = [np.where(is_d, diff[i], np.where(refract, tdir[i], refl[i])) for i in range(3)]
-            Tn = [np.where(is_r, Tn[i] * wt, Tn[i]) for i in range(3)]
-            outward = np.where(refract, ~into, into)
-            # sample + shadow: DIFF hits of live paths, never at the last bounce; one light of the table per path
-            new_sampled = np.zeros(n, dtype=bool)
-            if dd + 1 < depth:
-                u, _ = uniforms(lkey, dd)
-                i_sel = np.searchsorted(tb.cdf, u, side="right")          # the first entry with u < cdf[i]
-                assert i_sel.max() < tb.n and u.dtype == F
-                j = tb.idx[i_sel]
-                lc, lr2 = [sph[1 + i][j] for i in range(3)], sph[0][j]
-                ok, l, cosl, wgt0 = nr.light_sample(h, nl, nkey, dd, lc, lr2)
-                wgt = wgt0 * tb.invp[i_sel]
-                bounce = live & is_d
-                can = bounce & (j != k) & ok                                 # S(j, k, h)
-                want = can & (cosl > F(0))
-                rows = np.nonzero(want)[0]
-                segments += rows.size
-                if rows.size:
-                    sskip = np.where(into, k, -1)[rows]
-                    _, ks = mr._intersect([h[i][rows] for i in range(3)], [l[i][rows] for i in range(3)], geo, eps, sskip)
-                    vis = np.zeros(n, dtype=bool)
-                    vis[rows] = ks == j[rows]
-                    add = [(Tn[i] * sph[4 + i][j]) * wgt for i in range(3)]
-                    f32(wgt, *add)
-                    Ln = [np.where(vis, Ln[i] + add[i], Ln[i]) for i in range(3)]
-                new_sampled = bounce                                         # sampled, whatever the chosen light allowed
-            f32(*h, *Ln, *Tn, *newd)
-            for i in range(3):
-                L[i] = np.where(live, Ln[i], L[i])
-                T[i] = np.where(live, Tn[i], T[i])
-                d[i] = np.where(live, newd[i], d[i])
-                o[i] = np.where(live, h[i], o[i])
-            skip = np.where(live, np.where(outward, k, -1), skip)
-            sampled = np.where(live, new_sampled, sampled)
-            kprev = np.where(live, k, kprev)
-            if rr_start and dd + 1 >= rr_start:
-                T = mr.roulette(T, live, rkey, dd)
-            if not live.any():
-                break
-    return np.stack(L), bad_any, segments
-
-
-def render_frame(params, spheres, materials, table, pixel_begin=0, pixel_count=None):
-    """-> (fb float32 [3][count], u8 [count][3], bad [N]) of apt_render_frame_lights for `params` (an oracle.Params)."""
-    from oracle import oracle
-    w, h, s = params.width, params.height, params.samples
-    rays = oracle.gen_rays_counter(params)
-    n = rays.shape[1]
-    rr = (params.rr_start or 3) if params.flags & oracle.FLAG_RR else 0
-    L, bad, _ = trace(rays, spheres, materials, params.num_spheres, params.depth, params.eps, params.seed, np.arange(n, dtype=U), table, rr)
-    _, fb, u8 = oracle.decode_color(L, w, h, s)
-    if pixel_count is None:
-        pixel_count = w * h - pixel_begin
-    return fb[:, pixel_begin:pixel_begin + pixel_count], u8[pixel_begin:pixel_begin + pixel_count], bad
 
 
 # ---- scenes the tests share ----------------------------------------------------------------------------------------------------------

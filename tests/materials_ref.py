@@ -1,9 +1,17 @@
-"""NumPy restatement of the per-sphere material renderer (include/render_mi355x.h "per-sphere materials"), for the tests only.
+"""NumPy restatement of the material renderer (include/render_mi355x.h "per-sphere materials", "Direct light sampling", "several
+lights", the GLOSS block and "environment"), for the tests only.  It is the one restatement: every GPU test of the material kernels
+compares against this module bit for bit, and tests/test_restatement_frozen.py holds it to recorded bytes.
+
+The whole bounce in one place (_trace_chunk): plain, direct light sampling (nee=True, the sphere `light`), a light table (table=the
+words), the rough-metal material (gloss=True: the launch carries APT_FLAG_GLOSS), roulette, and an environment (env=an Env) with its
+three changes -- the miss, `sampled_sun` cleared at every hit, the sun sample after a DIFF bounce.  A block that cannot reach the result
+for the given arguments is not run: the GLOSS block without the flag or without a gloss word in the table, the light sample without
+`nee` and without a table, the sky and the sun without an environment.
 
 float32 arrays vectorised over paths, every constant an np.float32 (NumPy >= 2 promotes by NEP 50: float32 op float32 stays float32),
-one separately rounded operation per step in the header's order; NumPy's float32 sqrt and division are IEEE.  The polynomial and
-glass constants are read from the header itself.  Camera rays come from the oracle's counter generator and colours are decoded by the
-oracle's decode_color, both existing and exact.
+one separately rounded operation per step in the header's order, f32() on the intermediates -- f32 fails on a float64 one; NumPy's
+float32 sqrt and division are IEEE.  The polynomial and glass constants and the sun's salt are read from the header itself.  Camera
+rays come from the oracle's counter generator and colours are decoded by the oracle's decode_color, both existing and exact.
 """
 import os
 import re
@@ -14,17 +22,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 U = np.uint64
 MISS = F(1e20)
-SPEC, DIFF, REFR = 0, 1, 2
+SPEC, DIFF, REFR, GLOSS = 0, 1, 2, 3
+FLAG_RR, FLAG_NEE, FLAG_GLOSS = 2, 32, 64
+ENV_SAMPLE_SUN = 1
+MAT_SALT = U(0x6A09E667F3BCC909)
+NEE_SALT = U(0xBB67AE8584CAA73B)
+LIGHT_SALT = U(0x3C6EF372FE94F82B)
+LIGHTS_MAGIC, LIGHTS_HEAD = 0x4C474854, 16
 
-
-def _header_constants():
-    text = open(os.path.join(ROOT, "include", "render_mi355x.h")).read()
-    return {m.group(1): F(float.fromhex(m.group(2))) for m in re.finditer(r"#define (APT_MAT_\w+)\s+(-?0x[0-9a-fA-Fp.+-]+)f", text)}
-
-
-C = _header_constants()
+_HEADER = open(os.path.join(ROOT, "include", "render_mi355x.h")).read()
+C = {m.group(1): F(float.fromhex(m.group(2))) for m in re.finditer(r"#define (APT_MAT_\w+)\s+(-?0x[0-9a-fA-Fp.+-]+)f", _HEADER)}
 S_COEF = [C[f"APT_MAT_S{k}"] for k in (1, 3, 5, 7, 9, 11)]
 C_COEF = [F(1.0)] + [C[f"APT_MAT_C{k}"] for k in (2, 4, 6, 8, 10, 12)]
+SUN_SALT = U(int(re.search(r"#define APT_ENV_SUN_SALT\s+(0x[0-9A-Fa-f]+)ull", _HEADER).group(1), 16))
+assert int(SUN_SALT) not in (0, int(MAT_SALT), int(NEE_SALT), int(LIGHT_SALT), 0xA54FF53A5F1D36F1)
 
 
 def f32(*arrays):
@@ -34,6 +45,7 @@ def f32(*arrays):
     return arrays[0] if len(arrays) == 1 else arrays
 
 
+# ---- streams --------------------------------------------------------------------------------------------------------------------------
 def splitmix64(x):
     x = np.asarray(x, dtype=U)
     with np.errstate(over="ignore"):
@@ -44,11 +56,23 @@ def splitmix64(x):
 
 
 def mat_key(seed, path):
-    return splitmix64(U(seed) ^ splitmix64(path) ^ U(0x6A09E667F3BCC909))
+    return splitmix64(U(seed) ^ splitmix64(path) ^ MAT_SALT)
 
 
 def rr_key(seed, path):
     return splitmix64(U(seed) ^ splitmix64(path))
+
+
+def nee_key(seed, path):
+    return splitmix64(U(seed) ^ splitmix64(path) ^ NEE_SALT)
+
+
+def light_key(seed, path):
+    return splitmix64(U(seed) ^ splitmix64(path) ^ LIGHT_SALT)
+
+
+def sun_key(seed, path):
+    return splitmix64(U(seed) ^ splitmix64(path) ^ SUN_SALT)
 
 
 def uniforms(mkey, d):
@@ -59,6 +83,7 @@ def uniforms(mkey, d):
     return f32(u1, u2)
 
 
+# ---- the bounce's pieces ----------------------------------------------------------------------------------------------------------------
 def sincos(u1):
     """(sin, cos) of 2*pi*u1: quadrant / fraction of u1 * 4, the header's polynomial pair, swap / negate."""
     x = u1 * F(4)
@@ -102,6 +127,156 @@ def fresnel(c):
     return f32(re, F(1) - re)
 
 
+def word(q):
+    """APT_MAT_GLOSS_WORD(q)."""
+    return GLOSS | (int(q) << 8)
+
+
+def decode(materials, gloss):
+    """The material words as the kernels read them -> (code int64 [Ns]: 0..2, 3 = gloss, anything else bad; alpha float32 [Ns])."""
+    w = np.asarray(materials).astype(np.int64) & 0xFFFFFFFF
+    if not gloss:
+        return w, np.zeros(w.size, F)
+    q = (w >> 8) & 0xFFFF
+    well = ((w & 0xFF) == GLOSS) & (q != 0) & ((w >> 24) == 0)
+    code = np.where(w <= 2, w, np.where(well, GLOSS, 15))
+    alpha = q.astype(F) * F(2.0 ** -16)
+    return code, f32(alpha)
+
+
+def flags_of(materials):
+    """apt_materials_flags_host restated."""
+    code, _ = decode(materials, True)
+    return FLAG_GLOSS if (code == GLOSS).any() else 0
+
+
+def gloss_sample(d, nl, alpha, u1, u2):
+    """The header's GLOSS block for directions d at oriented normals nl -> (new direction, g = G1(l), up: l.z > 0)."""
+    (tx, ty, tz), (bx, by, bz) = basis(*nl)
+    w = [-d[0], -d[1], -d[2]]
+    vx, vy, vz = dot(*w, tx, ty, tz), dot(*w, bx, by, bz), dot(*w, *nl)
+    s0x, s0y = alpha * vx, alpha * vy
+    sl = np.sqrt(dot(s0x, s0y, vz, s0x, s0y, vz))
+    sx, sy, sz = s0x / sl, s0y / sl, vz / sl
+    sn, cs = sincos(u1)
+    z = (F(1) - u2) * (F(1) + sz) - sz
+    r2 = F(1) - z * z
+    r = np.sqrt(np.where(r2 > F(0), r2, F(0)))
+    m0x, m0y, m0z = alpha * (r * cs + sx), alpha * (r * sn + sy), z + sz
+    ml = np.sqrt(dot(m0x, m0y, m0z, m0x, m0y, m0z))
+    mx, my, mz = m0x / ml, m0y / ml, m0z / ml
+    vm2 = F(2) * dot(vx, vy, vz, mx, my, mz)
+    lx, ly, lz = mx * vm2 - vx, my * vm2 - vy, mz * vm2 - vz
+    a2 = alpha * alpha
+    g = (F(2) * lz) / (lz + np.sqrt(a2 + (F(1) - a2) * (lz * lz)))
+    q = [(tx * lx + bx * ly) + nl[0] * lz, (ty * lx + by * ly) + nl[1] * lz, (tz * lx + bz * ly) + nl[2] * lz]
+    ql = np.sqrt(dot(*q, *q))
+    newd = [q[i] / ql for i in range(3)]
+    f32(vx, vy, vz, sx, sy, sz, z, r, mx, my, mz, lx, ly, lz, g, *newd)
+    return newd, g, lz > F(0)
+
+
+def light_sample(h, nl, nkey, bounce, lc, lr2):
+    """The header's `sample` step of "Direct light sampling" for hit points h with oriented normals nl
+    -> (ok: h strictly outside the light, l, cosl, wgt)."""
+    w0 = [lc[i] - h[i] for i in range(3)]
+    d2 = dot(*w0, *w0)
+    ok = d2 > lr2
+    x = lr2 / d2
+    cmax = np.sqrt(F(1) - x)
+    omc = x / (F(1) + cmax)
+    v1, v2 = uniforms(nkey, bounce)
+    cos_a = F(1) - v1 * omc
+    sin_a = np.sqrt(F(1) - cos_a * cos_a)
+    sp, cp = sincos(v2)
+    dl = np.sqrt(d2)
+    w = [w0[i] / dl for i in range(3)]
+    (ax, ay, az), (bx, by, bz) = basis(*w)
+    ca, sa = cp * sin_a, sp * sin_a
+    q = [(ax * ca + bx * sa) + w[0] * cos_a, (ay * ca + by * sa) + w[1] * cos_a, (az * ca + bz * sa) + w[2] * cos_a]
+    ql = np.sqrt(dot(*q, *q))
+    l = [q[i] / ql for i in range(3)]
+    cosl = dot(*l, *nl)
+    wgt = cosl * (F(2) * omc)
+    f32(d2, x, cmax, omc, cos_a, sin_a, *l, cosl, wgt)
+    return ok, l, cosl, wgt
+
+
+class Table:
+    """A light table (the header's "several lights" layout) as the kernels read it."""
+
+    def __init__(self, words):
+        t = np.ascontiguousarray(words).view(np.uint32).ravel()
+        assert t[0] == LIGHTS_MAGIC and t.size == t[3]
+        self.ns, self.n = int(t[1]), int(t[2])
+        n = self.n
+        self.idx = t[LIGHTS_HEAD:LIGHTS_HEAD + n].astype(np.int64)
+        self.cdf = t[LIGHTS_HEAD + n:LIGHTS_HEAD + 2 * n].view(F).copy()
+        self.invp = t[LIGHTS_HEAD + 2 * n:LIGHTS_HEAD + 3 * n].view(F).copy()
+        bits = t[LIGHTS_HEAD + 3 * n:]
+        self.listed = ((bits[np.arange(self.ns) >> 5] >> (np.arange(self.ns) & 31).astype(np.uint32)) & 1).astype(bool)
+
+    def prob(self):
+        return np.diff(self.cdf.astype(np.float64), prepend=0.0)
+
+
+class Env:
+    """An apt_environment as the kernels read it: float32 fields."""
+
+    def __init__(self, horizon=(0, 0, 0), zenith=(0, 0, 0), sun_dir=(0, 1, 0), sun_radiance=(0, 0, 0), sun_omc=0.0, flags=0):
+        self.horizon = [F(x) for x in horizon]
+        self.zenith = [F(x) for x in zenith]
+        self.sun_dir = [F(x) for x in sun_dir]
+        self.sun_radiance = [F(x) for x in sun_radiance]
+        self.sun_omc = F(sun_omc)
+        self.flags = int(flags)
+
+    @classmethod
+    def from_ctypes(cls, e):
+        """From the record the library built (ascendpathtracing_amd._lib.ApEnvironment): the fields as they are."""
+        return cls(list(e.horizon), list(e.zenith), list(e.sun_dir), list(e.sun_radiance), e.sun_omc, e.flags)
+
+    @property
+    def samples_sun(self):
+        return bool(self.flags & ENV_SAMPLE_SUN) and self.sun_omc > F(0)
+
+
+def sky(env, dy):
+    """The miss step's sky radiance along directions with y component dy -> three float32 arrays."""
+    t = dy * F(0.5) + F(0.5)
+    t = np.where(t > F(0), t, F(0))
+    t = np.where(t < F(1), t, F(1))
+    out = [env.horizon[c] + (env.zenith[c] - env.horizon[c]) * t for c in range(3)]
+    f32(t, *out)
+    return out
+
+
+def in_sun(env, d):
+    """The miss step's cone test: sun_omc > 0 and dot(d, sun_dir) >= 1.0f - sun_omc."""
+    if not env.sun_omc > F(0):
+        return np.zeros(d[0].shape, dtype=bool)
+    return f32(dot(*d, *env.sun_dir)) >= F(1) - env.sun_omc
+
+
+def sun_sample(env, nl, skey, bounce):
+    """The header's `sun sample` step -> (l, cosl, wgt): "Direct light sampling" with w = sun_dir and omc = sun_omc."""
+    omc = env.sun_omc
+    w = env.sun_dir
+    v1, v2 = uniforms(skey, bounce)
+    cos_a = F(1) - v1 * omc
+    sin_a = np.sqrt(F(1) - cos_a * cos_a)
+    sp, cp = sincos(v2)
+    (ax, ay, az), (bx, by, bz) = basis(*[np.full(v1.shape, x, F) for x in w])
+    ca, sa = cp * sin_a, sp * sin_a
+    q = [(ax * ca + bx * sa) + w[0] * cos_a, (ay * ca + by * sa) + w[1] * cos_a, (az * ca + bz * sa) + w[2] * cos_a]
+    ql = np.sqrt(dot(*q, *q))
+    l = [q[i] / ql for i in range(3)]
+    cosl = dot(*l, *nl)
+    wgt = cosl * (F(2) * omc)
+    f32(cos_a, sin_a, *l, cosl, wgt)
+    return l, cosl, wgt
+
+
 def _intersect(o, d, geo, eps, skip):
     """-> (tmin, idx): render_do_ex's K-mode test of every sphere, the skip sphere excluded; idx -1 = no hit."""
     cx, cy, cz, r2 = geo
@@ -127,24 +302,54 @@ def _intersect(o, d, geo, eps, skip):
     return tmin, np.where(tmin < MISS, idx, -1)
 
 
-def trace(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start=0, chunk=1 << 16):
-    """rays float32 [6][n], spheres the padded [10][Ns] table, materials uint32/int32 [Ns], paths uint64 [n] (path indices)
-    -> (L float32 [3][n], bad bool [n]: the path hit a bad material code)."""
+def roulette(T, alive, key, bounce):
+    """APT_FLAG_RR (include/render_mi355x.h) on the throughput."""
+    q = T[0]
+    q = np.where(T[1] > q, T[1], q)
+    q = np.where(T[2] > q, T[2], q)
+    act = alive & (q > F(0))
+    p = np.where(q < F(0.05), F(0.05), q)
+    p = np.where(p > F(0.95), F(0.95), p)
+    with np.errstate(over="ignore"):
+        h = splitmix64(key + U(0x9E3779B97F4A7C15) * U(bounce + 1))
+    u = (h >> U(40)).astype(F) * F(2.0 ** -24)
+    kill = act & (u >= p)
+    inv = F(1) / p
+    f32(u, inv, *T)
+    return [np.where(kill, F(0), np.where(act, t * inv, t)) for t in T]
+
+
+# ---- the renderer -------------------------------------------------------------------------------------------------------------------------
+def trace(rays, spheres, materials, ns, depth, eps, seed, paths, env=None, rr_start=0, light=-1, nee=False, table=None, gloss=True,
+          chunk=1 << 16):
+    """rays float32 [6][n], spheres the padded [10][Ns] table, materials the words [Ns], paths uint64 [n] (path indices); env: an Env or
+    None (no environment); gloss: the launch carries APT_FLAG_GLOSS; nee / light: APT_FLAG_NEE; table: the *_lights entries (then nee /
+    light are not read) -> (L float32 [3][n], bad bool [n]: the path hit a bad material word, segments int: the lights' and the sun's
+    shadow segments included)."""
     rays = np.asarray(rays, dtype=F).reshape(6, -1)
     n = rays.shape[1]
+    tb = None if table is None else (table if isinstance(table, Table) else Table(table))
+    assert tb is None or tb.ns == ns
     L = np.zeros((3, n), dtype=F)
     bad_all = np.zeros(n, dtype=bool)
+    segments = 0
     step = max(1, (1 << 20) // ns) if ns > 64 else chunk   # the [paths][spheres] arrays of one chunk stay at ~4 MB
     for lo in range(0, n, step):
         hi = min(n, lo + step)
-        L[:, lo:hi], bad_all[lo:hi] = _trace_chunk(rays[:, lo:hi], spheres, materials, ns, depth, eps, seed,
-                                                    np.asarray(paths, dtype=U)[lo:hi], rr_start)
-    return L, bad_all
+        L[:, lo:hi], bad_all[lo:hi], seg = _trace_chunk(rays[:, lo:hi], spheres, materials, ns, depth, eps, seed,
+                                                         np.asarray(paths, dtype=U)[lo:hi], rr_start, light, nee and tb is None, tb, gloss, env)
+        segments += seg
+    return L, bad_all, segments
 
 
-def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start):
+def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start, light, nee, tb, gloss, env):
+    assert not nee or 0 <= light < ns
     sph = np.asarray(spheres, dtype=F).ravel()[:10 * ns].reshape(10, ns)
-    codes = np.asarray(materials).astype(np.int64).view(np.int64) & 0xFFFFFFFF
+    codes, alphas = decode(materials, gloss)
+    top = GLOSS if gloss else REFR
+    has_gloss = gloss and bool((codes == GLOSS).any())
+    lit = nee or tb is not None
+    sun = env is not None and env.samples_sun
     eps = F(eps)
     o = [rays[k].copy() for k in range(3)]
     d = [rays[k].copy() for k in range(3, 6)]
@@ -153,30 +358,57 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
     L = [np.zeros(n, F) for _ in range(3)]
     skip = np.full(n, -1, dtype=np.int64)
     live = np.ones(n, dtype=bool)
+    sampled = np.zeros(n, dtype=bool)
+    sampled_sun = np.zeros(n, dtype=bool)
+    kprev = np.full(n, -1, dtype=np.int64)
     bad_any = np.zeros(n, dtype=bool)
+    segments = 0
     mkey, rkey = mat_key(seed, paths), rr_key(seed, paths)
+    nkey = nee_key(seed, paths) if lit else None
+    lkey = light_key(seed, paths) if tb is not None else None
+    skey = sun_key(seed, paths) if sun else None
+    geo = (sph[1], sph[2], sph[3], sph[0])
     with np.errstate(all="ignore"):
         for dd in range(depth):
-            tmin, k = _intersect(o, d, (sph[1], sph[2], sph[3], sph[0]), eps, skip)
+            # hit, code
+            tmin, k = _intersect(o, d, geo, eps, skip)
             g = np.where(k < 0, 0, k)
             code = codes[g]
+            # miss: the sky, and the sun unless the bounce before sampled it; the path ends
+            if env is not None:
+                miss = live & (k < 0)
+                s = sky(env, d[1])
+                Lm = [L[i] + T[i] * s[i] for i in range(3)]
+                add_sun = in_sun(env, d) & ~sampled_sun
+                Lm = [np.where(add_sun, Lm[i] + T[i] * env.sun_radiance[i], Lm[i]) for i in range(3)]
+                f32(*Lm)
+                L = [np.where(miss, Lm[i], L[i]) for i in range(3)]
             hit = live & (k >= 0)
-            bad = hit & (code > 2)
+            bad = hit & (code > top)
             bad_any |= bad
             live = hit & ~bad
-            # point and normal (render_do_ex's K-mode)
+            segments += int(live.sum())
+            # point
             h = [o[i] + d[i] * tmin for i in range(3)]
             nr = [h[i] - sph[1 + i][g] for i in range(3)]
             ln = np.sqrt(dot(*nr, *nr))
             nu = [nr[i] / ln for i in range(3)]
-            # light, throughput
+            # light: an emission that the previous bounce's sample stood for is left out
             Ln = [L[i] + T[i] * sph[4 + i][g] for i in range(3)]
+            if lit:
+                if nee:
+                    noem = sampled & (k == light)
+                else:
+                    w0 = [sph[1 + i][g] - o[i] for i in range(3)]
+                    noem = sampled & tb.listed[g] & (g != kprev) & (f32(dot(*w0, *w0)) > sph[0][g])
+                Ln = [np.where(noem, L[i], Ln[i]) for i in range(3)]
             Tn = [T[i] * sph[7 + i][g] for i in range(3)]
+            # orient, draws
             ddn = dot(*d, *nu)
             into = ddn < F(0)
             nl = [np.where(into, nu[i], -nu[i]) for i in range(3)]
             u1, u2 = uniforms(mkey, dd)
-            # SPEC / reflection
+            # reflect (SPEC, and the reflection of REFR)
             k2 = ddn * F(2)
             refl = [d[i] - nu[i] * k2 for i in range(3)]
             # DIFF
@@ -198,15 +430,70 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
             vl = np.sqrt(dot(*v, *v))
             tdir = [v[i] / vl for i in range(3)]
             cc = F(1) - np.where(into, -ddn, dot(*tdir, *nu))
-            re, tr = fresnel(cc)
-            P = F(0.25) + F(0.5) * re
+            re_, tr = fresnel(cc)
+            P = F(0.25) + F(0.5) * re_
             take_r = u1 < P
-            wt = np.where(take_r, re / P, tr / (F(1) - P))
+            wt = np.where(take_r, re_ / P, tr / (F(1) - P))
             is_d, is_r = code == DIFF, (code == REFR) & ~tir
             refract = is_r & ~take_r
             newd = [np.where(is_d, diff[i], np.where(refract, tdir[i], refl[i])) for i in range(3)]
-            Tn = [np.where(is_r, Tn[i] * wt, Tn[i]) for i in range(3)]
+            Tw = [np.where(is_r, Tn[i] * wt, Tn[i]) for i in range(3)]
             outward = np.where(refract, ~into, into)
+            # GLOSS: a code of its own, so its direction and weight go over the three above where the word says so
+            ended = None
+            if has_gloss:
+                gdir, gw, up = gloss_sample(d, nl, alphas[g], u1, u2)
+                is_g = code == GLOSS
+                newd = [np.where(is_g, gdir[i], newd[i]) for i in range(3)]
+                Tw = [np.where(is_g, Tn[i] * gw, Tw[i]) for i in range(3)]
+                ended = live & is_g & ~up                                # drawn below the horizon: the path ends, L keeps its value
+            Tn = Tw
+            # sample + shadow: DIFF hits of live paths, never at the last bounce
+            new_sampled = np.zeros(n, dtype=bool)
+            if lit and dd + 1 < depth:
+                bounce = live & is_d
+                if nee:
+                    j = np.full(n, light, dtype=np.int64)
+                    ok, l, cosl, wgt = light_sample(h, nl, nkey, dd, [sph[1 + i][light] for i in range(3)], sph[0][light])
+                    can = bounce & (k != light) & ok
+                    new_sampled = can
+                else:
+                    u, _ = uniforms(lkey, dd)
+                    i_sel = np.searchsorted(tb.cdf, u, side="right")          # the first entry with u < cdf[i]
+                    assert i_sel.max() < tb.n and u.dtype == F
+                    j = tb.idx[i_sel]
+                    ok, l, cosl, wgt = light_sample(h, nl, nkey, dd, [sph[1 + i][j] for i in range(3)], sph[0][j])
+                    wgt = wgt * tb.invp[i_sel]
+                    can = bounce & (j != k) & ok
+                    new_sampled = bounce                                     # sampled, whatever the chosen light allowed
+                want = can & (cosl > F(0))
+                rows = np.nonzero(want)[0]
+                segments += rows.size
+                if rows.size:
+                    sskip = np.where(into, k, -1)[rows]
+                    _, ks = _intersect([h[i][rows] for i in range(3)], [l[i][rows] for i in range(3)], geo, eps, sskip)
+                    vis = np.zeros(n, dtype=bool)
+                    vis[rows] = ks == j[rows]
+                    add = [(Tn[i] * sph[4 + i][j]) * wgt for i in range(3)]
+                    f32(wgt, *add)
+                    Ln = [np.where(vis, Ln[i] + add[i], Ln[i]) for i in range(3)]
+            # sun sample: after the light's; the sun is visible iff the shadow segment finds no sphere
+            new_sampled_sun = np.zeros(n, dtype=bool)
+            if sun and dd + 1 < depth:
+                bounce = live & is_d
+                l, cosl, wgt = sun_sample(env, nl, skey, dd)
+                new_sampled_sun = bounce                                     # sampled, whatever follows
+                want = bounce & (cosl > F(0))
+                rows = np.nonzero(want)[0]
+                segments += rows.size
+                if rows.size:
+                    sskip = np.where(into, k, -1)[rows]
+                    _, ks = _intersect([h[i][rows] for i in range(3)], [l[i][rows] for i in range(3)], geo, eps, sskip)
+                    vis = np.zeros(n, dtype=bool)
+                    vis[rows] = ks < 0
+                    add = [(Tn[i] * env.sun_radiance[i]) * wgt for i in range(3)]
+                    f32(wgt, *add)
+                    Ln = [np.where(vis, Ln[i] + add[i], Ln[i]) for i in range(3)]
             f32(*h, *Ln, *Tn, *newd)
             for i in range(3):
                 L[i] = np.where(live, Ln[i], L[i])
@@ -214,39 +501,34 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
                 d[i] = np.where(live, newd[i], d[i])
                 o[i] = np.where(live, h[i], o[i])
             skip = np.where(live, np.where(outward, k, -1), skip)
+            if lit:
+                sampled = np.where(live, new_sampled, sampled)
+                kprev = np.where(live, k, kprev)
+            if sun:
+                sampled_sun = np.where(live, new_sampled_sun, sampled_sun)  # cleared at every hit, set by a sampling DIFF bounce
+            if ended is not None:
+                live = live & ~ended
             if rr_start and dd + 1 >= rr_start:
                 T = roulette(T, live, rkey, dd)
             if not live.any():
                 break
-    return np.stack(L), bad_any
+    f32(*L)
+    return np.stack(L), bad_any, segments
 
 
-def roulette(T, alive, key, bounce):
-    """APT_FLAG_RR (include/render_mi355x.h) on the throughput."""
-    q = T[0]
-    q = np.where(T[1] > q, T[1], q)
-    q = np.where(T[2] > q, T[2], q)
-    act = alive & (q > F(0))
-    p = np.where(q < F(0.05), F(0.05), q)
-    p = np.where(p > F(0.95), F(0.95), p)
-    with np.errstate(over="ignore"):
-        h = splitmix64(key + U(0x9E3779B97F4A7C15) * U(bounce + 1))
-    u = (h >> U(40)).astype(F) * F(2.0 ** -24)
-    kill = act & (u >= p)
-    inv = F(1) / p
-    f32(u, inv, *T)
-    return [np.where(kill, F(0), np.where(act, t * inv, t)) for t in T]
-
-
-def render_frame(params, spheres, materials, pixel_begin=0, pixel_count=None):
-    """-> (fb float32 [3][count], u8 [count][3], bad [N]) of apt_render_frame_materials for `params` (an oracle.Params)."""
+def render_frame(params, spheres, materials, env=None, table=None, pixel_begin=0, pixel_count=None, rays=None):
+    """-> (fb float32 [3][count], u8 [count][3], bad [N], segments) of apt_render_frame_materials (table: apt_render_frame_lights) with the
+    environment `env` set, for `params` (an oracle.Params); APT_FLAG_NEE / APT_FLAG_GLOSS / APT_FLAG_RR are read from params.flags.
+    rays: a camera's (camera_ref.rays)."""
     from oracle import oracle
     w, h, s = params.width, params.height, params.samples
-    rays = oracle.gen_rays_counter(params)
+    if rays is None:
+        rays = oracle.gen_rays_counter(params)
     n = rays.shape[1]
-    rr = (params.rr_start or 3) if params.flags & oracle.FLAG_RR else 0
-    L, bad = trace(rays, spheres, materials, params.num_spheres, params.depth, params.eps, params.seed, np.arange(n, dtype=U), rr)
+    rr = (params.rr_start or 3) if params.flags & FLAG_RR else 0
+    L, bad, seg = trace(rays, spheres, materials, params.num_spheres, params.depth, params.eps, params.seed, np.arange(n, dtype=U), env, rr,
+                        light=params.light_index, nee=bool(params.flags & FLAG_NEE), table=table, gloss=bool(params.flags & FLAG_GLOSS))
     _, fb, u8 = oracle.decode_color(L, w, h, s)
     if pixel_count is None:
         pixel_count = w * h - pixel_begin
-    return fb[:, pixel_begin:pixel_begin + pixel_count], u8[pixel_begin:pixel_begin + pixel_count], bad
+    return fb[:, pixel_begin:pixel_begin + pixel_count], u8[pixel_begin:pixel_begin + pixel_count], bad, seg

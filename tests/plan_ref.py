@@ -245,21 +245,14 @@ def lens_camera(gen_data):
 
 
 def mat_colours(oracle, gen_data, name, mode, s, cam=None):
-    """The restatement's per-path colours [3][W * H * 4 * s] of a material case (materials_ref / nee_ref / lights_ref), from the
+    """The restatement's per-path colours [3][W * H * 4 * s] of a material case (materials_ref), from the
     counter generator's rays or, with `cam` (an ApCamera), from camera_ref's."""
     import camera_ref as cr
-    import lights_ref as lr
     import materials_ref as mr
-    import nee_ref as nr
     sph, mat, ns, light, table = mat_scene(gen_data, name)
     p = oracle.make_params(W, H, s, depth=MAT_DEPTH, num_spheres=ns, light_index=light, seed=MAT_SEED)
     rays = oracle.gen_rays_counter(p) if cam is None else cr.rays(cr.from_ctypes(cam), W, H, s, seed=MAT_SEED)
     args = (rays, sph, mat, ns, MAT_DEPTH, p.eps, MAT_SEED, np.arange(rays.shape[1], dtype=np.uint64))
-    if mode == "plain":
-        L, bad = mr.trace(*args, 0)
-    elif mode == "nee":
-        L, bad, _ = nr.trace(*args, 0, light=light, nee=True)
-    else:
-        L, bad, _ = lr.trace(*args, table, 0)
+    L, bad, _ = mr.trace(*args, light=light, nee=mode == "nee", table=table if mode == "table" else None, gloss=False)
     assert not bad.any()
     return L

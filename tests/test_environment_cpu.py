@@ -1,5 +1,5 @@
 """CPU-only: the environment (include/render_mi355x.h "environment") -- the record's host entries through ctypes with every refusal and
-the context state, the restatement tests/env_ref.py with a black environment against the four existing restatements bit for bit, and
+the context state, the restatement tests/materials_ref.py with a black environment against itself without one bit for bit, and
 the restatement against physics written in float64 from geometry alone (tests/env_physics.py, which imports no restatement): a uniform
 and a graded sky, the sun sampled and not, an occluder, a mirror ball, a glass ball, the sun next to a sphere lamp.
 
@@ -10,11 +10,8 @@ import numpy as np
 import pytest
 
 import env_physics as ep
-import env_ref as er
-import gloss_ref as gr
 import lights_ref as lr
 import materials_ref as mr
-import nee_ref as nr
 
 F, U = np.float32, np.uint64
 
@@ -43,7 +40,7 @@ def test_record_layout_and_symbols(apt):
     for name in ("apt_environment_build_host", "apt_environment_check_host", "apt_context_set_environment", "apt_set_environment"):
         assert name in apt._lib.ABI_SYMBOLS
     header = open(mr.ROOT + "/include/render_mi355x.h").read()
-    assert "APT_ENV_SUN_SALT 0x%016Xull" % int(er.SUN_SALT) in header and "#define APT_ABI_VERSION 3 " in header
+    assert "APT_ENV_SUN_SALT 0x%016Xull" % int(mr.SUN_SALT) in header and "#define APT_ABI_VERSION 3 " in header
 
 
 def test_build_then_check_round_trip(apt):
@@ -202,7 +199,7 @@ def test_open_scenes_and_their_grids(apt):
 
 
 # ---- a black environment is no environment -------------------------------------------------------------------------------------------
-BLACK = er.Env()
+BLACK = mr.Env()
 
 
 def _frame_rays(oracle, w, h, s, seed):
@@ -210,73 +207,74 @@ def _frame_rays(oracle, w, h, s, seed):
 
 
 @pytest.mark.parametrize("rr", [0, 2], ids=["", "rr"])
-def test_black_environment_equals_the_four_restatements(apt, oracle, rr):
+def test_black_environment_equals_no_environment(apt, oracle, rr):
+    """env=the black Env() against env=None (whose bytes tests/test_restatement_frozen.py records) in every mode: plain, APT_FLAG_NEE,
+    a light table, a gloss ball in all three."""
     g = apt.gen_data
     rays = _frame_rays(oracle, 24, 16, 2, 7)
     n = rays.shape[1]
     paths = np.arange(n, dtype=U)
-    # materials_ref: the demo scene (9 spheres, glass ball) and the 8-sphere DIFF room
+    # plain: the demo scene (9 spheres, glass ball) and the 8-sphere DIFF room
     for sph, mat, ns in ((*g.gen_spheres_materials(), 9), (g.gen_spheres(), np.array([1, 1, 1, 1, 1, 1, 0, 1], dtype=np.int32), 8)):
-        want, bad = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, rr)
-        for env in (None, BLACK):
-            got, gbad, _ = er.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, env, rr, gloss=False)
-            _bits_equal(got, want)
-            assert np.array_equal(gbad, bad) and want.max() > 0
-    # nee_ref: the same scenes with smallpt's lamp
+        want, bad, seg = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, None, rr, gloss=False)
+        got, gbad, gseg = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, BLACK, rr, gloss=False)
+        _bits_equal(got, want)
+        assert np.array_equal(gbad, bad) and gseg == seg and want.max() > 0
+    # APT_FLAG_NEE: the demo scene with smallpt's lamp
     sph, mat = g.gen_spheres_materials()
     sph = g.with_lamp(sph, 9, 7)
-    want, bad, seg = nr.trace(rays, sph, mat, 9, 5, 1e-4, 7, paths, rr, light=7, nee=True)
-    got, gbad, gseg = er.trace(rays, sph, mat, 9, 5, 1e-4, 7, paths, BLACK, rr, light=7, nee=True, gloss=False)
+    want, bad, seg = mr.trace(rays, sph, mat, 9, 5, 1e-4, 7, paths, None, rr, light=7, nee=True, gloss=False)
+    got, gbad, gseg = mr.trace(rays, sph, mat, 9, 5, 1e-4, 7, paths, BLACK, rr, light=7, nee=True, gloss=False)
     _bits_equal(got, want)
     assert gseg == seg and not bad.any() and not gbad.any()
-    # lights_ref: two lights of the demo scene, and the 8-sphere room with two lamps
+    # a light table: two lights of the demo scene, and the 8-sphere room with two lamps
     for sph, mat, ns in (lr.demo_two_lights(g), lr.two_lamps(g)):
         table = lr.build_table(sph, ns, [7, 6])
-        want, bad, seg = lr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, table, rr)
-        got, gbad, gseg = er.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, BLACK, rr, table=table, gloss=False)
+        want, bad, seg = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, None, rr, table=table, gloss=False)
+        got, gbad, gseg = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, BLACK, rr, table=table, gloss=False)
         _bits_equal(got, want)
         assert gseg == seg and not gbad.any()
-    # gloss_ref: the room with a gloss ball, all three light modes
+    # the rough-metal material: the room with a gloss ball, all three light modes
     sph, mat, ns = lr.two_lamps(g)
     mat = mat.copy()
     mat[6] = g.gloss(0.3)
     table = lr.build_table(sph, ns, [7, 6])
     for kw in ({}, dict(light=7, nee=True), dict(table=table)):
-        want, bad, seg = gr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, rr, **kw)
-        got, gbad, gseg = er.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, BLACK, rr, **kw)
+        want, bad, seg = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, None, rr, **kw)
+        got, gbad, gseg = mr.trace(rays, sph, mat, ns, 5, 1e-4, 7, paths, BLACK, rr, **kw)
         _bits_equal(got, want)
         assert gseg == seg and not gbad.any() and want.max() > 0
     # and an environment that is not black changes an open scene, so the comparison above is not vacuous
     sph, mat = g.gen_spheres_open()
-    lit, _, _ = er.trace(rays, sph, mat, 8, 5, 1e-4, 7, paths, er.Env(horizon=(1, 1, 1), zenith=(1, 1, 1)), rr)
-    dark, _, _ = er.trace(rays, sph, mat, 8, 5, 1e-4, 7, paths, BLACK, rr)
+    lit, _, _ = mr.trace(rays, sph, mat, 8, 5, 1e-4, 7, paths, mr.Env(horizon=(1, 1, 1), zenith=(1, 1, 1)), rr)
+    dark, _, _ = mr.trace(rays, sph, mat, 8, 5, 1e-4, 7, paths, BLACK, rr)
     assert dark.max() == 0 and (lit > 0).mean() > 0.9
 
 
 def test_the_restatement_has_no_float64_intermediates(apt):
-    """f32() guards every step of env_ref; a float64 constant slipped into the environment's own steps must trip it."""
-    env = er.Env(horizon=(0.25, 0.5, 0.75), zenith=(1, 2, 3), sun_dir=(0, 1, 0), sun_radiance=(4, 4, 4), sun_omc=0.0625, flags=1)
+    """f32() guards every step of the restatement; a float64 constant slipped into the environment's own steps must trip it."""
+    env = mr.Env(horizon=(0.25, 0.5, 0.75), zenith=(1, 2, 3), sun_dir=(0, 1, 0), sun_radiance=(4, 4, 4), sun_omc=0.0625, flags=1)
     rays = ep.sun_only(True).rays()[:, :256]
-    L, _, _ = er.trace(rays, ep.sun_only(True).table(8), ep.sun_only(True).materials(8), 8, 3, 1e-4, 1, np.arange(256, dtype=U), env)
+    L, _, _ = mr.trace(rays, ep.sun_only(True).table(8), ep.sun_only(True).materials(8), 8, 3, 1e-4, 1, np.arange(256, dtype=U), env)
     assert L.dtype == F
-    wide = er.Env(horizon=(0.25, 0.5, 0.75), zenith=(1, 2, 3))
+    wide = mr.Env(horizon=(0.25, 0.5, 0.75), zenith=(1, 2, 3))
     wide.horizon = [np.float64(x) for x in wide.horizon]
     with pytest.raises(AssertionError):
-        er.sky(wide, rays[4])
-    wide = er.Env(sun_dir=(0, 1, 0), sun_radiance=(4, 4, 4), sun_omc=0.0625, flags=1)
+        mr.sky(wide, rays[4])
+    wide = mr.Env(sun_dir=(0, 1, 0), sun_radiance=(4, 4, 4), sun_omc=0.0625, flags=1)
     wide.sun_omc = np.float64(0.0625)
     with pytest.raises(AssertionError):
-        er.sun_sample(wide, [rays[3], rays[4], rays[5]], er.splitmix64(np.arange(256, dtype=U)), 0)
+        mr.sun_sample(wide, [rays[3], rays[4], rays[5]], mr.splitmix64(np.arange(256, dtype=U)), 0)
 
 
 # ---- physics --------------------------------------------------------------------------------------------------------------------------
 def _env_of(case):
     e = case.env
-    return er.Env(e["horizon"], e["zenith"], e["sun_dir"], e["sun_radiance"], e["sun_omc"], e.get("flags", 0))
+    return mr.Env(e["horizon"], e["zenith"], e["sun_dir"], e["sun_radiance"], e["sun_omc"], e.get("flags", 0))
 
 
 def _render(case, ns=8, mode="plain", real_only=False):
-    """env_ref on the case's rays; real_only: the scene without its parked spheres."""
+    """materials_ref on the case's rays; real_only: the scene without its parked spheres."""
     n = len(case.rows) if real_only else ns
     sph, mat = case.table(n), case.materials(n)
     kw = {}
@@ -284,7 +282,7 @@ def _render(case, ns=8, mode="plain", real_only=False):
         kw = dict(light=case.light, nee=True)
     elif mode == "table":
         kw = dict(table=lr.build_table(sph, n, case.lights))
-    L, bad, _ = er.trace(case.rays(), sph, mat, n, case.depth, 1e-4, ep.SEED, case.paths(), _env_of(case), gloss=False, **kw)
+    L, bad, _ = mr.trace(case.rays(), sph, mat, n, case.depth, 1e-4, ep.SEED, case.paths(), _env_of(case), gloss=False, **kw)
     assert not bad.any()
     return L
 

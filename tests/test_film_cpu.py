@@ -1,4 +1,4 @@
-"""CPU-only: the film (include/render_mi355x.h "film") -- the restatement tests/film_ref.py against tests/env_ref.py's frames, the pass
+"""CPU-only: the film (include/render_mi355x.h "film") -- the restatement tests/film_ref.py against tests/materials_ref.py's frames, the pass
 seed, the independence of passes, the curve tables, the resolve's CPU twin apt_film_resolve_host bit for bit against the restatement
 with every refusal, and the PFM writer.
 
@@ -8,7 +8,6 @@ import ctypes
 import numpy as np
 import pytest
 
-import env_ref as er
 import film_ref as fr
 import materials_ref as mr
 
@@ -51,18 +50,18 @@ def test_symbols_and_record(apt):
 
 
 def test_pass_zero_clipped_is_the_frame(apt):
-    """clip(pass 0) is env_ref.render_frame's fb bit for bit (NaNs as bits), in the closed room and under a sun far above 1."""
+    """clip(pass 0) is materials_ref.render_frame's fb bit for bit (NaNs as bits), in the closed room and under a sun far above 1."""
     g = apt.gen_data
     sph, mat = g.gen_spheres_materials()
     room = (g.with_lamp(sph, 9, 7), mat, 9, 7, None, apt.APT_FLAG_NEE)
     sph, mat = g.gen_spheres_open()
-    env = er.Env.from_ctypes(g.environment(horizon=(0.5, 0.6, 0.7), zenith=(0.1, 0.3, 0.9), sun_dir=(0.4, 0.8, 0.45),
+    env = mr.Env.from_ctypes(g.environment(horizon=(0.5, 0.6, 0.7), zenith=(0.1, 0.3, 0.9), sun_dir=(0.4, 0.8, 0.45),
                                            sun_radiance=(300.0, 280.0, 240.0), sun_angle_deg=8.0, sample_sun=True))
     open_ = (sph, mat, 8, -1, env, g.materials_flags(mat))
     for name, (sph, mat, ns, light, env, flags) in (("room", room), ("open", open_)):
         p = _oparams(width=16, height=8, samples=3, depth=4, num_spheres=ns, light_index=light, seed=5, flags=flags)
         film, _ = fr.render_pass(p, sph, mat, env=env)
-        fb = er.render_frame(p, sph, mat, env=env)[0]
+        fb = mr.render_frame(p, sph, mat, env=env)[0]
         assert film.dtype == F and film.shape == fb.shape == (3, 128)
         with np.errstate(invalid="ignore"):
             _bits_equal(np.clip(film, F(0), F(1)), fb)

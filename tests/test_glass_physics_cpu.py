@@ -1,4 +1,4 @@
-"""CPU-only: the NumPy restatements of the material renderer (tests/materials_ref.py, nee_ref.py, lights_ref.py) against an expectation
+"""CPU-only: the NumPy restatement of the material renderer (tests/materials_ref.py: plain, APT_FLAG_NEE, a light table) against an expectation
 tree that shares no text with them (tests/physics_ref.py), in the APT_MAT_SPEC / APT_MAT_REFR branches.
 
 The bitwise tests tie the kernels to the restatements; this file ties the restatements to the physics: Snell's law, which index ratio
@@ -20,7 +20,9 @@ Teeth (test_mutant_is_rejected; box9, depth 7, plain, N = 16384): the largest |z
     probability 0.5, / P    102.3                       refraction weight Tr / P   156.4
     exit cosine from inside 264.8                       index ratios swapped      1598
     skip rule outward = into 2513                       sign of the normal term   2513
-The requirement is |z| >= 10, twice the cap, or a non-finite colour.
+The requirement is |z| >= 10, twice the cap, or a non-finite colour.  The restatement is one loop for every light mode, so one mutant
+of each kind is also run with APT_FLAG_NEE and with a light table (same scene, depth and N): sign of the normal term 2513 / 2513,
+refraction weight Tr / P 156.4 / 156.4, skip rule 2513 / 2513 -- the plain figures, the rays being those of the glass and the mirror.
 Total internal reflection not detected (cos2t < -9) is different: the square root of a negative number becomes the direction, the next
 segment hits nothing, and the path ends with the colour it had -- finite.  In box8 and box9 a ray that meets total internal reflection
 is trapped in a ball that emits nothing, so the mutant returns the unmodified colours (asserted below) and no check on colours can
@@ -35,7 +37,6 @@ import pytest
 
 import lights_ref as lr
 import materials_ref as mr
-import nee_ref as nr
 import physics_ref as ph
 
 N = 16384
@@ -68,13 +69,8 @@ def _tree(name, depth):
 def _restated(sc, mode, depth, materials_ref=mr):
     """-> (L float32 [3][16 N], bad) of the restatement of `mode`: plain, rr, nee or lights."""
     a = (ph.copies(_rays16(), N), sc.table, sc.materials, sc.ns, depth, EPS, RENDER_SEED, np.arange(16 * N, dtype=np.uint64))
-    if mode == "plain":
-        return materials_ref.trace(*a)
-    if mode == "rr":
-        return materials_ref.trace(*a, 2)
-    if mode == "nee":
-        return nr.trace(*a, light=LIGHT, nee=True)[:2]
-    return lr.trace(*a, lr.build_table(sc.table, sc.ns, TABLE_LIGHTS))[:2]
+    kw = {"plain": {}, "rr": dict(rr_start=2), "nee": dict(light=LIGHT, nee=True), "lights": dict(table=lr.build_table(sc.table, sc.ns, TABLE_LIGHTS))}[mode]
+    return materials_ref.trace(*a, gloss=False, **kw)[:2]
 
 
 def test_the_rays_are_what_they_are_said_to_be():
@@ -158,13 +154,20 @@ def _mutant(old, new):
     return mod
 
 
-@pytest.mark.parametrize("what", list(MUTANTS))
-def test_mutant_is_rejected(what):
+# every mutant in the plain mode; one of each kind -- a direction, a weight, the skip rule -- with APT_FLAG_NEE and with a light table
+# too: the loop is one, so a mutant of it is a mutant of what every light mode runs
+MUTANT_CASES = [pytest.param(what, "plain", id=what) for what in MUTANTS]
+MUTANT_CASES += [pytest.param(what, mode, id="%s-%s" % (what, mode)) for what in ("sign of the normal term", "refraction weight Tr / P", "skip rule: outward = into")
+                 for mode in ("nee", "lights")]
+
+
+@pytest.mark.parametrize("what,mode", MUTANT_CASES)
+def test_mutant_is_rejected(what, mode):
     tir = what.startswith("total internal")
     name = "box8_glow" if tir else "box9"
-    L, _ = _restated(_scene(name), "plain", 7, _mutant(*MUTANTS[what]))
+    L, _ = _restated(_scene(name), mode, 7, _mutant(*MUTANTS[what]))
     c = ph.compare(L, _tree(name, 7), N)
-    print("%-40s finite %s  max |z| %.1f at %s  all-equal error %.2e at %s" % (what, c["finite"], c["zmax"], c["z_at"], c["exact"], c["exact_at"]))
+    print("%-40s %-6s finite %s  max |z| %.1f at %s  all-equal error %.2e at %s" % (what, mode, c["finite"], c["zmax"], c["z_at"], c["exact"], c["exact_at"]))
     assert not ph.agrees(c)
     if not tir:
         assert not c["finite"] or c["zmax"] >= MUTANT_Z

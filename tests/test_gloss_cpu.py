@@ -1,5 +1,5 @@
-"""CPU-only: the rough-metal material (include/render_mi355x.h GLOSS, APT_FLAG_GLOSS) -- the restatement tests/gloss_ref.py against the
-three existing restatements bit for bit where no gloss word is in play, against the float64 expectation of tests/gloss_physics.py (which
+"""CPU-only: the rough-metal material (include/render_mi355x.h GLOSS, APT_FLAG_GLOSS) -- the restatement tests/materials_ref.py with
+APT_FLAG_GLOSS against itself without the flag, bit for bit, where no gloss word is in play, against the float64 expectation of tests/gloss_physics.py (which
 shares no text with it) where one is, the agreement of its three light modes, its near-mirror limit, and the host helpers.
 
 The physics rule is tests/physics_ref.py's: 16384 copies of each ray, |mean - expectation| <= 5 standard errors per ray and channel,
@@ -12,10 +12,8 @@ import numpy as np
 import pytest
 
 import gloss_physics as gp
-import gloss_ref as gr
 import lights_ref as lr
 import materials_ref as mr
-import nee_ref as nr
 import physics_ref as ph
 
 F = np.float32
@@ -39,33 +37,33 @@ def _bits_equal(a, b):
 
 # ---- the restatement against the existing ones ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("scene", ["demo9", "gen1030"])
-def test_without_gloss_words_it_is_the_three_existing_restatements(apt, scene, oracle):
+def test_without_gloss_words_the_flag_changes_nothing_in_the_three_light_modes(apt, scene, oracle):
     if scene == "demo9":
         sph, mat, ns, light, lights, (w, h) = *lr.demo_two_lights(apt.gen_data), 7, [7, 6], (12, 8)
     else:
         sph, mat, ns, idx = lr.sixteen_lamps(apt.gen_data)
         light, lights, (w, h) = ns - 1, [ns - 1, idx[5]], (8, 6)
-    assert gr.flags_of(mat) == 0
+    assert mr.flags_of(mat) == 0
     table = lr.build_table(sph, ns, lights)
     for depth in range(1, 9):
         rr = 0 if depth == 1 else 1 + depth % 3
         rays = oracle.gen_rays_counter(oracle.make_params(w, h, 1, depth=depth, num_spheres=ns, seed=depth))
         paths = np.arange(rays.shape[1], dtype=np.uint64)
-        a = (rays, sph, mat, ns, depth, EPS, depth, paths, rr)
-        want = {"plain": mr.trace(*a)[0], "nee": nr.trace(*a, light=light, nee=True)[0], "table": lr.trace(*a[:8], table, rr)[0]}
-        for flag in (False, True):                                        # the flag changes nothing on such a table
-            assert _bits_equal(gr.trace(*a, gloss=flag)[0], want["plain"]), (depth, flag)
-            assert _bits_equal(gr.trace(*a, light=light, nee=True, gloss=flag)[0], want["nee"]), (depth, flag)
-            assert _bits_equal(gr.trace(*a, table=table, gloss=flag)[0], want["table"]), (depth, flag)
+        a = (rays, sph, mat, ns, depth, EPS, depth, paths)
+        for kw in ({}, dict(light=light, nee=True), dict(table=table)):    # the flag changes nothing on such a table
+            without = mr.trace(*a, rr_start=rr, gloss=False, **kw)
+            with_flag = mr.trace(*a, rr_start=rr, gloss=True, **kw)
+            assert _bits_equal(with_flag[0], without[0]), (depth, kw)
+            assert np.array_equal(with_flag[1], without[1]) and with_flag[2] == without[2] > 0
 
 
 def test_a_float64_intermediate_is_refused():
     d = [np.zeros(4, F), np.zeros(4, F), -np.ones(4, F)]
     nl = [np.zeros(4, F), np.zeros(4, F), np.ones(4, F)]
     u = np.full(4, 0.25, F)
-    gr.gloss_sample(d, nl, np.full(4, 0.5, F), u, u)
+    mr.gloss_sample(d, nl, np.full(4, 0.5, F), u, u)
     with pytest.raises(AssertionError):
-        gr.gloss_sample(d, nl, np.full(4, 0.5, np.float64), u, u)
+        mr.gloss_sample(d, nl, np.full(4, 0.5, np.float64), u, u)
 
 
 # ---- the restatement against physics --------------------------------------------------------------------------------------------------
@@ -80,7 +78,7 @@ class Physics:
     def trace(self, name, mode, rr):
         sc = self.scenes[name]
         kw = dict(light=LIGHT, nee=True) if mode == "nee" else (dict(table=lr.build_table(sc.table, sc.ns, TABLE_LIGHTS)) if mode == "table" else {})
-        L, bad, _ = gr.trace(self.rays, sc.table, sc.materials, sc.ns, gp.DEPTH, EPS, SEED, self.paths, 1 if rr else 0, **kw)
+        L, bad, _ = mr.trace(self.rays, sc.table, sc.materials, sc.ns, gp.DEPTH, EPS, SEED, self.paths, rr_start=1 if rr else 0, **kw)
         assert not bad.any()
         return L
 
@@ -128,14 +126,14 @@ def test_plain_nee_and_table_agree_in_the_demo_scene(apt, oracle):
     sph = apt.gen_data.with_lamp(sph, 9, 7)
     sph[:90].reshape(10, 9)[4:7, 6] = [F(3.0), F(6.0), F(9.0)]         # the gloss ball glows too: the table's second light
     ns, w, h, s = 9, 32, 24, 2
-    assert gr.flags_of(mat) == gr.FLAG_GLOSS and (np.asarray(mat)[6] & 0xFF) == gr.GLOSS
+    assert mr.flags_of(mat) == mr.FLAG_GLOSS and (np.asarray(mat)[6] & 0xFF) == mr.GLOSS
     table = lr.build_table(sph, ns, [7, 6])
     px = {"plain": [], "nee": [], "table": []}
     for seed in (1, 2, 3):
         rays = oracle.gen_rays_counter(oracle.make_params(w, h, s, depth=5, num_spheres=ns, seed=seed))
         a = (rays, sph, mat, ns, 5, EPS, seed, np.arange(rays.shape[1], dtype=np.uint64))
         for mode, kw in (("plain", {}), ("nee", dict(light=7, nee=True)), ("table", dict(table=table))):
-            L, bad, _ = gr.trace(*a, **kw)
+            L, bad, _ = mr.trace(*a, **kw)
             assert not bad.any()
             px[mode].append(L.astype(np.float64).reshape(3, w * h, 4 * s).mean(axis=2))
     px = {k: np.concatenate(v, axis=1) for k, v in px.items()}
@@ -168,7 +166,7 @@ def test_q_of_one_is_a_mirror():
     keep = cos > 0.05
     d, nl = d[:, keep].astype(F), nl[:, keep]
     u1, u2 = mr.uniforms(mr.mat_key(5, np.arange(d.shape[1], dtype=np.uint64)), 0)
-    newd, g, up = gr.gloss_sample(list(d), list(nl), np.full(d.shape[1], 2.0 ** -16, F), u1, u2)
+    newd, g, up = mr.gloss_sample(list(d), list(nl), np.full(d.shape[1], 2.0 ** -16, F), u1, u2)
     dn = (d.astype(np.float64) * nl).sum(axis=0)
     mirror = d.astype(np.float64) - 2.0 * dn * nl
     dev = np.abs(np.array(newd, dtype=np.float64) - mirror).max(axis=0)
@@ -183,12 +181,12 @@ def test_q_of_one_is_a_mirror():
 # ---- host helpers ---------------------------------------------------------------------------------------------------------------------
 def test_gloss_words_and_flags(apt):
     gd, L = apt.gen_data, apt._lib.lib()
-    assert apt._lib.APT_FLAG_GLOSS == 64 == gr.FLAG_GLOSS and apt._lib.MAT_GLOSS == 3 == gr.GLOSS and apt.APT_FLAG_GLOSS == 64
-    assert gd.gloss(0.5) == 3 | (32768 << 8) == gr.word(32768) == gp.gloss_word(0.5)
+    assert apt._lib.APT_FLAG_GLOSS == 64 == mr.FLAG_GLOSS and apt._lib.MAT_GLOSS == 3 == mr.GLOSS and apt.APT_FLAG_GLOSS == 64
+    assert gd.gloss(0.5) == 3 | (32768 << 8) == mr.word(32768) == gp.gloss_word(0.5)
     assert gd.gloss(0.2) == gp.gloss_word(0.2) and (gd.gloss(0.2) >> 8) == 13107
     assert gd.gloss(0.0) == 3 | (1 << 8) and gd.gloss(-1) == 3 | (1 << 8) and gd.gloss(1.0) == gd.gloss(7.0) == 3 | (65535 << 8)
     assert gd.gloss(1.0) >> 24 == 0
-    flags = lambda t: (gd.materials_flags(np.array(t, dtype=np.int64)), gr.flags_of(np.array(t, dtype=np.int64)))
+    flags = lambda t: (gd.materials_flags(np.array(t, dtype=np.int64)), mr.flags_of(np.array(t, dtype=np.int64)))
     assert flags([1, 0, 2]) == (0, 0)
     assert flags([1, gd.gloss(0.3), 2]) == (64, 64)
     assert flags([1, 3, 2]) == (0, 0)                                     # q == 0
@@ -201,7 +199,7 @@ def test_gloss_words_and_flags(apt):
     assert L.apt_materials_flags_host(None, ctypes.c_uint32(5)) == 0
     one = (ctypes.c_uint32 * 1)(gd.gloss(0.5))
     assert L.apt_materials_flags_host(one, ctypes.c_uint32(0)) == 0 and L.apt_materials_flags_host(one, ctypes.c_uint32(1)) == 64
-    code, alpha = gr.decode([gd.gloss(0.5), 3, 1, 3 | (1 << 8) | (1 << 24), 4 | (9 << 8)], True)
+    code, alpha = mr.decode([gd.gloss(0.5), 3, 1, 3 | (1 << 8) | (1 << 24), 4 | (9 << 8)], True)
     assert code.tolist() == [3, 15, 1, 15, 15] and alpha[0] == F(0.5)
     sph, mat = gd.gen_spheres_materials(gloss=0.25)
     sph0, mat0 = gd.gen_spheres_materials()

@@ -1,7 +1,7 @@
 """GPU: the movable camera of the material renderer (include/render_mi355x.h "camera").
 Pinned to the code that exists -- apt_camera_default_host's record set gives the no-camera launch bit for bit, and aperture 0 gives the
 pinhole whatever `focus` holds --, then bit for bit against the NumPy restatement tests/camera_ref.py (rays, and frames through
-materials_ref / nee_ref / lights_ref) for look-at cameras with and without a lens on all three scene forms, fused against buffers, and a
+materials_ref) for look-at cameras with and without a lens on all three scene forms, fused against buffers, and a
 check that the lens blurs what is out of focus by the thin-lens circle of confusion, which depends on neither."""
 import ctypes
 import math
@@ -12,7 +12,6 @@ import pytest
 import camera_ref as cr
 import lights_ref as lr
 import materials_ref as mr
-import nee_ref as nr
 
 pytestmark = pytest.mark.gpu
 MODES = ["plain", "nee", "table"]
@@ -73,12 +72,7 @@ class Scene:
         """The restatement's path colours for `rays` under `mode`."""
         rr = (p.rr_start or 3) if p.flags & 2 else 0
         args = (rays, self.sph, self.mat, self.ns, p.depth, p.eps, p.seed, paths)
-        if mode == "plain":
-            L, bad = mr.trace(*args, rr)
-        elif mode == "nee":
-            L, bad, _ = nr.trace(*args, rr, light=self.light, nee=True)
-        else:
-            L, bad, _ = lr.trace(*args, self.table, rr)
+        L, bad, _ = mr.trace(*args, rr_start=rr, light=self.light, nee=mode == "nee", table=self.table if mode == "table" else None, gloss=False)
         assert not bad.any()
         return L
 

@@ -234,7 +234,7 @@ def _mat_frame(apt, name, mode, s, rng=None, grid=False, cam=None):
 @pytest.mark.parametrize("s", pr.MAT_SAMPLES)
 @pytest.mark.parametrize("mode", ["plain", "nee"])
 def test_material_frame_8_spheres(apt, mode, s):
-    """render_frame_mat_kernel's 8-sphere form, plain and with APT_FLAG_NEE, against materials_ref / nee_ref."""
+    """render_frame_mat_kernel's 8-sphere form, plain and with APT_FLAG_NEE, against materials_ref."""
     want = _mat_want("diff8", mode, s)
     for rng in RANGES:
         _assert_same(_mat_frame(apt, "diff8", mode, s, rng), _cut(want, rng), (mode, s, rng))
@@ -242,7 +242,7 @@ def test_material_frame_8_spheres(apt, mode, s):
 
 @pytest.mark.parametrize("s", pr.MAT_SAMPLES)
 def test_material_frame_light_table_by_tiles_and_through_the_grid(apt, s):
-    """The demo scene with the lamp and a light table, against lights_ref: the tile form and the grid form, the same frame."""
+    """The demo scene with the lamp and a light table, against materials_ref: the tile form and the grid form, the same frame."""
     want = _mat_want("demo9lamp", "table", s)
     for grid in (False, True):
         for rng in RANGES:

@@ -1,6 +1,6 @@
 """GPU: the environment (include/render_mi355x.h "environment": a sky and a sampled sun for the material renderer) through the C-ABI.
 
-  frames    bit for bit against the NumPy restatement tests/env_ref.py with the status word clean and the trace counter equal to the
+  frames    bit for bit against the NumPy restatement tests/materials_ref.py with the status word clean and the trace counter equal to the
             restatement's count of segments (the lights' and the sun's shadow segments included): the three scene forms -- the open
             8-sphere scene (SGPRs), 40 open spheres (LDS tiles), 220 open spheres behind the grid with grid image == tile image -- x
             {plain, APT_FLAG_NEE, a light table} x {sun sampled, not}, each over samples 1 / 4 / 8 / 9 (both groups and the n % 8
@@ -10,7 +10,7 @@
             bit, in all three forms with no camera and a gloss-free table: the environment kernels are always the general-camera,
             gloss instantiations, and this is what ties them to the kernels they stand in for.
   physics   the rays of tests/env_physics.py (float64 expectations from geometry alone) through render_paths in all three forms:
-            the expectations hold, and the same buffers equal env_ref bit for bit.
+            the expectations hold, and the same buffers equal the restatement bit for bit.
   grid      a grid that is not the scene's still writes nothing and reports APT_DEV_GRID_MISMATCH.
 
 On the parent every test here fails: the entries do not exist."""
@@ -21,7 +21,6 @@ import pytest
 
 import camera_ref as cr
 import env_physics as ep
-import env_ref as er
 import materials_ref as mr
 
 pytestmark = pytest.mark.gpu
@@ -104,13 +103,13 @@ class Scene:
         return fb.cpu().numpy(), u8.cpu().numpy(), traced
 
     def frame_ref(self, p, mode, env, gloss=True, rays=None):
-        """env_ref's frame for the launch `p` and the record `env` (the grid changes no image: it is not part of the key)."""
+        """materials_ref's frame for the launch `p` and the record `env` (the grid changes no image: it is not part of the key)."""
         key = (p.width, p.height, p.samples, p.depth, p.seed, mode, p.flags & (2 | 32 | 64), p.rr_start, rays is not None, gloss,
                None if env is None else bytes(env))
         if key not in self.ref:
             from oracle import oracle
-            fb, u8, bad, seg = er.render_frame(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat[gloss],
-                                               env=None if env is None else er.Env.from_ctypes(env),
+            fb, u8, bad, seg = mr.render_frame(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat[gloss],
+                                               env=None if env is None else mr.Env.from_ctypes(env),
                                                table=self.table if mode == "table" else None, rays=rays)
             assert not bad.any()
             self.ref[key] = (fb, u8, seg)
@@ -342,7 +341,7 @@ class Physics:
         if key not in self.want:
             sc, _ = self.scene(case, ns, False)
             kw = dict(light=case.light, nee=True) if mode == "nee" else (dict(table=sc.table) if mode == "table" else {})
-            L, bad, _ = er.trace(case.rays(), sc.sph, sc.mat[False], ns, case.depth, 1e-4, ep.SEED, case.paths(), er.Env.from_ctypes(self.env(case)),
+            L, bad, _ = mr.trace(case.rays(), sc.sph, sc.mat[False], ns, case.depth, 1e-4, ep.SEED, case.paths(), mr.Env.from_ctypes(self.env(case)),
                                  gloss=False, **kw)
             assert not bad.any()
             self.want[key] = L

@@ -20,7 +20,6 @@ import numpy as np
 import pytest
 
 import camera_ref as cr
-import env_ref as er
 import film_ref as fr
 import materials_ref as mr
 
@@ -130,7 +129,7 @@ class Scene:
         if key not in self.ref:
             from oracle import oracle
             rays = None if cam is None else (lambda seed: cr.rays(cr.from_ctypes(cam), p.width, p.height, p.samples, seed=seed))
-            planes, seg = fr.render_pass(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat, env=None if env is None else er.Env.from_ctypes(env),
+            planes, seg = fr.render_pass(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat, env=None if env is None else mr.Env.from_ctypes(env),
                                          table=self.table if mode == "table" else None, pass_index=k, rays=rays)
             planes.setflags(write=False)
             self.ref[key] = (planes, seg)

@@ -15,7 +15,6 @@ import pytest
 
 import lights_ref as lr
 import materials_ref as mr
-import nee_ref as nr
 import physics_ref as ph
 
 pytestmark = pytest.mark.gpu
@@ -69,13 +68,8 @@ class Work:
         key = (name, mode, rr)
         if key not in self.want:
             sc = self.scene(name)
-            a = (self.rays, sc.table, sc.materials, sc.ns, DEPTH, EPS, RENDER_SEED, self.paths, 2 if rr else 0)
-            if mode == "plain":
-                L, bad = mr.trace(*a)
-            elif mode == "nee":
-                L, bad, _ = nr.trace(*a, light=LIGHT, nee=True)
-            else:
-                L, bad, _ = lr.trace(*a[:8], lr.build_table(sc.table, sc.ns, TABLE_LIGHTS), a[8])
+            kw = {"plain": {}, "nee": dict(light=LIGHT, nee=True), "lights": dict(table=lr.build_table(sc.table, sc.ns, TABLE_LIGHTS))}[mode]
+            L, bad, _ = mr.trace(self.rays, sc.table, sc.materials, sc.ns, DEPTH, EPS, RENDER_SEED, self.paths, rr_start=2 if rr else 0, gloss=False, **kw)
             assert not bad.any()
             self.want[key] = L
         return self.want[key]

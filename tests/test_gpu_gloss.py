@@ -1,5 +1,5 @@
 """GPU: the rough-metal material (include/render_mi355x.h GLOSS, APT_FLAG_GLOSS) through the C-ABI, bit for bit against the NumPy
-restatement tests/gloss_ref.py with the status word clean -- frames of every scene form, light mode and accumulation arm, a camera
+restatement tests/materials_ref.py with the status word clean -- frames of every scene form, light mode and accumulation arm, a camera
 with a lens, a pixel range; hand-made rays in buffer mode; the flag's rules -- and against the float64 expectation of
 tests/gloss_physics.py (tests/golden/gloss_expectations.json), which shares no text with either.
 
@@ -12,7 +12,6 @@ import pytest
 
 import camera_ref as cr
 import gloss_physics as gp
-import gloss_ref as gr
 import lights_ref as lr
 import materials_ref as mr
 import physics_ref as ph
@@ -89,12 +88,12 @@ class Scene:
         return fb.cpu().numpy(), u8.cpu().numpy()
 
     def frame_ref(self, p, mode, rays=None):
-        """gloss_ref's frame for the launch `p` (the grid changes no image: its flag and address are not part of the key)."""
+        """materials_ref's frame for the launch `p` (the grid changes no image: its flag and address are not part of the key)."""
         key = (p.width, p.height, p.samples, p.depth, p.seed, mode, p.flags & (2 | 32 | 64), p.rr_start, rays is not None)
         if key not in self.ref:
             from oracle import oracle
-            fb, u8, bad = gr.render_frame(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat,
-                                          table=self.table if mode == "table" else None, rays=rays)
+            fb, u8, bad, _ = mr.render_frame(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat,
+                                             table=self.table if mode == "table" else None, rays=rays)
             assert not bad.any()
             self.ref[key] = (fb, u8)
         return self.ref[key]
@@ -130,7 +129,7 @@ def _scene(apt, name):
             mirrors = np.nonzero(mat == mr.SPEC)[0][::2]
             assert mirrors.size > 100
             for i in mirrors:
-                mat[i] = gr.word(600 + (int(i) * 977) % 64000)
+                mat[i] = mr.word(600 + (int(i) * 977) % 64000)
             _scenes[name] = Scene(apt, sph, mat, ns, [ns - 1, idx[5]], ns - 1, grid=True)
         assert _scenes[name].mat_flags == apt.APT_FLAG_GLOSS
     return _scenes[name]
@@ -242,7 +241,7 @@ def test_hand_made_rays_in_buffer_mode(apt, ns, mode):
     p = sc.params(16, 16, 1, 6, mode=mode, rr=True, seed=9)
     assert p.num_paths == n
     kw = dict(light=7, nee=True) if mode == "nee" else (dict(table=sc.table) if mode == "table" else {})
-    want, bad, _ = gr.trace(rays, sc.sph, sc.mat, ns, 6, 1e-4, 9, paths, 2, **kw)
+    want, bad, _ = mr.trace(rays, sc.sph, sc.mat, ns, 6, 1e-4, 9, paths, rr_start=2, **kw)
     assert not bad.any()
     # some grazing lanes draw a direction below the horizon and end there: their colour is what the ball itself emits
     f32 = np.float32
@@ -251,7 +250,7 @@ def test_hand_made_rays_in_buffer_mode(apt, ns, mode):
     ln = np.sqrt(mr.dot(*nrm, *nrm))
     u1, u2 = mr.uniforms(mr.mat_key(9, paths), 0)
     with np.errstate(all="ignore"):
-        _, _, up = gr.gloss_sample(list(rays[3:]), [x / ln for x in nrm], np.full(n, (int(sc.mat[6]) >> 8) * 2.0 ** -16, f32), u1, u2)
+        _, _, up = mr.gloss_sample(list(rays[3:]), [x / ln for x in nrm], np.full(n, (int(sc.mat[6]) >> 8) * 2.0 ** -16, f32), u1, u2)
     ended = ~up[256:512]
     assert 0 < ended.sum() < 256
     assert (want[:, 256:512][:, ended] == geo[4:7, 6][:, None]).all()
@@ -285,7 +284,7 @@ def test_gloss_words_need_the_flag_and_malformed_ones_are_bad(apt, name):
     for s_ in (1, 8):
         sc.frame(sc.params(16, 16, s_, 3, seed=1, gloss=0), "plain", check=False)      # well-formed words, no flag: as before the flag existed
         _bad_material(apt)
-    for word in (3, gr.word(700) | (1 << 24), 4 | (700 << 8)):             # q == 0, bit 24, a low byte of 4
+    for word in (3, mr.word(700) | (1 << 24), 4 | (700 << 8)):             # q == 0, bit 24, a low byte of 4
         mat = sc.mat.copy()
         mat[2] = word                                                      # the back wall: every frame hits it
         sc.frame(sc.params(16, 16, 8, 3, seed=1), "plain", mat=_dev(mat), check=False)
@@ -337,7 +336,7 @@ class Physics:
         if (name, mode, rr) not in self.want:
             sc = self.scene(name, False)
             kw = dict(light=LIGHT, nee=True) if mode == "nee" else (dict(table=sc.table) if mode == "table" else {})
-            L, bad, _ = gr.trace(self.rays, sc.sph, sc.mat, sc.ns, gp.DEPTH, 1e-4, 1, self.paths, 1 if rr else 0, **kw)
+            L, bad, _ = mr.trace(self.rays, sc.sph, sc.mat, sc.ns, gp.DEPTH, 1e-4, 1, self.paths, rr_start=1 if rr else 0, **kw)
             assert not bad.any()
             self.want[name, mode, rr] = L
         return self.want[name, mode, rr]

@@ -1,13 +1,13 @@
 """GPU: a light table in the material renderer (the *_lights entries, include/render_mi355x.h "several lights").
 Pinned to the code that exists -- a one-light table against the same launch with APT_FLAG_NEE, bit for bit --, then bit for bit against
-the NumPy restatement tests/lights_ref.py with several lights on all three scene forms (8 spheres in SGPRs, LDS tiles, the uniform
+the NumPy restatement tests/materials_ref.py with several lights on all three scene forms (8 spheres in SGPRs, LDS tiles, the uniform
 grid), against a closed form that depends on neither, and statistically against the renderer without sampling: same expectation, less
 variance than sampling no lamp or one lamp of two."""
 import numpy as np
 import pytest
 
 import lights_ref as lr
-import nee_ref as nr
+import materials_ref as mr
 
 pytestmark = pytest.mark.gpu
 
@@ -169,7 +169,7 @@ def test_frame_bitwise(apt, name, s_, depth, rr, w, h):
     sc = _scene(apt, name)
     p = sc.params(apt, w, h, s_, depth, rr=rr, seed=11 + s_)
     fb, u8 = sc.frame(apt, p)
-    fb_w, u8_w, bad = lr.render_frame(_oracle_params(p), sc.sph, sc.mat, sc.table)
+    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat, table=sc.table)
     assert not bad.any()
     _same(fb, u8, fb_w, u8_w)
     off = sc.frame(apt, p, lights=False)
@@ -189,7 +189,7 @@ def test_frame_bitwise_16_lamps_by_tiles_and_through_the_grid(apt, s_, depth, rr
     fb_g, u8_g = sc.frame(apt, p)
     fb_t, u8_t = sc.frame(apt, sc.params(apt, 24, 16, s_, depth, rr=rr, grid=False))
     _same(fb_g, u8_g, fb_t, u8_t)                         # grid form == tile form
-    fb_w, u8_w, bad = lr.render_frame(_oracle_params(p), sc.sph, sc.mat, sc.table)
+    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat, table=sc.table)
     assert not bad.any()
     _same(fb_t, u8_t, fb_w, u8_w)
     if depth > 1:
@@ -203,7 +203,7 @@ def test_frame_mid_image_pixel_range(apt, name, grid, b, c):
     w, h = (48, 32) if name != "big16" else (24, 16)
     p = sc.params(apt, w, h, 16, 5, seed=2, grid=grid, flags=apt.APT_FLAG_RETIRE)      # RETIRE: accepted, changes nothing
     fb, u8 = sc.frame(apt, p, pixel_begin=b, pixel_count=c)
-    fb_w, u8_w, _ = lr.render_frame(_oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, sc.table, b, c)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, table=sc.table, pixel_begin=b, pixel_count=c)
     _same(fb, u8, fb_w, u8_w)
 
 
@@ -214,7 +214,7 @@ def test_paths_bitwise_with_ranges(apt, name, grid):
     p = sc.params(apt, 16, 16, 4, 8, rr=True, seed=9, grid=grid)
     rays = oracle.gen_rays_counter(_oracle_params(p))
     n = rays.shape[1]
-    want, bad, segments = lr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), sc.table, 2)
+    want, bad, segments = mr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=2, table=sc.table, gloss=False)
     assert not bad.any()
     with apt.render.TraceCounter() as tc:
         got = sc.paths(apt, p, rays)
@@ -229,7 +229,7 @@ def test_paths_bitwise_with_ranges(apt, name, grid):
     assert _bits_equal(got, want[:, b:b + c])
     for depth in (1, 2, 5):                               # no roulette, the other depths
         q = sc.params(apt, 16, 16, 4, depth, seed=9, grid=grid)
-        want, _, _ = lr.trace(rays, sc.sph, sc.mat, sc.ns, depth, q.eps, q.seed, np.arange(n, dtype=np.uint64), sc.table)
+        want, _, _ = mr.trace(rays, sc.sph, sc.mat, sc.ns, depth, q.eps, q.seed, np.arange(n, dtype=np.uint64), table=sc.table, gloss=False)
         got = sc.paths(apt, q, rays)
         assert _bits_equal(got, want), depth
         if depth == 1:
@@ -275,7 +275,7 @@ def test_a_light_we_are_inside_of_is_gathered_by_the_next_hit(apt):
     from oracle import oracle
     sph, mat, ns = lr.furnace(True)
     sc = Scene(apt, sph, mat, ns)
-    assert lr.Table(sc.table).idx.tolist() == [0, 1]
+    assert mr.Table(sc.table).idx.tolist() == [0, 1]
     p = apt.make_params(128, 64, 4, depth=4, num_spheres=ns, eps=0.5, seed=21, light_index=-1)
     rays = oracle.gen_rays_counter(_oracle_params(p))
     on, off = sc.paths(apt, p, rays).astype(np.float64), sc.paths(apt, p, rays, lights=False).astype(np.float64)
@@ -365,7 +365,7 @@ def test_a_table_for_another_scene_renders_nothing_and_is_reported(apt, name):
     sc = _scene(apt, name)
     other = apt.gen_data.build_lights(np.concatenate([sc.sph[:10 * sc.ns].reshape(10, sc.ns), np.ones((10, 1), np.float32)], axis=1).ravel(),
                                       sc.ns + 1, [0])
-    assert lr.Table(other).ns == sc.ns + 1
+    assert mr.Table(other).ns == sc.ns + 1
     wrong_magic = sc.table.copy()
     wrong_magic[0] ^= 1
     apt.render.check_device_status()                      # nothing pending

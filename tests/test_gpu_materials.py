@@ -91,7 +91,7 @@ def test_frame_bitwise(apt, scene, s_, depth, rr):
     p = apt.make_params(48, 32, s_, depth=depth, num_spheres=ns, light_index=light, seed=11 + s_,
                         flags=apt.APT_FLAG_RR if rr else 0, rr_start=2 if rr else 0)
     fb, u8 = _frame_gpu(apt, p, sph, mat)
-    fb_w, u8_w, bad = mr.render_frame(_oracle_params(p), sph, mat)
+    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sph, mat)
     assert not bad.any()
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32)), np.argwhere(fb.view(np.uint32) != fb_w.view(np.uint32))[:5]
     assert np.array_equal(u8, u8_w)
@@ -103,7 +103,7 @@ def test_frame_bitwise_large_scene(apt, s_, depth, rr):
     p = apt.make_params(24, 16, s_, depth=depth, num_spheres=mat.size, light_index=light, seed=3,
                         flags=apt.APT_FLAG_RR if rr else 0, rr_start=1 if rr else 0)
     fb, u8 = _frame_gpu(apt, p, sph, mat)
-    fb_w, u8_w, _ = mr.render_frame(_oracle_params(p), sph, mat)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sph, mat)
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32))
     assert np.array_equal(u8, u8_w)
 
@@ -115,7 +115,7 @@ def test_frame_pixel_range_and_u8_forms(apt, scene, u8):
     p = apt.make_params(48, 32, 16, depth=5, num_spheres=mat.size, light_index=light, seed=2, flags=apt.APT_FLAG_RETIRE)
     b, c = 517, 700
     fb, got8 = _frame_gpu(apt, p, sph, mat, b, c, u8=u8)
-    fb_w, u8_w, _ = mr.render_frame(_oracle_params(p), sph, mat, b, c)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sph, mat, pixel_begin=b, pixel_count=c)
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32))
     if u8 == "misaligned":
         assert np.array_equal(got8, u8_w)
@@ -139,7 +139,7 @@ def test_paths_bitwise_with_ranges(apt, scene):
     p = apt.make_params(16, 16, 4, depth=8, num_spheres=mat.size, light_index=light, seed=9, flags=apt.APT_FLAG_RR, rr_start=3)
     rays = oracle.gen_rays_counter(_oracle_params(p))
     n = rays.shape[1]
-    want, bad = mr.trace(rays, sph, mat, mat.size, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), 3)
+    want, bad, _ = mr.trace(rays, sph, mat, mat.size, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=3, gloss=False)
     assert not bad.any()
     got = _paths_gpu(apt, p, rays, sph, mat)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
@@ -184,7 +184,7 @@ def test_paths_bitwise_handmade_rays(apt):
     sph, mat, light = _scene(apt, "demo9")
     p = apt.make_params(16, 16, 1, depth=6, num_spheres=9, light_index=light, seed=4)
     rays = _handmade_rays(p.num_paths)
-    want, _ = mr.trace(rays, sph, mat, 9, 6, p.eps, p.seed, np.arange(p.num_paths, dtype=np.uint64))
+    want, _, _ = mr.trace(rays, sph, mat, 9, 6, p.eps, p.seed, np.arange(p.num_paths, dtype=np.uint64), gloss=False)
     got = _paths_gpu(apt, p, rays, sph, mat)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 

@@ -86,7 +86,7 @@ def _generated(apt, ns, builder="host"):
 def _want_frame(sc, p, key):
     """The restatement's frame, computed once per case (it does not depend on who built the grid)."""
     if key not in _wanted:
-        fb_w, u8_w, bad = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+        fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
         assert not bad.any()
         _wanted[key] = (fb_w, u8_w)
     return _wanted[key]
@@ -157,7 +157,7 @@ def test_degenerate_grids(apt, name):
         fb, u8 = sc.frame(apt, p)
         pt = p.copy(accel=0, flags=p.flags & ~apt.APT_FLAG_GRID_SLOTS)
         _same(fb, u8, *sc.frame(apt, pt))
-        fb_w, u8_w, bad = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+        fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
         assert not bad.any()
         _same(fb, u8, fb_w, u8_w)
 
@@ -190,7 +190,7 @@ def test_paths_bitwise_with_ranges(apt):
     p = sc.params(apt, 16, 16, 4, 8, rr=True, seed=9)
     rays = oracle.gen_rays_counter(_oracle_params(p))
     n = rays.shape[1]
-    want, bad = mr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), 2)
+    want, bad, _ = mr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=2, gloss=False)
     assert not bad.any()
     got = _paths(apt, sc, p, rays)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
@@ -243,7 +243,7 @@ def test_paths_bitwise_handmade_rays(apt):
     sc = _generated(apt, 2000)
     p = sc.params(apt, 16, 16, 1, 6, seed=4)
     rays = _handmade_rays(sc, p.num_paths)
-    want, bad = mr.trace(rays, sc.sph, sc.mat, sc.ns, 6, p.eps, p.seed, np.arange(p.num_paths, dtype=np.uint64))
+    want, bad, _ = mr.trace(rays, sc.sph, sc.mat, sc.ns, 6, p.eps, p.seed, np.arange(p.num_paths, dtype=np.uint64), gloss=False)
     assert not bad.any()
     got = _paths(apt, sc, p, rays)
     diff = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
@@ -256,7 +256,7 @@ def test_frame_pixel_range_and_u8_forms(apt):
     sc = _generated(apt, 2000)
     p = sc.params(apt, 24, 16, 8, 5, seed=2, flags=apt.APT_FLAG_RETIRE)
     b, c = 117, 203
-    fb_w, u8_w, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat, b, c)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat, pixel_begin=b, pixel_count=c)
     L = apt._lib.lib()
     for off in (None, 1):                              # fb_u8 null, then one byte off a dword
         fb = torch.full((3, c), float("nan"), dtype=torch.float32, device="cuda")
@@ -280,7 +280,7 @@ def test_bad_material_code_on_a_binned_sphere_is_reported(apt):
     mat[6:base.ns - 1][base.mat[6:base.ns - 1] == mr.REFR] = 3      # every glass sphere: the coverage frame sends 14.7 % of its segments there
     sc = Scene(apt, base.sph, mat)
     p = sc.params(apt, 24, 16, 2, 6)
-    _, _, bad = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    _, _, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
     assert bad.any()
     apt.render.check_device_status()                   # nothing pending from earlier tests
     sc.frame(apt, p)

@@ -1,11 +1,11 @@
 """GPU: direct light sampling in the material renderer (APT_FLAG_NEE, include/render_mi355x.h "Direct light sampling").
-Bit for bit against the NumPy restatement tests/nee_ref.py on all three scene forms (8 spheres in SGPRs, LDS tiles, the uniform grid),
+Bit for bit against the NumPy restatement tests/materials_ref.py on all three scene forms (8 spheres in SGPRs, LDS tiles, the uniform grid),
 with the stock light and with smallpt's small lamp; and statistically against the renderer that exists -- the same launches without
 the flag: same expectation, less variance where a small light makes the plain renderer noisy."""
 import numpy as np
 import pytest
 
-import nee_ref as nr
+import materials_ref as mr
 
 pytestmark = pytest.mark.gpu
 
@@ -106,7 +106,7 @@ def test_frame_bitwise(apt, name, lamp, s_, depth, rr, w, h):
     sc = _scene(apt, name, lamp)
     p = sc.params(apt, w, h, s_, depth, rr=rr, seed=11 + s_)
     fb, u8 = sc.frame(apt, p)
-    fb_w, u8_w, bad = nr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
     assert not bad.any()
     _same(fb, u8, fb_w, u8_w)
     off = sc.frame(apt, sc.params(apt, w, h, s_, depth, nee=False, rr=rr, seed=11 + s_))
@@ -127,7 +127,7 @@ def test_frame_bitwise_1030_spheres_by_tiles_and_through_the_grid(apt, lamp, s_,
     fb_g, u8_g = sc.frame(apt, p)
     fb_t, u8_t = sc.frame(apt, sc.params(apt, 24, 16, s_, depth, rr=rr, grid=False))
     _same(fb_g, u8_g, fb_t, u8_t)                         # grid form == tile form, flag on
-    fb_w, u8_w, bad = nr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
     assert not bad.any()
     _same(fb_t, u8_t, fb_w, u8_w)
     off = sc.frame(apt, sc.params(apt, 24, 16, s_, depth, nee=False, rr=rr))
@@ -145,7 +145,7 @@ def test_the_lamp_is_binned_in_the_grid(apt):
     p = sc.params(apt, 48, 32, 8, 5, rr=True, seed=11)
     fb, u8 = sc.frame(apt, p)
     _same(fb, u8, *sc.frame(apt, sc.params(apt, 48, 32, 8, 5, rr=True, seed=11, grid=False)))
-    fb_w, u8_w, _ = nr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
     _same(fb, u8, fb_w, u8_w)
 
 
@@ -156,7 +156,7 @@ def test_frame_mid_image_pixel_range(apt, name, grid, b, c):
     w, h = (48, 32) if name != "big1030" else (24, 16)
     p = sc.params(apt, w, h, 16, 5, seed=2, grid=grid, flags=apt.APT_FLAG_RETIRE)      # RETIRE: accepted, changes nothing
     fb, u8 = sc.frame(apt, p, pixel_begin=b, pixel_count=c)
-    fb_w, u8_w, _ = nr.render_frame(_oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, b, c)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, pixel_begin=b, pixel_count=c)
     _same(fb, u8, fb_w, u8_w)
 
 
@@ -168,7 +168,7 @@ def test_paths_bitwise_with_ranges(apt, name, grid, lamp):
     p = sc.params(apt, 16, 16, 4, 8, rr=True, seed=9, grid=grid)
     rays = oracle.gen_rays_counter(_oracle_params(p))
     n = rays.shape[1]
-    want, bad, segments = nr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), 2, light=sc.light, nee=True)
+    want, bad, segments = mr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=2, light=sc.light, nee=True, gloss=False)
     assert not bad.any()
     with apt.render.TraceCounter() as tc:
         got = sc.paths(apt, p, rays)
@@ -183,7 +183,7 @@ def test_paths_bitwise_with_ranges(apt, name, grid, lamp):
     assert np.array_equal(got.view(np.uint32), want[:, b:b + c].view(np.uint32))
     for depth in (1, 2, 5):                               # no roulette, the other depths
         q = sc.params(apt, 16, 16, 4, depth, seed=9, grid=grid)
-        want, _, _ = nr.trace(rays, sc.sph, sc.mat, sc.ns, depth, q.eps, q.seed, np.arange(n, dtype=np.uint64), light=sc.light, nee=True)
+        want, _, _ = mr.trace(rays, sc.sph, sc.mat, sc.ns, depth, q.eps, q.seed, np.arange(n, dtype=np.uint64), light=sc.light, nee=True, gloss=False)
         got = sc.paths(apt, q, rays)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), depth
         if depth == 1:
@@ -202,7 +202,7 @@ def test_a_light_of_any_material_needs_no_special_case(apt):
     sc.d_sph, sc.d_mat = _dev(sc.sph), _dev(sc.mat)
     p = sc.params(apt, 48, 32, 8, 6, seed=5)
     fb, u8 = sc.frame(apt, p)
-    fb_w, u8_w, _ = nr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
     _same(fb, u8, fb_w, u8_w)
 
 

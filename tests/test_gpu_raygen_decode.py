@@ -126,7 +126,7 @@ def test_material_frame_through_the_shared_decode(apt):
                                           ctypes.c_void_p(raw.data_ptr() + off))
         apt._lib.check(rc, "apt_render_frame_materials")
         torch.cuda.synchronize()
-        fb_w, u8_w, bad = mr.render_frame(oracle.Params.from_buffer_copy(bytes(p)), sph, mat)
+        fb_w, u8_w, bad, _ = mr.render_frame(oracle.Params.from_buffer_copy(bytes(p)), sph, mat)
         assert not bad.any()
         assert np.array_equal(fb.cpu().numpy().view(np.uint32), fb_w.view(np.uint32))
         assert np.array_equal(raw[off:off + 105].cpu().numpy().reshape(35, 3), u8_w)

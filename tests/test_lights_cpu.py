@@ -1,6 +1,6 @@
 """CPU-only: the light table of the material renderer (include/render_mi355x.h "several lights") -- the host builder against its NumPy
 restatement byte for byte and against the invariants the estimator needs, the entries' refusals (no GPU needed: the checks run before
-any HIP call), the lamp helper, and the restatement tests/lights_ref.py: equal to tests/nee_ref.py bit for bit with a one-light table,
+any HIP call), the lamp helper, and the restatement tests/materials_ref.py with a table: equal to nee=True bit for bit with a one-light table,
 equal to a closed form that does not depend on the library with three lights, and with the plain renderer's expectation."""
 import ctypes
 
@@ -9,7 +9,6 @@ import pytest
 
 import lights_ref as lr
 import materials_ref as mr
-import nee_ref as nr
 
 F = np.float32
 
@@ -41,12 +40,12 @@ def test_symbols_and_status_bit(apt):
 
 def test_the_selection_stream_is_a_fourth_one():
     paths = np.arange(4096, dtype=np.uint64)
-    s1, _ = mr.uniforms(lr.light_key(7, paths), 0)
-    for other in (nr.nee_key(7, paths), mr.mat_key(7, paths), mr.rr_key(7, paths)):
+    s1, _ = mr.uniforms(mr.light_key(7, paths), 0)
+    for other in (mr.nee_key(7, paths), mr.mat_key(7, paths), mr.rr_key(7, paths)):
         o1, o2 = mr.uniforms(other, 0)
         assert not np.array_equal(s1, o1) and abs(float(np.corrcoef(s1, o1)[0, 1])) < 0.06 and abs(float(np.corrcoef(s1, o2)[0, 1])) < 0.06
     assert abs(float(s1.mean()) - 0.5) < 0.02
-    assert len({int(lr.LIGHT_SALT), int(nr.NEE_SALT), 0x6A09E667F3BCC909}) == 3
+    assert len({int(mr.LIGHT_SALT), int(mr.NEE_SALT), 0x6A09E667F3BCC909}) == 3
 
 
 def test_builder_equals_the_restatement_byte_for_byte(apt):
@@ -63,7 +62,7 @@ def test_builder_equals_the_restatement_byte_for_byte(apt):
         assert np.array_equal(got, lr.build_table(sph2, 8, ind)), ind
         t = lr.check_table_invariants(got)
         assert t.idx.tolist() == ([6, 7] if ind is None else ind)
-    p = lr.Table(gd.build_lights(sph2, 8, [0, 7, 3])).prob()
+    p = mr.Table(gd.build_lights(sph2, 8, [0, 7, 3])).prob()
     assert abs(p[0] - p[2]) <= 2.0 ** -24 and abs(p[0] - 1 / 6) < 2.0 ** -23 and abs(p[1] - 4 / 6) < 2.0 ** -23      # half by power (all sphere 7's), half uniform
     sph, _, ns, idx = lr.sixteen_lamps(apt.gen_data)
     got = gd.build_lights(sph, ns)                                          # NULL: the 16 lamps and the scene's own light
@@ -182,6 +181,7 @@ def test_lamps_helper(apt):
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("scene", ["diff8", "demo9", "lamp8"])
 def test_one_light_table_is_nee_ref_bit_for_bit(apt, scene):
+    """table=a one-light table against nee=True on that light (the mode that tests/nee_ref.py once held): the same bits."""
     from oracle import oracle
     sph, mat, ns, light = _scenes(apt)["diff8" if scene == "lamp8" else scene]
     if scene == "lamp8":
@@ -192,19 +192,19 @@ def test_one_light_table_is_nee_ref_bit_for_bit(apt, scene):
             p = oracle.make_params(16, 12, 2, depth=depth, num_spheres=ns, light_index=light, seed=3 + depth)
             rays = oracle.gen_rays_counter(p)
             paths = np.arange(rays.shape[1], dtype=np.uint64)
-            want, bad_w, seg_w = nr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr, light=light, nee=True)
-            got, bad, seg = lr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, table, rr)
+            want, bad_w, seg_w = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr_start=rr, light=light, nee=True, gloss=False)
+            got, bad, seg = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr_start=rr, table=table, gloss=False)
             assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), (depth, rr)
             assert np.array_equal(bad, bad_w) and seg == seg_w
-    p = oracle.make_params(8, 8, 1, depth=4, num_spheres=ns, light_index=light, seed=1, flags=nr.FLAG_NEE)
-    fb, u8, _ = lr.render_frame(p, sph, mat, table)
-    fb_w, u8_w, _ = nr.render_frame(p, sph, mat)
+    p = oracle.make_params(8, 8, 1, depth=4, num_spheres=ns, light_index=light, seed=1, flags=mr.FLAG_NEE)
+    fb, u8, _, _ = mr.render_frame(p, sph, mat, table=table)
+    fb_w, u8_w, _, _ = mr.render_frame(p, sph, mat)
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32)) and np.array_equal(u8, u8_w)
 
 
 def test_the_standing_sphere_is_never_sampled(apt):
     """The white furnace (albedo 0.5, emission 0.25 everywhere inside one sphere) listed as the only light: S is false at every bounce
-    (we stand on it), so every colour is materials_ref's, bit for bit, and exactly 0.5 (1 - 2^-D)."""
+    (we stand on it), so every colour is the plain renderer's, bit for bit, and exactly 0.5 (1 - 2^-D)."""
     from oracle import oracle
     sph, mat, _ = lr.furnace(False)
     table = apt.gen_data.build_lights(sph, 1)
@@ -212,8 +212,8 @@ def test_the_standing_sphere_is_never_sampled(apt):
         p = oracle.make_params(16, 12, 2, depth=depth, num_spheres=1, light_index=0, seed=5, eps=0.5)
         rays = oracle.gen_rays_counter(p)
         paths = np.arange(rays.shape[1], dtype=np.uint64)
-        got, _, seg = lr.trace(rays, sph, mat, 1, depth, p.eps, p.seed, paths, table)
-        want, _ = mr.trace(rays, sph, mat, 1, depth, p.eps, p.seed, paths)
+        got, _, seg = mr.trace(rays, sph, mat, 1, depth, p.eps, p.seed, paths, table=table, gloss=False)
+        want, _, _ = mr.trace(rays, sph, mat, 1, depth, p.eps, p.seed, paths, gloss=False)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and seg == depth * paths.size
         assert (got == F(0.5 * (1 - 2.0 ** -depth))).all()
 
@@ -227,7 +227,7 @@ def test_closed_form_lambertian_point_under_three_lights(apt, j):
     rays, sph, mat, ns, paths, want = lr.three_lights_point(j, per)
     table = lr.build_table(sph, ns, [1, 2, 3])
     assert np.array_equal(table, apt.gen_data.build_lights(sph, ns))
-    L, bad, _ = lr.trace(rays, sph, mat, ns, 2, 1e-4, 7, paths, table)
+    L, bad, _ = mr.trace(rays, sph, mat, ns, 2, 1e-4, 7, paths, table=table, gloss=False)
     assert not bad.any()
     for ch in range(3):
         x = L[ch].astype(np.float64)
@@ -240,7 +240,7 @@ def test_closed_form_plain_renderer_agrees_too():
     """The plain renderer on the same scene has the same expectation (with far more noise): the closed form is the scene's."""
     per = 1 << 16
     rays, sph, mat, ns, paths, want = lr.three_lights_point(2, per)
-    L, _ = mr.trace(rays, sph, mat, ns, 2, 1e-4, 7, paths)
+    L, _, _ = mr.trace(rays, sph, mat, ns, 2, 1e-4, 7, paths, gloss=False)
     for ch in range(3):
         x = L[ch].astype(np.float64)
         sigma = x.std(ddof=1) / np.sqrt(per)
@@ -258,10 +258,10 @@ def test_same_expectation_and_less_variance_on_the_restatement(apt, depth):
     rays = oracle.gen_rays_counter(p)
     n = rays.shape[1]
     paths = np.arange(n, dtype=np.uint64)
-    on = lr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, table)[0].astype(np.float64)
-    off = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths)[0].astype(np.float64)
-    first = mr.trace(rays, sph, mat, ns, 1, p.eps, p.seed, paths)[0].any(axis=0)
-    nee = [nr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, light=l, nee=True)[0].astype(np.float64) for l in (6, 7)]
+    on = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, table=table, gloss=False)[0].astype(np.float64)
+    off = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, gloss=False)[0].astype(np.float64)
+    first = mr.trace(rays, sph, mat, ns, 1, p.eps, p.seed, paths, gloss=False)[0].any(axis=0)
+    nee = [mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, light=l, nee=True, gloss=False)[0].astype(np.float64) for l in (6, 7)]
     for ch in range(3):
         s_on, s_off = on[ch].std(ddof=1) / np.sqrt(n), off[ch].std(ddof=1) / np.sqrt(n)
         z = (on[ch].mean() - off[ch].mean()) / np.hypot(s_on, s_off)

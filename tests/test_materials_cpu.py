@@ -77,9 +77,9 @@ def test_furnace_on_the_restatement():
         p = oracle.make_params(8, 8, 2, depth=depth, num_spheres=1, light_index=-1, eps=0.5, seed=depth)
         rays = oracle.gen_rays_counter(p)
         n = rays.shape[1]
-        L, bad = mr.trace(rays, _furnace_table(1.0, 1.0), np.array([mr.DIFF]), 1, depth, 0.5, p.seed, np.arange(n, dtype=np.uint64))
+        L, bad, _ = mr.trace(rays, _furnace_table(1.0, 1.0), np.array([mr.DIFF]), 1, depth, 0.5, p.seed, np.arange(n, dtype=np.uint64), gloss=False)
         assert not bad.any() and (L == F(depth)).all()
-        fb, _, _ = mr.render_frame(p, _furnace_table(0.5, 0.25), np.array([mr.DIFF]))
+        fb, _, _, _ = mr.render_frame(p, _furnace_table(0.5, 0.25), np.array([mr.DIFF]))
         assert (fb == F(0.5 * (1 - 2.0 ** -depth))).all()
 
 
@@ -90,7 +90,7 @@ def test_restatement_stays_float32():
     p = oracle.make_params(4, 4, 1, depth=3)
     rays = oracle.gen_rays_counter(p)
     sph = oracle.gen_spheres()
-    L, _ = mr.trace(rays, sph, np.array([1, 1, 1, 1, 1, 1, 0, 2]), 8, 3, 1e-4, 0, np.arange(rays.shape[1], dtype=np.uint64), rr_start=1)
+    L, _, _ = mr.trace(rays, sph, np.array([1, 1, 1, 1, 1, 1, 0, 2]), 8, 3, 1e-4, 0, np.arange(rays.shape[1], dtype=np.uint64), rr_start=1, gloss=False)
     assert L.dtype == np.float32
 
 

@@ -105,7 +105,7 @@ def test_gpu_frames_exercise_the_grid(apt, monkeypatch, ns, w, h, s_):
 
     monkeypatch.setattr(mr, "_intersect", recording)
     p = oracle.make_params(w, h, s_, depth=6, num_spheres=ns, light_index=ns - 1, seed=3)
-    _, _, bad = mr.render_frame(p, sph, mat)
+    _, _, bad, _ = mr.render_frame(p, sph, mat)
     assert not bad.any()
     idx = np.concatenate([a for a, _ in seen])
     skip = np.concatenate([b for _, b in seen])

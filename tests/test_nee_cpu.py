@@ -1,13 +1,12 @@
 """CPU-only: direct light sampling (APT_FLAG_NEE, include/render_mi355x.h "Direct light sampling") -- the flag and the entries'
-argument checks (no GPU needed), the lamp helper, and the restatement tests/nee_ref.py: equal to tests/materials_ref.py bit for bit
-with the flag off, equal to a closed form that does not depend on the library with it on, and with the plain renderer's expectation."""
+argument checks (no GPU needed), the lamp helper, and the restatement tests/materials_ref.py with nee=True: with the flag off a light
+index changes nothing, bit for bit; with it on, equal to a closed form that does not depend on the library with it on, and with the plain renderer's expectation."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import materials_ref as mr
-import nee_ref as nr
 
 F = np.float32
 
@@ -23,7 +22,7 @@ def apt():
 
 
 def test_flag_value(apt):
-    assert apt.APT_FLAG_NEE == 32 == nr.FLAG_NEE and "APT_FLAG_NEE" in apt.__all__
+    assert apt.APT_FLAG_NEE == 32 == mr.FLAG_NEE and "APT_FLAG_NEE" in apt.__all__
     text = open(mr.ROOT + "/include/render_mi355x.h").read()
     assert "APT_FLAG_NEE = 32u" in text
     others = (apt.APT_FLAG_RETIRE, apt.APT_FLAG_RR, apt.APT_FLAG_EMISSION, apt.APT_FLAG_BAND_BUFFERS, apt.APT_FLAG_GRID_SLOTS)
@@ -89,30 +88,32 @@ def _scenes(apt):
 
 
 @pytest.mark.parametrize("scene", ["demo9", "diff8"])
-def test_flag_off_is_materials_ref_bit_for_bit(apt, scene):
+def test_flag_off_is_the_plain_renderer_bit_for_bit(apt, scene):
+    """nee=False with a light index given against the same call without one (the plain renderer, whose bytes
+    tests/test_restatement_frozen.py records)."""
     from oracle import oracle
     sph, mat, ns, light = _scenes(apt)[scene]
     for depth, rr in ((1, 0), (5, 0), (8, 2)):
         p = oracle.make_params(16, 12, 2, depth=depth, num_spheres=ns, light_index=light, seed=3 + depth)
         rays = oracle.gen_rays_counter(p)
         paths = np.arange(rays.shape[1], dtype=np.uint64)
-        want, bad_w = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr)
-        got, bad, seg = nr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr, light=light, nee=False)
+        want, bad_w, _ = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr_start=rr, gloss=False)
+        got, bad, seg = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr_start=rr, light=light, nee=False, gloss=False)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and np.array_equal(bad, bad_w) and seg > 0
-        on, _, seg_on = nr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr, light=light, nee=True)
+        on, _, seg_on = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, rr_start=rr, light=light, nee=True, gloss=False)
         if depth == 1:                                   # no sample at the last bounce: depth 1 has no other
             assert np.array_equal(on.view(np.uint32), want.view(np.uint32)) and seg_on == seg
         else:
             assert not np.array_equal(on, want) and seg_on > seg and on.dtype == np.float32
     p = oracle.make_params(8, 8, 1, depth=4, num_spheres=ns, light_index=light, seed=1)
-    fb, u8, _ = nr.render_frame(p, sph, mat)
-    fb_w, u8_w, _ = mr.render_frame(p, sph, mat)
+    fb, u8, _, _ = mr.render_frame(p, sph, mat)
+    fb_w, u8_w, _, _ = mr.render_frame(oracle.make_params(8, 8, 1, depth=4, num_spheres=ns, light_index=-1, seed=1), sph, mat)
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32)) and np.array_equal(u8, u8_w)
 
 
 def test_the_sampling_stream_is_a_third_one():
     paths = np.arange(4096, dtype=np.uint64)
-    v1, v2 = mr.uniforms(nr.nee_key(7, paths), 0)
+    v1, v2 = mr.uniforms(mr.nee_key(7, paths), 0)
     u1, u2 = mr.uniforms(mr.mat_key(7, paths), 0)
     r1, _ = mr.uniforms(mr.rr_key(7, paths), 0)
     assert not np.array_equal(v1, u1) and not np.array_equal(v1, r1) and not np.array_equal(v2, u2)
@@ -131,7 +132,7 @@ def test_sampled_directions_stay_inside_the_cone():
         u /= np.linalg.norm(u, axis=0)
         h = [(np.float64(lc[i]) + dist * u[i]).astype(F) for i in range(3)]
         nl = [(-u[i]).astype(F) for i in range(3)]                                # facing the light
-        ok, l, cosl, wgt = nr.light_sample(h, nl, nr.nee_key(1, np.arange(n, dtype=np.uint64)), 0, lc, F(r * r))
+        ok, l, cosl, wgt = mr.light_sample(h, nl, mr.nee_key(1, np.arange(n, dtype=np.uint64)), 0, lc, F(r * r))
         assert ok.all() and (wgt > 0).all()
         w = np.stack([np.float64(lc[i]) - h[i].astype(np.float64) for i in range(3)])
         d = np.linalg.norm(w, axis=0)
@@ -163,7 +164,7 @@ def _floor_and_lamp_point(j, per, nee=True, rule=True):
     dd = (tgt - o) / np.linalg.norm(tgt - o)
     rays = np.tile(np.concatenate([o, dd])[:, None], (1, per)).astype(F)
     paths = np.arange(j * per, (j + 1) * per, dtype=np.uint64)
-    L, bad, _ = nr.trace(rays, sph, mat, 2, 2, 1e-4, 7, paths, light=1, nee=nee)
+    L, bad, _ = mr.trace(rays, sph, mat, 2, 2, 1e-4, 7, paths, light=1, nee=nee, gloss=False)
     assert not bad.any()
     nrm = (tgt - np.array([0.0, -R, 0.0])) / R
     w = np.array([0.0, height, 0.0]) - tgt
@@ -202,8 +203,8 @@ def test_same_expectation_on_the_restatement(apt, lamp, depth):
     p = oracle.make_params(64, 32, 4, depth=depth, num_spheres=ns, light_index=light, seed=21)
     rays = oracle.gen_rays_counter(p)
     paths = np.arange(rays.shape[1], dtype=np.uint64)
-    on = nr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, light=light, nee=True)[0].astype(np.float64)
-    off = nr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, light=light, nee=False)[0].astype(np.float64)
+    on = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, light=light, nee=True, gloss=False)[0].astype(np.float64)
+    off = mr.trace(rays, sph, mat, ns, depth, p.eps, p.seed, paths, light=light, nee=False, gloss=False)[0].astype(np.float64)
     n = rays.shape[1]
     for ch in range(3):
         s_on, s_off = on[ch].std(ddof=1) / np.sqrt(n), off[ch].std(ddof=1) / np.sqrt(n)
