@@ -24,6 +24,8 @@ APT_ENV_SAMPLE_SUN = 1                  # apt_environment.flags: DIFF hits sampl
 APT_TONEMAP_CLIP, APT_TONEMAP_REINHARD = 0, 1   # apt_film_resolve.tonemap
 APT_CURVE_LINEAR, APT_CURVE_SRGB = 0, 1         # apt_film_curve_host
 APT_FILM_PASS_SALT = 0x9B05688C2B3E6C1F
+# planes of apt_render_frame_features' buffer [APT_FEATURE_PLANES][count]: coverage, depth, normal (3 planes from 2), albedo (3 from 5)
+APT_FEATURE_COVERAGE, APT_FEATURE_DEPTH, APT_FEATURE_NORMAL, APT_FEATURE_ALBEDO, APT_FEATURE_PLANES = 0, 1, 2, 5, 8
 MAT_GLOSS = 3                           # with APT_FLAG_GLOSS: gen_data.gloss(alpha) makes the word (APT_MAT_GLOSS_WORD)
 MAT_SPEC, MAT_DIFF, MAT_REFR = 0, 1, 2  # material codes of the *_materials entries (include/render_mi355x.h APT_MAT_*)
 
@@ -48,6 +50,7 @@ ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "ren
                "apt_environment_build_host", "apt_environment_check_host", "apt_context_set_environment", "apt_set_environment",
                "apt_film_pass_seed", "apt_render_frame_film", "apt_context_render_frame_film", "apt_film_curve_host",
                "apt_film_resolve_device", "apt_film_resolve_host", "apt_write_pfm",
+               "apt_render_frame_features", "apt_context_render_frame_features",
                "apt_selftest_direction", "apt_selftest_direction_host", "apt_selftest_chain_states_host", "apt_selftest_div3_seeded",
                "apt_selftest_tent_bits_host"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too

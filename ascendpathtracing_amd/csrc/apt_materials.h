@@ -1,5 +1,6 @@
 // apt_materials.h -- what render_kernels.hip (argument checks, C-ABI) hands to the material kernels' launches (include/render_mi355x.h
-// "per-sphere materials").  The material kernels live in translation units of their own (materials.hip, environment.hip, film.hip), so
+// "per-sphere materials").  The material kernels live in translation units of their own (materials.hip, environment.hip, film.hip,
+// features.hip), so
 // that the code object of render_kernels.hip -- every kernel the mirror renderer had before -- is built exactly as before.  Which of
 // them serves a call is decided behind mat_render_frame / mat_render_paths (materials.hip).
 // Plain data only: the kernels' own argument types are internal to each translation unit.
@@ -73,6 +74,25 @@ void mat_gen_rays_camera(const CamRaysCall &call);
 // film.hip's resolve: the checked arguments of apt_film_resolve_device, pixel_count > 0.
 void film_resolve(const apt_film_resolve &r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev, float *out_or_null,
                   uint8_t *u8_or_null);
+
+// features.hip's launch ("features" in the header): the checked arguments of apt_render_frame_features, pixel_count > 0 and no more
+// pixels than a film launch takes.  grid and status: as MatTrace's.  -> APT_OK with the launch enqueued, or, with the error record set
+// and nothing launched, the entry's last two refusals in the contract's order: the status of apt_camera_default_host for an image
+// shape that has no record (camera null), then APT_ERR_ARG for a null `features`.
+struct FeaturesCall {
+    const float *spheres;
+    uint32_t ns;
+    float eps;
+    uint64_t seed;
+    const uint32_t *grid;
+    uint32_t *status;
+    uint32_t width, height, samples;
+    uint64_t pixel_begin, pixel_count;
+    float *features;
+    void *stream;
+    const apt_camera *camera;     // the context's camera, or null: the reference's
+};
+int mat_render_features(const FeaturesCall &call);
 
 // apt_selftest_direction's launch (count > 0): the test kernel is kept out of render_kernels.hip's code object as well.
 void selftest_direction(void *stream, const double *d3_dev, uint64_t count, uint64_t *result5_dev, uint8_t *flags_dev);

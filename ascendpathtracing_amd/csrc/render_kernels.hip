@@ -374,6 +374,31 @@ int do_mat_frame(apt_context *ctx, const apt_render_params *p, void *stream, con
     return launched();
 }
 
+// The feature planes ("features" in the header).  Of the params record only what the entry reads is checked; from the pointers on,
+// the refusals are do_mat_frame's for a film, in its order, so that a film and its features accept the same calls: the launch shape is
+// the film's (a features launch has fewer workgroups), the last two refusals are mat_render_features'.
+int do_features(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres, uint64_t pixel_begin, uint64_t pixel_count,
+                float *features) {
+    clear_error();
+    if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
+    if (!p) return fail(APT_ERR_ARG, "params is null%s");
+    if (p->struct_size != sizeof(apt_render_params)) return fail(APT_ERR_STRUCT, "apt_render_params.struct_size mismatch%s");
+    if (!p->width || !p->height || !p->samples) return fail(APT_ERR_ARG, "width/height/samples must be non-zero%s");
+    if (p->num_spheres == 0) return fail(APT_ERR_SCENE, "num_spheres is 0%s");
+    if (p->accel && !(p->flags & APT_FLAG_GRID_SLOTS)) return fail(APT_ERR_ARG, "features: accel (grid) needs APT_FLAG_GRID_SLOTS (apt_grid_flags of the built grid)%s");
+    const Launch ls = launch_state(*ctx, stream);
+    int rc;
+    FrameShape fs;
+    if ((rc = frame_launch_shape(p, spheres != nullptr, pixel_begin, pixel_count, fs)) || fs.blocks == 0) return rc;
+    if (!apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "features: the frame takes a pairwise-sum plan of at most 44 leaves, as a film's does (every samples <= 4199 has one)%s");
+    // the grid only with a status word to report a broken promise through, and never for the 8-sphere scene (make_mat_trace)
+    const uint32_t *grid = (p->num_spheres != 8 && ls.status) ? reinterpret_cast<const uint32_t *>((uintptr_t)p->accel) : nullptr;
+    if ((rc = apt::mat_render_features(apt::FeaturesCall{spheres, p->num_spheres, p->eps, p->seed, grid, ls.status, p->width, p->height, p->samples,
+                                                         pixel_begin, pixel_count, features, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr})))
+        return rc;
+    return launched();
+}
+
 } // namespace
 
 // ---- one process, several GPUs (include/render_mi355x.h: apt_multi_*) ---------------------------
@@ -559,6 +584,17 @@ int apt_context_render_frame_film(apt_context *ctx, const apt_render_params *p, 
 int apt_render_frame_film(const apt_render_params *p, void *stream, const float *spheres, const uint32_t *materials, const void *lights,
                           uint64_t pixel_begin, uint64_t pixel_count, float *film, uint32_t pass) {
     return apt_context_render_frame_film(&apt::default_context(), p, stream, spheres, materials, lights, pixel_begin, pixel_count, film, pass);
+}
+
+// The feature planes ("features" in the header): do_features.
+int apt_context_render_frame_features(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres, uint64_t pixel_begin,
+                                      uint64_t pixel_count, float *features) {
+    return do_features(ctx, p, stream, spheres, pixel_begin, pixel_count, features);
+}
+
+int apt_render_frame_features(const apt_render_params *p, void *stream, const float *spheres, uint64_t pixel_begin, uint64_t pixel_count,
+                              float *features) {
+    return do_features(&apt::default_context(), p, stream, spheres, pixel_begin, pixel_count, features);
 }
 
 int apt_film_resolve_device(const apt_film_resolve *r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev,

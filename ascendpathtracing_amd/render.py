@@ -111,6 +111,19 @@ def _render_frame_film(entry, handle, params, spheres, materials, lights, pixel_
     return film
 
 
+def _render_frame_features(entry, handle, params, spheres, features, pixel_begin, pixel_count, stream):
+    require_gpu()
+    if pixel_count is None:
+        pixel_count = params.width * params.height - pixel_begin
+    if features is None:
+        features = torch.empty((_lib.APT_FEATURE_PLANES, pixel_count), dtype=torch.float32, device=spheres.device)
+    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
+                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                                ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count),
+                                _dev_f32(features, "features", _lib.APT_FEATURE_PLANES * pixel_count)), entry)
+    return features
+
+
 def render_do(blockDim, l2ctrl, stream, rays, spheres, colors):
     """void render_do(blockDim, l2ctrl, stream, rays, spheres, colors) -- src/main.cpp:9-10,74.
     Asynchronous on `stream`; uses the process-wide defaults (apt_set_default_params)."""
@@ -190,6 +203,10 @@ class Context:
                           stream=None):
         return _render_frame_film("apt_context_render_frame_film", (self._h,), params, spheres, materials, lights, pixel_begin,
                                   pixel_count, film, pass_index, stream)
+
+    def render_frame_features(self, params, spheres, features=None, pixel_begin=0, pixel_count=None, stream=None):
+        return _render_frame_features("apt_context_render_frame_features", (self._h,), params, spheres, features, pixel_begin,
+                                      pixel_count, stream)
 
 
 def render_host(blockDim, rays, spheres, colors):
@@ -337,6 +354,14 @@ def render_frame_film(params: RenderParams, spheres, materials, film=None, pass_
                               pass_index, stream)
 
 
+def render_frame_features(params: RenderParams, spheres, features=None, pixel_begin=0, pixel_count=None, stream=None):
+    """apt_render_frame_features: the first-hit feature planes of the pixel range -- coverage, depth, normal, albedo (APT_FEATURE_*),
+    each the mean over the pixel's camera rays, the ones render_frame(materials=) traces with these params -- stored in `features`
+    (float32 [APT_FEATURE_PLANES][count]; None: a new tensor).  Reads no material table and no flag but APT_FLAG_GRID_SLOTS with
+    params.accel.  Returns the tensor; not synchronised."""
+    return _render_frame_features("apt_render_frame_features", (), params, spheres, features, pixel_begin, pixel_count, stream)
+
+
 class Film:
     """An unclipped float32 accumulation buffer for the pixels [pixel_begin, pixel_begin + pixel_count) of a width x height image
     (include/render_mi355x.h "film"): add_pass renders one more independent frame into it, resolve turns the mean into a displayable
@@ -362,6 +387,15 @@ class Film:
                            self.passes, stream)
         self.passes += 1
         return self
+
+    def features(self, params, spheres, stream=None, context=None):
+        """apt_render_frame_features for the film's own pixel range (params.width and height must be the film's) -> a new float32
+        [APT_FEATURE_PLANES][count] tensor: what lies under the film's pixels.  Independent of the passes the film holds."""
+        if (params.width, params.height) != (self.width, self.height):
+            raise _lib.AptError("Film.features: params.width / height are not the film's")
+        entry, handle = ("apt_render_frame_features", ()) if context is None else ("apt_context_render_frame_features", (context._h,))
+        out = torch.empty((_lib.APT_FEATURE_PLANES, self.pixel_count), dtype=torch.float32, device=self.buffer.device)
+        return _render_frame_features(entry, handle, params, spheres, out, self.pixel_begin, self.pixel_count, stream)
 
     def mean(self):
         """The film divided by its passes (fp32, as the resolve's first step) -> float32 [3][count]."""

@@ -652,6 +652,44 @@ int apt_film_resolve_host(const apt_film_resolve *r, const float *film, uint64_t
                           uint8_t *u8_or_null);
 int apt_write_pfm(const char *path, uint32_t width, uint32_t height, const float *planes_host);
 
+/* ---- features (EXTENSION: first-hit feature planes of the material renderer's film: coverage, depth, normal, albedo) -----------------
+ * What lies under each pixel, without light transport: the guides of an external denoiser, depth for compositing and fog, masks, a
+ * look at a scene or a camera.  The planes describe the FIRST surface a camera ray meets: a mirror or a pane of glass is that surface,
+ * nothing is followed through it.  One launch is one stored result; there is no per-pass accumulation.  APT_ABI_VERSION is unchanged:
+ * callers detect the feature by its symbols.
+ *
+ * apt_render_frame_features / apt_context_render_frame_features:
+ *   - features is a DEVICE buffer [APT_FEATURE_PLANES][pixel_count] float32, band-relative and x-major exactly as fb and the film are
+ *     (pixel (x, y) of a whole image at x * height + y).  Plane APT_FEATURE_COVERAGE (0) is the coverage, APT_FEATURE_DEPTH (1) the
+ *     depth, APT_FEATURE_NORMAL (2, 3, 4) the normal, APT_FEATURE_ALBEDO (5, 6, 7) the albedo.
+ *   - Rays.  The paths of pixel P are [P * 4 * S, (P + 1) * 4 * S), S = samples, and their rays are the ones a material frame launch
+ *     with the same width, height, samples, seed and context camera generates (without a camera: apt_camera_default_host's record):
+ *     tent filter and thin lens included, so the planes are anti-aliased and carry the image's depth of field.
+ *   - First hit.  render_do_ex's K-mode test of every sphere with p->eps, no sphere skipped, the lowest index on ties: the first
+ *     segment of a material path.
+ *   - Per path, on a hit of sphere k at tmin, every step one fp32 operation (no FMA), as in the bounce:
+ *         c = 1;  t = tmin;  h = o + d * tmin;  nr = h - centre_k;  nu = nr / sqrt(dot(nr, nr));
+ *         n = dot(d, nu) < 0 ? nu : -nu      (the bounce's nl; dot as ((0 + x) + y) + z)
+ *         a = the sphere table's albedo, rows 7..9 of k
+ *     On a miss all eight values are 0.
+ *   - Per pixel, each of the eight values is summed over the pixel's paths in ascending path order in float64, the sum is divided by
+ *     (double)(4 * S), and the quotient, rounded once to fp32, is STORED: whatever the buffer held, NaN included, is gone.  No clip;
+ *     the mean normal is not renormalised.
+ *   - Of *p the entry reads width, height, samples, seed, num_spheres, eps, and accel together with APT_FLAG_GRID_SLOTS (the grid
+ *     form, as the material entries take it; the 8-sphere scene ignores a grid).  Every other flag and field is ignored, so the record
+ *     of a film pass can be handed over as it is.  There is no material table.
+ *   - Refusals, nothing written: the params record's own (NULL, struct_size, a zero width / height / samples / num_spheres, accel
+ *     without APT_FLAG_GRID_SLOTS), then those of a film launch in its order -- a NULL `spheres`, the pixel range, the size of one
+ *     launch, a pairwise-sum plan of more than 44 leaves (every samples <= 4199 has one), an image shape apt_camera_default_host
+ *     refuses when no camera is set -- so that a film and its features accept the same calls; after them a NULL `features`
+ *     (APT_ERR_ARG).  An empty pixel range is APT_OK and launches nothing.  A grid that is not the scene's leaves the buffer untouched
+ *     and reports APT_DEV_GRID_MISMATCH through the status word. */
+enum { APT_FEATURE_COVERAGE = 0, APT_FEATURE_DEPTH = 1, APT_FEATURE_NORMAL = 2, APT_FEATURE_ALBEDO = 5, APT_FEATURE_PLANES = 8 };
+int apt_render_frame_features(const apt_render_params *p, void *stream, const float *spheres, uint64_t pixel_begin, uint64_t pixel_count,
+                              float *features);
+int apt_context_render_frame_features(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
+                                      uint64_t pixel_begin, uint64_t pixel_count, float *features);
+
 /* ---- one process, several GPUs (the reference's 8-block split, src/render.cpp:9-10,24-27, across devices) ----
  * The frame's x-major pixel range is cut into num_bands*stripes contiguous stripes; band b renders stripes
  * b, b+num_bands, ... (stripes == 1: one contiguous band per device, the reference's split; stripes > 1
