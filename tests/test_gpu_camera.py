@@ -11,109 +11,21 @@ import pytest
 
 import camera_ref as cr
 import lights_ref as lr
-import materials_ref as mr
+from gpu_harness import apt, bits_equal, dev, same, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 MODES = ["plain", "nee", "table"]
 
 
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
-class Scene:
-    """A scene on the device: sphere table, codes, a light table of `lights`, the light of APT_FLAG_NEE; grid=True builds a grid."""
-
-    def __init__(self, apt, sph, mat, ns, lights, light, grid=False):
-        import torch
-        self.sph, self.mat, self.ns, self.light = sph, np.asarray(mat, dtype=np.int32), int(ns), light
-        self.d_sph, self.d_mat = _dev(self.sph), _dev(self.mat)
-        self.table = apt.gen_data.build_lights(sph, ns, lights)
-        self.d_table = _dev(self.table.view(np.int32))
-        self.grid, self.grid_flags = None, 0
-        if grid:
-            hgrid = apt.gen_data.build_grid(self.sph, self.ns)
-            self.grid = torch.from_numpy(hgrid.view(np.int32)).cuda()
-            self.grid_flags = apt.gen_data.grid_flags(hgrid, self.ns)
-            assert self.grid_flags == apt.APT_FLAG_GRID_SLOTS
-
-    def params(self, apt, w, h, s_, depth, mode="plain", rr=False, seed=3, grid=True, **kw):
-        use_grid = grid and self.grid is not None
-        flags = kw.pop("flags", 0) | (apt.APT_FLAG_NEE if mode == "nee" else 0) | (apt.APT_FLAG_RR if rr else 0) | (self.grid_flags if use_grid else 0)
-        return apt.make_params(w, h, s_, depth=depth, num_spheres=self.ns, light_index=self.light, seed=seed, flags=flags,
-                               rr_start=2 if rr else 0, accel=self.grid.data_ptr() if use_grid else 0, **kw)
-
-    def frame(self, apt, p, mode, cam=None, **kw):
-        """One launch through the default context with `cam` set (None: no camera), its status word checked: -> (fb, u8, traced)."""
-        import torch
-        apt.render.set_camera(cam)
-        try:
-            with apt.render.TraceCounter() as tc:
-                fb, u8 = apt.render.render_frame(p, self.d_sph, materials=self.d_mat, lights=self.d_table if mode == "table" else None, **kw)
-            torch.cuda.synchronize()
-            apt.render.check_device_status()                  # the status word is clean after every launch
-        finally:
-            apt.render.set_camera(None)
-        return fb.cpu().numpy(), u8.cpu().numpy(), tc.value
-
-    def trace_ref(self, p, mode, rays, paths):
-        """The restatement's path colours for `rays` under `mode`."""
-        rr = (p.rr_start or 3) if p.flags & 2 else 0
-        args = (rays, self.sph, self.mat, self.ns, p.depth, p.eps, p.seed, paths)
-        L, bad, _ = mr.trace(*args, rr_start=rr, light=self.light, nee=mode == "nee", table=self.table if mode == "table" else None, gloss=False)
-        assert not bad.any()
-        return L
-
-    def frame_ref(self, p, mode, rec):
-        """camera_ref -> *_ref.trace -> oracle.decode_color: (fb [3][W*H], u8 [W*H][3])."""
-        from oracle import oracle
-        rays = cr.rays(rec, p.width, p.height, p.samples, seed=p.seed)
-        L = self.trace_ref(p, mode, rays, np.arange(rays.shape[1], dtype=np.uint64))
-        _, fb, u8 = oracle.decode_color(L, p.width, p.height, p.samples)
-        return fb, u8
-
-
-_scenes = {}
-
-
 def _scene(apt, name):
     """two8: 8 spheres (SGPR form), two lamps; demo9x2: the demo scene with the glass ball (tiles), two lights; big: 1030 spheres by tiles
     and through a grid, a two-light table of the stock light and one lamp."""
-    if name not in _scenes:
-        gd = apt.gen_data
-        if name == "two8":
-            sph, mat, ns = lr.two_lamps(gd)
-            _scenes[name] = Scene(apt, sph, mat, ns, None, 7)
-        elif name == "demo9x2":
-            sph, mat, ns = lr.demo_two_lights(gd)
-            _scenes[name] = Scene(apt, sph, mat, ns, [7, 6], 7)
-        else:
-            sph, mat, ns, idx = lr.sixteen_lamps(gd)
-            _scenes[name] = Scene(apt, sph, mat, ns, [ns - 1, idx[5]], ns - 1, grid=True)
-    return _scenes[name]
+    return scene(apt, "big1030x2" if name == "big" else name)
 
 
-def _same(got, want):
-    fb, u8, fb_w, u8_w = got[0], got[1], want[0], want[1]
-    diff = np.argwhere(fb.view(np.uint32) != fb_w.view(np.uint32))
-    assert diff.size == 0, (diff.shape, diff[:5], fb[tuple(diff[0])], fb_w[tuple(diff[0])])
-    assert np.array_equal(u8, u8_w)
-
-
-def _bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+def _frame(sc, p, mode, cam=None, **kw):
+    """-> (fb, u8, traced)"""
+    return sc.frame(p, mode, cam, count=True, **kw)
 
 
 # (samples, depth, roulette): both GROUP arms (samples < 8, >= 8), a tail (13 = 8 + 5), roulette
@@ -130,17 +42,17 @@ def test_pin_default_record_is_the_frame_without_a_camera(apt, name, mode):
     cam = apt.gen_data.default_camera(w, h)
     for grid in ((True, False) if big else (False,)):
         for s_, depth, rr in CASES:
-            p = sc.params(apt, w, h, s_, depth, mode=mode, rr=rr, seed=11 + s_, grid=grid)
-            want, got = sc.frame(apt, p, mode), sc.frame(apt, p, mode, cam)
-            _same(got, want)
+            p = sc.params(w, h, s_, depth, mode=mode, rr=rr, seed=11 + s_, grid=grid)
+            want, got = _frame(sc, p, mode), _frame(sc, p, mode, cam)
+            same(got, want)
             assert got[2] == want[2] > 0                           # the trace counter
         b, c = (117, 203) if big else (517, 700)                   # a mid-image pixel range
-        p = sc.params(apt, w, h, 16, 5, mode=mode, seed=2, grid=grid)
-        want, got = sc.frame(apt, p, mode, pixel_begin=b, pixel_count=c), sc.frame(apt, p, mode, cam, pixel_begin=b, pixel_count=c)
-        _same(got, want)
+        p = sc.params(w, h, 16, 5, mode=mode, seed=2, grid=grid)
+        want, got = _frame(sc, p, mode, pixel_begin=b, pixel_count=c), _frame(sc, p, mode, cam, pixel_begin=b, pixel_count=c)
+        same(got, want)
         assert got[2] == want[2] > 0
-    p136 = sc.params(apt, w, h, 136, 2, mode=mode, seed=5)          # two pairwise leaves: the LDS stack, next to the camera's tail in the plan
-    _same(sc.frame(apt, p136, mode, cam), sc.frame(apt, p136, mode))
+    p136 = sc.params(w, h, 136, 2, mode=mode, seed=5, grid=big)       # two pairwise leaves: the LDS stack, next to the camera's tail in the plan
+    same(_frame(sc, p136, mode, cam), _frame(sc, p136, mode))
 
 
 def test_pin_gen_rays_camera_with_the_default_record_is_gen_rays_device(apt):
@@ -182,11 +94,11 @@ def test_second_pin_aperture_zero_is_the_pinhole_whatever_focus_holds(apt):
     odd = pin.copy(focus=77.0, offset_over_focus=5.0, lens_u=(0.0, 1.0, 0.0))
     assert odd.aperture == 0.0
     for mode, (s_, depth, rr) in zip(MODES, CASES):
-        p = sc.params(apt, w, h, s_, depth, mode=mode, rr=rr, seed=4)
-        want, got = sc.frame(apt, p, mode, pin), sc.frame(apt, p, mode, odd)
-        _same(got, want)
+        p = sc.params(w, h, s_, depth, mode=mode, rr=rr, seed=4)
+        want, got = _frame(sc, p, mode, pin), _frame(sc, p, mode, odd)
+        same(got, want)
         assert got[2] == want[2]
-        assert not np.array_equal(want[0], sc.frame(apt, p, mode)[0])    # and it is not the reference's viewpoint
+        assert not np.array_equal(want[0], _frame(sc, p, mode)[0])    # and it is not the reference's viewpoint
     import torch
     p = apt.make_params(w, h, 3, seed=4)
     assert torch.equal(apt.render.gen_rays_camera(p, pin).view(torch.int32), apt.render.gen_rays_camera(p, odd).view(torch.int32))
@@ -202,7 +114,7 @@ def test_gen_rays_camera_is_the_restatement_bit_for_bit(apt, ci):
         n = p.num_paths
         want = cr.rays(rec, w, h, s_, seed=seed)
         got = apt.render.gen_rays_camera(p, cam).cpu().numpy()
-        assert np.isfinite(got).all() and _bits_equal(got, want)
+        assert np.isfinite(got).all() and bits_equal(got, want)
         norm = np.linalg.norm(got[3:].astype(np.float64), axis=0)
         assert np.abs(norm - 1).max() < 1e-6
         # a path range of whole buffers: nothing outside it is written; and a band buffer
@@ -213,13 +125,13 @@ def test_gen_rays_camera_is_the_restatement_bit_for_bit(apt, ci):
                        "apt_gen_rays_camera_device")
         torch.cuda.synchronize()
         part = buf.cpu().numpy().reshape(6, n)
-        assert _bits_equal(part[:, b:b + c], want[:, b:b + c]) and np.isnan(part[:, :b]).all() and np.isnan(part[:, b + c:]).all()
+        assert bits_equal(part[:, b:b + c], want[:, b:b + c]) and np.isnan(part[:, :b]).all() and np.isnan(part[:, b + c:]).all()
         band = apt.render.gen_rays_camera(q.copy(flags=apt.APT_FLAG_BAND_BUFFERS), cam).cpu().numpy()
-        assert band.shape == (6, c) and _bits_equal(band, want[:, b:b + c])
+        assert band.shape == (6, c) and bits_equal(band, want[:, b:b + c])
         tail = apt.render.gen_rays_camera(p.copy(path_begin=n - 5, flags=apt.APT_FLAG_BAND_BUFFERS), cam).cpu().numpy()   # path_count 0: to the end
-        assert tail.shape == (6, 5) and _bits_equal(tail, want[:, n - 5:])
+        assert tail.shape == (6, 5) and bits_equal(tail, want[:, n - 5:])
     if cam.aperture > 0:                                               # the lens does move the origins
-        assert not _bits_equal(got[:3], apt.render.gen_rays_camera(p, _cameras(apt, w, h)[ci - 1]).cpu().numpy()[:3])
+        assert not bits_equal(got[:3], apt.render.gen_rays_camera(p, _cameras(apt, w, h)[ci - 1]).cpu().numpy()[:3])
     apt.render.check_device_status()
 
 
@@ -234,17 +146,17 @@ def test_fused_frames_are_the_restatement_bit_for_bit(apt, ci):
         cam = _cameras(apt, w, h)[ci]
         mode = MODES[(ci + si) % 3]
         s_, depth, rr = CASES[(ci // 3 + ci + si) % 3]
-        p = sc.params(apt, w, h, s_, depth, mode=mode, rr=rr, seed=20 + ci)
-        got = sc.frame(apt, p, mode, cam)
-        want = sc.frame_ref(p, mode, cr.from_ctypes(cam))
-        _same(got, want)
+        p = sc.params(w, h, s_, depth, mode=mode, rr=rr, seed=20 + ci, grid=big)
+        got = _frame(sc, p, mode, cam)
+        want = sc.frame_ref(p, mode, cam)[:2]
+        same(got, want)
         assert got[0].max() > 0                                        # the camera sees something
         b, c = (117, 203) if big else (517, 700)
-        part = sc.frame(apt, p, mode, cam, pixel_begin=b, pixel_count=c)
-        _same(part, (want[0][:, b:b + c], want[1][b:b + c]))
+        part = _frame(sc, p, mode, cam, pixel_begin=b, pixel_count=c)
+        same(part, (want[0][:, b:b + c], want[1][b:b + c]))
         if big:
-            tiles = sc.frame(apt, sc.params(apt, w, h, s_, depth, mode=mode, rr=rr, seed=20 + ci, grid=False), mode, cam)
-            _same(tiles, got)
+            tiles = _frame(sc, sc.params(w, h, s_, depth, mode=mode, rr=rr, seed=20 + ci, grid=False), mode, cam)
+            same(tiles, got)
             assert tiles[2] == got[2]
 
 
@@ -257,15 +169,15 @@ def test_fused_equals_buffers(apt, name, mode):
     cam = _cameras(apt, w, h)[1 if name != "big" else 3]
     assert cam.aperture > 0
     for s_, depth, rr in CASES:
-        p = sc.params(apt, w, h, s_, depth, mode=mode, rr=rr, seed=31)
-        fused = sc.frame(apt, p, mode, cam)
+        p = sc.params(w, h, s_, depth, mode=mode, rr=rr, seed=31, grid=name == "big")
+        fused = _frame(sc, p, mode, cam)
         rays = apt.render.gen_rays_camera(p, cam)
         with apt.render.TraceCounter() as tc:
             colors = apt.render.render_paths(p, rays.reshape(-1), sc.d_sph, materials=sc.d_mat, lights=sc.d_table if mode == "table" else None)
         fb, u8 = apt.render.decode_color_device(p, colors)
         torch.cuda.synchronize()
         apt.render.check_device_status()
-        _same((fb.cpu().numpy(), u8.cpu().numpy()), fused)
+        same((fb.cpu().numpy(), u8.cpu().numpy()), fused)
         assert tc.value == fused[2]
 
 
@@ -274,7 +186,7 @@ def test_the_mirror_renderer_gets_the_camera_through_buffers_and_refuses_frames(
     w, h, s_ = 48, 32, 8
     cam = _cameras(apt, w, h)[1]
     sph = apt.gen_data.gen_spheres()
-    d_sph = _dev(sph)
+    d_sph = dev(sph)
     p = apt.make_params(w, h, s_, depth=5, seed=6)
     apt.render.set_camera(cam)
     try:
@@ -288,7 +200,7 @@ def test_the_mirror_renderer_gets_the_camera_through_buffers_and_refuses_frames(
         apt.render.set_camera(None)
     want, _ = oracle.render_paths(oracle.Params.from_buffer_copy(bytes(p)), cr.rays(cr.from_ctypes(cam), w, h, s_, seed=6), sph)
     _, fb_w, u8_w = oracle.decode_color(want, w, h, s_)
-    _same((fb.cpu().numpy(), u8.cpu().numpy()), (fb_w, u8_w))
+    same((fb.cpu().numpy(), u8.cpu().numpy()), (fb_w, u8_w))
     fb2, _ = apt.render.render_frame(p, d_sph)                         # NULL: the entry accepts again
     torch.cuda.synchronize()
     assert fb2.shape == (3, w * h)
@@ -297,12 +209,12 @@ def test_the_mirror_renderer_gets_the_camera_through_buffers_and_refuses_frames(
 def test_a_plan_that_reaches_the_cameras_words_is_refused(apt):
     sc = _scene(apt, "two8")
     cam = apt.gen_data.default_camera(8, 4)
-    ok = sc.params(apt, 8, 4, 4199, 1)                                 # the last count whose plan leaves the words free
-    assert sc.frame(apt, ok, "plain", cam)[0].shape == (3, 32)
-    many = sc.params(apt, 8, 4, 4200, 1)                               # the first with more than 44 leaves
-    assert sc.frame(apt, many, "plain")[0].shape == (3, 32)            # fine without a camera
+    ok = sc.params(8, 4, 4199, 1)                                 # the last count whose plan leaves the words free
+    assert _frame(sc, ok, "plain", cam)[0].shape == (3, 32)
+    many = sc.params(8, 4, 4200, 1)                               # the first with more than 44 leaves
+    assert _frame(sc, many, "plain")[0].shape == (3, 32)            # fine without a camera
     with pytest.raises(apt.AptError, match="44 leaves"):
-        sc.frame(apt, many, "plain", cam)
+        _frame(sc, many, "plain", cam)
 
 
 # ---- the lens does what a lens does ------------------------------------------------------------------------------------------------
@@ -329,7 +241,7 @@ def test_lens_blurs_by_the_circle_of_confusion(apt):
     spheres = [(-3.0, 20.0, 1.0), (15.0, 60.0, 3.0)]                   # (x, forward depth z, radius); y = 0
     rows = [[r, x, 0.0, -z, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0] for x, z, r in spheres]
     sph, mat = lr.table_of(rows), np.array([1, 1], dtype=np.int32)
-    d_sph, d_mat = _dev(sph), _dev(mat)
+    d_sph, d_mat = dev(sph), dev(mat)
     px_per_unit = H / scale                                            # pixels per unit length at forward depth 1
     p = apt.make_params(W, H, S, depth=1, num_spheres=2, light_index=-1, seed=12)
 
@@ -386,8 +298,8 @@ def test_a_contexts_camera_does_not_leak_into_another_context(apt):
     sc = _scene(apt, "demo9x2")
     w, h = 48, 32
     cams = _cameras(apt, w, h)
-    p = sc.params(apt, w, h, 8, 5, seed=9)
-    want_a, want_b, want_none = sc.frame(apt, p, "plain", cams[0]), sc.frame(apt, p, "plain", cams[3]), sc.frame(apt, p, "plain")
+    p = sc.params(w, h, 8, 5, seed=9)
+    want_a, want_b, want_none = _frame(sc, p, "plain", cams[0]), _frame(sc, p, "plain", cams[3]), _frame(sc, p, "plain")
     assert not np.array_equal(want_a[0], want_b[0]) and not np.array_equal(want_a[0], want_none[0])
     a, b = apt.render.Context(), apt.render.Context()
     try:
@@ -397,17 +309,17 @@ def test_a_contexts_camera_does_not_leak_into_another_context(apt):
             for ctx, want in ((a, want_a), (b, want_b)):
                 fb, u8 = ctx.render_frame(p, sc.d_sph, materials=sc.d_mat)
                 ctx.check()
-                _same((fb.cpu().numpy(), u8.cpu().numpy()), want)
+                same((fb.cpu().numpy(), u8.cpu().numpy()), want)
             fb, u8 = apt.render.render_frame(p, sc.d_sph, materials=sc.d_mat)     # the default context has none
             torch.cuda.synchronize()
-            _same((fb.cpu().numpy(), u8.cpu().numpy()), want_none)
+            same((fb.cpu().numpy(), u8.cpu().numpy()), want_none)
         a.set_camera(None)
         fb, u8 = a.render_frame(p, sc.d_sph, materials=sc.d_mat)
         a.check()
-        _same((fb.cpu().numpy(), u8.cpu().numpy()), want_none)
+        same((fb.cpu().numpy(), u8.cpu().numpy()), want_none)
         fb, u8 = b.render_frame(p, sc.d_sph, materials=sc.d_mat)
         b.check()
-        _same((fb.cpu().numpy(), u8.cpu().numpy()), want_b)
+        same((fb.cpu().numpy(), u8.cpu().numpy()), want_b)
     finally:
         a.close()
         b.close()

@@ -16,28 +16,13 @@ import numpy as np
 import pytest
 
 import plan_ref as pr
+from gpu_harness import apt, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 K, O, RETIRE, RR = pr.K, pr.O, pr.RETIRE, pr.RR
 NPIX = pr.W * pr.H
 RANGES = (None, pr.SUB)
-
-
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()                   # a no-op when the in-tree library is current
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.render, pkg.gen_data = render, gen_data
-    return pkg
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
 
 
 def _assert_same(got, want, what):
@@ -81,7 +66,7 @@ def _mirror_dev(apt, scene):
         if scene == "grid":
             grid = torch.from_numpy(apt.gen_data.build_grid(sph, ns).view(np.int32)).cuda()
             assert int(grid[26]) != 0           # off_cellslot: the grid carries the pair-slot tables of the sample-queue kernel's grid form
-        _DEV[scene] = (_dev(sph), grid)
+        _DEV[scene] = (dev(sph), grid)
     return _DEV[scene]
 
 
@@ -205,7 +190,7 @@ def _mat_dev(apt, name):
         sph, mat, ns, light, table = pr.mat_scene(apt.gen_data, name)
         hgrid = apt.gen_data.build_grid(sph, ns)
         assert apt.gen_data.grid_flags(hgrid, ns) == apt.APT_FLAG_GRID_SLOTS
-        _MAT_DEV[name] = dict(sph=_dev(sph), mat=_dev(mat, np.int32), ns=ns, light=light, table=None if table is None else _dev(table.view(np.int32)),
+        _MAT_DEV[name] = dict(sph=dev(sph), mat=dev(mat, np.int32), ns=ns, light=light, table=None if table is None else dev(table.view(np.int32)),
                               grid=torch.from_numpy(hgrid.view(np.int32)).cuda())
     return _MAT_DEV[name]
 
@@ -274,7 +259,7 @@ def test_mt_frame_any_sample_count(apt, oracle, s):
     from ascendpathtracing_amd import _lib
     w, h = pr.MT_W, pr.MT_H
     _, fb_w, u8_w = oracle.decode_color(pr.mt_colours(oracle, s), w, h, s)
-    d_sph = _dev(apt.gen_data.gen_spheres())
+    d_sph = dev(apt.gen_data.gen_spheres())
     p = apt.make_params(w, h, s, depth=pr.MT_DEPTH, mode=apt.APT_MODE_ORACLE, gain=pr.MT_GAIN)
     for rng in (None, pr.MT_SUB):
         pb, pc = rng or (0, w * h)
@@ -309,11 +294,11 @@ def test_decode_color_device_and_band(apt, oracle, s):
     _, fb_w, u8_w = oracle.decode_color(col, pr.W, pr.H, s)
     assert 0 < (fb_w == 1).sum() < fb_w.size // 3
     p = apt.make_params(pr.W, pr.H, s)
-    fb, u8 = apt.render.decode_color_device(p, _dev(col))
+    fb, u8 = apt.render.decode_color_device(p, dev(col))
     torch.cuda.synchronize()
     _assert_same((fb.cpu().numpy(), u8.cpu().numpy()), (fb_w, u8_w), (s, "device"))
     b, c = pr.SUB
-    band = _dev(col.reshape(3, NPIX * 4 * s)[:, b * 4 * s:(b + c) * 4 * s])
+    band = dev(col.reshape(3, NPIX * 4 * s)[:, b * 4 * s:(b + c) * 4 * s])
     assert band.is_contiguous() and band.numel() == 3 * c * 4 * s
     fb_b = torch.full((3, c), float("nan"), dtype=torch.float32, device="cuda")
     u8_b = torch.full((c, 3), 77, dtype=torch.uint8, device="cuda")

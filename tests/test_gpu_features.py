@@ -19,108 +19,53 @@ import pytest
 import camera_ref as cr
 import features_ref as ft
 import materials_ref as mr
+from gpu_harness import Scene, apt, assert_bits_equal, dev, lens, pinhole  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 F, D = np.float32, np.float64
 W, H = 48, 32
 SIZE = {"open220": (24, 16)}            # the restatement tests every path against every sphere: a quarter of the pixels for 220 of them
-EPS = 1e-4
+EPS = 1e-4                              # make_params' default, which the launches take
+DEPTH = 5                               # not read by the entry: make_params' default
 
 
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _bits_equal(got, want):
-    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    diff = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert diff.size == 0, (diff.shape[0], diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
-
-
-class Scene:
-    """A scene on the device: the sphere table and, with grid=True, its grid; the restatement's planes are computed once per launch."""
-
-    def __init__(self, apt, sph, ns, grid=False):
-        import torch
-        self.apt, self.sph, self.ns = apt, np.asarray(sph, dtype=F), int(ns)
-        self.d_sph = _dev(self.sph)
-        self.grid, self.grid_flags = None, 0
-        if grid:
-            hgrid = apt.gen_data.build_grid(self.sph, self.ns)
-            self.grid = torch.from_numpy(hgrid.view(np.int32)).cuda()
-            self.grid_flags = apt.gen_data.grid_flags(hgrid, self.ns)
-            assert self.grid_flags == apt.APT_FLAG_GRID_SLOTS
-        self.cache = {}
-
-    def params(self, w, h, s_, seed=3, grid=False, **kw):
-        use_grid = grid and self.grid is not None
-        return self.apt.make_params(w, h, s_, num_spheres=self.ns, seed=seed, eps=EPS, flags=self.grid_flags if use_grid else 0,
-                                    accel=self.grid.data_ptr() if use_grid else 0, **kw)
-
-    def run(self, p, cam=None, **kw):
-        """The planes of the launch `p` through the default context with the camera `cam` set -> host [8][count]; status word clean."""
-        import torch
-        apt = self.apt
-        apt.render.set_camera(cam)
-        try:
-            out = apt.render.render_frame_features(p, self.d_sph, **kw)
-            torch.cuda.synchronize()
-        finally:
-            apt.render.set_camera(None)
-        apt.render.check_device_status()
-        return out.cpu().numpy()
-
-    def ref(self, p, cam=None):
-        """features_ref's planes of the whole frame (the grid changes no plane: not part of the key); read-only, shared."""
-        key = (p.width, p.height, p.samples, p.seed, None if cam is None else bytes(cam))
-        if key not in self.cache:
-            rec = cr.default_record(p.width, p.height) if cam is None else cr.from_ctypes(cam)
-            planes = ft.planes(rec, p.width, p.height, p.samples, p.seed, self.sph, self.ns, EPS)
-            planes.setflags(write=False)
-            self.cache[key] = planes
-        return self.cache[key]
+def _ref(sc, p, cam=None):
+    """features_ref's planes of the whole frame (the grid changes no plane: not part of the key); read-only, shared."""
+    key = ("planes", p.width, p.height, p.samples, p.seed, None if cam is None else bytes(cam))
+    if key not in sc.ref:
+        rec = cr.default_record(p.width, p.height) if cam is None else cr.from_ctypes(cam)
+        planes = ft.planes(rec, p.width, p.height, p.samples, p.seed, sc.sph, sc.ns, EPS)
+        planes.setflags(write=False)
+        sc.ref[key] = planes
+    return sc.ref[key]
 
 
 _scenes = {}
 
 
 def _scene(apt, name):
+    """Sphere tables alone (the open ones without the lamps of the catalogue's): the entry reads no material word and no light, so the
+    words are DIFF and never uploaded, and the light is make_params' default, the last sphere."""
     if name not in _scenes:
         gd = apt.gen_data
         if name == "room8":
-            _scenes[name] = Scene(apt, gd.gen_spheres(), 8)
+            sph, ns = gd.gen_spheres(), 8
         elif name == "open8":
-            _scenes[name] = Scene(apt, gd.gen_spheres_open()[0], 8)
+            sph, ns = gd.gen_spheres_open()[0], 8
         elif name == "glow8":                                                     # every sphere emits its albedo (all positive)
-            sph = gd.gen_spheres_open()[0].copy()
+            sph, ns = gd.gen_spheres_open()[0].copy(), 8
             t = sph[:80].reshape(10, 8)
             t[4:7] = t[7:10]
             assert (t[7:10] > 0).all()
-            _scenes[name] = Scene(apt, sph, 8)
         else:
             ns = 40 if name == "open40" else 220
-            _scenes[name] = Scene(apt, gd.gen_scene_open(ns, seed=2)[0], ns, grid=ns > 64)
+            sph = gd.gen_scene_open(ns, seed=2)[0]
+        _scenes[name] = Scene(apt, sph, np.full(ns, mr.DIFF, dtype=np.int32), ns, light=ns - 1, grid=ns > 64)
     return _scenes[name]
 
 
 def _camera(apt, kind, w, h):
-    if kind is None:
-        return None
-    return apt.gen_data.camera(width=w, height=h, aperture=1.5 if kind == "lens" else 0.0, eye=(50.0, 45.0, 210.0), target=(50.0, 10.0, 60.0),
-                               up=(0.05, 1.0, 0.0), vfov_deg=42.0, offset=0.0)
+    return None if kind is None else {"lens": lens, "pinhole": pinhole}[kind](apt, w, h)
 
 
 # (samples, camera) per scene: every sample count and every camera meets both 8-sphere scenes and each of the other forms
@@ -137,33 +82,33 @@ def test_planes_equal_the_restatement(apt, name, grid):
     seen = np.zeros(3, dtype=bool)
     for s_, kind in LAUNCHES[name]:
         cam = _camera(apt, kind, w, h)
-        p = sc.params(w, h, s_, seed=50 + s_, grid=grid)
-        got = sc.run(p, cam)
-        want = sc.ref(p, cam)
-        _bits_equal(got, want)
+        p = sc.params(w, h, s_, DEPTH, seed=50 + s_, grid=grid)
+        got = sc.features(p, cam)
+        want = _ref(sc, p, cam)
+        assert_bits_equal(got, want)
         cov = want[ft.COVERAGE]
         seen |= [(cov == 0).any(), ((cov > 0) & (cov < 1)).any(), (cov == 1).any()]
         if grid:                                                                  # the grid form is the tile form
-            tiles = sc.params(w, h, s_, seed=50 + s_)
+            tiles = sc.params(w, h, s_, DEPTH, seed=50 + s_)
             assert tiles.accel == 0 and p.accel != 0
-            _bits_equal(sc.run(tiles, cam), got)
+            assert_bits_equal(sc.features(tiles, cam), got)
     assert seen[2] and (name == "room8" or seen.all())                            # hits everywhere; the open scenes also miss and straddle
 
 
 def test_a_sum_of_516_terms(apt):
     """16 x 8 at 129 samples: the longest per-pixel sum of this file (tests/test_features_cpu.py says why it is not a test of the order)."""
     sc = _scene(apt, "open8")
-    p = sc.params(16, 8, 129, seed=13)
-    _bits_equal(sc.run(p), sc.ref(p))
+    p = sc.params(16, 8, 129, DEPTH, seed=13)
+    assert_bits_equal(sc.features(p), _ref(sc, p))
     cam = _camera(apt, "lens", 16, 8)
-    _bits_equal(sc.run(p, cam), sc.ref(p, cam))
+    assert_bits_equal(sc.features(p, cam), _ref(sc, p, cam))
 
 
 def test_seeds(apt):
     sc = _scene(apt, "open8")
-    a, b = sc.run(sc.params(W, H, 3, seed=53)), sc.run(sc.params(W, H, 3, seed=54))
-    _bits_equal(a, sc.run(sc.params(W, H, 3, seed=53)))
-    _bits_equal(a, sc.ref(sc.params(W, H, 3, seed=53)))
+    a, b = sc.features(sc.params(W, H, 3, DEPTH, seed=53)), sc.features(sc.params(W, H, 3, DEPTH, seed=54))
+    assert_bits_equal(a, sc.features(sc.params(W, H, 3, DEPTH, seed=53)))
+    assert_bits_equal(a, _ref(sc, sc.params(W, H, 3, DEPTH, seed=53)))
     assert (a != b).any(axis=1)[[ft.COVERAGE, ft.DEPTH, ft.NORMAL, ft.ALBEDO]].all()
 
 
@@ -171,11 +116,11 @@ def test_a_buffer_of_nan_is_overwritten(apt):
     import torch
     for name, s_ in (("open8", 3), ("open40", 8)):
         sc = _scene(apt, name)
-        p = sc.params(W, H, s_, seed=50 + s_)
+        p = sc.params(W, H, s_, DEPTH, seed=50 + s_)
         buf = torch.full((8, W * H), float("nan"), dtype=torch.float32, device="cuda")
-        got = sc.run(p, features=buf)
-        assert not np.isnan(got).any() and not np.isnan(sc.ref(p)).any()
-        _bits_equal(got, sc.ref(p))
+        got = sc.features(p, features=buf)
+        assert not np.isnan(got).any() and not np.isnan(_ref(sc, p)).any()
+        assert_bits_equal(got, _ref(sc, p))
 
 
 @pytest.mark.parametrize("name,grid", [("open8", False), ("open40", False), ("open220", True)], ids=["8", "tiles40", "grid220"])
@@ -187,23 +132,23 @@ def test_a_pixel_range_inside_guards(apt, name, grid):
     b, guard = 37, 64
     c = min(1001, w * h - b - 3)
     assert c > 256 and c % 256
-    p = sc.params(w, h, 3, seed=53, grid=grid)
+    p = sc.params(w, h, 3, DEPTH, seed=53, grid=grid)
     block = torch.full((guard + 8 * c + guard,), -9.0, dtype=torch.float32, device="cuda")
-    sc.run(p, features=block[guard:guard + 8 * c].view(8, c), pixel_begin=b, pixel_count=c)
+    sc.features(p, features=block[guard:guard + 8 * c].view(8, c), pixel_begin=b, pixel_count=c)
     host = block.cpu().numpy()
     assert (host[:guard] == -9.0).all() and (host[guard + 8 * c:] == -9.0).all()
-    _bits_equal(host[guard:guard + 8 * c].reshape(8, c), sc.ref(p)[:, b:b + c])
+    assert_bits_equal(host[guard:guard + 8 * c].reshape(8, c), _ref(sc, p)[:, b:b + c])
 
 
 def test_two_bands_that_split_a_column(apt):
     sc = _scene(apt, "open8")
-    p = sc.params(W, H, 9, seed=59)
+    p = sc.params(W, H, 9, DEPTH, seed=59)
     cam = _camera(apt, "lens", W, H)
-    whole = sc.run(p, cam)
+    whole = sc.features(p, cam)
     cut = H + 18                                                                  # inside column 1
-    _bits_equal(sc.run(p, cam, pixel_begin=0, pixel_count=cut), whole[:, :cut])
-    _bits_equal(sc.run(p, cam, pixel_begin=cut, pixel_count=W * H - cut), whole[:, cut:])
-    _bits_equal(whole, sc.ref(p, cam))
+    assert_bits_equal(sc.features(p, cam, pixel_begin=0, pixel_count=cut), whole[:, :cut])
+    assert_bits_equal(sc.features(p, cam, pixel_begin=cut, pixel_count=W * H - cut), whole[:, cut:])
+    assert_bits_equal(whole, _ref(sc, p, cam))
 
 
 def test_a_grid_that_is_not_the_scenes_leaves_the_buffer_untouched(apt):
@@ -212,7 +157,7 @@ def test_a_grid_that_is_not_the_scenes_leaves_the_buffer_untouched(apt):
     other = apt.gen_data.build_grid(apt.gen_data.gen_scene_open(100, seed=9)[0], 100)
     d_other = torch.from_numpy(other.view(np.int32)).cuda()
     apt.render.check_device_status()                                             # nothing pending
-    p = sc.params(24, 16, 3)
+    p = sc.params(24, 16, 3, DEPTH)
     p.flags |= apt.APT_FLAG_GRID_SLOTS
     p.accel = d_other.data_ptr()
     buf = torch.full((8, 24 * 16), -2.0, dtype=torch.float32, device="cuda")
@@ -227,7 +172,7 @@ def test_the_entrys_own_refusals(apt):
     import torch
     sc = _scene(apt, "open8")
     L = apt._lib.lib()
-    p = sc.params(W, H, 8)
+    p = sc.params(W, H, 8, DEPTH)
     buf = torch.full((8, W * H), -2.0, dtype=torch.float32, device="cuda")
     ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     call = lambda q, sph, out, n=W * H: L.apt_render_frame_features(ctypes.byref(q), None, ptr(sph), ctypes.c_uint64(0), ctypes.c_uint64(n), ptr(out))
@@ -247,13 +192,13 @@ def test_the_entrys_own_refusals(apt):
         apt.render.render_frame_features(p, sc.d_sph, features=torch.zeros((8, 5), dtype=torch.float32, device="cuda"))
     # fields the entry does not read: a film pass's record as it is
     q = p.copy(depth=0, flags=apt.APT_FLAG_NEE | apt.APT_FLAG_RR | apt.APT_FLAG_GLOSS, light_index=-1, mode=1)
-    _bits_equal(sc.run(q), sc.ref(p))
+    assert_bits_equal(sc.features(q), _ref(sc, p))
 
 
 def test_film_features_end_to_end(apt):
     import torch
     sc = _scene(apt, "open40")
-    p = sc.params(W, H, 8, seed=58)
+    p = sc.params(W, H, 8, DEPTH, seed=58)
     cam = _camera(apt, "pinhole", W, H)
     ctx = apt.render.Context()
     try:
@@ -263,15 +208,15 @@ def test_film_features_end_to_end(apt):
         torch.cuda.synchronize()
         ctx.check()
         assert tuple(got.shape) == (apt.APT_FEATURE_PLANES, W * H) and film.passes == 0
-        _bits_equal(got.cpu().numpy(), sc.ref(p, cam))
+        assert_bits_equal(got.cpu().numpy(), _ref(sc, p, cam))
         band = apt.render.Film(W, H, pixel_begin=100, pixel_count=300)
         got = band.features(p, sc.d_sph, context=ctx)
         torch.cuda.synchronize()
-        _bits_equal(got.cpu().numpy(), sc.ref(p, cam)[:, 100:400])
-        _bits_equal(ctx.render_frame_features(p, sc.d_sph, pixel_begin=100, pixel_count=300).cpu().numpy(), sc.ref(p, cam)[:, 100:400])
-        _bits_equal(film.features(p, sc.d_sph).cpu().numpy(), sc.ref(p))        # the default context: no camera
+        assert_bits_equal(got.cpu().numpy(), _ref(sc, p, cam)[:, 100:400])
+        assert_bits_equal(ctx.render_frame_features(p, sc.d_sph, pixel_begin=100, pixel_count=300).cpu().numpy(), _ref(sc, p, cam)[:, 100:400])
+        assert_bits_equal(film.features(p, sc.d_sph).cpu().numpy(), _ref(sc, p))        # the default context: no camera
         with pytest.raises(apt.AptError, match="width / height"):
-            film.features(sc.params(W, H + 1, 8), sc.d_sph)
+            film.features(sc.params(W, H + 1, 8, DEPTH), sc.d_sph)
         ctx.check()
     finally:
         ctx.close()
@@ -296,14 +241,14 @@ def test_albedo_planes_against_a_film_pass_at_depth_one(apt, s_):
     sc = _scene(apt, "glow8")
     a = {3: 2, 8: 3, 9: 4, 16: 4}[s_]
     assert a + 3 <= math.ceil(math.log2(4 * s_)) + 2
-    p = sc.params(W, H, s_, seed=61, depth=1, light_index=-1)
-    mat = _dev(np.full(8, mr.DIFF, dtype=np.int32))
+    p = sc.params(W, H, s_, 1, seed=61).copy(light_index=-1)
+    mat = dev(np.full(8, mr.DIFF, dtype=np.int32))
     film = apt.render.render_frame_film(p, sc.d_sph, mat)
     torch.cuda.synchronize()
     apt.render.check_device_status()
     film = film.cpu().numpy().astype(D)
-    got = sc.run(p)
-    _bits_equal(got, sc.ref(p))
+    got = sc.features(p)
+    assert_bits_equal(got, _ref(sc, p))
     rays = cr.rays(cr.default_record(W, H), W, H, s_, seed=61)
     M = ft.path_values(rays, sc.sph, 8, EPS)[ft.ALBEDO:ft.ALBEDO + 3].reshape(3, W * H, 4 * s_).max(axis=2).astype(D)
     bound = (math.ceil(math.log2(4 * s_)) + 2) * 2.0 ** -24 * M

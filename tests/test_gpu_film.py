@@ -22,6 +22,7 @@ import pytest
 import camera_ref as cr
 import film_ref as fr
 import materials_ref as mr
+from gpu_harness import Scene, apt, assert_bits_equal, dev, lens, scene, sky_and_sun  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -29,156 +30,36 @@ W, H = 48, 32
 SIZE = {"open220": (24, 16)}            # the restatement tests every path against every sphere: a quarter of the pixels for 220 of them
 
 
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
+def _pass_ref(sc, p, mode, env, cam, k):
+    """film_ref's pass k of the launch `p` -> (planes, segments); computed once (the grid changes no image: not part of the key)."""
+    key = ("pass", p.width, p.height, p.samples, p.depth, p.seed, mode, p.flags & (2 | 32 | 64), p.rr_start, None if cam is None else bytes(cam),
+           None if env is None else bytes(env), k)
+    if key not in sc.ref:
+        from oracle import oracle
+        rays = None if cam is None else (lambda seed: cr.rays(cr.from_ctypes(cam), p.width, p.height, p.samples, seed=seed))
+        planes, seg = fr.render_pass(oracle.Params.from_buffer_copy(bytes(p)), sc.sph, sc.mat, env=None if env is None else mr.Env.from_ctypes(env),
+                                     table=sc.table if mode == "table" else None, pass_index=k, rays=rays)
+        planes.setflags(write=False)
+        sc.ref[key] = (planes, seg)
+    return sc.ref[key]
 
 
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
-def _bits_equal(got, want):
-    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
-    diff = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert diff.size == 0, (diff.shape[0], diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
-
-
-class Scene:
-    """A scene on the device: the sphere table, its material words, a two-light table, the light of APT_FLAG_NEE; grid=True builds a grid."""
-
-    def __init__(self, apt, sph, mat, ns, lights, light, grid=False):
-        import torch
-        self.apt, self.sph, self.ns, self.light = apt, np.asarray(sph, dtype=F), int(ns), light
-        self.mat = np.asarray(mat, dtype=np.int32)
-        self.d_sph, self.d_mat = _dev(self.sph), _dev(self.mat)
-        self.table = apt.gen_data.build_lights(self.sph, ns, lights)
-        self.d_table = _dev(self.table.view(np.int32))
-        self.mat_flags = apt.gen_data.materials_flags(self.mat)
-        self.grid, self.grid_flags = None, 0
-        if grid:
-            hgrid = apt.gen_data.build_grid(self.sph, self.ns)
-            self.grid = torch.from_numpy(hgrid.view(np.int32)).cuda()
-            self.grid_flags = apt.gen_data.grid_flags(hgrid, self.ns)
-            assert self.grid_flags == apt.APT_FLAG_GRID_SLOTS
-        self.ref = {}
-
-    def params(self, w, h, s_, depth, mode="plain", rr=False, seed=3, grid=False):
-        apt = self.apt
-        use_grid = grid and self.grid is not None
-        flags = (apt.APT_FLAG_NEE if mode == "nee" else 0) | (apt.APT_FLAG_RR if rr else 0) | (self.grid_flags if use_grid else 0) | self.mat_flags
-        return apt.make_params(w, h, s_, depth=depth, num_spheres=self.ns, light_index=self.light, seed=seed, flags=flags,
-                               rr_start=2 if rr else 0, accel=self.grid.data_ptr() if use_grid else 0)
-
-    def with_state(self, env, cam, fn):
-        apt = self.apt
-        apt.render.set_camera(cam)
-        apt.render.set_environment(env)
-        try:
-            return fn()
-        finally:
-            apt.render.set_camera(None)
-            apt.render.set_environment(None)
-
-    def film_passes(self, p, mode, env, cam, upto, film=None, checkpoints=()):
-        """Passes 0 .. upto - 1 of `p` through the default context -> ({k: the film after k passes, for k in checkpoints}, [segments traced
-        per pass]); the status word is clean after them."""
-        import torch
-        apt = self.apt
-        if film is None:
-            film = torch.full((3, p.width * p.height), -5.0, dtype=torch.float32, device="cuda")
-        snaps, traced = {}, []
-
-        def run():
-            for k in range(upto):
-                with apt.render.TraceCounter() as tc:
-                    apt.render.render_frame_film(p, self.d_sph, self.d_mat, film=film, pass_index=k, lights=self.d_table if mode == "table" else None)
-                    torch.cuda.synchronize()
-                traced.append(tc.value)
-                if k + 1 in checkpoints:
-                    snaps[k + 1] = film.cpu().numpy().copy()
-        self.with_state(env, cam, run)
-        apt.render.check_device_status()
-        return snaps, traced
-
-    def frame(self, p, mode, env, cam):
-        """The frame entry on the same launch -> (fb, segments traced)."""
-        import torch
-        apt = self.apt
-
-        def run():
-            with apt.render.TraceCounter() as tc:
-                fb, _ = apt.render.render_frame(p, self.d_sph, materials=self.d_mat, lights=self.d_table if mode == "table" else None)
-                torch.cuda.synchronize()
-            return fb.cpu().numpy(), tc.value
-        out = self.with_state(env, cam, run)
-        apt.render.check_device_status()
-        return out
-
-    def pass_ref(self, p, mode, env, cam, k):
-        """film_ref's pass k of the launch `p` -> (planes, segments); computed once (the grid changes no image: not part of the key)."""
-        key = (p.width, p.height, p.samples, p.depth, p.seed, mode, p.flags & (2 | 32 | 64), p.rr_start, None if cam is None else bytes(cam),
-               None if env is None else bytes(env), k)
-        if key not in self.ref:
-            from oracle import oracle
-            rays = None if cam is None else (lambda seed: cr.rays(cr.from_ctypes(cam), p.width, p.height, p.samples, seed=seed))
-            planes, seg = fr.render_pass(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat, env=None if env is None else mr.Env.from_ctypes(env),
-                                         table=self.table if mode == "table" else None, pass_index=k, rays=rays)
-            planes.setflags(write=False)
-            self.ref[key] = (planes, seg)
-        return self.ref[key]
-
-
-_scenes = {}
-
-
-def _glossy(apt, mat, every):
-    mat = np.array(mat, dtype=np.int32)
-    for i in np.nonzero(mat == mr.SPEC)[0][::every]:
-        mat[i] = apt.gen_data.gloss((600 + (int(i) * 977) % 64000) / 65536.0)
-    return mat
+_demo9 = []
 
 
 def _scene(apt, name):
-    """open8: gen_spheres_open with two of its DIFF balls as lamps; open40 / open220: gen_scene_open (one LDS tile / a grid) with two small
-    spheres as lamps and some mirrors as rough metal; demo9: the closed demo scene with smallpt's lamp and a second emitter."""
-    if name not in _scenes:
+    """The catalogue's open8 / open40 / open220; demo9: the closed demo scene with smallpt's lamp and a second emitter."""
+    if name != "demo9":
+        return scene(apt, name)
+    if not _demo9:
         gd = apt.gen_data
-        if name == "open8":
-            sph, mat = gd.gen_spheres_open()
-            sph = gd.with_lamps(sph, 8, [5, 4], radius=8.0, emission=[(30.0, 20.0, 10.0), 12.0])
-            _scenes[name] = Scene(apt, sph, mat, 8, [5, 4], 5)
-        elif name == "demo9":
-            sph, mat = gd.gen_spheres_materials()
-            sph = gd.with_lamp(sph, 9, 7)                                        # emission 400: far above 1 wherever it is seen
-            sph = gd.with_lamps(sph, 9, [6], radius=[16.5], emission=[(3.0, 2.0, 1.0)])
-            mat = np.array(mat, dtype=np.int32)
-            mat[6] = mr.DIFF
-            _scenes[name] = Scene(apt, sph, mat, 9, [7, 6], 7)
-        else:
-            ns = 40 if name == "open40" else 220
-            sph, mat = gd.gen_scene_open(ns, seed=2)
-            a, b = (7, 19) if ns == 40 else (11, 97)
-            sph = gd.with_lamps(sph, ns, [a, b], radius=[1.5, 2.0], emission=[(40.0, 30.0, 20.0), 25.0])
-            _scenes[name] = Scene(apt, sph, _glossy(apt, mat, 2), ns, [a, b], a, grid=ns > 64)
-    return _scenes[name]
-
-
-def _env(apt):
-    return apt.gen_data.environment(horizon=(0.5, 0.6, 0.7), zenith=(0.1, 0.3, 0.9), sun_dir=(0.4, 0.8, 0.45), sun_radiance=(30.0, 28.0, 24.0),
-                                    sun_angle_deg=8.0, sample_sun=True)
-
-
-def _lens(apt, w=W, h=H):
-    return apt.gen_data.camera(width=w, height=h, aperture=1.5, eye=(50.0, 45.0, 210.0), target=(50.0, 10.0, 60.0), up=(0.05, 1.0, 0.0),
-                               vfov_deg=42.0, offset=0.0)
+        sph, mat = gd.gen_spheres_materials()
+        sph = gd.with_lamp(sph, 9, 7)                                        # emission 400: far above 1 wherever it is seen
+        sph = gd.with_lamps(sph, 9, [6], radius=[16.5], emission=[(3.0, 2.0, 1.0)])
+        mat = np.array(mat, dtype=np.int32)
+        mat[6] = mr.DIFF
+        _demo9.append(Scene(apt, sph, mat, 9, [7, 6], 7))
+    return _demo9[0]
 
 
 def _check_passes(sc, p, mode, env, cam, checkpoints, grid=False):
@@ -186,22 +67,22 @@ def _check_passes(sc, p, mode, env, cam, checkpoints, grid=False):
     the restatement's segments and pass 1's against the frame entry's with that pass's seed."""
     upto = max(checkpoints)
     snaps, traced = sc.film_passes(p, mode, env, cam, upto, checkpoints=checkpoints)
-    refs = [sc.pass_ref(p, mode, env, cam, k) for k in range(upto)]
+    refs = [_pass_ref(sc, p, mode, env, cam, k) for k in range(upto)]
     for k in checkpoints:
-        _bits_equal(snaps[k], fr.accumulate([r[0] for r in refs[:k]]))
+        assert_bits_equal(snaps[k], fr.accumulate([r[0] for r in refs[:k]]))
     assert traced == [r[1] for r in refs], (traced, [r[1] for r in refs])
-    fb, seg = sc.frame(p, mode, env, cam)
+    fb, _, seg = sc.frame(p, mode, cam, env, count=True)
     with np.errstate(invalid="ignore"):
-        _bits_equal(np.clip(snaps[1], F(0), F(1)) if 1 in snaps else np.clip(refs[0][0], F(0), F(1)), fb)
+        assert_bits_equal(np.clip(snaps[1], F(0), F(1)) if 1 in snaps else np.clip(refs[0][0], F(0), F(1)), fb)
     assert seg == traced[0]
     if upto > 1:
         q = p.copy(seed=fr.pass_seed(p.seed, 1))
-        assert sc.frame(q, mode, env, cam)[1] == traced[1]
+        assert sc.frame(q, mode, cam, env, count=True)[2] == traced[1]
     if grid:                                                                     # the grid form is the tile form
         tiles = sc.params(p.width, p.height, p.samples, p.depth, mode=mode, rr=bool(p.flags & 2), seed=p.seed)
         assert tiles.accel == 0 and p.accel != 0
         other, _ = sc.film_passes(tiles, mode, env, cam, upto, checkpoints=(upto,))
-        _bits_equal(other[upto], snaps[upto])
+        assert_bits_equal(other[upto], snaps[upto])
     return snaps
 
 
@@ -220,9 +101,9 @@ LAUNCHES = {"plain": [(1, 5, True, False, False), (9, 2, False, True, True)],
 def test_film_passes_equal_the_restatement(apt, name, grid, mode):
     sc = _scene(apt, name)
     w, h = SIZE.get(name, (W, H))
-    for s_, depth, with_env, lens, rr in LAUNCHES[mode]:
+    for s_, depth, with_env, with_lens, rr in LAUNCHES[mode]:
         p = sc.params(w, h, s_, depth, mode=mode, rr=rr, seed=50 + s_, grid=grid)
-        snaps = _check_passes(sc, p, mode, _env(apt) if with_env else None, _lens(apt, w, h) if lens else None, (1, 2), grid)
+        snaps = _check_passes(sc, p, mode, sky_and_sun(apt) if with_env else None, lens(apt, w, h) if with_lens else None, (1, 2), grid)
         assert snaps[2].max() > (1.0 if with_env else 0.0)                       # with the sky: radiance the frame entries clip
 
 
@@ -236,7 +117,7 @@ def test_the_closed_demo_scene_with_its_lamp(apt, mode):
 
 def test_five_passes(apt):
     sc = _scene(apt, "open8")
-    _check_passes(sc, sc.params(W, H, 9, 2, mode="nee", seed=11), "nee", _env(apt), None, (1, 2, 5))
+    _check_passes(sc, sc.params(W, H, 9, 2, mode="nee", seed=11), "nee", sky_and_sun(apt), None, (1, 2, 5))
 
 
 def test_a_plan_of_two_leaves(apt):
@@ -244,7 +125,7 @@ def test_a_plan_of_two_leaves(apt):
     import plan_ref
     assert len(plan_ref.plan(128)) == 1 and len(plan_ref.plan(129)) == 2
     sc = _scene(apt, "open8")
-    _check_passes(sc, sc.params(16, 8, 129, 2, seed=13), "plain", _env(apt), None, (1, 2))
+    _check_passes(sc, sc.params(16, 8, 129, 2, seed=13), "plain", sky_and_sun(apt), None, (1, 2))
 
 
 def test_pass_zero_stores_over_nan(apt):
@@ -253,9 +134,9 @@ def test_pass_zero_stores_over_nan(apt):
     for s_ in (3, 8):
         p = sc.params(W, H, s_, 2, seed=17)
         film = torch.full((3, W * H), float("nan"), dtype=torch.float32, device="cuda")
-        snaps, _ = sc.film_passes(p, "plain", _env(apt), None, 1, film=film, checkpoints=(1,))
-        want = sc.pass_ref(p, "plain", _env(apt), None, 0)[0]
-        _bits_equal(snaps[1], want)
+        snaps, _ = sc.film_passes(p, "plain", sky_and_sun(apt), None, 1, film=film, checkpoints=(1,))
+        want = _pass_ref(sc, p, "plain", sky_and_sun(apt), None, 0)[0]
+        assert_bits_equal(snaps[1], want)
         assert not np.isnan(want).any() and not np.isnan(snaps[1]).any()
 
 
@@ -268,18 +149,17 @@ def test_a_pixel_range_inside_guards(apt, s_):
     p = sc.params(W, H, s_, 2, mode="table", seed=19)
     block = torch.full((guard + 3 * c + guard,), -9.0, dtype=torch.float32, device="cuda")
     film = block[guard:guard + 3 * c].view(3, c)
-    env = _env(apt)
+    env = sky_and_sun(apt)
 
-    def run():
+    with sc.view(env=env):
         for k in range(2):
             apt.render.render_frame_film(p, sc.d_sph, sc.d_mat, film=film, pass_index=k, lights=sc.d_table, pixel_begin=b, pixel_count=c)
         torch.cuda.synchronize()
-    sc.with_state(env, None, run)
     apt.render.check_device_status()
     host = block.cpu().numpy()
     assert (host[:guard] == -9.0).all() and (host[guard + 3 * c:] == -9.0).all()
-    want = fr.accumulate([sc.pass_ref(p, "table", env, None, k)[0][:, b:b + c] for k in range(2)])
-    _bits_equal(host[guard:guard + 3 * c].reshape(3, c), want)
+    want = fr.accumulate([_pass_ref(sc, p, "table", env, None, k)[0][:, b:b + c] for k in range(2)])
+    assert_bits_equal(host[guard:guard + 3 * c].reshape(3, c), want)
 
 
 def test_a_grid_that_is_not_the_scenes_leaves_the_film_untouched(apt):
@@ -330,7 +210,7 @@ def resolve_device(apt, film, passes, exposure, tonemap, inv_white2, d_table, of
     import torch
     L = apt._lib.lib()
     n = film.shape[1]
-    d_film = _dev(film)
+    d_film = dev(film)
     rec = apt._lib.film_resolve_record(passes, exposure, tonemap, inv_white2)
     out = torch.full((3, n), -7.0, dtype=torch.float32, device="cuda")
     block = torch.full((3 * n + 16,), 0xA5, dtype=torch.uint8, device="cuda")
@@ -348,7 +228,7 @@ def resolve_device(apt, film, passes, exposure, tonemap, inv_white2, d_table, of
 @pytest.mark.parametrize("tonemap", [fr.TONEMAP_CLIP, fr.TONEMAP_REINHARD], ids=["clip", "reinhard"])
 def test_resolve_device_equals_the_host_twin(apt, tonemap, curve):
     tables = [apt.gen_data.film_curve(c) for c in (fr.CURVE_LINEAR, fr.CURVE_SRGB)]
-    table, d_table = tables[curve], _dev(tables[curve])
+    table, d_table = tables[curve], dev(tables[curve])
     pool = fr.value_pool(tables)
     pool = np.concatenate([pool, np.zeros(-len(pool) % 3, dtype=F)])
     whole = pool.reshape(3, -1)                                                  # more than two workgroups of pixels
@@ -357,7 +237,7 @@ def test_resolve_device_equals_the_host_twin(apt, tonemap, curve):
         out, u8, guards = resolve_device(apt, whole, passes, exposure, tonemap, iw, d_table)
         rc, want_out, want_u8, _ = fr.resolve_host(apt, whole, passes, exposure, tonemap, iw, table)
         assert rc == 0 and guards
-        _bits_equal(out, want_out)
+        assert_bits_equal(out, want_out)
         assert np.array_equal(u8, want_u8)
     for n in (1, 2, 3, 5, 64, 257):
         for offset in range(4):
@@ -365,12 +245,12 @@ def test_resolve_device_equals_the_host_twin(apt, tonemap, curve):
             out, u8, guards = resolve_device(apt, film, 3, 7.5, tonemap, 1.0 / 16.0, d_table, offset)
             rc, want_out, want_u8, _ = fr.resolve_host(apt, film, 3, 7.5, tonemap, 1.0 / 16.0, table)
             assert guards
-            _bits_equal(out, want_out)
+            assert_bits_equal(out, want_out)
             assert np.array_equal(u8, want_u8)
     film = np.resize(pool, (3, 300))
     rc, want_out, want_u8, _ = fr.resolve_host(apt, film, 1, 1.0, tonemap, 0.0, table)
     out, u8, _ = resolve_device(apt, film, 1, 1.0, tonemap, 0.0, d_table, want_u8=False)
-    _bits_equal(out, want_out)
+    assert_bits_equal(out, want_out)
     assert np.all(u8 == 0xA5)
     out, u8, _ = resolve_device(apt, film, 1, 1.0, tonemap, 0.0, d_table, offset=1, want_out=False)
     assert np.all(out == -7.0) and np.array_equal(u8, want_u8)
@@ -379,7 +259,7 @@ def test_resolve_device_equals_the_host_twin(apt, tonemap, curve):
 def test_resolve_device_refusals_write_nothing(apt):
     import torch
     L = apt._lib.lib()
-    d_table = _dev(apt.gen_data.film_curve("srgb"))
+    d_table = dev(apt.gen_data.film_curve("srgb"))
     film = torch.full((3, 5), 0.5, dtype=torch.float32, device="cuda")
     out = torch.full((3, 5), -7.0, dtype=torch.float32, device="cuda")
     u8 = torch.full((5, 3), 0xA5, dtype=torch.uint8, device="cuda")
@@ -399,18 +279,18 @@ def test_resolve_device_refusals_write_nothing(apt):
 def test_resolve_of_a_real_film(apt):
     sc = _scene(apt, "open8")
     p = sc.params(W, H, 9, 2, mode="nee", seed=11)                               # test_five_passes' launch: its restatement is shared
-    env = _env(apt)
+    env = sky_and_sun(apt)
     snaps, _ = sc.film_passes(p, "nee", env, None, 5, checkpoints=(5,))
-    _bits_equal(snaps[5], fr.accumulate([sc.pass_ref(p, "nee", env, None, k)[0] for k in range(5)]))
+    assert_bits_equal(snaps[5], fr.accumulate([_pass_ref(sc, p, "nee", env, None, k)[0] for k in range(5)]))
     for tonemap, curve, exposure, iw in ((fr.TONEMAP_CLIP, "srgb", 1.0, 0.0), (fr.TONEMAP_REINHARD, "srgb", 0.5, 1.0 / 64.0), (fr.TONEMAP_REINHARD, "linear", 2.0, 0.0)):
         table = apt.gen_data.film_curve(curve)
-        out, u8, guards = resolve_device(apt, snaps[5], 5, exposure, tonemap, iw, _dev(table), offset=3)
+        out, u8, guards = resolve_device(apt, snaps[5], 5, exposure, tonemap, iw, dev(table), offset=3)
         rc, want_out, want_u8, _ = fr.resolve_host(apt, snaps[5], 5, exposure, tonemap, iw, table)
         assert rc == 0 and guards
-        _bits_equal(out, want_out)
+        assert_bits_equal(out, want_out)
         assert np.array_equal(u8, want_u8)
         ref_out, ref_u8 = fr.resolve(snaps[5], 5, exposure, tonemap, iw, table)
-        _bits_equal(out, ref_out)
+        assert_bits_equal(out, ref_out)
         assert np.array_equal(u8, ref_u8) and len(np.unique(u8)) > 50
 
 
@@ -419,8 +299,8 @@ def test_film_object_end_to_end(apt, tmp_path):
     import torch
     sc = _scene(apt, "open8")
     p = sc.params(W, H, 9, 2, mode="nee", seed=11)
-    env = _env(apt)
-    refs = [sc.pass_ref(p, "nee", env, None, k)[0] for k in range(3)]
+    env = sky_and_sun(apt)
+    refs = [_pass_ref(sc, p, "nee", env, None, k)[0] for k in range(3)]
     ctx = apt.render.Context()
     try:
         ctx.set_environment(env)
@@ -431,13 +311,13 @@ def test_film_object_end_to_end(apt, tmp_path):
         ctx.check()
         assert film.passes == 3
         total = fr.accumulate(refs)
-        _bits_equal(film.buffer.cpu().numpy(), total)
-        _bits_equal(film.mean().cpu().numpy(), total / F(3))
+        assert_bits_equal(film.buffer.cpu().numpy(), total)
+        assert_bits_equal(film.mean().cpu().numpy(), total / F(3))
         u8, out = film.resolve(exposure=0.5, tonemap="reinhard", white=8.0, curve="srgb", want_float=True)
         torch.cuda.synchronize()
         rc, want_out, want_u8, _ = fr.resolve_host(apt, total, 3, 0.5, fr.TONEMAP_REINHARD, 1.0 / 64.0, apt.gen_data.film_curve("srgb"))
         assert rc == 0
-        _bits_equal(out.cpu().numpy(), want_out)
+        assert_bits_equal(out.cpu().numpy(), want_out)
         assert np.array_equal(u8.cpu().numpy(), want_u8)
         assert np.array_equal(film.resolve().cpu().numpy(), fr.resolve(total, 3, 1.0, fr.TONEMAP_CLIP, 0.0, apt.gen_data.film_curve("srgb"))[1])
         path = tmp_path / "film.pfm"
@@ -445,14 +325,14 @@ def test_film_object_end_to_end(apt, tmp_path):
         data = open(path, "rb").read()
         assert data.startswith(b"PF\n48 32\n-1.0\n") and len(data) == 14 + W * H * 12
         px = np.frombuffer(data[14:], dtype="<f4").reshape(H, W, 3)
-        _bits_equal(px[5, 7], (total / F(3))[:, 7 * H + 5])
+        assert_bits_equal(px[5, 7], (total / F(3))[:, 7 * H + 5])
         film.reset()
         film.add_pass(p, sc.d_sph, sc.d_mat, context=ctx)
         torch.cuda.synchronize()
         assert film.passes == 1
-        _bits_equal(film.buffer.cpu().numpy(), refs[0])
+        assert_bits_equal(film.buffer.cpu().numpy(), refs[0])
         got = ctx.render_frame_film(p, sc.d_sph, sc.d_mat)                       # the thin wrapper: a film of its own, pass 0
         torch.cuda.synchronize()
-        _bits_equal(got.cpu().numpy(), refs[0])
+        assert_bits_equal(got.cpu().numpy(), refs[0])
     finally:
         ctx.close()

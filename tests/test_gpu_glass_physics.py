@@ -16,6 +16,7 @@ import pytest
 import lights_ref as lr
 import materials_ref as mr
 import physics_ref as ph
+from gpu_harness import apt, assert_bits_equal, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +27,6 @@ EPS = 1e-4
 LIGHT, TABLE_LIGHTS = 0, [0, 2]          # walls
 
 
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
 class Work:
     """What the cases share, each piece computed once: the rays, the trees, the restatements' colours, the scenes on the device and
     the colours of every launch (the grid form is compared with the tile form's)."""
@@ -50,7 +35,7 @@ class Work:
         self.apt = apt
         self.rays16 = ph.rays(RAY_SEED)
         self.rays = ph.copies(self.rays16, N)
-        self.d_rays = _dev(self.rays.ravel())
+        self.d_rays = dev(self.rays.ravel())
         self.paths = np.arange(16 * N, dtype=np.uint64)
         self.scenes, self.trees, self.want, self.dev, self.got = {}, {}, {}, {}, {}
 
@@ -81,7 +66,7 @@ class Work:
             apt, sc = self.apt, self.scene(name)
             table = apt.gen_data.build_lights(sc.table, sc.ns, TABLE_LIGHTS)
             assert np.array_equal(table, lr.build_table(sc.table, sc.ns, TABLE_LIGHTS))
-            d = dict(sph=_dev(sc.table), mat=_dev(sc.materials, np.int32), lights=_dev(table.view(np.int32)), grid=None, flags=0)
+            d = dict(sph=dev(sc.table), mat=dev(sc.materials, np.int32), lights=dev(table.view(np.int32)), grid=None, flags=0)
             if grid:
                 hgrid = apt.gen_data.build_grid(sc.table, sc.ns)
                 d["flags"] = apt.gen_data.grid_flags(hgrid, sc.ns)
@@ -112,11 +97,6 @@ def work(apt):
     return Work(apt)
 
 
-def _bits_equal(got, want):
-    diff = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert diff.size == 0, (diff.shape[0], diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
-
-
 def _check(work, name, grid, mode, rr):
     got = work.launch(name, grid, mode, rr)
     c = ph.compare(got, work.tree(name), N)
@@ -125,7 +105,7 @@ def _check(work, name, grid, mode, rr):
     assert c["finite"]
     assert c["zmax"] <= ph.Z_CAP and c["exact"] <= ph.EXACT_TOL
     assert c["differing"] >= 8
-    _bits_equal(got, work.restated(name, mode, rr))
+    assert_bits_equal(got, work.restated(name, mode, rr))
     return got
 
 
@@ -139,7 +119,7 @@ def test_tree_and_restatement(work, name, grid, mode, rr):
     got = _check(work, name, grid, mode, rr)
     assert not got[:, 12 * N:].any()                                      # the trapped rays: exactly dark
     if grid:
-        _bits_equal(got, work.launch(name, False, mode, rr))              # the grid form is the tile form
+        assert_bits_equal(got, work.launch(name, False, mode, rr))              # the grid form is the tile form
 
 
 def test_a_total_internal_reflection_reflects(work):

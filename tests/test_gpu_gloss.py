@@ -10,11 +10,11 @@ import ctypes
 import numpy as np
 import pytest
 
-import camera_ref as cr
 import gloss_physics as gp
 import lights_ref as lr
 import materials_ref as mr
 import physics_ref as ph
+from gpu_harness import Scene, apt, assert_bits_equal, dev, same, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 MODES = ["plain", "nee", "table"]
@@ -22,86 +22,6 @@ W, H = 48, 32
 # (samples, depth): samples 1, 3 and 8 are the GROUP == 1 arm, its longer leaf, and the GROUP == 8 arm
 CASES = [(1, 1), (3, 5), (8, 8)]
 BIG_CASES = [(1, 8), (3, 5), (8, 1)]     # 1030 spheres: the same sample counts and depths, paired so that the restatement stays quick
-
-
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
-def _bits_equal(got, want):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    diff = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert diff.size == 0, (diff.shape[0], diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
-
-
-class Scene:
-    """A scene on the device: sphere table, material words, a two-light table, the light of APT_FLAG_NEE; grid=True builds a grid."""
-
-    def __init__(self, apt, sph, mat, ns, lights, light, grid=False):
-        import torch
-        self.apt, self.sph, self.mat, self.ns, self.light = apt, np.asarray(sph, dtype=np.float32), np.asarray(mat, dtype=np.int32), int(ns), light
-        self.d_sph, self.d_mat = _dev(self.sph), _dev(self.mat)
-        self.table = apt.gen_data.build_lights(self.sph, ns, lights)
-        self.d_table = _dev(self.table.view(np.int32))
-        self.mat_flags = apt.gen_data.materials_flags(self.mat)
-        self.grid, self.grid_flags = None, 0
-        if grid:
-            hgrid = apt.gen_data.build_grid(self.sph, self.ns)
-            self.grid = torch.from_numpy(hgrid.view(np.int32)).cuda()
-            self.grid_flags = apt.gen_data.grid_flags(hgrid, self.ns)
-            assert self.grid_flags == apt.APT_FLAG_GRID_SLOTS
-        self.ref = {}
-
-    def params(self, w, h, s_, depth, mode="plain", rr=False, seed=3, grid=False, gloss=None, **kw):
-        apt = self.apt
-        use_grid = grid and self.grid is not None
-        flags = kw.pop("flags", 0) | (apt.APT_FLAG_NEE if mode == "nee" else 0) | (apt.APT_FLAG_RR if rr else 0)
-        flags |= (self.grid_flags if use_grid else 0) | (self.mat_flags if gloss is None else gloss)
-        return apt.make_params(w, h, s_, depth=depth, num_spheres=self.ns, light_index=self.light, seed=seed, flags=flags,
-                               rr_start=2 if rr else 0, accel=self.grid.data_ptr() if use_grid else 0, **kw)
-
-    def frame(self, p, mode, cam=None, mat=None, check=True):
-        """One launch through the default context -> (fb, u8); the status word is clean after it."""
-        import torch
-        apt = self.apt
-        apt.render.set_camera(cam)
-        try:
-            fb, u8 = apt.render.render_frame(p, self.d_sph, materials=self.d_mat if mat is None else mat,
-                                             lights=self.d_table if mode == "table" else None)
-            torch.cuda.synchronize()
-        finally:
-            apt.render.set_camera(None)
-        if check:
-            apt.render.check_device_status()
-        return fb.cpu().numpy(), u8.cpu().numpy()
-
-    def frame_ref(self, p, mode, rays=None):
-        """materials_ref's frame for the launch `p` (the grid changes no image: its flag and address are not part of the key)."""
-        key = (p.width, p.height, p.samples, p.depth, p.seed, mode, p.flags & (2 | 32 | 64), p.rr_start, rays is not None)
-        if key not in self.ref:
-            from oracle import oracle
-            fb, u8, bad, _ = mr.render_frame(oracle.Params.from_buffer_copy(bytes(p)), self.sph, self.mat,
-                                             table=self.table if mode == "table" else None, rays=rays)
-            assert not bad.any()
-            self.ref[key] = (fb, u8)
-        return self.ref[key]
-
-
-def _same(got, want):
-    _bits_equal(got[0], want[0])
-    assert np.array_equal(got[1], want[1])
 
 
 _scenes = {}
@@ -148,10 +68,10 @@ def test_frames_equal_the_restatement(apt, name, grid, mode, rr):
     for s_, depth in (BIG_CASES if name == "big" else CASES):
         p = sc.params(W, H, s_, depth, mode=mode, rr=rr, seed=10 + s_, grid=grid)
         got = sc.frame(p, mode)
-        _same(got, sc.frame_ref(p, mode))
+        same(got, sc.frame_ref(p, mode))
         assert got[0].max() > 0
         if grid:
-            _same(got, sc.frame(sc.params(W, H, s_, depth, mode=mode, rr=rr, seed=10 + s_), mode))     # the grid form is the tile form
+            same(got, sc.frame(sc.params(W, H, s_, depth, mode=mode, rr=rr, seed=10 + s_), mode))     # the grid form is the tile form
 
 
 def test_frame_with_a_camera_and_a_lens(apt):
@@ -160,8 +80,7 @@ def test_frame_with_a_camera_and_a_lens(apt):
                               vfov_deg=40.0, offset=0.0)
     for mode, (s_, depth) in zip(MODES, CASES[::-1]):
         p = sc.params(W, H, s_, depth, mode=mode, rr=True, seed=21)
-        rays = cr.rays(cr.from_ctypes(cam), W, H, s_, seed=21)
-        _same(sc.frame(p, mode, cam), sc.frame_ref(p, mode, rays))
+        same(sc.frame(p, mode, cam), sc.frame_ref(p, mode, cam))
 
 
 @pytest.mark.parametrize("name,grid", FORMS, ids=FORM_IDS)
@@ -178,7 +97,7 @@ def test_a_pixel_range_without_the_byte_frame(apt, name, grid):
     assert rc == 0
     torch.cuda.synchronize()
     apt.render.check_device_status()
-    _bits_equal(fb.cpu().numpy(), sc.frame_ref(p, "plain")[0][:, b:b + c])
+    assert_bits_equal(fb.cpu().numpy(), sc.frame_ref(p, "plain")[0][:, b:b + c])
 
 
 # ---- buffer mode ----------------------------------------------------------------------------------------------------------------------
@@ -254,20 +173,20 @@ def test_hand_made_rays_in_buffer_mode(apt, ns, mode):
     ended = ~up[256:512]
     assert 0 < ended.sum() < 256
     assert (want[:, 256:512][:, ended] == geo[4:7, 6][:, None]).all()
-    d_rays = _dev(rays.ravel())
+    d_rays = dev(rays.ravel())
     got = apt.render.render_paths(p, d_rays, sc.d_sph, materials=sc.d_mat, lights=sc.d_table if mode == "table" else None)
     torch.cuda.synchronize()
     apt.render.check_device_status()
-    _bits_equal(got.cpu().numpy(), want)
+    assert_bits_equal(got.cpu().numpy(), want)
     # a path range in band-relative buffers
     b, c = 300, 600
     pb = sc.params(16, 16, 1, 6, mode=mode, rr=True, seed=9, flags=apt.APT_FLAG_BAND_BUFFERS, path_begin=b, path_count=c)
     band = torch.full((3 * c,), -1.0, dtype=torch.float32, device="cuda")
-    apt.render.render_do_ex(pb, None, _dev(rays[:, b:b + c].ravel()), sc.d_sph, band, materials=sc.d_mat,
+    apt.render.render_do_ex(pb, None, dev(rays[:, b:b + c].ravel()), sc.d_sph, band, materials=sc.d_mat,
                             lights=sc.d_table if mode == "table" else None)
     torch.cuda.synchronize()
     apt.render.check_device_status()
-    _bits_equal(band.cpu().numpy().reshape(3, c), want[:, b:b + c])
+    assert_bits_equal(band.cpu().numpy().reshape(3, c), want[:, b:b + c])
 
 
 # ---- the flag -------------------------------------------------------------------------------------------------------------------------
@@ -287,9 +206,10 @@ def test_gloss_words_need_the_flag_and_malformed_ones_are_bad(apt, name):
     for word in (3, mr.word(700) | (1 << 24), 4 | (700 << 8)):             # q == 0, bit 24, a low byte of 4
         mat = sc.mat.copy()
         mat[2] = word                                                      # the back wall: every frame hits it
-        sc.frame(sc.params(16, 16, 8, 3, seed=1), "plain", mat=_dev(mat), check=False)
+        bad = Scene(apt, sc.sph, mat, sc.ns)                               # launched with the flags that sc's own words earn
+        bad.frame(sc.params(16, 16, 8, 3, seed=1), "plain", check=False)
         _bad_material(apt)
-        sc.frame(sc.params(16, 16, 8, 3, seed=1, gloss=0), "plain", mat=_dev(mat), check=False)
+        bad.frame(sc.params(16, 16, 8, 3, seed=1, gloss=0), "plain", check=False)
         _bad_material(apt)
     sc.frame(sc.params(16, 16, 8, 3, seed=1), "plain")                     # and the table as it is renders clean
 
@@ -297,19 +217,12 @@ def test_gloss_words_need_the_flag_and_malformed_ones_are_bad(apt, name):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name,grid", FORMS, ids=FORM_IDS)
 def test_the_flag_changes_nothing_without_gloss_words(apt, name, grid, mode):
-    if name == "gloss8":
-        sph, mat, ns = lr.two_lamps(apt.gen_data)
-        sc = Scene(apt, sph, mat, ns, [7, 6], 7)
-    elif name == "demo9":
-        sc = Scene(apt, *lr.demo_two_lights(apt.gen_data), [7, 6], 7)
-    else:
-        sph, mat, ns, idx = lr.sixteen_lamps(apt.gen_data)
-        sc = Scene(apt, sph, mat, ns, [ns - 1, idx[5]], ns - 1, grid=grid)
+    sc = scene(apt, {"gloss8": "room8", "demo9": "demo9x2", "big": "big1030x2"}[name])
     assert sc.mat_flags == 0
     for s_, depth in ((3, 5), (8, 3)):
         off = sc.frame(sc.params(W, H, s_, depth, mode=mode, rr=True, seed=5, grid=grid, gloss=0), mode)
         on = sc.frame(sc.params(W, H, s_, depth, mode=mode, rr=True, seed=5, grid=grid, gloss=apt.APT_FLAG_GLOSS), mode)
-        _same(on, off)
+        same(on, off)
         assert off[0].max() > 0
 
 
@@ -321,7 +234,7 @@ class Physics:
     def __init__(self, apt):
         self.apt = apt
         self.rays = gp.copies(gp.rays())
-        self.d_rays = _dev(self.rays.ravel())
+        self.d_rays = dev(self.rays.ravel())
         self.paths = np.arange(8 * gp.COPIES, dtype=np.uint64)
         self.fixture, _ = gp.load_fixture()
         self.scenes, self.want, self.got = {}, {}, {}
@@ -373,6 +286,6 @@ def test_physics_and_restatement(physics, name, grid, mode, rr):
     assert c["finite"]
     assert c["zmax"] <= ph.Z_CAP and c["exact"] <= ph.EXACT_TOL
     assert c["differing"] >= 8
-    _bits_equal(got, physics.restated(name, mode, rr))
+    assert_bits_equal(got, physics.restated(name, mode, rr))
     if grid:
-        _bits_equal(got, physics.launch(name, False, mode, rr))
+        assert_bits_equal(got, physics.launch(name, False, mode, rr))

@@ -8,115 +8,29 @@ import pytest
 
 import lights_ref as lr
 import materials_ref as mr
+from gpu_harness import Scene, apt, bits_equal, dev, oracle_params, same, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
-class Scene:
-    """A scene on the device: sphere table, codes, light table; grid=True builds a grid FROM THIS TABLE."""
-
-    def __init__(self, apt, sph, mat, ns, lights=None, light=-1, grid=False):
-        import torch
-        self.sph, self.mat, self.ns, self.light = sph, np.asarray(mat, dtype=np.int32), int(ns), light
-        self.d_sph, self.d_mat = _dev(self.sph), _dev(self.mat)
-        self.table = apt.gen_data.build_lights(sph, ns, lights)
-        assert np.array_equal(self.table, lr.build_table(sph, ns, lights))
-        self.d_table = _dev(self.table.view(np.int32))
-        self.grid, self.grid_flags = None, 0
-        if grid:
-            hgrid = apt.gen_data.build_grid(self.sph, self.ns)
-            self.grid = torch.from_numpy(hgrid.view(np.int32)).cuda()
-            self.grid_flags = apt.gen_data.grid_flags(hgrid, self.ns)
-            assert self.grid_flags == apt.APT_FLAG_GRID_SLOTS
-
-    def params(self, apt, w, h, s_, depth, nee=False, rr=False, seed=3, grid=True, **kw):
-        use_grid = grid and self.grid is not None
-        flags = kw.pop("flags", 0) | (apt.APT_FLAG_NEE if nee else 0) | (apt.APT_FLAG_RR if rr else 0) | (self.grid_flags if use_grid else 0)
-        return apt.make_params(w, h, s_, depth=depth, num_spheres=self.ns, light_index=self.light, seed=seed, flags=flags,
-                               rr_start=2 if rr else 0, accel=self.grid.data_ptr() if use_grid else 0, **kw)
-
-    def frame(self, apt, p, lights=True, **kw):
-        """lights=True: the table launch; False: the *_materials launch (plain, or APT_FLAG_NEE when p carries the flag)."""
-        import torch
-        fb, u8 = apt.render.render_frame(p, self.d_sph, materials=self.d_mat, lights=self.d_table if lights else None, **kw)
-        torch.cuda.synchronize()
-        apt.render.check_device_status()                  # the status word is clean after each launch
-        return fb.cpu().numpy(), u8.cpu().numpy()
-
-    def paths(self, apt, p, rays, lights=True):
-        import torch
-        n = rays.shape[1]
-        colors = torch.full((3 * n,), float("nan"), dtype=torch.float32, device="cuda")
-        apt.render.render_do_ex(p, None, _dev(rays.ravel()), self.d_sph, colors, materials=self.d_mat, lights=self.d_table if lights else None)
-        torch.cuda.synchronize()
-        apt.render.check_device_status()
-        return colors.cpu().numpy().reshape(3, n)
-
-
-_scenes = {}
-
-
-def _scene(apt, name):
-    """pin scenes "<diff8|demo9|big1030>-<stock|lamp>": one light, listed alone; the several-light scenes by name."""
-    if name in _scenes:
-        return _scenes[name]
-    gd = apt.gen_data
-    if name == "two8":
-        sph, mat, ns = lr.two_lamps(gd)
-        sc = Scene(apt, sph, mat, ns, light=7)
-    elif name == "demo9x2":
-        sph, mat, ns = lr.demo_two_lights(gd)
-        sc = Scene(apt, sph, mat, ns, lights=[7, 6], light=7)
-    elif name == "big16":
-        sph, mat, ns, idx = lr.sixteen_lamps(gd)
-        sc = Scene(apt, sph, mat, ns, lights=idx, grid=True)
-    else:
-        base, kind = name.split("-")
-        if base == "diff8":
-            sph, mat, light = gd.gen_spheres(), np.array([1, 1, 1, 1, 1, 1, 0, 1], dtype=np.int32), 7
-        elif base == "demo9":
-            sph, mat = gd.gen_spheres_materials()
-            light = 7
-        else:
-            sph, mat = gd.gen_scene_materials(1030, seed=5)
-            light = 1029
-        ns = int(np.asarray(mat).size)
-        if kind == "lamp":
-            sph = gd.with_lamp(sph, ns, light)
-        sc = Scene(apt, sph, mat, ns, lights=[light], light=light, grid=base == "big1030")
-    _scenes[name] = sc
+def _checked(sc):
+    """Every light table of this file is also lights_ref's."""
+    assert np.array_equal(sc.table, lr.build_table(sc.sph, sc.ns, sc.lights))
     return sc
 
 
-def _oracle_params(p):
-    from oracle import oracle
-    return oracle.Params.from_buffer_copy(bytes(p.copy(accel=0, flags=p.flags & ~16)))   # the restatement knows no grid
+_big16 = []
 
 
-def _same(fb, u8, fb_w, u8_w):
-    diff = np.argwhere(fb.view(np.uint32) != fb_w.view(np.uint32))
-    assert diff.size == 0, (diff.shape, diff[:5], fb[tuple(diff[0])], fb_w[tuple(diff[0])])
-    assert np.array_equal(u8, u8_w)
-
-
-def _bits_equal(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+def _scene(apt, name):
+    """The catalogue's pin scenes "<diff8|demo9|big1030>-<stock|lamp>" (one light, listed alone), two8 and demo9x2; big16: sixteen lamps
+    among 1030 spheres, by tiles and through a grid."""
+    if name != "big16":
+        return _checked(scene(apt, name))
+    if not _big16:
+        sph, mat, ns, idx = lr.sixteen_lamps(apt.gen_data)
+        _big16.append(_checked(Scene(apt, sph, mat, ns, lights=idx, grid=True)))
+    return _big16[0]
 
 
 # ---- the pin: a one-light table IS APT_FLAG_NEE with that light ----------------------------------------------------------------------------
@@ -131,29 +45,29 @@ def test_pin_one_light_table_is_the_flag_bit_for_bit(apt, name):
     w, h = (24, 16) if big else (48, 32)
     for grid in ((True, False) if big else (False,)):
         for s_, depth, rr in ((3, 5, True), (8, 5, False), (13, 8, True)):           # both GROUP arms, a tail, roulette
-            on = sc.params(apt, w, h, s_, depth, nee=True, rr=rr, seed=11 + s_, grid=grid)
-            off = sc.params(apt, w, h, s_, depth, rr=rr, seed=11 + s_, grid=grid)
+            on = sc.params(w, h, s_, depth, mode="nee", rr=rr, seed=11 + s_, grid=grid)
+            off = sc.params(w, h, s_, depth, rr=rr, seed=11 + s_, grid=grid)
             with apt.render.TraceCounter() as tc_f:
-                want = sc.frame(apt, on, lights=False)
+                want = sc.frame(on)
             with apt.render.TraceCounter() as tc_t:
-                got = sc.frame(apt, off)
-            _same(*got, *want)
+                got = sc.frame(off, "table")
+            same(got, want)
             assert tc_f.value == tc_t.value > 0
-            assert not np.array_equal(got[0], sc.frame(apt, off, lights=False)[0])   # and it is not the plain frame
+            assert not np.array_equal(got[0], sc.frame(off)[0])   # and it is not the plain frame
         b, c = (117, 203) if big else (517, 700)                                     # a pixel range
-        on = sc.params(apt, w, h, 16, 5, nee=True, seed=2, grid=grid)
-        _same(*sc.frame(apt, on.copy(flags=on.flags & ~apt.APT_FLAG_NEE, light_index=-1), pixel_begin=b, pixel_count=c),
-              *sc.frame(apt, on, lights=False, pixel_begin=b, pixel_count=c))          # light_index is not read
-        on = sc.params(apt, 16, 16, 4, 8, nee=True, rr=True, seed=9, grid=grid)        # paths, and a path range
-        rays = oracle.gen_rays_counter(_oracle_params(on))
+        on = sc.params(w, h, 16, 5, mode="nee", seed=2, grid=grid)
+        same(sc.frame(on.copy(flags=on.flags & ~apt.APT_FLAG_NEE, light_index=-1), "table", pixel_begin=b, pixel_count=c),
+             sc.frame(on, pixel_begin=b, pixel_count=c))            # light_index is not read
+        on = sc.params(16, 16, 4, 8, mode="nee", rr=True, seed=9, grid=grid)        # paths, and a path range
+        rays = oracle.gen_rays_counter(oracle_params(on))
         with apt.render.TraceCounter() as tc_f:
-            want = sc.paths(apt, on, rays, lights=False)
+            want = sc.paths(on, rays)
         with apt.render.TraceCounter() as tc_t:
-            got = sc.paths(apt, on, rays)                                            # the flag bit itself is not read either
-        assert _bits_equal(got, want) and tc_f.value == tc_t.value > rays.shape[1]
+            got = sc.paths(on, rays, "table")                                            # the flag bit itself is not read either
+        assert bits_equal(got, want) and tc_f.value == tc_t.value > rays.shape[1]
         b, c = 1001, 1537
-        got = sc.paths(apt, on.copy(path_begin=b, path_count=c), rays)
-        assert _bits_equal(got[:, b:b + c], want[:, b:b + c]) and np.isnan(got[:, :b]).all() and np.isnan(got[:, b + c:]).all()
+        got = sc.paths(on.copy(path_begin=b, path_count=c), rays, "table")
+        assert bits_equal(got[:, b:b + c], want[:, b:b + c]) and np.isnan(got[:, :b]).all() and np.isnan(got[:, b + c:]).all()
 
 
 # ---- bit for bit against the restatement, several lights -----------------------------------------------------------------------------
@@ -167,14 +81,14 @@ FRAME_CASES = [(1, 1, False, 48, 32), (8, 1, True, 48, 32), (3, 2, False, 48, 32
 @pytest.mark.parametrize("s_,depth,rr,w,h", FRAME_CASES)
 def test_frame_bitwise(apt, name, s_, depth, rr, w, h):
     sc = _scene(apt, name)
-    p = sc.params(apt, w, h, s_, depth, rr=rr, seed=11 + s_)
-    fb, u8 = sc.frame(apt, p)
-    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat, table=sc.table)
+    p = sc.params(w, h, s_, depth, rr=rr, seed=11 + s_)
+    fb, u8 = sc.frame(p, "table")
+    fb_w, u8_w, bad, _ = mr.render_frame(oracle_params(p), sc.sph, sc.mat, table=sc.table)
     assert not bad.any()
-    _same(fb, u8, fb_w, u8_w)
-    off = sc.frame(apt, p, lights=False)
+    same((fb, u8), (fb_w, u8_w))
+    off = sc.frame(p)
     if depth == 1:                                        # no sample at the last bounce: the table changes nothing
-        _same(fb, u8, *off)
+        same((fb, u8), off)
     else:
         assert not np.array_equal(fb, off[0])
 
@@ -185,15 +99,15 @@ BIG_CASES = [(2, 1, False), (2, 2, False), (8, 5, True), (13, 8, False)]
 @pytest.mark.parametrize("s_,depth,rr", BIG_CASES)
 def test_frame_bitwise_16_lamps_by_tiles_and_through_the_grid(apt, s_, depth, rr):
     sc = _scene(apt, "big16")
-    p = sc.params(apt, 24, 16, s_, depth, rr=rr)
-    fb_g, u8_g = sc.frame(apt, p)
-    fb_t, u8_t = sc.frame(apt, sc.params(apt, 24, 16, s_, depth, rr=rr, grid=False))
-    _same(fb_g, u8_g, fb_t, u8_t)                         # grid form == tile form
-    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat, table=sc.table)
+    p = sc.params(24, 16, s_, depth, rr=rr, grid=True)
+    fb_g, u8_g = sc.frame(p, "table")
+    fb_t, u8_t = sc.frame(sc.params(24, 16, s_, depth, rr=rr, grid=False), "table")
+    same((fb_g, u8_g), (fb_t, u8_t))                         # grid form == tile form
+    fb_w, u8_w, bad, _ = mr.render_frame(oracle_params(p), sc.sph, sc.mat, table=sc.table)
     assert not bad.any()
-    _same(fb_t, u8_t, fb_w, u8_w)
+    same((fb_t, u8_t), (fb_w, u8_w))
     if depth > 1:
-        assert not np.array_equal(fb_g, sc.frame(apt, p, lights=False)[0])
+        assert not np.array_equal(fb_g, sc.frame(p)[0])
 
 
 @pytest.mark.parametrize("name,grid,b,c", [("two8", False, 517, 700), ("demo9x2", False, 517, 700), ("big16", True, 117, 203),
@@ -201,51 +115,51 @@ def test_frame_bitwise_16_lamps_by_tiles_and_through_the_grid(apt, s_, depth, rr
 def test_frame_mid_image_pixel_range(apt, name, grid, b, c):
     sc = _scene(apt, name)
     w, h = (48, 32) if name != "big16" else (24, 16)
-    p = sc.params(apt, w, h, 16, 5, seed=2, grid=grid, flags=apt.APT_FLAG_RETIRE)      # RETIRE: accepted, changes nothing
-    fb, u8 = sc.frame(apt, p, pixel_begin=b, pixel_count=c)
-    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, table=sc.table, pixel_begin=b, pixel_count=c)
-    _same(fb, u8, fb_w, u8_w)
+    p = sc.params(w, h, 16, 5, seed=2, grid=grid, flags=apt.APT_FLAG_RETIRE)      # RETIRE: accepted, changes nothing
+    fb, u8 = sc.frame(p, "table", pixel_begin=b, pixel_count=c)
+    fb_w, u8_w, _, _ = mr.render_frame(oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, table=sc.table, pixel_begin=b, pixel_count=c)
+    same((fb, u8), (fb_w, u8_w))
 
 
 @pytest.mark.parametrize("name,grid", [("two8", False), ("demo9x2", False), ("big16", False), ("big16", True)])
 def test_paths_bitwise_with_ranges(apt, name, grid):
     from oracle import oracle
     sc = _scene(apt, name)
-    p = sc.params(apt, 16, 16, 4, 8, rr=True, seed=9, grid=grid)
-    rays = oracle.gen_rays_counter(_oracle_params(p))
+    p = sc.params(16, 16, 4, 8, rr=True, seed=9, grid=grid)
+    rays = oracle.gen_rays_counter(oracle_params(p))
     n = rays.shape[1]
     want, bad, segments = mr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=2, table=sc.table, gloss=False)
     assert not bad.any()
     with apt.render.TraceCounter() as tc:
-        got = sc.paths(apt, p, rays)
-    assert _bits_equal(got, want), np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:5]
+        got = sc.paths(p, rays, "table")
+    assert bits_equal(got, want), np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:5]
     assert tc.value == segments > n                       # shadow segments count as traced segments
     b, c = 1001, 1537                                     # a path range of the whole-image buffers, then the same range in band buffers
-    got = sc.paths(apt, p.copy(path_begin=b, path_count=c), rays)
-    assert _bits_equal(got[:, b:b + c], want[:, b:b + c])
+    got = sc.paths(p.copy(path_begin=b, path_count=c), rays, "table")
+    assert bits_equal(got[:, b:b + c], want[:, b:b + c])
     assert np.isnan(got[:, :b]).all() and np.isnan(got[:, b + c:]).all()
     pb = p.copy(path_begin=b, path_count=c, flags=p.flags | apt.APT_FLAG_BAND_BUFFERS)
-    got = sc.paths(apt, pb, np.ascontiguousarray(rays[:, b:b + c]))
-    assert _bits_equal(got, want[:, b:b + c])
+    got = sc.paths(pb, np.ascontiguousarray(rays[:, b:b + c]), "table")
+    assert bits_equal(got, want[:, b:b + c])
     for depth in (1, 2, 5):                               # no roulette, the other depths
-        q = sc.params(apt, 16, 16, 4, depth, seed=9, grid=grid)
+        q = sc.params(16, 16, 4, depth, seed=9, grid=grid)
         want, _, _ = mr.trace(rays, sc.sph, sc.mat, sc.ns, depth, q.eps, q.seed, np.arange(n, dtype=np.uint64), table=sc.table, gloss=False)
-        got = sc.paths(apt, q, rays)
-        assert _bits_equal(got, want), depth
+        got = sc.paths(q, rays, "table")
+        assert bits_equal(got, want), depth
         if depth == 1:
-            assert _bits_equal(got, sc.paths(apt, q, rays, lights=False))
+            assert bits_equal(got, sc.paths(q, rays))
 
 
 def test_context_methods_take_the_table(apt):
     import torch
     sc = _scene(apt, "two8")
-    p = sc.params(apt, 48, 32, 8, 5, seed=4)
-    want = sc.frame(apt, p)
+    p = sc.params(48, 32, 8, 5, seed=4)
+    want = sc.frame(p, "table")
     ctx = apt.render.Context()
     try:
         fb, u8 = ctx.render_frame(p, sc.d_sph, materials=sc.d_mat, lights=sc.d_table)
         ctx.check()
-        _same(fb.cpu().numpy(), u8.cpu().numpy(), *want)
+        same((fb.cpu().numpy(), u8.cpu().numpy()), want)
     finally:
         ctx.close()
     with pytest.raises(apt.AptError, match="lights needs materials"):
@@ -258,13 +172,13 @@ def test_a_light_we_stand_on_is_never_sampled(apt):
     """The white furnace listed as the only light: S is false at every bounce, so the frame is the plain frame bit for bit and every
     pixel is exactly 0.5 (1 - 2^-D)."""
     sph, mat, ns = lr.furnace(False)
-    sc = Scene(apt, sph, mat, ns, lights=[0])
+    sc = _checked(Scene(apt, sph, mat, ns, lights=[0]))
     for depth, s_ in ((1, 1), (2, 3), (5, 8), (8, 16)):
         p = apt.make_params(32, 16, s_, depth=depth, num_spheres=ns, eps=0.5, seed=depth, light_index=-1)
         with apt.render.TraceCounter() as tc:
-            fb, u8 = sc.frame(apt, p)
+            fb, u8 = sc.frame(p, "table")
         assert tc.value == depth * p.num_paths            # no shadow segment either
-        _same(fb, u8, *sc.frame(apt, p, lights=False))
+        same((fb, u8), sc.frame(p))
         assert (fb == np.float32(0.5 * (1 - 2.0 ** -depth))).all(), (depth, np.unique(fb))
 
 
@@ -274,11 +188,11 @@ def test_a_light_we_are_inside_of_is_gathered_by_the_next_hit(apt):
     mean is the plain renderer's."""
     from oracle import oracle
     sph, mat, ns = lr.furnace(True)
-    sc = Scene(apt, sph, mat, ns)
+    sc = _checked(Scene(apt, sph, mat, ns))
     assert mr.Table(sc.table).idx.tolist() == [0, 1]
     p = apt.make_params(128, 64, 4, depth=4, num_spheres=ns, eps=0.5, seed=21, light_index=-1)
-    rays = oracle.gen_rays_counter(_oracle_params(p))
-    on, off = sc.paths(apt, p, rays).astype(np.float64), sc.paths(apt, p, rays, lights=False).astype(np.float64)
+    rays = oracle.gen_rays_counter(oracle_params(p))
+    on, off = sc.paths(p, rays, "table").astype(np.float64), sc.paths(p, rays).astype(np.float64)
     _expect_equal_means("furnace + lamp", on, off)
 
 
@@ -300,13 +214,13 @@ def test_closed_form_lambertian_point_under_three_lights(apt, j):
     every point within 4 sigma (tests/test_nee_cpu.py's protocol for one light)."""
     per = 4096
     rays, sph, mat, ns, paths, want = lr.three_lights_point(j, per)
-    sc = Scene(apt, sph, mat, ns, lights=[1, 2, 3])
+    sc = _checked(Scene(apt, sph, mat, ns, lights=[1, 2, 3]))
     # path ids j * per ..: the launch's own numbering is 0 .. per - 1, so render the point as the j-th band of an 8-band buffer
     n = 8 * per
     p = apt.make_params(64, 32, 4, depth=2, num_spheres=ns, eps=1e-4, seed=7, light_index=-1, path_begin=j * per, path_count=per,
                         flags=apt.APT_FLAG_BAND_BUFFERS)
     assert p.num_paths == n
-    L = sc.paths(apt, p, rays).astype(np.float64)
+    L = sc.paths(p, rays, "table").astype(np.float64)
     for ch in range(3):
         sigma = L[ch].std(ddof=1) / np.sqrt(per)
         print("x = %4.1f ch %d  closed form %.6f  mean %.6f  sigma %.3e  z %+.2f" % (2.0 * j - 6.0, ch, want[ch], L[ch].mean(), sigma,
@@ -319,12 +233,12 @@ def _on_off(apt, name, depth, seed, grid=False):
     """-> (radiance with the table, plain, the camera ray hits an emitter) for 2^17 camera rays; float64 [3][n], bool [n]."""
     from oracle import oracle
     sc = _scene(apt, name)
-    p = sc.params(apt, 128, 64, 4, depth, seed=seed, grid=grid)
+    p = sc.params(128, 64, 4, depth, seed=seed, grid=grid)
     assert p.num_paths == 1 << 17
-    rays = oracle.gen_rays_counter(_oracle_params(p))
-    on = sc.paths(apt, p, rays).astype(np.float64)
-    off = sc.paths(apt, p, rays, lights=False).astype(np.float64)
-    first = sc.paths(apt, sc.params(apt, 128, 64, 4, 1, seed=seed, grid=grid), rays, lights=False)
+    rays = oracle.gen_rays_counter(oracle_params(p))
+    on = sc.paths(p, rays, "table").astype(np.float64)
+    off = sc.paths(p, rays).astype(np.float64)
+    first = sc.paths(sc.params(128, 64, 4, 1, seed=seed, grid=grid), rays)
     return on, off, first.any(axis=0), rays
 
 
@@ -347,7 +261,7 @@ def test_it_pays_less_variance_than_no_sampling_and_than_one_lamp_of_two(apt):
     on, off, direct, rays = _on_off(apt, "two8", 5, 21)
     sc = _scene(apt, "two8")
     assert 0 < direct.sum() < direct.size // 20
-    nee = [sc.paths(apt, sc.params(apt, 128, 64, 4, 5, nee=True, seed=21).copy(light_index=l), rays, lights=False).astype(np.float64)
+    nee = [sc.paths(sc.params(128, 64, 4, 5, mode="nee", seed=21).copy(light_index=l), rays).astype(np.float64)
            for l in (6, 7)]
     for ch in range(3):
         v_on, v_off = on[ch][~direct].var(ddof=1), off[ch][~direct].var(ddof=1)
@@ -370,9 +284,9 @@ def test_a_table_for_another_scene_renders_nothing_and_is_reported(apt, name):
     wrong_magic[0] ^= 1
     apt.render.check_device_status()                      # nothing pending
     for bad in (other, wrong_magic):
-        d_bad = _dev(bad.view(np.int32))
+        d_bad = dev(bad.view(np.int32))
         for grid in ((True, False) if sc.grid is not None else (False,)):
-            p = sc.params(apt, 24, 16, 8, 3, grid=grid)
+            p = sc.params(24, 16, 8, 3, grid=grid)
             fb = torch.full((3, 24 * 16), float("nan"), dtype=torch.float32, device="cuda")
             u8 = torch.full((24 * 16, 3), 7, dtype=torch.uint8, device="cuda")
             apt.render.render_frame(p, sc.d_sph, materials=sc.d_mat, lights=d_bad, fb=fb, fb_u8=u8)

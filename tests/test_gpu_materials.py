@@ -6,26 +6,11 @@ import numpy as np
 import pytest
 
 import materials_ref as mr
+from gpu_harness import Scene, apt, dev, oracle_params, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CAMERA = (50.0, 52.0, 295.6)     # camera_init: the camera position of gen_rays
-
-
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(apt, a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
 
 
 def _table(cols):
@@ -40,11 +25,6 @@ def _table(cols):
 
 def _scene(apt, name):
     """-> (spheres, materials int32, light_index)"""
-    if name == "demo9":                               # tile form: gen_spheres + the glass ball
-        s, m = apt.gen_data.gen_spheres_materials()
-        return s, m, 7
-    if name == "diff8":                               # 8-sphere form: gen_spheres with DIFF walls and light, the mirror SPEC
-        return apt.gen_data.gen_spheres(), np.array([1, 1, 1, 1, 1, 1, 0, 1], dtype=np.int32), 7
     if name == "big1030":                             # > one 1024-sphere tile: random codes, every 5th small sphere glass
         ns = 1030
         s = apt.gen_data.gen_scene(ns, seed=5)
@@ -54,7 +34,8 @@ def _scene(apt, name):
         m[:6] = 1
         m[ns - 1] = 1
         return s, m, ns - 1
-    raise KeyError(name)
+    sc = scene(apt, name + "-stock")                  # demo9: the tile form, diff8: the 8-sphere form
+    return sc.sph, sc.mat, sc.light
 
 
 def _frame_gpu(apt, p, sph, mat, pixel_begin=0, pixel_count=None, u8="normal"):
@@ -62,7 +43,7 @@ def _frame_gpu(apt, p, sph, mat, pixel_begin=0, pixel_count=None, u8="normal"):
     L = apt._lib.lib()
     npix = p.width * p.height
     pc = npix - pixel_begin if pixel_count is None else pixel_count
-    d_sph, d_mat = _dev(apt, sph), _dev(apt, mat, np.int32)
+    d_sph, d_mat = dev(sph), dev(mat, np.int32)
     fb = torch.full((3, pc), float("nan"), dtype=torch.float32, device="cuda")
     raw = torch.zeros(pc * 3 + 4, dtype=torch.uint8, device="cuda")
     off = 1 if u8 == "misaligned" else 0
@@ -72,11 +53,6 @@ def _frame_gpu(apt, p, sph, mat, pixel_begin=0, pixel_count=None, u8="normal"):
     apt._lib.check(rc, "apt_render_frame_materials")
     torch.cuda.synchronize()
     return fb.cpu().numpy(), raw[off:off + 3 * pc].cpu().numpy().reshape(pc, 3)
-
-
-def _oracle_params(p):
-    from oracle import oracle
-    return oracle.Params.from_buffer_copy(bytes(p))
 
 
 # (136, 3): two pairwise leaves (64 + 72, no tail), combined through the LDS stack
@@ -91,7 +67,7 @@ def test_frame_bitwise(apt, scene, s_, depth, rr):
     p = apt.make_params(48, 32, s_, depth=depth, num_spheres=ns, light_index=light, seed=11 + s_,
                         flags=apt.APT_FLAG_RR if rr else 0, rr_start=2 if rr else 0)
     fb, u8 = _frame_gpu(apt, p, sph, mat)
-    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sph, mat)
+    fb_w, u8_w, bad, _ = mr.render_frame(oracle_params(p), sph, mat)
     assert not bad.any()
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32)), np.argwhere(fb.view(np.uint32) != fb_w.view(np.uint32))[:5]
     assert np.array_equal(u8, u8_w)
@@ -103,7 +79,7 @@ def test_frame_bitwise_large_scene(apt, s_, depth, rr):
     p = apt.make_params(24, 16, s_, depth=depth, num_spheres=mat.size, light_index=light, seed=3,
                         flags=apt.APT_FLAG_RR if rr else 0, rr_start=1 if rr else 0)
     fb, u8 = _frame_gpu(apt, p, sph, mat)
-    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sph, mat)
+    fb_w, u8_w, _, _ = mr.render_frame(oracle_params(p), sph, mat)
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32))
     assert np.array_equal(u8, u8_w)
 
@@ -115,7 +91,7 @@ def test_frame_pixel_range_and_u8_forms(apt, scene, u8):
     p = apt.make_params(48, 32, 16, depth=5, num_spheres=mat.size, light_index=light, seed=2, flags=apt.APT_FLAG_RETIRE)
     b, c = 517, 700
     fb, got8 = _frame_gpu(apt, p, sph, mat, b, c, u8=u8)
-    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sph, mat, pixel_begin=b, pixel_count=c)
+    fb_w, u8_w, _, _ = mr.render_frame(oracle_params(p), sph, mat, pixel_begin=b, pixel_count=c)
     assert np.array_equal(fb.view(np.uint32), fb_w.view(np.uint32))
     if u8 == "misaligned":
         assert np.array_equal(got8, u8_w)
@@ -123,13 +99,8 @@ def test_frame_pixel_range_and_u8_forms(apt, scene, u8):
         assert not got8.any()
 
 
-def _paths_gpu(apt, p, rays, sph, mat, band=False):
-    import torch
-    n = rays.shape[1]
-    colors = torch.full((3 * n,), float("nan"), dtype=torch.float32, device="cuda")
-    apt.render.render_do_ex(p, None, _dev(apt, rays.ravel()), _dev(apt, sph), colors, materials=_dev(apt, mat, np.int32))
-    torch.cuda.synchronize()
-    return colors.cpu().numpy().reshape(3, n)
+def _paths_gpu(apt, p, rays, sph, mat):
+    return Scene(apt, sph, mat, mat.size).paths(p, rays)
 
 
 @pytest.mark.parametrize("scene", ["demo9", "diff8"])
@@ -137,7 +108,7 @@ def test_paths_bitwise_with_ranges(apt, scene):
     from oracle import oracle
     sph, mat, light = _scene(apt, scene)
     p = apt.make_params(16, 16, 4, depth=8, num_spheres=mat.size, light_index=light, seed=9, flags=apt.APT_FLAG_RR, rr_start=3)
-    rays = oracle.gen_rays_counter(_oracle_params(p))
+    rays = oracle.gen_rays_counter(oracle_params(p))
     n = rays.shape[1]
     want, bad, _ = mr.trace(rays, sph, mat, mat.size, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=3, gloss=False)
     assert not bad.any()
@@ -204,7 +175,7 @@ def test_furnace_paths_exact(apt, eight):
     for depth in (1, 2, 5, 8, 32):
         p = apt.make_params(16, 16, 2, depth=depth, num_spheres=mat.size, light_index=-1, eps=0.5, seed=depth,
                             flags=apt.APT_FLAG_EMISSION)
-        rays = oracle.gen_rays_counter(_oracle_params(p))
+        rays = oracle.gen_rays_counter(oracle_params(p))
         got = _paths_gpu(apt, p, rays, sph, mat)
         assert (got == np.float32(depth)).all(), (depth, np.unique(got))
 
@@ -224,7 +195,7 @@ def test_furnace_roulette_mean(apt, eight):
     sph, mat = _furnace(0.5, 0.25, eight)
     depth = 8
     p = apt.make_params(32, 32, 8, depth=depth, num_spheres=mat.size, eps=0.5, seed=17, flags=apt.APT_FLAG_RR, rr_start=1)
-    rays = oracle.gen_rays_counter(_oracle_params(p))
+    rays = oracle.gen_rays_counter(oracle_params(p))
     got = _paths_gpu(apt, p, rays, sph, mat)[0].astype(np.float64)
     want = 0.5 * (1 - 2.0 ** -depth)
     sigma = got.std() / np.sqrt(got.size)
@@ -252,9 +223,9 @@ def test_materials_none_is_the_mirror_renderer(apt):
     from oracle import oracle
     sph = apt.gen_data.gen_spheres()
     p = apt.make_params(16, 16, 8, depth=5, seed=1)
-    fb, u8 = apt.render.render_frame(p, _dev(apt, sph), materials=None)
-    fb_w, u8_w, _, _ = oracle.render_frame(_oracle_params(p), sph)
+    fb, u8 = apt.render.render_frame(p, dev(sph), materials=None)
+    fb_w, u8_w, _, _ = oracle.render_frame(oracle_params(p), sph)
     assert np.array_equal(fb.cpu().numpy().view(np.uint32), fb_w.view(np.uint32))
-    mat = _dev(apt, np.zeros(8, dtype=np.int32))       # and a zero table is all mirrors -- but with emitted light, not gain x throughput
-    fb_m, _ = apt.render.render_frame(p, _dev(apt, sph), materials=mat)
+    mat = dev(np.zeros(8, dtype=np.int32))       # and a zero table is all mirrors -- but with emitted light, not gain x throughput
+    fb_m, _ = apt.render.render_frame(p, dev(sph), materials=mat)
     assert not np.array_equal(fb_m.cpu().numpy(), fb.cpu().numpy())

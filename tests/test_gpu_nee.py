@@ -6,91 +6,13 @@ import numpy as np
 import pytest
 
 import materials_ref as mr
+from gpu_harness import Scene, apt, oracle_params, same, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def apt():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import _lib, gen_data, render
-    _lib.require_gpu()
-    pkg.gen_data, pkg.render = gen_data, render
-    return pkg
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
-class Scene:
-    """A scene on the device: table, codes, light; grid=True builds a grid FROM THIS TABLE (with the lamp the light is binned in cells)."""
-
-    def __init__(self, apt, name, lamp, grid=False):
-        import torch
-        if name == "diff8":                               # 8-sphere form: DIFF walls and light, the mirror SPEC
-            sph, mat, light = apt.gen_data.gen_spheres(), np.array([1, 1, 1, 1, 1, 1, 0, 1], dtype=np.int32), 7
-        elif name == "demo9":                             # tile form: gen_spheres + the glass ball
-            sph, mat = apt.gen_data.gen_spheres_materials()
-            light = 7
-        else:                                             # > one 1024-sphere tile; small spheres of every code
-            sph, mat = apt.gen_data.gen_scene_materials(1030, seed=5)
-            light = 1029
-        self.ns, self.light, self.mat = int(mat.size), light, np.asarray(mat, dtype=np.int32)
-        self.sph = apt.gen_data.with_lamp(sph, self.ns, light) if lamp else sph
-        self.d_sph, self.d_mat = _dev(self.sph), _dev(self.mat)
-        self.grid, self.grid_flags = None, 0
-        if grid:
-            self.hgrid = apt.gen_data.build_grid(self.sph, self.ns)
-            self.grid = torch.from_numpy(self.hgrid.view(np.int32)).cuda()
-            self.grid_flags = apt.gen_data.grid_flags(self.hgrid, self.ns)
-            assert self.grid_flags == apt.APT_FLAG_GRID_SLOTS
-
-    def params(self, apt, w, h, s_, depth, nee=True, rr=False, seed=3, grid=True, **kw):
-        use_grid = grid and self.grid is not None
-        flags = kw.pop("flags", 0) | (apt.APT_FLAG_NEE if nee else 0) | (apt.APT_FLAG_RR if rr else 0) | (self.grid_flags if use_grid else 0)
-        return apt.make_params(w, h, s_, depth=depth, num_spheres=self.ns, light_index=self.light, seed=seed, flags=flags,
-                               rr_start=2 if rr else 0, accel=self.grid.data_ptr() if use_grid else 0, **kw)
-
-    def frame(self, apt, p, **kw):
-        import torch
-        fb, u8 = apt.render.render_frame(p, self.d_sph, materials=self.d_mat, **kw)
-        torch.cuda.synchronize()
-        apt.render.check_device_status()                  # the status word is clean after each launch
-        return fb.cpu().numpy(), u8.cpu().numpy()
-
-    def paths(self, apt, p, rays):
-        import torch
-        n = rays.shape[1]
-        colors = torch.full((3 * n,), float("nan"), dtype=torch.float32, device="cuda")
-        apt.render.render_do_ex(p, None, _dev(rays.ravel()), self.d_sph, colors, materials=self.d_mat)
-        torch.cuda.synchronize()
-        apt.render.check_device_status()
-        return colors.cpu().numpy().reshape(3, n)
-
-
-_scenes = {}
-
-
-def _scene(apt, name, lamp, grid=False):
-    key = (name, lamp, grid)
-    if key not in _scenes:
-        _scenes[key] = Scene(apt, name, lamp, grid)
-    return _scenes[key]
-
-
-def _oracle_params(p):
-    from oracle import oracle
-    return oracle.Params.from_buffer_copy(bytes(p.copy(accel=0, flags=p.flags & ~16)))   # the restatement knows no grid
-
-
-def _same(fb, u8, fb_w, u8_w):
-    diff = np.argwhere(fb.view(np.uint32) != fb_w.view(np.uint32))
-    assert diff.size == 0, (diff.shape, diff[:5], fb[tuple(diff[0])], fb_w[tuple(diff[0])])
-    assert np.array_equal(u8, u8_w)
+def _scene(apt, name, lamp):
+    return scene(apt, "%s-%s" % (name, "lamp" if lamp else "stock"))
 
 
 # (samples, depth, roulette, width, height): both GROUP arms (samples < 8, >= 8), a tail (13 = 8 + 5), depths 1, 2, 5, 8, and
@@ -104,14 +26,14 @@ FRAME_CASES = [(1, 1, False, 48, 32), (8, 1, True, 48, 32), (3, 2, False, 48, 32
 @pytest.mark.parametrize("s_,depth,rr,w,h", FRAME_CASES)
 def test_frame_bitwise(apt, name, lamp, s_, depth, rr, w, h):
     sc = _scene(apt, name, lamp)
-    p = sc.params(apt, w, h, s_, depth, rr=rr, seed=11 + s_)
-    fb, u8 = sc.frame(apt, p)
-    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    p = sc.params(w, h, s_, depth, mode="nee", rr=rr, seed=11 + s_)
+    fb, u8 = sc.frame(p)
+    fb_w, u8_w, bad, _ = mr.render_frame(oracle_params(p), sc.sph, sc.mat)
     assert not bad.any()
-    _same(fb, u8, fb_w, u8_w)
-    off = sc.frame(apt, sc.params(apt, w, h, s_, depth, nee=False, rr=rr, seed=11 + s_))
+    same((fb, u8), (fb_w, u8_w))
+    off = sc.frame(sc.params(w, h, s_, depth, rr=rr, seed=11 + s_))
     if depth == 1:                                        # no sample at the last bounce: the flag changes nothing
-        _same(fb, u8, *off)
+        same((fb, u8), off)
     else:                                                 # and otherwise it does (what fails while the bit is ignored)
         assert not np.array_equal(fb, off[0])
 
@@ -122,88 +44,87 @@ BIG_CASES = [(2, 1, False), (2, 2, False), (8, 5, True), (13, 8, False)]
 @pytest.mark.parametrize("lamp", [False, True], ids=["stock", "lamp"])
 @pytest.mark.parametrize("s_,depth,rr", BIG_CASES)
 def test_frame_bitwise_1030_spheres_by_tiles_and_through_the_grid(apt, lamp, s_, depth, rr):
-    sc = _scene(apt, "big1030", lamp, grid=True)
-    p = sc.params(apt, 24, 16, s_, depth, rr=rr)
-    fb_g, u8_g = sc.frame(apt, p)
-    fb_t, u8_t = sc.frame(apt, sc.params(apt, 24, 16, s_, depth, rr=rr, grid=False))
-    _same(fb_g, u8_g, fb_t, u8_t)                         # grid form == tile form, flag on
-    fb_w, u8_w, bad, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
+    sc = _scene(apt, "big1030", lamp)
+    p = sc.params(24, 16, s_, depth, mode="nee", rr=rr, grid=True)
+    fb_g, u8_g = sc.frame(p)
+    fb_t, u8_t = sc.frame(sc.params(24, 16, s_, depth, mode="nee", rr=rr, grid=False))
+    same((fb_g, u8_g), (fb_t, u8_t))                         # grid form == tile form, flag on
+    fb_w, u8_w, bad, _ = mr.render_frame(oracle_params(p), sc.sph, sc.mat)
     assert not bad.any()
-    _same(fb_t, u8_t, fb_w, u8_w)
-    off = sc.frame(apt, sc.params(apt, 24, 16, s_, depth, nee=False, rr=rr))
+    same((fb_t, u8_t), (fb_w, u8_w))
+    off = sc.frame(sc.params(24, 16, s_, depth, rr=rr, grid=True))
     if depth == 1:
-        _same(fb_g, u8_g, *off)
+        same((fb_g, u8_g), off)
     else:
         assert not np.array_equal(fb_g, off[0])
 
 
 def test_the_lamp_is_binned_in_the_grid(apt):
     """With the lamp the light is no longer in the always-tested list: shadow rays find it by walking cells."""
-    stock, lamp = _scene(apt, "big1030", False, grid=True), _scene(apt, "big1030", True, grid=True)
+    stock, lamp = _scene(apt, "big1030", False), _scene(apt, "big1030", True)
     assert int(lamp.hgrid[6]) == int(stock.hgrid[6]) - 1      # GridHeader.nlarge (pt_core.h)
-    sc = Scene(apt, "demo9", True, grid=True)                # a degenerate grid: nothing is large
-    p = sc.params(apt, 48, 32, 8, 5, rr=True, seed=11)
-    fb, u8 = sc.frame(apt, p)
-    _same(fb, u8, *sc.frame(apt, sc.params(apt, 48, 32, 8, 5, rr=True, seed=11, grid=False)))
-    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
-    _same(fb, u8, fb_w, u8_w)
+    demo = _scene(apt, "demo9", True)
+    sc = Scene(apt, demo.sph, demo.mat, demo.ns, light=demo.light, grid=True)     # a degenerate grid: nothing is large
+    p = sc.params(48, 32, 8, 5, mode="nee", rr=True, seed=11, grid=True)
+    fb, u8 = sc.frame(p)
+    same((fb, u8), sc.frame(sc.params(48, 32, 8, 5, mode="nee", rr=True, seed=11, grid=False)))
+    fb_w, u8_w, _, _ = mr.render_frame(oracle_params(p), sc.sph, sc.mat)
+    same((fb, u8), (fb_w, u8_w))
 
 
 @pytest.mark.parametrize("name,grid,b,c", [("diff8", False, 517, 700), ("demo9", False, 517, 700), ("big1030", True, 117, 203),
                                            ("big1030", False, 117, 203)])
 def test_frame_mid_image_pixel_range(apt, name, grid, b, c):
-    sc = _scene(apt, name, True, grid=name == "big1030")
+    sc = _scene(apt, name, True)
     w, h = (48, 32) if name != "big1030" else (24, 16)
-    p = sc.params(apt, w, h, 16, 5, seed=2, grid=grid, flags=apt.APT_FLAG_RETIRE)      # RETIRE: accepted, changes nothing
-    fb, u8 = sc.frame(apt, p, pixel_begin=b, pixel_count=c)
-    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, pixel_begin=b, pixel_count=c)
-    _same(fb, u8, fb_w, u8_w)
+    p = sc.params(w, h, 16, 5, mode="nee", seed=2, grid=grid, flags=apt.APT_FLAG_RETIRE)      # RETIRE: accepted, changes nothing
+    fb, u8 = sc.frame(p, pixel_begin=b, pixel_count=c)
+    fb_w, u8_w, _, _ = mr.render_frame(oracle_params(p.copy(flags=p.flags & ~apt.APT_FLAG_RETIRE)), sc.sph, sc.mat, pixel_begin=b, pixel_count=c)
+    same((fb, u8), (fb_w, u8_w))
 
 
 @pytest.mark.parametrize("lamp", [False, True], ids=["stock", "lamp"])
 @pytest.mark.parametrize("name,grid", [("diff8", False), ("demo9", False), ("big1030", False), ("big1030", True)])
 def test_paths_bitwise_with_ranges(apt, name, grid, lamp):
     from oracle import oracle
-    sc = _scene(apt, name, lamp, grid=name == "big1030")
-    p = sc.params(apt, 16, 16, 4, 8, rr=True, seed=9, grid=grid)
-    rays = oracle.gen_rays_counter(_oracle_params(p))
+    sc = _scene(apt, name, lamp)
+    p = sc.params(16, 16, 4, 8, mode="nee", rr=True, seed=9, grid=grid)
+    rays = oracle.gen_rays_counter(oracle_params(p))
     n = rays.shape[1]
     want, bad, segments = mr.trace(rays, sc.sph, sc.mat, sc.ns, 8, p.eps, p.seed, np.arange(n, dtype=np.uint64), rr_start=2, light=sc.light, nee=True, gloss=False)
     assert not bad.any()
     with apt.render.TraceCounter() as tc:
-        got = sc.paths(apt, p, rays)
+        got = sc.paths(p, rays)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:5]
     assert tc.value == segments > n                       # shadow segments count as traced segments
     b, c = 1001, 1537                                     # a path range of the whole-image buffers, then the same range in band buffers
-    got = sc.paths(apt, p.copy(path_begin=b, path_count=c), rays)
+    got = sc.paths(p.copy(path_begin=b, path_count=c), rays)
     assert np.array_equal(got[:, b:b + c].view(np.uint32), want[:, b:b + c].view(np.uint32))
     assert np.isnan(got[:, :b]).all() and np.isnan(got[:, b + c:]).all()
     pb = p.copy(path_begin=b, path_count=c, flags=p.flags | apt.APT_FLAG_BAND_BUFFERS)
-    got = sc.paths(apt, pb, np.ascontiguousarray(rays[:, b:b + c]))
+    got = sc.paths(pb, np.ascontiguousarray(rays[:, b:b + c]))
     assert np.array_equal(got.view(np.uint32), want[:, b:b + c].view(np.uint32))
     for depth in (1, 2, 5):                               # no roulette, the other depths
-        q = sc.params(apt, 16, 16, 4, depth, seed=9, grid=grid)
+        q = sc.params(16, 16, 4, depth, mode="nee", seed=9, grid=grid)
         want, _, _ = mr.trace(rays, sc.sph, sc.mat, sc.ns, depth, q.eps, q.seed, np.arange(n, dtype=np.uint64), light=sc.light, nee=True, gloss=False)
-        got = sc.paths(apt, q, rays)
+        got = sc.paths(q, rays)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), depth
         if depth == 1:
-            off = sc.paths(apt, sc.params(apt, 16, 16, 4, 1, nee=False, seed=9, grid=grid), rays)
+            off = sc.paths(sc.params(16, 16, 4, 1, seed=9, grid=grid), rays)
             assert np.array_equal(got.view(np.uint32), off.view(np.uint32))
 
 
 def test_a_light_of_any_material_needs_no_special_case(apt):
     """A mirror light with a non-zero albedo: bit for bit the restatement (the header gives it no special case)."""
     base = _scene(apt, "demo9", True)
-    sc = Scene(apt, "demo9", True)
-    sc.mat = base.mat.copy()
-    sc.mat[sc.light] = 0                                  # APT_MAT_SPEC
-    sc.sph = sc.sph.copy()
-    sc.sph[:90].reshape(10, 9)[7:, sc.light] = 0.5
-    sc.d_sph, sc.d_mat = _dev(sc.sph), _dev(sc.mat)
-    p = sc.params(apt, 48, 32, 8, 6, seed=5)
-    fb, u8 = sc.frame(apt, p)
-    fb_w, u8_w, _, _ = mr.render_frame(_oracle_params(p), sc.sph, sc.mat)
-    _same(fb, u8, fb_w, u8_w)
+    sph, mat = base.sph.copy(), base.mat.copy()
+    mat[base.light] = 0                                   # APT_MAT_SPEC
+    sph[:90].reshape(10, 9)[7:, base.light] = 0.5
+    sc = Scene(apt, sph, mat, base.ns, light=base.light)
+    p = sc.params(48, 32, 8, 6, mode="nee", seed=5)
+    fb, u8 = sc.frame(p)
+    fb_w, u8_w, _, _ = mr.render_frame(oracle_params(p), sc.sph, sc.mat)
+    same((fb, u8), (fb_w, u8_w))
 
 
 # ---- against the renderer that exists: the same launches without the flag (the yardstick is the flag-off path, never the new code) ----
@@ -211,12 +132,12 @@ def _on_off(apt, name, lamp, depth, seed):
     """-> (radiance with the flag, without it, the camera ray hits an emitter) for 2^17 camera rays; float64 [3][n], bool [n]."""
     from oracle import oracle
     sc = _scene(apt, name, lamp)
-    p = sc.params(apt, 128, 64, 4, depth, seed=seed)
+    p = sc.params(128, 64, 4, depth, mode="nee", seed=seed)
     assert p.num_paths == 1 << 17
-    rays = oracle.gen_rays_counter(_oracle_params(p))
-    on = sc.paths(apt, p, rays).astype(np.float64)
-    off = sc.paths(apt, sc.params(apt, 128, 64, 4, depth, nee=False, seed=seed), rays).astype(np.float64)
-    first = sc.paths(apt, sc.params(apt, 128, 64, 4, 1, nee=False, seed=seed), rays)
+    rays = oracle.gen_rays_counter(oracle_params(p))
+    on = sc.paths(p, rays).astype(np.float64)
+    off = sc.paths(sc.params(128, 64, 4, depth, seed=seed), rays).astype(np.float64)
+    first = sc.paths(sc.params(128, 64, 4, 1, seed=seed), rays)
     return on, off, first.any(axis=0)
 
 
