@@ -29,33 +29,107 @@ APT_FEATURE_COVERAGE, APT_FEATURE_DEPTH, APT_FEATURE_NORMAL, APT_FEATURE_ALBEDO,
 MAT_GLOSS = 3                           # with APT_FLAG_GLOSS: gen_data.gloss(alpha) makes the word (APT_MAT_GLOSS_WORD)
 MAT_SPEC, MAT_DIFF, MAT_REFR = 0, 1, 2  # material codes of the *_materials entries (include/render_mi355x.h APT_MAT_*)
 
-# every symbol include/render_mi355x.h declares
-ABI_SYMBOLS = ["apt_default_params", "render_do", "apt_set_default_params", "render_do_ex", "render_frame",
-               "apt_gen_rays_device", "apt_decode_color_device", "apt_gen_rays_host", "apt_gen_spheres_host",
-               "apt_gen_scene_host", "apt_write_ppm", "apt_abi_version", "apt_last_error", "apt_device_count",
-               "apt_set_trace_counter", "apt_selftest_sqrt", "apt_selftest_div3", "apt_set_refill_lanes", "apt_test_scene", "apt_mt19937_checkpoints_host", "apt_gen_rays_mt_device", "apt_build_grid_host",
-               "apt_last_status", "apt_render_do", "apt_render_host", "apt_context_create", "apt_context_destroy",
-               "apt_context_set_params", "apt_context_set_trace_counter", "apt_context_set_refill_lanes",
-               "apt_context_render_do", "apt_context_render_do_ex", "apt_context_render_frame",
-               "apt_multi_create", "apt_multi_render", "apt_multi_destroy",
-               "apt_decode_color_band", "apt_mt19937_checkpoints_window", "apt_gen_rays_mt_device_ex", "apt_build_grid_device", "apt_render_frame_mt",
-               "apt_context_check", "apt_check", "apt_context_set_debug", "apt_set_debug", "apt_context_get_debug", "apt_get_debug", "apt_grid_flags",
-               "apt_render_frame_materials", "apt_context_render_frame_materials", "apt_render_paths_materials",
-               "apt_context_render_paths_materials", "apt_gen_spheres_materials_host", "apt_gen_scene_materials_host",
-               "apt_materials_flags_host",
-               "apt_lights_bytes", "apt_build_lights_host", "apt_render_frame_lights", "apt_context_render_frame_lights",
-               "apt_render_paths_lights", "apt_context_render_paths_lights",
-               "apt_camera_default_host", "apt_camera_build_host", "apt_camera_check_host", "apt_context_set_camera", "apt_set_camera",
-               "apt_gen_rays_camera_device",
-               "apt_environment_build_host", "apt_environment_check_host", "apt_context_set_environment", "apt_set_environment",
-               "apt_film_pass_seed", "apt_render_frame_film", "apt_context_render_frame_film", "apt_film_curve_host",
-               "apt_film_resolve_device", "apt_film_resolve_host", "apt_write_pfm",
-               "apt_render_frame_features", "apt_context_render_frame_features",
-               "apt_selftest_direction", "apt_selftest_direction_host", "apt_selftest_chain_states_host", "apt_selftest_div3_seeded",
-               "apt_selftest_tent_bits_host"]
 # the reference declares render_do with C++ linkage (src/main.cpp:9-10): the mangled symbol is exported too
 CXX_RENDER_DO = "_Z9render_dojPvS_PhS0_S0_"
 ABI_VERSION = 3
+
+# The prototypes of include/render_mi355x.h, one line per symbol in the header's order: name -> (restype, [argtypes]).  lib() sets them
+# on the loaded library, so a bare Python int arrives at its full width and a value of the wrong kind raises instead of being
+# reinterpreted.  A new entry is declared HERE; tests/test_abi_prototypes.py holds the table to the header.  uint32_t U32, uint64_t U64,
+# int I, double D, size_t SZ, const char * S; every other pointer or array parameter is P (c_void_p also for pointers to records: it
+# takes None, an address, byref(...), arrays and typed pointers alike); a void return is None.
+P, U32, U64, I, D, SZ, S = (ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_size_t,
+                            ctypes.c_char_p)
+PROTOTYPES = {
+    "apt_default_params": (None, [P]),
+    "render_do": (None, [U32, P, P, P, P, P]),
+    "apt_render_do": (None, [U32, P, P, P, P, P]),
+    "apt_set_default_params": (I, [P]),
+    "apt_render_host": (I, [U32, P, P, P]),
+    "apt_context_create": (P, []),
+    "apt_context_destroy": (None, [P]),
+    "apt_context_set_params": (I, [P, P]),
+    "apt_context_set_trace_counter": (I, [P, P]),
+    "apt_context_set_refill_lanes": (I, [P, U32]),
+    "apt_context_check": (I, [P, P]),
+    "apt_check": (I, [P]),
+    "apt_context_set_debug": (I, [P, S, D]),
+    "apt_set_debug": (I, [S, D]),
+    "apt_context_get_debug": (I, [P, S, P]),
+    "apt_get_debug": (I, [S, P]),
+    "apt_context_render_do": (None, [P, U32, P, P, P, P, P]),
+    "apt_context_render_do_ex": (I, [P, P, P, P, P, P]),
+    "apt_context_render_frame": (I, [P, P, P, P, U64, U64, P, P]),
+    "render_do_ex": (I, [P, P, P, P, P]),
+    "render_frame": (I, [P, P, P, U64, U64, P, P]),
+    "apt_render_frame_materials": (I, [P, P, P, P, U64, U64, P, P]),
+    "apt_context_render_frame_materials": (I, [P, P, P, P, P, U64, U64, P, P]),
+    "apt_render_paths_materials": (I, [P, P, P, P, P, P]),
+    "apt_context_render_paths_materials": (I, [P, P, P, P, P, P, P]),
+    "apt_lights_bytes": (SZ, [U32, U32]),
+    "apt_build_lights_host": (I, [P, U32, P, U32, P, SZ, P]),
+    "apt_render_frame_lights": (I, [P, P, P, P, P, U64, U64, P, P]),
+    "apt_context_render_frame_lights": (I, [P, P, P, P, P, P, U64, U64, P, P]),
+    "apt_render_paths_lights": (I, [P, P, P, P, P, P, P]),
+    "apt_context_render_paths_lights": (I, [P, P, P, P, P, P, P, P]),
+    "apt_gen_spheres_materials_host": (I, [P, P]),
+    "apt_gen_scene_materials_host": (I, [U32, U64, P]),
+    "apt_materials_flags_host": (U32, [P, U32]),
+    "apt_camera_default_host": (I, [U32, U32, P]),
+    "apt_camera_build_host": (I, [P, P, P, D, D, D, D, U32, U32, P]),
+    "apt_camera_check_host": (I, [P]),
+    "apt_context_set_camera": (I, [P, P]),
+    "apt_set_camera": (I, [P]),
+    "apt_gen_rays_camera_device": (I, [P, P, P, P]),
+    "apt_environment_build_host": (I, [P, P, P, P, D, U32, P]),
+    "apt_environment_check_host": (I, [P]),
+    "apt_context_set_environment": (I, [P, P]),
+    "apt_set_environment": (I, [P]),
+    "apt_film_pass_seed": (U64, [U64, U32]),
+    "apt_render_frame_film": (I, [P, P, P, P, P, U64, U64, P, U32]),
+    "apt_context_render_frame_film": (I, [P, P, P, P, P, P, U64, U64, P, U32]),
+    "apt_film_curve_host": (I, [U32, P]),
+    "apt_film_resolve_device": (I, [P, P, P, U64, P, P, P]),
+    "apt_film_resolve_host": (I, [P, P, U64, P, P, P]),
+    "apt_write_pfm": (I, [S, U32, U32, P]),
+    "apt_render_frame_features": (I, [P, P, P, U64, U64, P]),
+    "apt_context_render_frame_features": (I, [P, P, P, P, U64, U64, P]),
+    "apt_multi_create": (I, [P, U32, U32, P, P, P]),
+    "apt_multi_render": (I, [P, P, P, P]),
+    "apt_multi_destroy": (None, [P]),
+    "apt_test_scene": (I, [P, P, P, P, P]),
+    "apt_gen_rays_device": (I, [P, P, P]),
+    "apt_mt19937_checkpoints_host": (I, [U32, U64, U32, P]),
+    "apt_gen_rays_mt_device": (I, [P, P, P, U32, U64, P]),
+    "apt_mt19937_checkpoints_window": (I, [P, U32, U64, U64, U32, P, P]),
+    "apt_gen_rays_mt_device_ex": (I, [P, P, P, U32, U64, U64, P]),
+    "apt_render_frame_mt": (I, [P, P, P, U64, U64, P, U64, U64, P, P]),
+    "apt_decode_color_device": (I, [P, P, P, P, P]),
+    "apt_decode_color_band": (I, [P, P, P, U64, P, P]),
+    "apt_gen_rays_host": (I, [U32, U32, U32, U32, P]),
+    "apt_gen_spheres_host": (I, [P]),
+    "apt_gen_scene_host": (I, [U32, U64, P, P]),
+    "apt_build_grid_host": (I, [P, U32, P, P]),
+    "apt_grid_flags": (U32, [P, U32]),
+    "apt_build_grid_device": (I, [P, U32, P, P, SZ, P]),
+    "apt_write_ppm": (I, [S, U32, U32, P]),
+    "apt_set_trace_counter": (I, [P]),
+    "apt_selftest_sqrt": (I, [I, P, U64, U64, P]),
+    "apt_selftest_div3": (I, [P, U64, U64, P]),
+    "apt_selftest_div3_seeded": (I, [P, I, U64, U64, P]),
+    "apt_selftest_direction": (I, [P, P, U64, P, P]),
+    "apt_selftest_direction_host": (I, [P, U64, D, P, P]),
+    "apt_selftest_chain_states_host": (I, [U32, U64, U64, U64, P]),
+    "apt_selftest_tent_bits_host": (I, [P, U64, P]),
+    "apt_set_refill_lanes": (I, [U32]),
+    "apt_abi_version": (I, []),
+    "apt_last_error": (S, []),
+    "apt_last_status": (I, []),
+    "apt_device_count": (I, []),
+    CXX_RENDER_DO: (None, [U32, P, P, P, P, P]),
+}
+# every symbol include/render_mi355x.h declares
+ABI_SYMBOLS = [name for name in PROTOTYPES if name != CXX_RENDER_DO]
 
 
 class AptError(RuntimeError):
@@ -143,21 +217,9 @@ def lib():
             h = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # e.g. libamdhip64 not found
             raise AptError(f"cannot load {LIB_PATH}: {e}") from e
-        h.apt_last_error.restype = ctypes.c_char_p
-        h.render_do.restype = None
-        h.apt_default_params.restype = None
-        for name in ABI_SYMBOLS + [CXX_RENDER_DO]:
-            getattr(h, name)
-        h.apt_context_create.restype = ctypes.c_void_p
-        h.apt_context_destroy.restype = None
-        h.apt_context_render_do.restype = None
-        h.apt_render_do.restype = None
-        h.apt_multi_destroy.restype = None
-        h.apt_lights_bytes.restype = ctypes.c_size_t
-        h.apt_materials_flags_host.restype = ctypes.c_uint32
-        h.apt_film_pass_seed.restype = ctypes.c_uint64
-        h.apt_film_pass_seed.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
-        getattr(h, CXX_RENDER_DO).restype = None
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(h, name)       # every symbol resolves, or AttributeError names the missing one
+            fn.restype, fn.argtypes = restype, argtypes
         if h.apt_abi_version() != ABI_VERSION:
             raise AptError("librender_mi355x.so ABI version mismatch")
         _lib = h

@@ -1,7 +1,6 @@
 """Per-sample colours -> image, the counterpart of scripts/data_visualization.py:
 decode_color (:20-59) runs on the GPU (apt_decode_color_device), write_ppm (:11-17) in the
 library's host code.  No CPU fallback for decode_color."""
-import ctypes
 import sys
 
 import numpy as np
@@ -18,8 +17,7 @@ def write_ppm(w, h, data, path="./output/color.ppm"):
     data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     if data.size != w * h * 3:
         raise ValueError("write_ppm: data does not match w*h*3")
-    check(lib().apt_write_ppm(path.encode(), ctypes.c_uint32(w), ctypes.c_uint32(h),
-                              data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "apt_write_ppm")
+    check(lib().apt_write_ppm(path.encode(), w, h, data.ctypes.data), "apt_write_ppm")
 
 
 def decode_color(path, w, h, s, out_path="./output/color.ppm", device="cuda"):

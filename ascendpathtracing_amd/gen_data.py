@@ -22,8 +22,7 @@ def gen_rays(w, h, s, seed=0, out_dir=None):
     (the reference always writes ./input/rays.bin, gen_data.py:71)."""
     n = w * h * 4 * s
     rays = np.empty(6 * n, dtype=np.float32)
-    check(lib().apt_gen_rays_host(ctypes.c_uint32(w), ctypes.c_uint32(h), ctypes.c_uint32(s), ctypes.c_uint32(seed),
-                                  _fptr(rays)), "apt_gen_rays_host")
+    check(lib().apt_gen_rays_host(w, h, s, seed, _fptr(rays)), "apt_gen_rays_host")
     if out_dir is not None:
         rays.tofile(os.path.join(out_dir, "rays.bin"))
     return rays.reshape(6, n)
@@ -34,9 +33,7 @@ def mt19937_checkpoints(num_paths, seed=0, stride=64):
     blocks = (num_paths + 155) // 156
     n = (blocks + stride - 1) // stride
     states = np.empty((n, 624), dtype=np.uint32)
-    check(lib().apt_mt19937_checkpoints_host(ctypes.c_uint32(seed), ctypes.c_uint64(blocks), ctypes.c_uint32(stride),
-                                             states.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
-          "apt_mt19937_checkpoints_host")
+    check(lib().apt_mt19937_checkpoints_host(seed, blocks, stride, states.ctypes.data), "apt_mt19937_checkpoints_host")
     return states
 
 
@@ -48,11 +45,8 @@ def mt19937_checkpoints_window(first_block, num_blocks, seed=0, stride=64, state
     states = np.empty((n, 624), dtype=np.uint32)
     out = np.empty(624, dtype=np.uint32)
     st = None if state_in is None else np.ascontiguousarray(state_in, dtype=np.uint32)
-    u32p = ctypes.POINTER(ctypes.c_uint32)
-    check(lib().apt_mt19937_checkpoints_window(None if st is None else st.ctypes.data_as(u32p), ctypes.c_uint32(seed),
-                                               ctypes.c_uint64(first_block), ctypes.c_uint64(num_blocks), ctypes.c_uint32(stride),
-                                               states.ctypes.data_as(u32p), out.ctypes.data_as(u32p)),
-          "apt_mt19937_checkpoints_window")
+    check(lib().apt_mt19937_checkpoints_window(None if st is None else st.ctypes.data, seed, first_block, num_blocks, stride,
+                                               states.ctypes.data, out.ctypes.data), "apt_mt19937_checkpoints_window")
     return states, out
 
 
@@ -68,10 +62,8 @@ def gen_rays_device(w, h, s, seed=0, stride=64, checkpoints=None, stream=None):
     if checkpoints is None:
         checkpoints = torch.from_numpy(mt19937_checkpoints(p.num_paths, seed, stride).view(np.int32)).cuda()
     rays = torch.empty(6 * p.num_paths, dtype=torch.float32, device="cuda")
-    check(lib().apt_gen_rays_mt_device(ctypes.byref(p), render._stream_handle(stream),
-                                       ctypes.c_void_p(checkpoints.data_ptr()), ctypes.c_uint32(stride),
-                                       ctypes.c_uint64(checkpoints.shape[0]), ctypes.c_void_p(rays.data_ptr())),
-          "apt_gen_rays_mt_device")
+    check(lib().apt_gen_rays_mt_device(ctypes.byref(p), render._stream_handle(stream), checkpoints.data_ptr(), stride,
+                                       checkpoints.shape[0], rays.data_ptr()), "apt_gen_rays_mt_device")
     return rays.view(6, -1)
 
 
@@ -99,9 +91,7 @@ def materials_flags(table):
     """apt_materials_flags_host: the flags a material table earns -- APT_FLAG_GLOSS when it holds a well-formed gloss word, else 0.
     `table`: the host array of codes (gen_spheres_materials / gen_scene_materials).  OR the result into make_params(flags=)."""
     t = np.ascontiguousarray(np.asarray(table).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32).ravel()
-    f = lib().apt_materials_flags_host
-    f.restype = ctypes.c_uint32
-    return int(f(t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.c_uint32(t.size)))
+    return int(lib().apt_materials_flags_host(t.ctypes.data, t.size))
 
 
 def gen_spheres_materials(gloss=None):
@@ -110,8 +100,7 @@ def gen_spheres_materials(gloss=None):
     gloss=alpha: the mirror ball (sphere 6) is a rough-metal ball of that roughness instead (render with APT_FLAG_GLOSS)."""
     sph = np.zeros(128, dtype=np.float32)
     mat = np.zeros(9, dtype=np.uint32)
-    check(lib().apt_gen_spheres_materials_host(_fptr(sph), mat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
-          "apt_gen_spheres_materials_host")
+    check(lib().apt_gen_spheres_materials_host(_fptr(sph), mat.ctypes.data), "apt_gen_spheres_materials_host")
     if gloss is not None:
         mat[6] = _gloss_word(gloss)
     return sph, mat.view(np.int32)
@@ -121,8 +110,7 @@ def gen_scene_materials(num_spheres, seed=0):
     """gen_scene(num_spheres, seed) and the material codes that go with it (apt_gen_scene_materials_host, the same seed): walls and
     light MAT_DIFF, every small sphere one of the three codes -> (spheres float32 zero-padded [10][Ns], materials int32 [Ns])."""
     mat = np.zeros(num_spheres, dtype=np.uint32)
-    check(lib().apt_gen_scene_materials_host(ctypes.c_uint32(num_spheres), ctypes.c_uint64(seed),
-                                             mat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "apt_gen_scene_materials_host")
+    check(lib().apt_gen_scene_materials_host(num_spheres, seed, mat.ctypes.data), "apt_gen_scene_materials_host")
     return gen_scene(num_spheres, seed), mat.view(np.int32)
 
 
@@ -169,7 +157,7 @@ def with_lamps(spheres, num_spheres, indices, radius=1.5, centres=None, emission
 
 def lights_bytes(num_spheres, num_lights):
     """apt_lights_bytes: the size of a light table of num_lights lights for a scene of num_spheres spheres."""
-    return int(lib().apt_lights_bytes(ctypes.c_uint32(num_spheres), ctypes.c_uint32(num_lights)))
+    return int(lib().apt_lights_bytes(num_spheres, num_lights))
 
 
 def build_lights(spheres, num_spheres, indices=None):
@@ -186,11 +174,10 @@ def build_lights(spheres, num_spheres, indices=None):
         if ind.size and (ind.min() < 0 or ind.max() > 0xFFFFFFFF):
             raise AptError("build_lights: a light index is out of range")
         ind = ind.astype(np.uint32)
-        ptr, n, bound = ind.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(ind.size), int(ind.size)
+        ptr, n, bound = ind.ctypes.data, int(ind.size), int(ind.size)
     buf = np.zeros(lights_bytes(num_spheres, bound) // 4, dtype=np.uint32)
     nbytes = ctypes.c_size_t(0)
-    check(lib().apt_build_lights_host(_fptr(spheres), ctypes.c_uint32(num_spheres), ptr, ctypes.c_uint32(n),
-                                      buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes), ctypes.byref(nbytes)),
+    check(lib().apt_build_lights_host(_fptr(spheres), num_spheres, ptr, n, buf.ctypes.data, buf.nbytes, ctypes.byref(nbytes)),
           "apt_build_lights_host")
     return buf[:nbytes.value // 4].copy()
 
@@ -199,11 +186,9 @@ def gen_scene(num_spheres, seed=0, out_dir=None):
     """Build-defined large scene (BASELINE config 4): six walls, Ns-7 random small spheres,
     light at index Ns-1.  -> zero-padded [10][Ns] table."""
     n = ctypes.c_size_t(0)
-    check(lib().apt_gen_scene_host(ctypes.c_uint32(num_spheres), ctypes.c_uint64(seed), None, ctypes.byref(n)),
-          "apt_gen_scene_host")
+    check(lib().apt_gen_scene_host(num_spheres, seed, None, ctypes.byref(n)), "apt_gen_scene_host")
     sph = np.zeros(n.value, dtype=np.float32)
-    check(lib().apt_gen_scene_host(ctypes.c_uint32(num_spheres), ctypes.c_uint64(seed), _fptr(sph), None),
-          "apt_gen_scene_host")
+    check(lib().apt_gen_scene_host(num_spheres, seed, _fptr(sph), None), "apt_gen_scene_host")
     if out_dir is not None:
         sph.tofile(os.path.join(out_dir, "spheres.bin"))
     return sph
@@ -214,11 +199,9 @@ def build_grid(spheres, num_spheres):
     device; pass its device address as RenderParams.accel."""
     spheres = np.ascontiguousarray(spheres, dtype=np.float32).ravel()
     nbytes = ctypes.c_size_t(0)
-    check(lib().apt_build_grid_host(_fptr(spheres), ctypes.c_uint32(num_spheres), None, ctypes.byref(nbytes)),
-          "apt_build_grid_host")
+    check(lib().apt_build_grid_host(_fptr(spheres), num_spheres, None, ctypes.byref(nbytes)), "apt_build_grid_host")
     buf = np.zeros(nbytes.value // 4, dtype=np.uint32)
-    check(lib().apt_build_grid_host(_fptr(spheres), ctypes.c_uint32(num_spheres),
-                                    buf.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nbytes)), "apt_build_grid_host")
+    check(lib().apt_build_grid_host(_fptr(spheres), num_spheres, buf.ctypes.data, ctypes.byref(nbytes)), "apt_build_grid_host")
     return buf
 
 
@@ -239,8 +222,7 @@ def grid_flags(grid, num_spheres):
             raise AptError("grid_flags: the buffer is shorter than a grid header (128 bytes)")
         head = flat.view(np.uint8)[:128]
     head = np.ascontiguousarray(head)
-    lib().apt_grid_flags.restype = ctypes.c_uint32
-    return int(lib().apt_grid_flags(head.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(num_spheres)))
+    return int(lib().apt_grid_flags(head.ctypes.data, num_spheres))
 
 
 def build_grid_device(spheres_dev, num_spheres, stream=None):
@@ -252,11 +234,9 @@ def build_grid_device(spheres_dev, num_spheres, stream=None):
     require_gpu()
     st = render._stream_handle(stream)
     nbytes = ctypes.c_size_t(0)
-    check(lib().apt_build_grid_device(ctypes.c_void_p(spheres_dev.data_ptr()), ctypes.c_uint32(num_spheres), st, None,
-                                      ctypes.c_size_t(0), ctypes.byref(nbytes)), "apt_build_grid_device")
+    check(lib().apt_build_grid_device(spheres_dev.data_ptr(), num_spheres, st, None, 0, ctypes.byref(nbytes)), "apt_build_grid_device")
     buf = torch.empty(nbytes.value // 4, dtype=torch.int32, device=spheres_dev.device)
-    check(lib().apt_build_grid_device(ctypes.c_void_p(spheres_dev.data_ptr()), ctypes.c_uint32(num_spheres), st,
-                                      ctypes.c_void_p(buf.data_ptr()), ctypes.c_size_t(nbytes.value), ctypes.byref(nbytes)),
+    check(lib().apt_build_grid_device(spheres_dev.data_ptr(), num_spheres, st, buf.data_ptr(), nbytes.value, ctypes.byref(nbytes)),
           "apt_build_grid_device")
     return buf
 
@@ -279,7 +259,7 @@ def default_camera(w, h):
     """The reference's camera for a w x h image as a record (apt_camera_default_host): gen_rays' frame bit for bit, offset 140, no lens.
     Setting it renders what no camera renders, through the camera kernels."""
     c = _new_camera()
-    check(lib().apt_camera_default_host(ctypes.c_uint32(w), ctypes.c_uint32(h), ctypes.byref(c)), "apt_camera_default_host")
+    check(lib().apt_camera_default_host(w, h, ctypes.byref(c)), "apt_camera_default_host")
     return c
 
 
@@ -310,9 +290,8 @@ def camera(eye, dir=None, target=None, up=(0, 1, 0), vfov_deg=None, scale=0.5135
         focus = 0.0
     d3 = ctypes.c_double * 3
     c = _new_camera()
-    check(lib().apt_camera_build_host(d3(*eye), d3(*[float(x) for x in dir]), d3(*[float(x) for x in up]), ctypes.c_double(scale),
-                                      ctypes.c_double(offset), ctypes.c_double(aperture), ctypes.c_double(focus), ctypes.c_uint32(width),
-                                      ctypes.c_uint32(height), ctypes.byref(c)), "apt_camera_build_host")
+    check(lib().apt_camera_build_host(d3(*eye), d3(*[float(x) for x in dir]), d3(*[float(x) for x in up]), scale, offset, aperture, focus,
+                                      width, height, ctypes.byref(c)), "apt_camera_build_host")
     return c
 
 
@@ -334,8 +313,7 @@ def environment(horizon=(0.0, 0.0, 0.0), zenith=None, sun_dir=(0.0, 1.0, 0.0), s
     e = ApEnvironment()
     e.struct_size = ctypes.sizeof(ApEnvironment)
     check(lib().apt_environment_build_host(d3(*rgb(horizon)), d3(*rgb(horizon if zenith is None else zenith)), d3(*[float(x) for x in sun_dir]),
-                                           d3(*rgb(sun_radiance)), ctypes.c_double(omc),
-                                           ctypes.c_uint32(APT_ENV_SAMPLE_SUN if sample_sun and omc > 0.0 else 0), ctypes.byref(e)),
+                                           d3(*rgb(sun_radiance)), omc, APT_ENV_SAMPLE_SUN if sample_sun and omc > 0.0 else 0, ctypes.byref(e)),
           "apt_environment_build_host")
     return e
 
@@ -358,7 +336,7 @@ def film_curve(curve="srgb"):
     if not isinstance(code, int):
         raise AptError(f"film_curve: unknown curve {curve!r}")
     table = np.zeros(256, dtype=np.float32)
-    check(lib().apt_film_curve_host(ctypes.c_uint32(code), _fptr(table)), "apt_film_curve_host")
+    check(lib().apt_film_curve_host(code, _fptr(table)), "apt_film_curve_host")
     return table
 
 

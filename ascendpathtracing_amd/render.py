@@ -12,9 +12,7 @@ from ._lib import MAT_DIFF, MAT_REFR, MAT_SPEC, RenderParams, check, lib, requir
 def _stream_handle(stream):
     if stream is None:
         stream = torch.cuda.current_stream()
-    if isinstance(stream, int):
-        return ctypes.c_void_p(stream)
-    return ctypes.c_void_p(stream.cuda_stream)
+    return stream if isinstance(stream, int) else stream.cuda_stream
 
 
 def _dev_f32(t, name, numel=None):
@@ -22,7 +20,7 @@ def _dev_f32(t, name, numel=None):
         raise _lib.AptError(f"{name} must be a contiguous float32 tensor on the GPU")
     if numel is not None and t.numel() != numel:
         raise _lib.AptError(f"{name} has {t.numel()} elements, expected {numel}")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def _buffer_paths(params):
@@ -37,13 +35,32 @@ def _dev_materials(t, num_spheres):
         raise _lib.AptError("materials must be a contiguous int32 tensor on the GPU")
     if t.numel() != num_spheres:
         raise _lib.AptError(f"materials has {t.numel()} elements, expected num_spheres = {num_spheres}")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def _dev_lights(t):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= 16):
         raise _lib.AptError("lights must be a contiguous int32 tensor on the GPU holding a light table (gen_data.build_lights)")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
+
+
+# The C entries by their context-free names, as the header pairs them (the pairs are irregular, so they are listed, not derived).
+# _MATERIAL_FORMS: the *_materials and *_lights forms of the two entries that take materials= / lights=.
+# _CONTEXT_ENTRY: the apt_context_* form of each, which takes the context's handle in front.
+_MATERIAL_FORMS = {"render_do_ex": ("apt_render_paths_materials", "apt_render_paths_lights"),
+                   "render_frame": ("apt_render_frame_materials", "apt_render_frame_lights")}
+_CONTEXT_ENTRY = {"apt_set_default_params": "apt_context_set_params", "apt_set_refill_lanes": "apt_context_set_refill_lanes",
+                  "apt_set_trace_counter": "apt_context_set_trace_counter", "apt_set_camera": "apt_context_set_camera",
+                  "apt_set_environment": "apt_context_set_environment", "apt_set_debug": "apt_context_set_debug",
+                  "apt_get_debug": "apt_context_get_debug", "apt_check": "apt_context_check",
+                  "render_do": "apt_context_render_do", "render_do_ex": "apt_context_render_do_ex",
+                  "render_frame": "apt_context_render_frame",
+                  "apt_render_paths_materials": "apt_context_render_paths_materials",
+                  "apt_render_frame_materials": "apt_context_render_frame_materials",
+                  "apt_render_paths_lights": "apt_context_render_paths_lights",
+                  "apt_render_frame_lights": "apt_context_render_frame_lights",
+                  "apt_render_frame_film": "apt_context_render_frame_film",
+                  "apt_render_frame_features": "apt_context_render_frame_features"}
 
 
 def _material_args(entry, params, materials, lights):
@@ -54,8 +71,8 @@ def _material_args(entry, params, materials, lights):
         return entry, ()
     mat = (_dev_materials(materials, params.num_spheres),)
     if lights is None:
-        return _MATERIALS_ENTRY[entry], mat
-    return _MATERIALS_ENTRY[entry].replace("_materials", "_lights"), mat + (_dev_lights(lights),)
+        return _MATERIAL_FORMS[entry][0], mat
+    return _MATERIAL_FORMS[entry][1], mat + (_dev_lights(lights),)
 
 
 def sphere_floats(num_spheres):
@@ -63,82 +80,13 @@ def sphere_floats(num_spheres):
     return (num_spheres * 10 + 127) // 128 * 128
 
 
-# The bodies of render_do_ex / render_frame, shared by the default-context functions and Context's methods: `entry` is the C entry
-# (also the name errors are reported under), `handle` its leading context argument, if any.
-# materials (int32 tensor of num_spheres codes, MAT_*): the entry's *_materials form; None: the entry itself, untouched.
-# lights (int32 tensor, a light table: gen_data.build_lights), with materials only: the entry's *_lights form.
-def _render_do_ex(entry, handle, params, stream, rays, spheres, colors, materials=None, lights=None):
-    require_gpu()
-    n = _buffer_paths(params)
-    entry, mat = _material_args(entry, params, materials, lights)
-    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
-                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat,
-                                _dev_f32(colors, "colors", 3 * n)), entry)
-
-
-_MATERIALS_ENTRY = {"render_do_ex": "apt_render_paths_materials", "apt_context_render_do_ex": "apt_context_render_paths_materials",
-                    "render_frame": "apt_render_frame_materials", "apt_context_render_frame": "apt_context_render_frame_materials"}
-
-
-def _render_frame(entry, handle, params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials=None, lights=None):
-    require_gpu()
-    npix = params.width * params.height
-    if pixel_count is None:
-        pixel_count = npix - pixel_begin
-    if fb is None:
-        fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
-    if fb_u8 is None:
-        fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
-    entry, mat = _material_args(entry, params, materials, lights)
-    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
-                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat,
-                                ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(fb, "fb", 3 * pixel_count),
-                                ctypes.c_void_p(fb_u8.data_ptr())), entry)
-    return fb, fb_u8
-
-
-def _render_frame_film(entry, handle, params, spheres, materials, lights, pixel_begin, pixel_count, film, pass_index, stream):
-    require_gpu()
-    if pixel_count is None:
-        pixel_count = params.width * params.height - pixel_begin
-    if film is None:
-        film = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
-    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
-                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
-                                _dev_materials(materials, params.num_spheres), None if lights is None else _dev_lights(lights),
-                                ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count), _dev_f32(film, "film", 3 * pixel_count),
-                                ctypes.c_uint32(pass_index)), entry)
-    return film
-
-
-def _render_frame_features(entry, handle, params, spheres, features, pixel_begin, pixel_count, stream):
-    require_gpu()
-    if pixel_count is None:
-        pixel_count = params.width * params.height - pixel_begin
-    if features is None:
-        features = torch.empty((_lib.APT_FEATURE_PLANES, pixel_count), dtype=torch.float32, device=spheres.device)
-    check(getattr(lib(), entry)(*handle, ctypes.byref(params), _stream_handle(stream),
-                                _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
-                                ctypes.c_uint64(pixel_begin), ctypes.c_uint64(pixel_count),
-                                _dev_f32(features, "features", _lib.APT_FEATURE_PLANES * pixel_count)), entry)
-    return features
-
-
-def render_do(blockDim, l2ctrl, stream, rays, spheres, colors):
-    """void render_do(blockDim, l2ctrl, stream, rays, spheres, colors) -- src/main.cpp:9-10,74.
-    Asynchronous on `stream`; uses the process-wide defaults (apt_set_default_params)."""
-    require_gpu()
-    lib().render_do(ctypes.c_uint32(blockDim), None, _stream_handle(stream), _dev_f32(rays, "rays"),
-                    _dev_f32(spheres, "spheres"), _dev_f32(colors, "colors"))
-    check(lib().apt_last_status(), "render_do")   # void like the reference: the outcome of THIS call, on this thread
-
-
 class Context:
     """apt_context: private settings for render_do / render_do_ex / render_frame (instead of the process-wide
     default context); safe to use from several threads, one context per thread needs no coordination at all."""
+    _private = True     # False in one object only: `_default` below, the process-wide default context, which has no handle
 
     def __init__(self, params=None):
-        self._h = ctypes.c_void_p(lib().apt_context_create())
+        self._h = lib().apt_context_create()
         if not self._h:
             raise _lib.AptError("apt_context_create failed")
         if params is not None:
@@ -151,62 +99,110 @@ class Context:
 
     __del__ = close
 
+    def _call(self, name, *args):
+        """Every entry's crossing of the boundary.  `name` is the context-free entry: the default context calls it, a private one
+        its apt_context_* form with the handle in front.  A failure is reported under the name of the entry that was called."""
+        entry, args = (_CONTEXT_ENTRY[name], (self._h,) + args) if self._private else (name, args)
+        rc = getattr(lib(), entry)(*args)
+        # render_do is void like the reference (rc None): the outcome of THIS call, on this thread, is apt_last_status()
+        check(lib().apt_last_status() if rc is None else rc, entry)
+
     def set_params(self, params):
-        check(lib().apt_context_set_params(self._h, ctypes.byref(params)), "apt_context_set_params")
+        self._call("apt_set_default_params", ctypes.byref(params))
 
     def set_refill_lanes(self, lanes):
-        check(lib().apt_context_set_refill_lanes(self._h, ctypes.c_uint32(lanes)), "apt_context_set_refill_lanes")
+        self._call("apt_set_refill_lanes", lanes)
 
     def set_trace_counter(self, tensor_or_none):
-        ptr = ctypes.c_void_p(tensor_or_none.data_ptr()) if tensor_or_none is not None else None
-        check(lib().apt_context_set_trace_counter(self._h, ptr), "apt_context_set_trace_counter")
+        self._call("apt_set_trace_counter", None if tensor_or_none is None else tensor_or_none.data_ptr())
 
     def set_camera(self, cam):
         """apt_context_set_camera: this context's material frames render from `cam` (gen_data.camera / default_camera; None: the
         reference's camera again), its mirror frame entries refuse while one is set."""
-        check(lib().apt_context_set_camera(self._h, None if cam is None else ctypes.byref(cam)), "apt_context_set_camera")
+        self._call("apt_set_camera", None if cam is None else ctypes.byref(cam))
 
     def set_environment(self, env):
         """apt_context_set_environment: this context's material and light-table entries, frame and buffer mode, gather `env`'s sky and
         sun where a path leaves the scene (gen_data.environment; None: no environment, every image as before); its mirror frame
         entries refuse while one is set."""
-        check(lib().apt_context_set_environment(self._h, None if env is None else ctypes.byref(env)), "apt_context_set_environment")
+        self._call("apt_set_environment", None if env is None else ctypes.byref(env))
 
     def set_debug(self, key, value):
-        check(lib().apt_context_set_debug(self._h, key.encode(), ctypes.c_double(value)), "apt_context_set_debug")
+        self._call("apt_set_debug", key.encode(), value)
 
     def get_debug(self, key):
         v = ctypes.c_double(0)
-        check(lib().apt_context_get_debug(self._h, key.encode(), ctypes.byref(v)), "apt_context_get_debug")
+        self._call("apt_get_debug", key.encode(), ctypes.byref(v))
         return v.value
 
     def check(self, stream=None):
         """apt_context_check: waits for `stream`, raises AptError when a kernel of this context reported a failure through the
         device status word (the reference asserts inside its kernel, src/render.cpp:68-73)."""
-        check(lib().apt_context_check(self._h, _stream_handle(stream)), "apt_context_check")
+        self._call("apt_check", _stream_handle(stream))
 
     def render_do(self, blockDim, l2ctrl, stream, rays, spheres, colors):
         require_gpu()
-        lib().apt_context_render_do(self._h, ctypes.c_uint32(blockDim), None, _stream_handle(stream), _dev_f32(rays, "rays"),
-                                    _dev_f32(spheres, "spheres"), _dev_f32(colors, "colors"))
-        check(lib().apt_last_status(), "apt_context_render_do")
+        self._call("render_do", blockDim, None, _stream_handle(stream), _dev_f32(rays, "rays"), _dev_f32(spheres, "spheres"),
+                   _dev_f32(colors, "colors"))
 
+    # materials (int32 tensor of num_spheres codes, MAT_*): the entry's *_materials form; None: the entry itself, untouched.
+    # lights (int32 tensor, a light table: gen_data.build_lights), with materials only: the entry's *_lights form.
     def render_do_ex(self, params, stream, rays, spheres, colors, materials=None, lights=None):
-        _render_do_ex("apt_context_render_do_ex", (self._h,), params, stream, rays, spheres, colors, materials, lights)
+        require_gpu()
+        n = _buffer_paths(params)
+        entry, mat = _material_args("render_do_ex", params, materials, lights)
+        self._call(entry, ctypes.byref(params), _stream_handle(stream), _dev_f32(rays, "rays", 6 * n),
+                   _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), *mat, _dev_f32(colors, "colors", 3 * n))
 
     def render_frame(self, params, spheres, pixel_begin=0, pixel_count=None, stream=None, fb=None, fb_u8=None, materials=None,
                      lights=None):
-        return _render_frame("apt_context_render_frame", (self._h,), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8,
-                             materials, lights)
+        require_gpu()
+        npix = params.width * params.height
+        if pixel_count is None:
+            pixel_count = npix - pixel_begin
+        if fb is None:
+            fb = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
+        if fb_u8 is None:
+            fb_u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device=spheres.device)
+        entry, mat = _material_args("render_frame", params, materials, lights)
+        self._call(entry, ctypes.byref(params), _stream_handle(stream), _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)),
+                   *mat, pixel_begin, pixel_count, _dev_f32(fb, "fb", 3 * pixel_count), fb_u8.data_ptr())
+        return fb, fb_u8
 
     def render_frame_film(self, params, spheres, materials, film=None, pass_index=0, lights=None, pixel_begin=0, pixel_count=None,
                           stream=None):
-        return _render_frame_film("apt_context_render_frame_film", (self._h,), params, spheres, materials, lights, pixel_begin,
-                                  pixel_count, film, pass_index, stream)
+        require_gpu()
+        if pixel_count is None:
+            pixel_count = params.width * params.height - pixel_begin
+        if film is None:
+            film = torch.empty((3, pixel_count), dtype=torch.float32, device=spheres.device)
+        self._call("apt_render_frame_film", ctypes.byref(params), _stream_handle(stream),
+                   _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), _dev_materials(materials, params.num_spheres),
+                   None if lights is None else _dev_lights(lights), pixel_begin, pixel_count, _dev_f32(film, "film", 3 * pixel_count),
+                   pass_index)
+        return film
 
     def render_frame_features(self, params, spheres, features=None, pixel_begin=0, pixel_count=None, stream=None):
-        return _render_frame_features("apt_context_render_frame_features", (self._h,), params, spheres, features, pixel_begin,
-                                      pixel_count, stream)
+        require_gpu()
+        if pixel_count is None:
+            pixel_count = params.width * params.height - pixel_begin
+        if features is None:
+            features = torch.empty((_lib.APT_FEATURE_PLANES, pixel_count), dtype=torch.float32, device=spheres.device)
+        self._call("apt_render_frame_features", ctypes.byref(params), _stream_handle(stream),
+                   _dev_f32(spheres, "spheres", sphere_floats(params.num_spheres)), pixel_begin, pixel_count,
+                   _dev_f32(features, "features", _lib.APT_FEATURE_PLANES * pixel_count))
+        return features
+
+
+# the process-wide default context as an object of the same class: the module-level functions below forward to it
+_default = object.__new__(Context)
+_default._h, _default._private = None, False
+
+
+def render_do(blockDim, l2ctrl, stream, rays, spheres, colors):
+    """void render_do(blockDim, l2ctrl, stream, rays, spheres, colors) -- src/main.cpp:9-10,74.
+    Asynchronous on `stream`; uses the process-wide defaults (apt_set_default_params)."""
+    _default.render_do(blockDim, l2ctrl, stream, rays, spheres, colors)
 
 
 def render_host(blockDim, rays, spheres, colors):
@@ -217,8 +213,7 @@ def render_host(blockDim, rays, spheres, colors):
     for a, name in ((rays, "rays"), (spheres, "spheres"), (colors, "colors")):
         if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
             raise _lib.AptError(f"{name} must be a C-contiguous float32 numpy array")
-    check(lib().apt_render_host(ctypes.c_uint32(blockDim), ctypes.c_void_p(rays.ctypes.data),
-                                ctypes.c_void_p(spheres.ctypes.data), ctypes.c_void_p(colors.ctypes.data)), "apt_render_host")
+    check(lib().apt_render_host(blockDim, rays.ctypes.data, spheres.ctypes.data, colors.ctypes.data), "apt_render_host")
 
 
 class MultiGpu:
@@ -233,8 +228,8 @@ class MultiGpu:
             raise _lib.AptError("spheres_host has the wrong length")
         ids = (ctypes.c_int * len(device_ids))(*device_ids)
         self._h = ctypes.c_void_p()
-        check(lib().apt_multi_create(ids, ctypes.c_uint32(len(device_ids)), ctypes.c_uint32(stripes), ctypes.byref(params),
-                                     ctypes.c_void_p(sph.ctypes.data), ctypes.byref(self._h)), "apt_multi_create")
+        check(lib().apt_multi_create(ids, len(device_ids), stripes, ctypes.byref(params), sph.ctypes.data, ctypes.byref(self._h)),
+              "apt_multi_create")
         self.params, self.device_ids, self.stripes = params, list(device_ids), stripes
         self.band_kernel_ms = [0.0] * len(device_ids)
 
@@ -247,8 +242,7 @@ class MultiGpu:
         if fb_u8 is None:
             fb_u8 = torch.empty((npix, 3), dtype=torch.uint8, device=dev)
         ms = (ctypes.c_float * len(self.device_ids))()
-        check(lib().apt_multi_render(self._h, ctypes.c_void_p(fb.data_ptr()), ctypes.c_void_p(fb_u8.data_ptr()), ms),
-              "apt_multi_render")
+        check(lib().apt_multi_render(self._h, fb.data_ptr(), fb_u8.data_ptr(), ms), "apt_multi_render")
         self.band_kernel_ms = list(ms)
         return fb, fb_u8
 
@@ -261,34 +255,32 @@ class MultiGpu:
 
 
 def set_default_params(params):
-    check(lib().apt_set_default_params(ctypes.byref(params)), "apt_set_default_params")
+    _default.set_params(params)
 
 
 def set_camera(cam):
     """apt_set_camera: the default context's camera (gen_data.camera / default_camera), or None for the reference's.  render_frame with
     materials= then renders from it; render_frame without materials refuses while it is set (gen_rays_camera + render_paths +
     decode_color_device gives the mirror renderer a camera)."""
-    check(lib().apt_set_camera(None if cam is None else ctypes.byref(cam)), "apt_set_camera")
+    _default.set_camera(cam)
 
 
 def set_environment(env):
     """apt_set_environment: the default context's environment (gen_data.environment), or None for none.  render_frame / render_do_ex
     with materials= (and lights=) then light every path that leaves the scene with its sky and sun; render_frame without materials
     refuses while it is set.  dist.py and MultiGpu render mirrors only: they take neither materials nor an environment."""
-    check(lib().apt_set_environment(None if env is None else ctypes.byref(env)), "apt_set_environment")
+    _default.set_environment(env)
 
 
 def set_debug(key, value):
     """Measurement knob of the default context (include/render_mi355x.h apt_context_set_debug): "queue_ppw", "queue_nbuf",
     "queue_lds_pad", "grid_walk" (1 = nested item walk), "grid_spheres_per_cell"; 0 = the library's own choice."""
-    check(lib().apt_set_debug(key.encode(), ctypes.c_double(value)), "apt_set_debug")
+    _default.set_debug(key, value)
 
 
 def get_debug(key):
     """The knob's current value in the default context (apt_get_debug)."""
-    v = ctypes.c_double(0)
-    check(lib().apt_get_debug(key.encode(), ctypes.byref(v)), "apt_get_debug")
-    return v.value
+    return _default.get_debug(key)
 
 
 class debug_knob:
@@ -312,7 +304,7 @@ def check_device_status(stream=None):
     """apt_check: waits for `stream` (None = torch's current stream) and raises AptError when a kernel launched through the default
     context reported a failure through the device status word since the last check (a tripped loop bound: the frame is incomplete)."""
     require_gpu()
-    check(lib().apt_check(_stream_handle(stream)), "apt_check")
+    _default.check(stream)
 
 
 def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=None, lights=None):
@@ -325,7 +317,7 @@ def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=
     lights (materials only): a light table on the GPU (gen_data.build_lights, as a contiguous int32 CUDA tensor) -> every diffuse hit
     samples ONE of the listed spheres (apt_render_paths_lights); APT_FLAG_NEE and light_index are not read then.  A table that is not
     this scene's renders nothing and check_device_status() raises lights-mismatch."""
-    _render_do_ex("render_do_ex", (), params, stream, rays, spheres, colors, materials, lights)
+    _default.render_do_ex(params, stream, rays, spheres, colors, materials, lights)
 
 
 def render_paths(params: RenderParams, rays, spheres, stream=None, materials=None, lights=None):
@@ -342,7 +334,7 @@ def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None,
     its rule for params.accel included: a grid needs APT_FLAG_GRID_SLOTS, changes which spheres are tested and never the image; a grid
     that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE, lights: as render_do_ex
     (apt_render_frame_lights)."""
-    return _render_frame("render_frame", (), params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials, lights)
+    return _default.render_frame(params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials, lights)
 
 
 def render_frame_film(params: RenderParams, spheres, materials, film=None, pass_index=0, lights=None, pixel_begin=0, pixel_count=None,
@@ -350,8 +342,7 @@ def render_frame_film(params: RenderParams, spheres, materials, film=None, pass_
     """apt_render_frame_film: one pass of a film.  The pixel range rendered as render_frame(materials=, lights=) would with the seed
     apt_film_pass_seed(params.seed, pass_index), unclipped, stored in `film` (float32 [3][count]; None: a new tensor) for pass 0 and
     added to it for a later pass.  Returns the film; not synchronised."""
-    return _render_frame_film("apt_render_frame_film", (), params, spheres, materials, lights, pixel_begin, pixel_count, film,
-                              pass_index, stream)
+    return _default.render_frame_film(params, spheres, materials, film, pass_index, lights, pixel_begin, pixel_count, stream)
 
 
 def render_frame_features(params: RenderParams, spheres, features=None, pixel_begin=0, pixel_count=None, stream=None):
@@ -359,7 +350,7 @@ def render_frame_features(params: RenderParams, spheres, features=None, pixel_be
     each the mean over the pixel's camera rays, the ones render_frame(materials=) traces with these params -- stored in `features`
     (float32 [APT_FEATURE_PLANES][count]; None: a new tensor).  Reads no material table and no flag but APT_FLAG_GRID_SLOTS with
     params.accel.  Returns the tensor; not synchronised."""
-    return _render_frame_features("apt_render_frame_features", (), params, spheres, features, pixel_begin, pixel_count, stream)
+    return _default.render_frame_features(params, spheres, features, pixel_begin, pixel_count, stream)
 
 
 class Film:
@@ -382,9 +373,8 @@ class Film:
         """One more frame of `params` (its width and height must be the film's), with pass index self.passes."""
         if (params.width, params.height) != (self.width, self.height):
             raise _lib.AptError("Film.add_pass: params.width / height are not the film's")
-        entry, handle = ("apt_render_frame_film", ()) if context is None else ("apt_context_render_frame_film", (context._h,))
-        _render_frame_film(entry, handle, params, spheres, materials, lights, self.pixel_begin, self.pixel_count, self.buffer,
-                           self.passes, stream)
+        (_default if context is None else context).render_frame_film(params, spheres, materials, self.buffer, self.passes, lights,
+                                                                     self.pixel_begin, self.pixel_count, stream)
         self.passes += 1
         return self
 
@@ -393,9 +383,9 @@ class Film:
         [APT_FEATURE_PLANES][count] tensor: what lies under the film's pixels.  Independent of the passes the film holds."""
         if (params.width, params.height) != (self.width, self.height):
             raise _lib.AptError("Film.features: params.width / height are not the film's")
-        entry, handle = ("apt_render_frame_features", ()) if context is None else ("apt_context_render_frame_features", (context._h,))
         out = torch.empty((_lib.APT_FEATURE_PLANES, self.pixel_count), dtype=torch.float32, device=self.buffer.device)
-        return _render_frame_features(entry, handle, params, spheres, out, self.pixel_begin, self.pixel_count, stream)
+        return (_default if context is None else context).render_frame_features(params, spheres, out, self.pixel_begin,
+                                                                                self.pixel_count, stream)
 
     def mean(self):
         """The film divided by its passes (fp32, as the resolve's first step) -> float32 [3][count]."""
@@ -417,10 +407,9 @@ class Film:
         rec = _lib.film_resolve_record(self.passes, exposure, tm, 0.0 if white is None else 1.0 / (float(white) * float(white)))
         u8 = torch.empty((self.pixel_count, 3), dtype=torch.uint8, device=self.buffer.device)
         out = torch.empty((3, self.pixel_count), dtype=torch.float32, device=self.buffer.device) if want_float else None
-        check(lib().apt_film_resolve_device(ctypes.byref(rec), _stream_handle(stream), _dev_f32(self.buffer, "film"),
-                                            ctypes.c_uint64(self.pixel_count), _dev_f32(self._tables[curve], "table", 256),
-                                            None if out is None else ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(u8.data_ptr())),
-              "apt_film_resolve_device")
+        check(lib().apt_film_resolve_device(ctypes.byref(rec), _stream_handle(stream), _dev_f32(self.buffer, "film"), self.pixel_count,
+                                            _dev_f32(self._tables[curve], "table", 256), None if out is None else out.data_ptr(),
+                                            u8.data_ptr()), "apt_film_resolve_device")
         return (u8, out) if want_float else u8
 
     def write_pfm(self, path):
@@ -428,8 +417,7 @@ class Film:
         if self.pixel_begin != 0 or self.pixel_count != self.width * self.height:
             raise _lib.AptError("Film.write_pfm: the film is a band of the image")
         planes = self.mean().cpu().numpy()
-        check(lib().apt_write_pfm(str(path).encode(), ctypes.c_uint32(self.width), ctypes.c_uint32(self.height),
-                                  planes.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), "apt_write_pfm")
+        check(lib().apt_write_pfm(str(path).encode(), self.width, self.height, planes.ctypes.data), "apt_write_pfm")
 
 
 def gen_rays_device(params: RenderParams, stream=None, device="cuda"):
@@ -459,8 +447,7 @@ def decode_color_device(params: RenderParams, colors, stream=None):
     fb = torch.empty((3, npix), dtype=torch.float32, device=colors.device)
     u8 = torch.empty((npix, 3), dtype=torch.uint8, device=colors.device)
     check(lib().apt_decode_color_device(ctypes.byref(params), _stream_handle(stream),
-                                        _dev_f32(colors.reshape(-1), "colors", 3 * params.num_paths),
-                                        ctypes.c_void_p(fb.data_ptr()), ctypes.c_void_p(u8.data_ptr())),
+                                        _dev_f32(colors.reshape(-1), "colors", 3 * params.num_paths), fb.data_ptr(), u8.data_ptr()),
           "apt_decode_color_device")
     return fb, u8
 
@@ -473,7 +460,7 @@ class TraceCounter:
 
     def __enter__(self):
         self.buf.zero_()
-        lib().apt_set_trace_counter(ctypes.c_void_p(self.buf.data_ptr()))
+        lib().apt_set_trace_counter(self.buf.data_ptr())
         return self
 
     def __exit__(self, *exc):
@@ -501,8 +488,7 @@ def selftest_sqrt(variant=0, first_bits=0, count=1 << 32, stream=None):
     """Exhaustive check of the hot loop's fast sqrt against sqrtf(): -> (mismatches, first bad bits)."""
     require_gpu()
     res = torch.tensor([0, -1], dtype=torch.int64, device="cuda")
-    check(lib().apt_selftest_sqrt(ctypes.c_int(variant), _stream_handle(stream), ctypes.c_uint64(first_bits),
-                                  ctypes.c_uint64(count), ctypes.c_void_p(res.data_ptr())), "apt_selftest_sqrt")
+    check(lib().apt_selftest_sqrt(variant, _stream_handle(stream), first_bits, count, res.data_ptr()), "apt_selftest_sqrt")
     torch.cuda.synchronize()
     bad, first = res.tolist()
     return bad, first & 0xFFFFFFFF
@@ -512,8 +498,7 @@ def selftest_div3(first=0, count=1 << 32, stream=None):
     """Shared-reciprocal divide vs `/` on hashed operand sets: -> (mismatches, first bad, accepted)."""
     require_gpu()
     res = torch.tensor([0, -1, 0], dtype=torch.int64, device="cuda")
-    check(lib().apt_selftest_div3(_stream_handle(stream), ctypes.c_uint64(first), ctypes.c_uint64(count),
-                                  ctypes.c_void_p(res.data_ptr())), "apt_selftest_div3")
+    check(lib().apt_selftest_div3(_stream_handle(stream), first, count, res.data_ptr()), "apt_selftest_div3")
     torch.cuda.synchronize()
     return tuple(res.tolist())
 
@@ -524,8 +509,7 @@ def selftest_div3_seeded(part=0, first=0, count=1 << 32, stream=None):
     flagged_other, in_range, shared_ok, recip_off)."""
     require_gpu()
     res = torch.tensor([0, -1, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device="cuda")
-    check(lib().apt_selftest_div3_seeded(_stream_handle(stream), ctypes.c_int(part), ctypes.c_uint64(first), ctypes.c_uint64(count),
-                                         ctypes.c_void_p(res.data_ptr())), "apt_selftest_div3_seeded")
+    check(lib().apt_selftest_div3_seeded(_stream_handle(stream), part, first, count, res.data_ptr()), "apt_selftest_div3_seeded")
     torch.cuda.synchronize()
     return dict(zip(("bad", "first", "accepted", "flagged", "flagged_other", "in_range", "shared_ok", "recip_off"), res.tolist()))
 
@@ -538,9 +522,8 @@ def selftest_direction(d3, flags=False, stream=None):
     assert d3.is_cuda and d3.dtype == torch.float64 and d3.dim() == 2 and d3.shape[1] == 3 and d3.is_contiguous()
     res = torch.zeros(5, dtype=torch.int64, device="cuda")
     fl = torch.zeros(d3.shape[0], dtype=torch.uint8, device="cuda") if flags else None
-    check(lib().apt_selftest_direction(_stream_handle(stream), ctypes.c_void_p(d3.data_ptr()), ctypes.c_uint64(d3.shape[0]),
-                                       ctypes.c_void_p(res.data_ptr()), ctypes.c_void_p(fl.data_ptr()) if flags else None),
-          "apt_selftest_direction")
+    check(lib().apt_selftest_direction(_stream_handle(stream), d3.data_ptr(), d3.shape[0], res.data_ptr(),
+                                       fl.data_ptr() if flags else None), "apt_selftest_direction")
     torch.cuda.synchronize()
     r = res.cpu()
     out = dict(accepted=int(r[0]), rejected=int(r[1]), bad=int(r[2]), ray_rejected=int(r[3]), max_cert=float(r[4:5].view(torch.float64)[0]))
@@ -549,7 +532,7 @@ def selftest_direction(d3, flags=False, stream=None):
 
 def set_refill_lanes(lanes):
     """Compaction batch threshold (1..64, default 32); speed only, results do not depend on it."""
-    check(lib().apt_set_refill_lanes(ctypes.c_uint32(lanes)), "apt_set_refill_lanes")
+    _default.set_refill_lanes(lanes)
 
 
 def test_scene(params: RenderParams, rays, spheres, stream=None):
@@ -622,9 +605,8 @@ def render_reference_frame_fused(w, h, s, depth=5, seed=0, spheres=None, mode=No
         p = make_params(w, h, s, depth=depth, mode=APT_MODE_ORACLE if mode is None else mode, flags=flags)
         fb = torch.empty((3, pixel_count), dtype=torch.float32, device="cuda")
         u8 = torch.empty((pixel_count, 3), dtype=torch.uint8, device="cuda")
-    check(lib().apt_render_frame_mt(ctypes.byref(p), _stream_handle(tstream), ctypes.c_void_p(ck_d.data_ptr()), ctypes.c_uint64(ck_d.shape[0]),
-                                    ctypes.c_uint64(g_lo), _dev_f32(spheres, "spheres"), ctypes.c_uint64(pixel_begin),
-                                    ctypes.c_uint64(pixel_count), ctypes.c_void_p(fb.data_ptr()), ctypes.c_void_p(u8.data_ptr())),
+    check(lib().apt_render_frame_mt(ctypes.byref(p), _stream_handle(tstream), ck_d.data_ptr(), ck_d.shape[0], g_lo,
+                                    _dev_f32(spheres, "spheres"), pixel_begin, pixel_count, fb.data_ptr(), u8.data_ptr()),
           "apt_render_frame_mt")
     return fb, u8
 
@@ -690,14 +672,11 @@ def render_reference_frame(w, h, s, depth=5, seed=0, spheres=None, mode=None, fl
             ck_d = torch.from_numpy(ck.view(np.int32)).cuda()
             fb_band = torch.empty((3, nq), dtype=torch.float32, device="cuda")
         p = make_params(w, h, s, depth=depth, mode=mode, flags=flags | APT_FLAG_BAND_BUFFERS, path_begin=b, path_count=c)
-        check(lib().apt_gen_rays_mt_device_ex(ctypes.byref(p), st, ctypes.c_void_p(ck_d.data_ptr()), ctypes.c_uint32(stride),
-                                              ctypes.c_uint64(ck.shape[0]), ctypes.c_uint64(blk0), ctypes.c_void_p(rays.data_ptr())),
+        check(lib().apt_gen_rays_mt_device_ex(ctypes.byref(p), st, ck_d.data_ptr(), stride, ck.shape[0], blk0, rays.data_ptr()),
               "apt_gen_rays_mt_device_ex")
-        check(lib().render_do_ex(ctypes.byref(p), st, ctypes.c_void_p(rays.data_ptr()), _dev_f32(spheres, "spheres"),
-                                 ctypes.c_void_p(colors.data_ptr())), "render_do_ex")
+        check(lib().render_do_ex(ctypes.byref(p), st, rays.data_ptr(), _dev_f32(spheres, "spheres"), colors.data_ptr()), "render_do_ex")
         o = q0 - pixel_begin
-        check(lib().apt_decode_color_band(ctypes.byref(p), st, ctypes.c_void_p(colors.data_ptr()), ctypes.c_uint64(nq),
-                                          ctypes.c_void_p(fb_band.data_ptr()), ctypes.c_void_p(u8[o:o + nq].data_ptr())),
+        check(lib().apt_decode_color_band(ctypes.byref(p), st, colors.data_ptr(), nq, fb_band.data_ptr(), u8[o:o + nq].data_ptr()),
               "apt_decode_color_band")
         with torch.cuda.stream(tstream):
             fb[:, o:o + nq] = fb_band

@@ -195,7 +195,6 @@ def test_gloss_words_and_flags(apt):
     assert flags([0x80000003]) == (0, 0)
     assert flags([3 | (1 << 24), 4, gd.gloss(1.0)]) == (64, 64)           # one well-formed word is enough
     assert flags([]) == (0, 0)
-    L.apt_materials_flags_host.restype = ctypes.c_uint32
     assert L.apt_materials_flags_host(None, ctypes.c_uint32(5)) == 0
     one = (ctypes.c_uint32 * 1)(gd.gloss(0.5))
     assert L.apt_materials_flags_host(one, ctypes.c_uint32(0)) == 0 and L.apt_materials_flags_host(one, ctypes.c_uint32(1)) == 64
