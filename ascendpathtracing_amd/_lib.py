@@ -131,6 +131,19 @@ PROTOTYPES = {
 # every symbol include/render_mi355x.h declares
 ABI_SYMBOLS = [name for name in PROTOTYPES if name != CXX_RENDER_DO]
 
+# libdenoise_mi355x.so (include/render_mi355x_denoise.h), a library of its own beside librender_mi355x.so: its prototypes by the same
+# rules, in its header's order.  tests/test_denoise_cpu.py holds the table to that header and to the library's exports.
+DENOISE_LIB_PATH = os.environ.get("APT_DENOISE_LIB_PATH") or os.path.join(_HERE, "libdenoise_mi355x.so")
+DENOISE_PROTOTYPES = {
+    "apt_film_accumulate_device": (I, [P, P, U64, P, P, U32]),
+    "apt_film_accumulate_host": (I, [P, U64, P, P, U32]),
+    "apt_film_denoise_default_host": (I, [P, U32]),
+    "apt_film_denoise_work_floats": (U64, [U32, U32]),
+    "apt_film_denoise_device": (I, [P, P, P, P, P, U32, U32, P, P]),
+    "apt_film_denoise_host": (I, [P, P, P, P, U32, U32, P, P]),
+    "apt_film_denoise_last_error": (S, []),
+}
+
 
 class AptError(RuntimeError):
     pass
@@ -196,6 +209,28 @@ def film_resolve_record(passes, exposure=1.0, tonemap=APT_TONEMAP_CLIP, inv_whit
     return ApFilmResolve(ctypes.sizeof(ApFilmResolve), passes, tonemap, 0, exposure, inv_white2)
 
 
+class ApFilmDenoise(ctypes.Structure):
+    """apt_film_denoise (include/render_mi355x_denoise.h): passes in the film and its moments, a-trous iterations, the five edge-stopping
+    sigmas (normal, depth, coverage, albedo, luminance) and the albedo floor."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("iterations", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("sigma_n", ctypes.c_float), ("sigma_z", ctypes.c_float), ("sigma_c", ctypes.c_float), ("sigma_a", ctypes.c_float),
+                ("sigma_l", ctypes.c_float), ("albedo_floor", ctypes.c_float)]
+
+
+def film_denoise_record(passes, iterations=None, **fields):
+    """apt_film_denoise_default_host's record for `passes`, with `iterations` and any of sigma_n, sigma_z, sigma_c, sigma_a, sigma_l,
+    albedo_floor replaced."""
+    rec = ApFilmDenoise()
+    denoise_check(denoise_lib().apt_film_denoise_default_host(ctypes.byref(rec), passes), "apt_film_denoise_default_host")
+    if iterations is not None:
+        rec.iterations = iterations
+    for k, v in fields.items():
+        if k not in ("sigma_n", "sigma_z", "sigma_c", "sigma_a", "sigma_l", "albedo_floor"):
+            raise AptError(f"film_denoise_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 _lib = None
 
 
@@ -226,6 +261,33 @@ def lib():
     return _lib
 
 
+_denoise_lib = None
+
+
+def denoise_lib():
+    """The loaded libdenoise_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
+    global _denoise_lib
+    if _denoise_lib is None:
+        if not os.path.exists(DENOISE_LIB_PATH):
+            raise AptError(f"{DENOISE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
+        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
+        try:
+            h = ctypes.CDLL(DENOISE_LIB_PATH)
+        except OSError as e:
+            raise AptError(f"cannot load {DENOISE_LIB_PATH}: {e}") from e
+        for name, (restype, argtypes) in DENOISE_PROTOTYPES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _denoise_lib = h
+    return _denoise_lib
+
+
+def denoise_check(rc, what):
+    if rc != APT_OK:
+        raise AptError(f"{what} failed ({rc}): {denoise_lib().apt_film_denoise_last_error().decode()}")
+
+
 def build_id():
     """Identifies the build of the library by its SOURCES (sha256 over ascendpathtracing_amd/csrc/*.{h,hip,cpp}, the Makefile and the
     public header, first 16 hex digits): what profiles/summarize.py stamps the recorded PMC traffic with and bench.py compares
@@ -234,7 +296,8 @@ def build_id():
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")))
-    files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map"), os.path.join(os.path.dirname(_HERE), "include", "render_mi355x.h")]
+    files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map"), os.path.join(os.path.dirname(_HERE), "include", "render_mi355x.h"),
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

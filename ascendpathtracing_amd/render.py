@@ -15,6 +15,13 @@ def _stream_handle(stream):
     return stream if isinstance(stream, int) else stream.cuda_stream
 
 
+def _torch_stream(stream):
+    """The same stream as a torch object, for work that torch itself enqueues."""
+    if stream is None:
+        return torch.cuda.current_stream()
+    return torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream
+
+
 def _dev_f32(t, name, numel=None):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
         raise _lib.AptError(f"{name} must be a contiguous float32 tensor on the GPU")
@@ -353,30 +360,86 @@ def render_frame_features(params: RenderParams, spheres, features=None, pixel_be
     return _default.render_frame_features(params, spheres, features, pixel_begin, pixel_count, stream)
 
 
+def film_accumulate(pass_planes, film, moments, pass_index, stream=None):
+    """apt_film_accumulate_device (libdenoise_mi355x.so, include/render_mi355x_denoise.h): ONE pass's planes (float32 [3][count]) stored in (pass_index 0) or added to `film` [3][count], its
+    luminance and squared luminance to `moments` [2][count].  Returns (film, moments); not synchronised."""
+    require_gpu()
+    count = pass_planes.numel() // 3
+    _lib.denoise_check(_lib.denoise_lib().apt_film_accumulate_device(_stream_handle(stream), _dev_f32(pass_planes, "pass_planes", 3 * count), count,
+                                           _dev_f32(film, "film", 3 * count), _dev_f32(moments, "moments", 2 * count), pass_index),
+          "apt_film_accumulate_device")
+    return film, moments
+
+
+def film_denoise(record, film, moments, features, width, height, work=None, out=None, stream=None):
+    """apt_film_denoise_device: the a-trous filter of `record` (_lib.film_denoise_record) over a whole width x height image -- film
+    [3][W*H], moments [2][W*H], features [APT_FEATURE_PLANES][W*H] -> `out` float32 [3][W*H], the denoised MEAN radiance (None: a new
+    tensor).  work: a float32 tensor of apt_film_denoise_work_floats elements (None: a new one).  Not synchronised."""
+    require_gpu()
+    n = width * height
+    if work is None:
+        work = torch.empty(_lib.denoise_lib().apt_film_denoise_work_floats(width, height), dtype=torch.float32, device=film.device)
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.float32, device=film.device)
+    _lib.denoise_check(_lib.denoise_lib().apt_film_denoise_device(ctypes.byref(record), _stream_handle(stream), _dev_f32(film, "film", 3 * n),
+                                        _dev_f32(moments, "moments", 2 * n), _dev_f32(features, "features", _lib.APT_FEATURE_PLANES * n),
+                                        width, height, _dev_f32(work, "work", 16 * n), _dev_f32(out, "out", 3 * n)),
+          "apt_film_denoise_device")
+    return out
+
+
 class Film:
     """An unclipped float32 accumulation buffer for the pixels [pixel_begin, pixel_begin + pixel_count) of a width x height image
     (include/render_mi355x.h "film"): add_pass renders one more independent frame into it, resolve turns the mean into a displayable
-    image.  `buffer` is the [3][count] tensor of sums, `passes` how many frames it holds."""
+    image.  `buffer` is the [3][count] tensor of sums, `passes` how many frames it holds.  moments=True (a whole image only) also
+    keeps `moments`, the [2][count] sums of each pass's luminance and its square (include/render_mi355x_denoise.h), which denoise() needs: a
+    pass is then rendered into a scratch film and added from there, to the same bits."""
 
-    def __init__(self, width, height, pixel_begin=0, pixel_count=None, device="cuda"):
+    def __init__(self, width, height, pixel_begin=0, pixel_count=None, device="cuda", moments=False):
         self.width, self.height, self.pixel_begin = width, height, pixel_begin
         self.pixel_count = width * height - pixel_begin if pixel_count is None else pixel_count
+        if moments and (pixel_begin != 0 or self.pixel_count != width * height):
+            raise _lib.AptError("Film: moments=True needs the whole image: the filter they serve has no band form")
         self.buffer = torch.zeros((3, self.pixel_count), dtype=torch.float32, device=device)
+        self.moments = torch.zeros((2, self.pixel_count), dtype=torch.float32, device=device) if moments else None
+        self._scratch = torch.empty((3, self.pixel_count), dtype=torch.float32, device=device) if moments else None
         self.passes = 0
         self._tables = {}
 
     def reset(self):
-        """Forget the passes: the next one stores."""
+        """Forget the passes: the next one stores, the moments too."""
         self.passes = 0
 
     def add_pass(self, params, spheres, materials, lights=None, stream=None, context=None):
         """One more frame of `params` (its width and height must be the film's), with pass index self.passes."""
         if (params.width, params.height) != (self.width, self.height):
             raise _lib.AptError("Film.add_pass: params.width / height are not the film's")
-        (_default if context is None else context).render_frame_film(params, spheres, materials, self.buffer, self.passes, lights,
-                                                                     self.pixel_begin, self.pixel_count, stream)
+        ctx = _default if context is None else context
+        if self.moments is None:
+            ctx.render_frame_film(params, spheres, materials, self.buffer, self.passes, lights, self.pixel_begin, self.pixel_count, stream)
+        else:
+            # the pass by itself: a later pass ADDS, so it goes onto zeros (0 + r is r: a pass holds no -0); pass 0 stores
+            if self.passes:
+                with torch.cuda.stream(_torch_stream(stream)):
+                    self._scratch.zero_()
+            ctx.render_frame_film(params, spheres, materials, self._scratch, self.passes, lights, 0, self.pixel_count, stream)
+            film_accumulate(self._scratch, self.buffer, self.moments, self.passes, stream)
         self.passes += 1
         return self
+
+    def denoise(self, params, spheres, iterations=None, features=None, stream=None, context=None, **sigmas):
+        """The film's mean through apt_film_denoise_device -> float32 [3][count], the denoised mean radiance; resolve(source=...)
+        makes an image of it.  The film needs moments=True and at least 2 passes.  iterations and sigma_n, sigma_z, sigma_c, sigma_a,
+        sigma_l, albedo_floor replace apt_film_denoise_default_host's values.  features: the film's feature planes (None: rendered
+        through Film.features with `params` and `spheres`)."""
+        if self.moments is None:
+            raise _lib.AptError("Film.denoise: the film keeps no moments (Film(..., moments=True))")
+        if self.passes < 2:
+            raise _lib.AptError("Film.denoise: the variance of the mean needs at least 2 passes")
+        if features is None:
+            features = self.features(params, spheres, stream, context)
+        rec = _lib.film_denoise_record(self.passes, iterations, **sigmas)
+        return film_denoise(rec, self.buffer, self.moments, features, self.width, self.height, stream=stream)
 
     def features(self, params, spheres, stream=None, context=None):
         """apt_render_frame_features for the film's own pixel range (params.width and height must be the film's) -> a new float32
@@ -393,21 +456,24 @@ class Film:
             raise _lib.AptError("Film.mean: the film holds no pass")
         return self.buffer / torch.tensor(self.passes, dtype=torch.float32, device=self.buffer.device)
 
-    def resolve(self, exposure=1.0, tonemap="clip", white=None, curve="srgb", want_float=False, stream=None):
+    def resolve(self, exposure=1.0, tonemap="clip", white=None, curve="srgb", want_float=False, stream=None, source=None):
         """apt_film_resolve_device: mean, exposure, tone operator ("clip" or "reinhard"; white: the radiance that maps to 1, None:
-        plain Reinhard) and the 8-bit encoding by `curve` ("srgb" or "linear") -> u8 [count][3], or (u8, float32 [3][count])."""
+        plain Reinhard) and the 8-bit encoding by `curve` ("srgb" or "linear") -> u8 [count][3], or (u8, float32 [3][count]).
+        source: planes of MEAN radiance [3][count] to resolve in the film's place, with passes = 1: what denoise() returns."""
         from . import gen_data
-        if self.passes == 0:
+        if source is None and self.passes == 0:
             raise _lib.AptError("Film.resolve: the film holds no pass")
         tm = {"clip": _lib.APT_TONEMAP_CLIP, "reinhard": _lib.APT_TONEMAP_REINHARD}.get(tonemap)
         if tm is None:
             raise _lib.AptError(f"Film.resolve: unknown tone operator {tonemap!r}")
         if curve not in self._tables:
             self._tables[curve] = torch.from_numpy(gen_data.film_curve(curve)).to(self.buffer.device)
-        rec = _lib.film_resolve_record(self.passes, exposure, tm, 0.0 if white is None else 1.0 / (float(white) * float(white)))
+        rec = _lib.film_resolve_record(self.passes if source is None else 1, exposure, tm,
+                                       0.0 if white is None else 1.0 / (float(white) * float(white)))
+        film = _dev_f32(self.buffer, "film") if source is None else _dev_f32(source, "source", 3 * self.pixel_count)
         u8 = torch.empty((self.pixel_count, 3), dtype=torch.uint8, device=self.buffer.device)
         out = torch.empty((3, self.pixel_count), dtype=torch.float32, device=self.buffer.device) if want_float else None
-        check(lib().apt_film_resolve_device(ctypes.byref(rec), _stream_handle(stream), _dev_f32(self.buffer, "film"), self.pixel_count,
+        check(lib().apt_film_resolve_device(ctypes.byref(rec), _stream_handle(stream), film, self.pixel_count,
                                             _dev_f32(self._tables[curve], "table", 256), None if out is None else out.data_ptr(),
                                             u8.data_ptr()), "apt_film_resolve_device")
         return (u8, out) if want_float else u8
