@@ -9,6 +9,7 @@
 
 #include "../../include/render_mi355x.h"
 #include "apt_materials.h"
+#include "film_ops.h"
 #include "pt_core.h"
 #include "pt_materials.h"
 #include "pt_mat_launch.h"
@@ -18,33 +19,18 @@ namespace {
 constexpr int kPins = kMatEnv | kMatGloss | kMatCamera | kMatFilm;
 
 // ---- resolve ----------------------------------------------------------------------------------------------------------------
-// One lane = one pixel: three coalesced plane reads, the header's operations one at a time, an 8-step search in the table (LDS), and
-// three coalesced plane stores.  The workgroup's 8-bit pixels -- kBlock * 3 consecutive bytes that start wherever u8 + 3 * first pixel
-// falls -- are gathered in LDS and leave as whole dwords; the bytes of a dword that the workgroup's range does not cover (its ragged
-// head and tail, and all of a short last workgroup's) leave as byte stores.
+// One lane = one pixel: three coalesced plane reads, the header's operations one at a time and an 8-step search in the table (LDS) --
+// film_ops.h's film_tone and film_code, as in the CPU twin --, and three coalesced plane stores.  The workgroup's 8-bit pixels --
+// kBlock * 3 consecutive bytes that start wherever u8 + 3 * first pixel falls -- are gathered in LDS and leave as whole dwords; the
+// bytes of a dword that the workgroup's range does not cover (its ragged head and tail, and all of a short last workgroup's) leave as
+// byte stores.
 struct ResolveArgs {
     const float *film, *table;
     float *out;
     uint8_t *u8;
     uint64_t pixel_count;
-    float fpasses, exposure, inv_white2;
-    uint32_t reinhard;
+    apt::FilmTone tone;
 };
-
-__device__ __forceinline__ float film_tone(float s, const ResolveArgs &a) {
-    const float m = s / a.fpasses;
-    float x = m * a.exposure;
-    x = x > 0.0f ? x : 0.0f;
-    float y = x;
-    if (a.reinhard) {   // (launch-uniform)
-        float t = x * a.inv_white2;
-        t = 1.0f + t;
-        const float num = x * t;
-        const float den = 1.0f + x;
-        y = x == __builtin_inff() ? 1.0f : num / den;
-    }
-    return y < 1.0f ? y : 1.0f;
-}
 
 __global__ __launch_bounds__(kBlock) void film_resolve_kernel(ResolveArgs a) {
     __shared__ float table[256];
@@ -57,12 +43,9 @@ __global__ __launch_bounds__(kBlock) void film_resolve_kernel(ResolveArgs a) {
     if (i < a.pixel_count) {
 #pragma unroll
         for (uint64_t c = 0; c < 3; ++c) {
-            const float y = film_tone(a.film[c * a.pixel_count + i], a);
+            const float y = apt::film_tone(a.film[c * a.pixel_count + i], a.tone);
             if (a.out) a.out[c * a.pixel_count + i] = y;
-            uint32_t code = 0;
-#pragma unroll
-            for (uint32_t b = 128; b; b >>= 1) code += table[code + b] <= y ? b : 0u;
-            bytes[threadIdx.x * 3 + c] = (uint8_t)code;
+            bytes[threadIdx.x * 3 + c] = (uint8_t)apt::film_code(table, y);
         }
     }
     if (!a.u8) return;                                                     // (launch-uniform)
@@ -91,8 +74,7 @@ void film_resolve(const apt_film_resolve &r, void *stream, const float *film, ui
                   uint8_t *u8) {
     ResolveArgs a;
     a.film = film; a.table = table_dev; a.out = out; a.u8 = u8; a.pixel_count = pixel_count;
-    a.fpasses = (float)r.passes; a.exposure = r.exposure; a.inv_white2 = r.inv_white2;
-    a.reinhard = r.tonemap == (uint32_t)APT_TONEMAP_REINHARD ? 1u : 0u;
+    a.tone = FilmTone{(float)r.passes, r.exposure, r.inv_white2, r.tonemap == (uint32_t)APT_TONEMAP_REINHARD ? 1u : 0u};
     const uint64_t blocks = (pixel_count + kBlock - 1) / kBlock;           // <= 2^31 - 1: checked by the caller
     hipLaunchKernelGGL(film_resolve_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
 }

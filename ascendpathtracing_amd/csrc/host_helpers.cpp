@@ -17,6 +17,7 @@
 
 #include "../../include/render_mi355x.h"
 #include "apt_host.h"
+#include "film_ops.h"
 #include "pt_core.h"
 #include "pt_camera.h"
 #include "pt_leaf.h"
@@ -833,38 +834,17 @@ int apt_film_curve_host(uint32_t curve, float table[256]) {
     return APT_OK;
 }
 
-// One value of the film -> y ("film" in the header, operation by operation; film.hip's kernel is the same text).
-static inline float film_tone(float s, float fpasses, float exposure, float inv_white2, bool reinhard) {
-    const float m = s / fpasses;
-    float x = m * exposure;
-    x = x > 0.0f ? x : 0.0f;
-    float y = x;
-    if (reinhard) {
-        float t = x * inv_white2;
-        t = 1.0f + t;
-        const float num = x * t;
-        const float den = 1.0f + x;
-        y = x == INFINITY ? 1.0f : num / den;
-    }
-    return y < 1.0f ? y : 1.0f;
-}
-static inline uint8_t film_code(const float *table, float y) {
-    uint32_t code = 0;
-    for (uint32_t b = 128; b; b >>= 1) code += table[code + b] <= y ? b : 0u;
-    return (uint8_t)code;
-}
-
+// The resolve kernel's CPU twin: film_ops.h's film_tone and film_code for every value, as film.hip's kernel runs them.
 int apt_film_resolve_host(const apt_film_resolve *r, const float *film, uint64_t pixel_count, const float *table, float *out, uint8_t *u8) {
     apt::clear_error();
     const int rc = apt::film_resolve_check(r, film, table, out, u8, "apt_film_resolve_host");
     if (rc) return rc;
-    const float fp = (float)r->passes;
-    const bool reinhard = r->tonemap == (uint32_t)APT_TONEMAP_REINHARD;
+    const apt::FilmTone tone = {(float)r->passes, r->exposure, r->inv_white2, r->tonemap == (uint32_t)APT_TONEMAP_REINHARD ? 1u : 0u};
     for (uint64_t c = 0; c < 3; ++c)
         for (uint64_t i = 0; i < pixel_count; ++i) {
-            const float y = film_tone(film[c * pixel_count + i], fp, r->exposure, r->inv_white2, reinhard);
+            const float y = apt::film_tone(film[c * pixel_count + i], tone);
             if (out) out[c * pixel_count + i] = y;
-            if (u8) u8[i * 3 + c] = film_code(table, y);
+            if (u8) u8[i * 3 + c] = (uint8_t)apt::film_code(table, y);
         }
     return APT_OK;
 }

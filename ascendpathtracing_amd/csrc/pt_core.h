@@ -18,12 +18,7 @@
 #include <cstring>
 #include <math.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define APT_HD __host__ __device__ __forceinline__
-#else
-#define APT_HD inline
-#endif
+#include "apt_hd.h"
 
 namespace apt {
 
@@ -79,6 +74,28 @@ APT_HD float intersect_post(HitPre h, float eps) {
     return (t > eps) ? t : kMissT;
 }
 
+#if defined(__HIPCC__) // device functions that host-pass code in pt_trace.h / pt_trace2.h / pt_queue.h names
+typedef float f2_t __attribute__((ext_vector_type(2)));
+// The one-transcendental square root (sqrt_rn_rsq1 below) from its seed on: with r0 = v_rsq_f32(x), y = x*r0, h = r0/2 and
+// fma(fma(-y,y,x), h, y) is RN(sqrt(x)).  Validity (|x| >= 2^-96) is the caller's business, and so is the seed: the bounce blocks
+// hand the same r0 to their validity test and to the divide.  The f2_t form is the same step on both halves of a register pair
+// (v_pk_mul_f32 / v_pk_fma_f32 round each half exactly like the scalar instructions).
+__device__ __forceinline__ float sqrt_rsq_step(float x, float r0) {
+    const float y = x * r0, h = 0.5f * r0;
+    const float r = __builtin_fmaf(-y, y, x);
+    return __builtin_fmaf(r, h, y);
+}
+__device__ __forceinline__ f2_t sqrt_rsq_step(f2_t x, f2_t r0) {
+    const f2_t y = x * r0, h = r0 * 0.5f;
+    const f2_t r = __builtin_elementwise_fma(-y, y, x);
+    return __builtin_elementwise_fma(r, h, y);
+}
+// sqrt_rn_rsq1 of the two discriminants of a sphere pair
+__device__ __forceinline__ f2_t sqrt_rn_rsq1_pair(f2_t x) {
+    return sqrt_rsq_step(x, f2_t{__builtin_amdgcn_rsqf(x.x), __builtin_amdgcn_rsqf(x.y)});
+}
+#endif
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // Correctly rounded sqrt for the device hot loop.  hipcc's sqrtf() is v_sqrt_f32 (<= 1 ulp)
 // followed by a check of the two neighbouring floats with exact FMA residuals, wrapped in a
@@ -117,10 +134,7 @@ __device__ __forceinline__ float sqrt_rn_markstein(float x, float &amin) {
 //   3: hipcc's flush-mode lowering (two steps): e = fma(-h,y,.5); y=fma(y,e,y); h=fma(h,e,h); y'=fma(fma(-y,y,x),h,y)
 __device__ __forceinline__ float sqrt_rn_rsq1(float x, float &amin) {
     amin = fminf(amin, fabsf(x));
-    const float r0 = __builtin_amdgcn_rsqf(x);
-    const float y = x * r0, h = 0.5f * r0;
-    const float r = __builtin_fmaf(-y, y, x);
-    return __builtin_fmaf(r, h, y);
+    return sqrt_rsq_step(x, __builtin_amdgcn_rsqf(x));
 }
 __device__ __forceinline__ float sqrt_rn_rsq2(float x, float &amin) {
     amin = fminf(amin, fabsf(x));
@@ -171,12 +185,11 @@ __device__ __forceinline__ void div3_shared(float nx, float ny, float nz, float 
 
 #endif
 
-#if defined(__HIPCC__) // device functions that host-pass code in pt_trace.h / pt_kernels.h names
+#if defined(__HIPCC__) // (as above: named by host-pass code in pt_trace.h / pt_kernels.h)
 // The same three quotients with x and y in one register pair (v_pk_mul_f32 / v_pk_fma_f32 round each half exactly
 // like the scalar instructions): the form the 8-sphere bounce block uses.  Validity is the caller's business:
 // div3_operands_ok() below states it, the bounce block evaluates the same conditions with two v_min3_f32 and two
 // compares for the whole wave, and apt_selftest_div3 checks this function under exactly that predicate.
-typedef float f2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void div3_packed(f2_t nxy, float nz, float d, f2_t &uxy, float &uz) {
     const float r0 = __builtin_amdgcn_rcpf(d);
     const float e0 = __builtin_fmaf(-d, r0, 1.0f);

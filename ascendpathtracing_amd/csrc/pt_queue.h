@@ -666,10 +666,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SC == kScene
         auto test_post = [&](const HitPre2 hp, uint32_t pos, auto ties_tag, auto swap_tag) __attribute__((always_inline)) {
             constexpr bool TIES = decltype(ties_tag)::value;
             constexpr bool SWAP = decltype(swap_tag)::value;
-            const f2 r0 = {__builtin_amdgcn_rsqf(hp.disc.x), __builtin_amdgcn_rsqf(hp.disc.y)};   // sqrt_rn_rsq1 on both halves
-            const f2 y = hp.disc * r0, hh = r0 * 0.5f;
-            const f2 res = __builtin_elementwise_fma(-y, y, hp.disc);
-            f2 q = __builtin_elementwise_fma(res, hh, y);
+            f2 q = sqrt_rn_rsq1_pair(hp.disc);
             // NaN discriminants (pads, NaN spheres) drop out of the minimum: they cannot hit either way
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(min3_abs(1.0f, hp.disc.x, hp.disc.y) < 0x1p-96f) != 0, 0)) {
                 asm volatile("" ::: "memory");

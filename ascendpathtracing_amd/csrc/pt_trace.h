@@ -114,6 +114,39 @@ __device__ __forceinline__ void report_status(const TraceArgs &ta, uint32_t bit)
 __device__ __forceinline__ float twice_canonical(float dot) { return __builtin_fmaf(dot, 2.0f, 0.0f); }
 __device__ __forceinline__ f2 twice_canonical(f2 dot) { return __builtin_elementwise_fma(dot, f2{2.0f, 2.0f}, f2{0.0f, 0.0f}); }
 
+// float32(sum in float64 of three float32 products): np.dot / np.linalg.norm of the NumPy oracle (gen_data.py:347,349).  sdot's start
+// value 0.0 is not added: squares are never -0, and the dot product's consumer is twice_canonical().
+__device__ __forceinline__ float sum3_f64(float p0, float p1, float p2) {
+    double acc = (double)p0;
+    acc = acc + (double)p1;
+    acc = acc + (double)p2;
+    return (float)acc;
+}
+
+// The three steps of GenerateNewRays (rt_helper.h:504-709) that every packed form of the 8-sphere bounce states -- the full trace
+// (bounce_ns8_v2), its two phases (bounce_ns8_v2_hit / _reflect) and the grid form (reflect_packed) -- with the x and y components
+// of a 3-vector in one register pair; the third, the one-rsq square root from its seed on, is pt_core.h's sqrt_rsq_step().
+// |normal|^2: K-mode rt_helper.h:641-649 in fp32 (0 + x^2 is x^2: a square is never -0), O-mode np.linalg.norm, gen_data.py:347.
+template <int MODE>
+__device__ __forceinline__ float normal_len2(f2 nxy, float nz) {
+    const f2 sq = nxy * nxy;
+    if (MODE == kModeOracle) return sum3_f64(sq.x, sq.y, nz * nz);
+    const float acc = sq.x + sq.y;
+    return acc + nz * nz;
+}
+// k2 = 2 (d . u) of the reflection: K-mode rt_helper.h:690 Duplicate(0), :694-697, O-mode np.dot, gen_data.py:349; the start value is
+// twice_canonical()'s business in both.
+template <int MODE>
+__device__ __forceinline__ float reflect_k2(f2 dxy, float dz, f2 uxy, float uz) {
+    const f2 pr = dxy * uxy;
+    const float pz = dz * uz;
+    if (MODE == kModeOracle) return twice_canonical(sum3_f64(pr.x, pr.y, pz));
+    float dot = pr.x;
+    dot = dot + pr.y;
+    dot = dot + pz;
+    return twice_canonical(dot);
+}
+
 struct HitPre2 { f2 b, disc; };
 __device__ __forceinline__ HitPre2 intersect_pre2(const f2 cx, const f2 cy, const f2 cz, const f2 r2, float ox,
                                                   float oy, float oz, float dx, float dy, float dz) {
@@ -324,11 +357,7 @@ __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, flo
             if (pair_misses_wave(h.disc)) continue; // nothing below can change best, b0 / b1 / b2 or any (see SKIP above)
         }
         amin = minimum3_abs(amin, h.disc.x, h.disc.y);
-        // sqrt_rn_rsq1 on both lanes of the pair (pt_core.h): y = x*r, hh = r/2, q = fma(fma(-y,y,x), hh, y)
-        const f2 r0 = {__builtin_amdgcn_rsqf(h.disc.x), __builtin_amdgcn_rsqf(h.disc.y)};
-        const f2 y = h.disc * r0, hh = r0 * 0.5f;
-        const f2 res = __builtin_elementwise_fma(-y, y, h.disc);
-        const f2 q = __builtin_elementwise_fma(res, hh, y);
+        const f2 q = sqrt_rn_rsq1_pair(h.disc);
         // Both keys of a sphere by ONE 64-bit add of (2^31 - bias, -bias) to its (-t0, t1) register pair (u(x) = bit pattern).
         // Low half: u(-t0) + 2^31 - bias (mod 2^32) is key(t0) = u(t0) - bias when t0 > eps (u(-t0) = 2^31 + u(t0)); for every other
         // t0 -- negative: u(|t0|) + 2^31 - bias; in [+0, eps]: 2^32 - (bias - u(t0)); NaN, inf -- it is >= key(kMissT), like the
@@ -380,45 +409,15 @@ __device__ __forceinline__ uint64_t bounce_ns8_v2(const Scene8 &sc, const Tab8 t
         const float hz = s.oz + s.dz * tmin;
         const f2 nxy = hxy - f2{c.x, c.y};                         // :635-637
         const float nz = hz - c.z;
-        const f2 sq = nxy * nxy;
-        float len2;
-        if (MODE == kModeOracle) {                                 // np.linalg.norm, gen_data.py:347: float64 accumulation
-            const float p2 = nz * nz;
-            double acc = (double)sq.x;                             // (sdot starts from 0.0: 0 + a square is that square)
-            acc = acc + (double)sq.y;
-            acc = acc + (double)p2;
-            len2 = (float)acc;
-        } else {
-            float acc = sq.x + sq.y;                               // :641-649 (0 + x^2 is x^2: a square is never -0)
-            acc = acc + nz * nz;
-            len2 = acc;
-        }
-        float L;
-        {
-            const float r0 = __builtin_amdgcn_rsqf(len2);
-            amin = minimum3_abs_after_trans(amin, r0, nxy.x); // validity of the fast sqrt / divide sequences: see kFastMin
-            amin = minimum3_abs(amin, nxy.y, nz);
-            const float y = len2 * r0, h = 0.5f * r0;
-            const float r = __builtin_fmaf(-y, y, len2);
-            L = __builtin_fmaf(r, h, y);
-        }
+        const float len2 = normal_len2<MODE>(nxy, nz);
+        const float r0 = __builtin_amdgcn_rsqf(len2);
+        amin = minimum3_abs_after_trans(amin, r0, nxy.x);          // validity of the fast sqrt / divide sequences: see kFastMin
+        amin = minimum3_abs(amin, nxy.y, nz);
+        const float L = sqrt_rsq_step(len2, r0);
         f2 uxy;
         float uz;
         div3_packed(nxy, nz, L, uxy, uz);           // pt_core.h; validity = the amin / huge tests of this function
-        const f2 pr = dxy * uxy;
-        const float pz = s.dz * uz;
-        float dot;
-        if (MODE == kModeOracle) {                                 // np.dot, gen_data.py:349
-            double acc = (double)pr.x;                             // (sdot's 0.0 start: twice_canonical() below)
-            acc = acc + (double)pr.y;
-            acc = acc + (double)pz;
-            dot = (float)acc;
-        } else {
-            dot = pr.x;                                            // :690 Duplicate(0): twice_canonical() below; :694-696
-            dot = dot + pr.y;
-            dot = dot + pz;
-        }
-        const float k2 = twice_canonical(dot);                    // :697
+        const float k2 = reflect_k2<MODE>(dxy, s.dz, uxy, uz);
         n.dxy = dxy - uxy * k2;                                    // :699-704
         n.dz = s.dz - uz * k2;
         n.oxy = hxy; n.oz = hz;                                    // :706-708
@@ -456,18 +455,7 @@ __device__ __forceinline__ uint64_t bounce_ns8_v2_hit(const Scene8 &sc, const Ta
     m.hz = s.oz + s.dz * tmin;
     m.nxy = m.hxy - f2{c.x, c.y};                              // :635-637
     m.nz = m.hz - c.z;
-    const f2 sq = m.nxy * m.nxy;
-    if (MODE == kModeOracle) {                                 // np.linalg.norm, gen_data.py:347: float64 accumulation
-        const float p2 = m.nz * m.nz;
-        double acc = (double)sq.x;                             // (sdot starts from 0.0: 0 + a square is that square)
-        acc = acc + (double)sq.y;
-        acc = acc + (double)p2;
-        m.len2 = (float)acc;
-    } else {
-        float acc = sq.x + sq.y;                               // :641-649 (0 + x^2 is x^2: a square is never -0)
-        acc = acc + m.nz * m.nz;
-        m.len2 = acc;
-    }
+    m.len2 = normal_len2<MODE>(m.nxy, m.nz);
     m.r0 = __builtin_amdgcn_rsqf(m.len2);
     amin = minimum3_abs_after_trans(amin, m.r0, m.nxy.x);      // validity of the fast sqrt / divide sequences: see kFastMin
     amin = minimum3_abs(amin, m.nxy.y, m.nz);
@@ -475,29 +463,11 @@ __device__ __forceinline__ uint64_t bounce_ns8_v2_hit(const Scene8 &sc, const Ta
 }
 template <int MODE>
 __device__ __forceinline__ void bounce_ns8_v2_reflect(PathState &s, const Bounce8Mid &m, uint64_t &alive, Albedo &albedo) {
-    float L;
-    {
-        const float y = m.len2 * m.r0, h = 0.5f * m.r0;
-        const float r = __builtin_fmaf(-y, y, m.len2);
-        L = __builtin_fmaf(r, h, y);
-    }
+    const float L = sqrt_rsq_step(m.len2, m.r0);
     f2 uxy;
     float uz;
     div3_packed(m.nxy, m.nz, L, uxy, uz);
-    const f2 pr = s.dxy * uxy;
-    const float pz = s.dz * uz;
-    float dot;
-    if (MODE == kModeOracle) {                                 // np.dot, gen_data.py:349
-        double acc = (double)pr.x;                             // (sdot's 0.0 start: twice_canonical() below)
-        acc = acc + (double)pr.y;
-        acc = acc + (double)pz;
-        dot = (float)acc;
-    } else {
-        dot = pr.x;                                            // :690 Duplicate(0): twice_canonical() below; :694-696
-        dot = dot + pr.y;
-        dot = dot + pz;
-    }
-    const float k2 = twice_canonical(dot);                    // :697
+    const float k2 = reflect_k2<MODE>(s.dxy, s.dz, uxy, uz);
     s.dxy = s.dxy - uxy * k2;                                  // :699-704
     s.dz = s.dz - uz * k2;
     s.oxy = m.hxy; s.oz = m.hz;                                // :706-708
@@ -516,45 +486,15 @@ __device__ __forceinline__ float reflect_packed(const PathState &s, float tmin, 
     const float hz = s.oz + s.dz * tmin;
     const f2 nxy = hxy - f2{cx, cy};                           // :635-637
     const float nz = hz - cz;
-    const f2 sq = nxy * nxy;
-    float len2;
-    if (MODE == kModeOracle) {                                 // np.linalg.norm, gen_data.py:347: float64 accumulation
-        const float p2 = nz * nz;
-        double acc = (double)sq.x;                             // (sdot starts from 0.0: 0 + a square is that square)
-        acc = acc + (double)sq.y;
-        acc = acc + (double)p2;
-        len2 = (float)acc;
-    } else {
-        float acc = sq.x + sq.y;                               // :641-649 (0 + x^2 is x^2: a square is never -0)
-        acc = acc + nz * nz;
-        len2 = acc;
-    }
+    const float len2 = normal_len2<MODE>(nxy, nz);
     const float r0 = __builtin_amdgcn_rsqf(len2);
     float amin = minimum3_abs_after_trans(1.0f, r0, nxy.x);    // validity of the fast sqrt / divide sequences: see kFastMin
     amin = minimum3_abs(amin, nxy.y, nz);
-    float L;
-    {
-        const float y = len2 * r0, h = 0.5f * r0;
-        const float r = __builtin_fmaf(-y, y, len2);
-        L = __builtin_fmaf(r, h, y);
-    }
+    const float L = sqrt_rsq_step(len2, r0);
     f2 uxy;
     float uz;
     div3_packed(nxy, nz, L, uxy, uz);
-    const f2 pr = s.dxy * uxy;
-    const float pz = s.dz * uz;
-    float dot;
-    if (MODE == kModeOracle) {                                 // np.dot, gen_data.py:349
-        double acc = (double)pr.x;                             // (sdot's 0.0 start: twice_canonical() below)
-        acc = acc + (double)pr.y;
-        acc = acc + (double)pz;
-        dot = (float)acc;
-    } else {
-        dot = pr.x;                                            // :690 Duplicate(0): twice_canonical() below; :694-696
-        dot = dot + pr.y;
-        dot = dot + pz;
-    }
-    const float k2 = twice_canonical(dot);                    // :697
+    const float k2 = reflect_k2<MODE>(s.dxy, s.dz, uxy, uz);
     n.dxy = s.dxy - uxy * k2;                                  // :699-704
     n.dz = s.dz - uz * k2;
     n.oxy = hxy; n.oz = hz;                                    // :706-708

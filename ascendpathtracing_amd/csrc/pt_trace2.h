@@ -45,15 +45,6 @@ __device__ __forceinline__ PathState unpack_path(const PathPair &p, int which, u
     return s;
 }
 
-// float32(sum in float64 of three float32 products): np.dot / np.linalg.norm of the NumPy oracle (gen_data.py:347,349).  sdot's start
-// value 0.0 is not added: squares are never -0, and the dot product's consumer is twice_canonical() (pt_trace.h).
-__device__ __forceinline__ float sum3_f64(float p0, float p1, float p2) {
-    double acc = (double)p0;
-    acc = acc + (double)p1;
-    acc = acc + (double)p2;
-    return (float)acc;
-}
-
 // One bounce of both paths.  aliveA / aliveB: wave masks (in: before, out: after).  redoA / redoB: wave masks of
 // the lanes whose path A / B left the validity range of the fast sequences.  `ones_off`: byte offset, relative to the albedo
 // table, of an entry (1, 1, 1) -- a path that is no longer alive multiplies its throughput by it (x1 is exact).
@@ -109,17 +100,12 @@ __device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, 
         len2 = nx * nx + ny * ny;                                                  // :641-649 (0 + x^2 is x^2)
         len2 = len2 + nz * nz;
     }
-    f2 L;
     const f2 r0 = {__builtin_amdgcn_rsqf(len2.x), __builtin_amdgcn_rsqf(len2.y)};
-    {   // sqrt_rn_rsq1 on both paths
-        aminA = minimum3_abs_after_trans(aminA, r0.x, nx.x);    // validity of the fast sqrt / divide sequences: see kFastMin (pt_trace.h)
-        aminA = minimum3_abs(aminA, ny.x, nz.x);
-        aminB = minimum3_abs_after_trans(aminB, r0.y, nx.y);
-        aminB = minimum3_abs(aminB, ny.y, nz.y);
-        const f2 y = len2 * r0, h = r0 * 0.5f;
-        const f2 r = __builtin_elementwise_fma(-y, y, len2);
-        L = __builtin_elementwise_fma(r, h, y);
-    }
+    aminA = minimum3_abs_after_trans(aminA, r0.x, nx.x);        // validity of the fast sqrt / divide sequences: see kFastMin (pt_trace.h)
+    aminA = minimum3_abs(aminA, ny.x, nz.x);
+    aminB = minimum3_abs_after_trans(aminB, r0.y, nx.y);
+    aminB = minimum3_abs(aminB, ny.y, nz.y);
+    const f2 L = sqrt_rsq_step(len2, r0);                       // sqrt_rn_rsq1 on both paths
     // the three quotients of both paths, the reciprocal refined from the square root's own seed (pt_core.h): no v_rcp_f32.  A lane
     // whose divisor has an all-ones mantissa can come out with e1 == 2^-24 and then joins the exact re-run below.
     f2 ux, uy, uz, e1;

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of two builds' `make asm` output:
    python profiles/isa_compare.py OLD_CSRC [NEW_CSRC]     (NEW_CSRC: this tree's ascendpathtracing_amd/csrc)
-Runs `make -B asm` in both directories.  For every kernel of render_kernels.s, materials.s, environment.s and film.s it compares the instruction lines
+Runs `make -B asm` in both directories.  For every kernel of the seven code objects -- render_kernels.s, materials.s, environment.s, film.s,
+features.s, selftest_seeded.s and denoise.s -- it compares the instruction lines
 between the symbol and its .Lfunc_end (labels, directives and comments dropped; block labels renumbered per function, since a
 function's index in the file moves them; differences counted by a sequence diff) and the kernel-resource-usage remarks (registers,
-spills, scratch, LDS, occupancy).  Kernels of render_kernels.s are matched by symbol; those of materials.s, environment.s and film.s by demangled name
-without the argument list, so that a kernel whose signature changed is compared with its predecessor.  environment.s and film.s are skipped
-when the old build has none.
-Prints one line per kernel that differs and a summary per file.  For materials.s it also prints whether every kernel keeps scratch 0,
+spills, scratch, LDS, occupancy).  Kernels of render_kernels.s are matched by symbol; those of the other files by demangled name
+without the argument list, so that a kernel whose signature changed is compared with its predecessor.  A file other than
+render_kernels.s and materials.s is skipped when the old build has none.
+Prints one line per kernel that differs -- with whether the two bodies still hold the same instructions, each mnemonic as often as
+before, i.e. differ by operands and order only -- and a summary per file.  For the files matched by name it also prints whether every kernel keeps scratch 0,
 no VGPR spills and at least the old occupancy (`conditions`).  Exit status 1 when a kernel of render_kernels.s differs at all, when a
 kernel of materials.s exists on one side only, or when one breaks those conditions."""
 import difflib, os, re, subprocess, sys
+from collections import Counter
 from concurrent.futures import ThreadPoolExecutor
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,8 +68,8 @@ def main():
     with ThreadPoolExecutor(2) as ex:
         ro, rn = ex.map(build, (old, new))
     differ = 0
-    for s in ("render_kernels.s", "materials.s", "environment.s", "film.s"):
-        if s in ("environment.s", "film.s") and not os.path.exists(os.path.join(old, s)):   # an old build from before there was one
+    for s in ("render_kernels.s", "materials.s", "environment.s", "film.s", "features.s", "selftest_seeded.s", "denoise.s"):
+        if s not in ("render_kernels.s", "materials.s") and not os.path.exists(os.path.join(old, s)):   # an old build from before there was one
             continue
         ko, kn = kernels(os.path.join(old, s)), kernels(os.path.join(new, s))
         dm = demangle(sorted(set(ko) | set(kn)))
@@ -96,8 +99,9 @@ def main():
             differ += not by_name
             ops = [o for o in difflib.SequenceMatcher(None, ko[n], kn[n]).get_opcodes() if o[0] != "equal"]
             lines = sum(max(i2 - i1, j2 - j1) for _, i1, i2, j1, j2 in ops)
+            mnemonics = "same" if Counter(l.split()[0] for l in ko[n]) == Counter(l.split()[0] for l in kn[n]) else "DIFFERENT"
             print(f"{s}: {dm[n]}: {len(ko[n])} -> {len(kn[n])} instructions, {lines} lines in {len(ops)} hunks differ "
-                  f"(first at instruction {ops[0][1] if ops else '-'}){res}")
+                  f"(first at instruction {ops[0][1] if ops else '-'}), {mnemonics} mnemonic counts{res}")
         print(f"{s}: {same} of {len(set(ko) | set(kn))} kernels identical (instructions and resources)")
         if by_name:
             print(f"{s}: conditions (scratch 0, no VGPR spills, occupancy not below the old build's): "
