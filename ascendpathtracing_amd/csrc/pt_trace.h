@@ -172,9 +172,13 @@ __device__ __forceinline__ HitPre2 intersect_pre2(const float4 a, const float4 c
 // returns them.  Distinct coordinates in register pairs:  X1 = (cx0, cx1)  X2 = (cx2, cx6)   Y1 = (cy4, cy5)  Y2 = (cy6, cy7)
 // Y3 = (cy0, cy0)   Z1 = (cz2, cz3)  Z2 = (cz0, cz6); every sum of a sphere pair finds both of its operands inside ONE pair per
 // source (op_sel picks the halves), so nothing is shuffled.  Operation for operation what intersect_pre2 computes per sphere.
+// WANT_C67: pair (6,7)'s c of disc = b*b - c as well, for sphere_reachable_mask() below.  A template flag and not a member of
+// HitPre2 or a run-time test: a second reader of c, even one that folds away later, makes the compiler commute the operands of
+// disc's subtraction in every kernel that computes it.
+template <bool WANT_C67 = false>
 __device__ __forceinline__ void intersect_pre_planes_pairs(const f2 X1, const f2 X2, const f2 Y1, const f2 Y2, const f2 Y3, const f2 Z1, const f2 Z2,
                                                            const f2 R0, const f2 R1, const f2 R2, const f2 R3, float ox, float oy, float oz,
-                                                           float dx, float dy, float dz, HitPre2 (&h)[4]) {
+                                                           float dx, float dy, float dz, HitPre2 (&h)[4], f2 *c67 = nullptr) {
     const f2 x1 = X1 - ox, x2 = X2 - ox, y1 = Y1 - oy, y2 = Y2 - oy, y3 = Y3 - oy, z1 = Z1 - oz, z2 = Z2 - oz;
     auto lo = [](f2 v) { return f2{v.x, v.x}; };
     auto swap = [](f2 v) { return f2{v.y, v.x}; };
@@ -191,13 +195,15 @@ __device__ __forceinline__ void intersect_pre_planes_pairs(const f2 X1, const f2
         c0 = c0 - R0; c1 = c1 - R1; c2 = c2 - R2; c3 = c3 - R3;
         h[0].disc = h[0].b * h[0].b - c0; h[1].disc = h[1].b * h[1].b - c1;
         h[2].disc = h[2].b * h[2].b - c2; h[3].disc = h[3].b * h[3].b - c3;
+        if (WANT_C67) *c67 = c3;
     }
 }
+template <bool WANT_C67 = false>
 __device__ __forceinline__ void intersect_pre_planes(const Scene8 &sc, float ox, float oy, float oz, float dx, float dy, float dz,
-                                                     HitPre2 (&h)[4]) {
-    intersect_pre_planes_pairs(f2{sc.cx[0], sc.cx[1]}, f2{sc.cx[2], sc.cx[6]}, f2{sc.cy[4], sc.cy[5]}, f2{sc.cy[6], sc.cy[7]}, f2{sc.cy[0], sc.cy[0]},
+                                                     HitPre2 (&h)[4], f2 *c67 = nullptr) {
+    intersect_pre_planes_pairs<WANT_C67>(f2{sc.cx[0], sc.cx[1]}, f2{sc.cx[2], sc.cx[6]}, f2{sc.cy[4], sc.cy[5]}, f2{sc.cy[6], sc.cy[7]}, f2{sc.cy[0], sc.cy[0]},
                                f2{sc.cz[2], sc.cz[3]}, f2{sc.cz[0], sc.cz[6]}, f2{sc.r2[0], sc.r2[1]}, f2{sc.r2[2], sc.r2[3]}, f2{sc.r2[4], sc.r2[5]},
-                               f2{sc.r2[6], sc.r2[7]}, ox, oy, oz, dx, dy, dz, h);
+                               f2{sc.r2[6], sc.r2[7]}, ox, oy, oz, dx, dy, dz, h, c67);
 }
 
 // ---- trace: reference scene (Ns == 8) ----------------------------------------------------
@@ -286,6 +292,14 @@ __device__ __forceinline__ float minimum3_abs_after_trans(float a, float b, floa
     asm("s_nop 0\n\tv_minimum3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// v_rsq_f32 that stays in the block it is written in: the compiler hoists the builtin above a wave-uniform branch when every side
+// of it takes the same seed, and a wave that branches round all of them then pays for two transcendentals.  The s_nop is the wait
+// state between a TRANS result and its first non-TRANS reader, which the compiler does not insert for inline asm.
+__device__ __forceinline__ float rsq_here(float x) {
+    float r;
+    asm("v_rsq_f32 %0, %1\n\ts_nop 0" : "=v"(r) : "v"(x));
+    return r;
+}
 __device__ __forceinline__ uint32_t min3_u32(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t r;
     asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -325,12 +339,44 @@ struct Hit8 { float tmin; uint32_t addr; uint64_t light; };
 __device__ __forceinline__ bool pair_misses_wave(f2 disc) {
     return __builtin_amdgcn_ballot_w64(__builtin_fmaxf(disc.x, disc.y) >= 0.0f) == 0;
 }
+// "This lane may hit the sphere", per sphere and with the ray's direction: wave mask of the lanes with med3(disc, b, -c) >= -2^-60 (one
+// v_med3_f32 with a negated source, one compare).  A lane outside the mask has at least two of disc, b, -c below -2^-60 (or NaN: a NaN
+// operand drops out of v_med3_f32, which then returns the minimum of the others), that is
+//   (a) disc < 0 or NaN: no real root; or
+//   (b) b < -2^-60 and c > 2^-60 with disc >= -2^-60: the sphere lies behind a ray that starts outside it.  Then, or (a) again, or
+//       disc = RN(RN(b*b) - c) <= RN(b*b) (c > 0, rounding is monotonic), q = RN(sqrt(disc)) <= RN(sqrt(RN(b*b))) = |b| (b*b is a
+//       normal number: |b| > 2^-60 -- the guard; a denormal square can round UP, and its root exceed |b|), so t1 = RN(b + q) <= 0 and
+//       t0 = RN(b - q) <= b < 0: no root is above eps >= 0.  (b*b = inf, |b| >= 2^64: disc is inf or NaN; t0 is -inf or NaN and t1 = b + inf
+//       is +inf or NaN.  A +inf root passes "t > eps" in the reference's selection, but it is not below kMissT and its key is not below
+//       key(kMissT): it wins no arg-min, with the stage or without.)
+// The mask errs to one side only: a lane inside it may still miss (a disc in [-2^-60, 0) with b or -c above the guard; an origin
+// inside the sphere), and the stage then runs as before.
+constexpr float kBehindGuard = 0x1p-60f;
+__device__ __forceinline__ uint64_t sphere_reachable_mask(float disc, float b, float c) {
+    return __builtin_amdgcn_ballot_w64(__builtin_amdgcn_fmed3f(disc, b, -c) >= -kBehindGuard);
+}
+// mask != 0 as a scalar integer the compiler cannot see through: a wave-uniform condition that two branches read otherwise travels
+// through a VGPR (v_cndmask + v_cmp, two VALU slots) between them.
+__device__ __forceinline__ uint32_t any_lane(uint64_t mask) {
+    uint32_t r;
+    asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, 1, 0" : "=s"(r) : "s"(mask) : "scc");
+    return r;
+}
 // SKIP, bit j: the root stage of sphere pair (2j, 2j+1) is branched round (a SCALAR branch) when pair_misses_wave().  The frame is the
 // same bit for bit: in such a wave v_rsq_f32 returns NaN for both discriminants of every lane, q and both (-t0, t1) register pairs are
 // NaN, their keys are >= key(kMissT) (the argument above update64 below) and never win v_min3_u32 -- `best`, b0 / b1 / b2 and `any` keep
 // their values whether the stage runs or not.  The stage's only other product is `amin`, which can only ask for the exact re-run of the
 // bounce, and that computes the same bounce (a negative discriminant is a miss there as well: sqrtf gives NaN, select_root kMissT).
-// Off by default: only the two-path bounce (pt_trace2.h) turns it on, every other caller's code is what it was.
+// SKIP, bit 4 + j: the per-sphere form of the same for pair (2j, 2j+1) -- two sphere_reachable_mask() tests (4 VALU) and scalar branches:
+// no lane can hit either sphere: the stage is branched round; no lane can hit ONE of them: the root stage of the other sphere alone
+// (v_minimum3_f32, v_rsq_f32, the four operations of sqrt_rsq_step, one root_pair, one 64-bit add, one v_min3_u32, one compare: 10 of the
+// 15, and a v_mov_b32 of `best`), which leaves `best`, b0 / b1 / b2, `any` and `amin` as the full stage's half for that sphere does
+// (the packed sqrt_rsq_step rounds each half like the scalar form, whatever the other half holds); otherwise the full stage.
+// The frame is the same bit for bit: a sphere that is left out has, in every lane, either no real root -- the argument above -- or,
+// by (b) above sphere_reachable_mask(), two roots <= 0 <= eps, whose keys are >= key(kMissT) as well (update64's comment: negative and
+// [+0, eps] roots), so its v_min3_u32 would not have changed `best` and its compare would have set no bit.  Its share of `amin` could
+// only have asked for the exact re-run of the bounce, which finds the same miss (select_root: both roots <= eps).
+// Off by default: only the two-path bounce (pt_trace2.h) turns them on, every other caller's code is what it was.
 template <int MODE, bool PLANES = false, int SKIP = 0>
 __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                                  const TraceArgs &ta, const KeyConsts &kc, float &amin) {
@@ -346,16 +392,7 @@ __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, flo
         if (MODE == kModeOracle) any |= better;
     };
     auto update64 = [&](uint64_t keys, int k) { update_keys((uint32_t)keys, (uint32_t)(keys >> 32), k); };
-    HitPre2 hp[4];
-    if (PLANES) intersect_pre_planes(sc, ox, oy, oz, dx, dy, dz, hp);
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) { // rt_helper.h:457-467, two spheres per packed instruction
-        const HitPre2 h = PLANES ? hp[k / 2]
-                                 : intersect_pre2(f2{sc.cx[k], sc.cx[k + 1]}, f2{sc.cy[k], sc.cy[k + 1]}, f2{sc.cz[k], sc.cz[k + 1]},
-                                                  f2{sc.r2[k], sc.r2[k + 1]}, ox, oy, oz, dx, dy, dz);
-        if ((SKIP >> (k / 2)) & 1) {
-            if (pair_misses_wave(h.disc)) continue; // nothing below can change best, b0 / b1 / b2 or any (see SKIP above)
-        }
+    auto full_stage = [&](const HitPre2 &h, int k) __attribute__((always_inline)) {   // the root stage of sphere pair (k, k + 1)
         amin = minimum3_abs(amin, h.disc.x, h.disc.y);
         const f2 q = sqrt_rn_rsq1_pair(h.disc);
         // Both keys of a sphere by ONE 64-bit add of (2^31 - bias, -bias) to its (-t0, t1) register pair (u(x) = bit pattern).
@@ -367,6 +404,40 @@ __device__ __forceinline__ Hit8 intersect_ns8_v2(const Scene8 &sc, float ox, flo
         // `best` therefore only ever holds a true key or the initial one, and tmin = value(best) as before.
         update64(root_pair<0>(h.b, q) + kc.nbias2, k);
         update64(root_pair<1>(h.b, q) + kc.nbias2, k + 1);
+    };
+    static_assert((SKIP >> 4) == 0 || ((SKIP >> 4) == 0x8 && PLANES), "the per-sphere form: pair (6,7) of the shared-planes form only");
+    HitPre2 hp[4];
+    f2 c67 = {0.0f, 0.0f};
+    if (PLANES) intersect_pre_planes<(SKIP >> 4) != 0>(sc, ox, oy, oz, dx, dy, dz, hp, &c67);
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) { // rt_helper.h:457-467, two spheres per packed instruction
+        const HitPre2 h = PLANES ? hp[k / 2]
+                                 : intersect_pre2(f2{sc.cx[k], sc.cx[k + 1]}, f2{sc.cy[k], sc.cy[k + 1]}, f2{sc.cz[k], sc.cz[k + 1]},
+                                                  f2{sc.r2[k], sc.r2[k + 1]}, ox, oy, oz, dx, dy, dz);
+        if ((SKIP >> (k / 2)) & 1) {
+            if (pair_misses_wave(h.disc)) continue; // nothing below can change best, b0 / b1 / b2 or any (see SKIP above)
+        }
+        if ((SKIP >> (4 + k / 2)) & 1) {
+            const uint32_t lo = any_lane(sphere_reachable_mask(h.disc.x, h.b.x, c67.x)), hi = any_lane(sphere_reachable_mask(h.disc.y, h.b.y, c67.y));
+            // Three blocks, each behind a scalar branch of its own on a flag of its own (so a wave that does nothing executes no
+            // VALU instruction here): the full stage, or one sphere's half of it.  There the square root's packed step runs on the
+            // pair with that sphere's seed in both halves (the other half's result is not read: root_pair<HALF> reads half HALF of q).
+            uint32_t both = lo & hi, only_lo = lo & ~hi, only_hi = hi & ~lo;
+            asm("" : "+s"(both), "+s"(only_lo), "+s"(only_hi));
+            if (both != 0u) full_stage(h, k);
+            if (only_lo != 0u) {
+                amin = minimum3_abs(amin, h.disc.x, h.disc.x);
+                const float r0 = rsq_here(h.disc.x);
+                update64(root_pair<0>(h.b, sqrt_rsq_step(h.disc, f2{r0, r0})) + kc.nbias2, k);
+            }
+            if (only_hi != 0u) {
+                amin = minimum3_abs(amin, h.disc.y, h.disc.y);
+                const float r0 = rsq_here(h.disc.y);
+                update64(root_pair<1>(h.b, sqrt_rsq_step(h.disc, f2{r0, r0})) + kc.nbias2, k + 1);
+            }
+            continue;
+        }
+        full_stage(h, k);
     }
     const float tmin = bits_f32(best + kc.bias);
     uint64_t light_mask; // lanes whose arg-min is the light

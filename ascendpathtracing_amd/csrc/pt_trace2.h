@@ -25,8 +25,14 @@ namespace {
 //   * no wall pair: a ray inside the room always has one of two opposite walls in front of it (0 of 4.1 million waves);
 //   * nothing in the general form: its pairing is whatever the table's order makes it (bench.py's general scene: 0 for every pair);
 //   * not path B of the LAST bounce: with that one the headline kernel keeps two VGPRs in scratch (at 12 % there it would pay nothing).
-template <bool PLANES> constexpr int kPairSkip = PLANES ? 0x8 : 0;
-constexpr int kPairSkipLastB = 0;
+// From the second bounce on, pair (6,7) takes the per-sphere form with the ray's direction (SKIP bit 7; profiles/pair67_split_counts.json):
+// whatever way a ray points, its line crosses the light's sphere (r = 600) for a large share of the room, so "both discriminants negative"
+// falls from 0.81 to 0.12 of the waves over eight bounces, while no lane can reach the ball in 0.97 .. 0.81 of them and neither sphere in
+// 0.85 .. 0.51; a wave then solves the light alone (0.06 .. 0.31), the ball alone (0.03 .. 0.10) or both (0.00 .. 0.13).  Camera rays
+// (FIRST) gain nothing from the direction -- the counts of the two predicates agree to four digits there -- and keep the two-instruction
+// test.  Path B of the last bounce stays off: the per-sphere form puts the same two VGPRs of the headline kernel into scratch.
+template <bool PLANES, bool FIRST> constexpr int kPairSkip = !PLANES ? 0 : FIRST ? 0x8 : 0x80;
+template <bool PLANES, bool FIRST> constexpr int kPairSkipLastB = 0;
 
 struct PathPair { // .x = path A, .y = path B
     f2 ox, oy, oz, dx, dy, dz; // rays
@@ -56,8 +62,8 @@ __device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, 
                                               const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                               uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f; // per path: a finished path's request for the exact form can be ignored (trace2_ns8)
-    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
-    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES>>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES, FIRST>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES, FIRST>>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
     if (FIRST) {
         aliveA = ~hA.light;
         aliveB = ~hB.light;
@@ -151,8 +157,8 @@ __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 ta
                                                  const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                                  uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f;
-    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
-    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkipLastB>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES, FIRST>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkipLastB<PLANES, FIRST>>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
     if (FIRST) {
         aliveA = ~hA.light;
         aliveB = ~hB.light;
@@ -221,13 +227,26 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
             const float ox = half ? in.ox.y : in.ox.x, oy = half ? in.oy.y : in.oy.x, oz = half ? in.oz.y : in.oz.x;
             const float dx = half ? in.dx.y : in.dx.x, dy = half ? in.dy.y : in.dy.x, dz = half ? in.dz.y : in.dz.x;
             HitPre2 hp[4];
-            if (PLANES) intersect_pre_planes(sc, ox, oy, oz, dx, dy, dz, hp);
+            f2 c67 = {0.0f, 0.0f};
+            if (PLANES) intersect_pre_planes<true>(sc, ox, oy, oz, dx, dy, dz, hp, &c67);
             for (int k = 0; k < 8; k += 2) {
                 const HitPre2 h = PLANES ? hp[k / 2]
                                          : intersect_pre2(f2{sc.cx[k], sc.cx[k + 1]}, f2{sc.cy[k], sc.cy[k + 1]}, f2{sc.cz[k], sc.cz[k + 1]},
                                                           f2{sc.r2[k], sc.r2[k + 1]}, ox, oy, oz, dx, dy, dz);
                 const uint32_t slot = 4u + (uint32_t)(half * 8 + (count_bounce < 7u ? count_bounce : 7u)) * 4u + (uint32_t)(k / 2);
                 if (pair_misses_wave(h.disc) && lane0) atomicAdd(ta.traced + slot, 1ull);
+                if (PLANES && k == 6) {   // pair (6,7) per sphere, with direction (profiles/pair67_split_counts.json): the block then needs 72 + 16 * 4 entries
+                    // [72 + (half * 8 + bounce) * 4 + j] += 1 per wave where no lane can hit  j = 0: sphere 6   1: sphere 7   2: either
+                    // (sphere_reachable_mask, what the kernel tests);  3: either, by the unguarded statement disc < 0 or NaN or (b < 0 and c > 0)
+                    const uint32_t s67 = 72u + (uint32_t)(half * 8 + (count_bounce < 7u ? count_bounce : 7u)) * 4u;
+                    const bool u6 = sphere_reachable_mask(h.disc.x, h.b.x, c67.x) == 0, u7 = sphere_reachable_mask(h.disc.y, h.b.y, c67.y) == 0;
+                    const bool r6 = h.disc.x >= 0.0f && !(h.b.x < 0.0f && c67.x > 0.0f), r7 = h.disc.y >= 0.0f && !(h.b.y < 0.0f && c67.y > 0.0f);
+                    const bool plain = __builtin_amdgcn_ballot_w64(r6 || r7) == 0;
+                    if (u6 && lane0) atomicAdd(ta.traced + s67, 1ull);
+                    if (u7 && lane0) atomicAdd(ta.traced + s67 + 1, 1ull);
+                    if (u6 && u7 && lane0) atomicAdd(ta.traced + s67 + 2, 1ull);
+                    if (plain && lane0) atomicAdd(ta.traced + s67 + 3, 1ull);
+                }
             }
         }
         if (count_bounce == 0 && lane0) atomicAdd(ta.traced + 68, 1ull);

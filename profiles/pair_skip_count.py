@@ -8,6 +8,10 @@ One C2 frame (bench.py's headline launch, render_frame_kernel<0, 0, 8, false, tr
 build (pt_trace2.h, APT_COUNT_PAIR_SKIP) adds one to entry [4 + (half * 8 + bounce) * 4 + pair] for every wave in which
 pair_misses_wave() holds -- both discriminants of the pair negative or NaN in all 64 lanes -- and one to entry [68] per wave and path pair it traces (the denominator).
 `--general`: the bench's general scene (spheres 0 and 6 exchanged), the non-shared-planes arm.
+`--split-out FILE` (profiles/pair67_split_counts.json): pair (6,7) per sphere and with the ray's direction, from the same frame -- the
+counting build adds one to entry [72 + (half * 8 + bounce) * 4 + j] per wave in which no lane can hit sphere 6 (j = 0), sphere 7 (1) or
+either (2) by pt_trace.h's sphere_reachable_mask(), and (3) either by the unguarded statement "disc < 0 or NaN, or b < 0 and c > 0" --
+and the price of every order of tests under the same model (ONE_STAGE_CYCLES: the root stage of one sphere, 11 VALU instructions, one of them v_rsq_f32).
 The price model of the table: a pair's root stage is 15 VALU + 2 v_rsq_f32 = 78 cycles, the test 2 VALU = 8 cycles, a pair-bounce 1250
 cycles, so a pair pays for itself from P = 0.10 on."""
 import argparse
@@ -23,6 +27,39 @@ import __graft_entry__  # noqa: E402
 
 W, H, S, DEPTH = 1920, 1080, 64, 8
 STAGE_CYCLES, TEST_CYCLES, PAIR_BOUNCE_CYCLES = 15 * 4.1 + 2 * 8.3, 2 * 4.1, 1250.0
+ONE_STAGE_CYCLES = 11 * 4.1 + 1 * 8.3   # as compiled: the full stage's half for one sphere is 10 instructions, and one v_mov
+
+
+def split_table(c, waves):
+    """Shares and prices of the per-sphere tests of pair (6,7), per path half and bounce.  Cycles per path-bounce of
+      now        the pair test, then the full stage                                  T + (1 - Pa) F
+      both       test 6, test 7: skip / sphere 7 only / sphere 6 only / full         2T + (P6 - P67) O + (P7 - P67) O + (1 - P6 - P7 + P67) F
+      six_first  test 6; if no lane can hit it test 7: skip / sphere 7 only; else full   T + P6 T + (P6 - P67) O + (1 - P6) F
+    with T = 2 VALU, F the full stage, O the one-sphere stage."""
+    T, F, O = TEST_CYCLES, STAGE_CYCLES, ONE_STAGE_CYCLES
+    sites = []
+    for h in (0, 1):
+        for b in range(DEPTH):
+            base = 72 + (h * 8 + b) * 4
+            p6, p7, p67, plain = (c[base + j] / waves for j in range(4))
+            pa = c[4 + (h * 8 + b) * 4 + 3] / waves
+            cost = {"now": T + (1 - pa) * F,
+                    "both": 2 * T + (p6 - p67) * O + (p7 - p67) * O + (1 - p6 - p7 + p67) * F,
+                    "six_first": T + p6 * T + (p6 - p67) * O + (1 - p6) * F}
+            best = min(cost, key=cost.get)
+            # what is built (pt_trace2.h kPairSkip): "now" at the first bounce, "both" from the second on, nothing on path B's last bounce
+            last_b = h == 1 and b == DEPTH - 1
+            valu_now = 15.0 if last_b else 2 + (1 - pa) * 15
+            valu_built = valu_now if (b == 0 or last_b) else 4 + (p6 + p7 - 2 * p67) * 11 + (1 - p6 - p7 + p67) * 15
+            cycles_now = F if last_b else cost["now"]
+            cycles_built = cycles_now if (b == 0 or last_b) else cost["both"]
+            sites.append({"path": "AB"[h], "bounce": b + 1, "U6": round(p6, 4), "U7": round(p7, 4), "U6_and_U7": round(p67, 4),
+                          "U6_not_U7": round(p6 - p67, 4), "U7_not_U6": round(p7 - p67, 4), "U6_and_U7_unguarded": round(plain, 4),
+                          "present_predicate": round(pa, 4), "cycles": {k: round(v, 2) for k, v in cost.items()}, "cheapest": best,
+                          "saving_cycles": round(cost["now"] - cost[best], 2),
+                          "built": "unchanged" if (b == 0 or last_b) else "both", "built_saving_cycles": round(cycles_now - cycles_built, 2),
+                          "built_valu_instructions_saved": round(valu_now - valu_built, 3)})
+    return sites
 
 
 def main():
@@ -30,6 +67,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(here, "pair_skip_counts.json"))
     ap.add_argument("--general", action="store_true")
+    ap.add_argument("--split-out", default=None)
     args = ap.parse_args()
     apt = __graft_entry__.build()
     from ascendpathtracing_amd import _lib, gen_data, render
@@ -39,7 +77,7 @@ def main():
         perm = sph.clone().view(-1)[:80].view(10, 8).clone()
         perm[:, [0, 6]] = perm[:, [6, 0]]
         sph[:80] = perm.reshape(-1)
-    buf = torch.zeros(128, dtype=torch.int64, device="cuda")
+    buf = torch.zeros(256, dtype=torch.int64, device="cuda")
     _lib.lib().apt_set_trace_counter(ctypes.c_void_p(buf.data_ptr()))
     render.render_frame(apt.make_params(W, H, S, depth=DEPTH), sph)
     torch.cuda.synchronize()
@@ -66,6 +104,24 @@ def main():
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))
+    if args.split_out:
+        sites = split_table(c, waves)
+        per_form = {k: round(sum(s["cycles"]["now"] - s["cycles"][k] for s in sites) / DEPTH, 2) for k in ("both", "six_first")}
+        split = {"what": "pair (6,7) of one C2 frame: share of the waves in which every lane satisfies U6 / U7 (the sphere cannot be hit: "
+                         "sphere_reachable_mask() is 0), per path half and bounce, and the cycles per path-bounce of each order of tests",
+                 "launch": out["launch"], "frame": out["frame"], "scene": out["scene"], "device": out["device"], "wave_pair_traces": waves,
+                 "price_model": f"VALU 4.1, transcendental 8.3 cycles: test {TEST_CYCLES:.1f}, full stage {STAGE_CYCLES:.1f}, "
+                                f"one-sphere stage {ONE_STAGE_CYCLES:.1f}, pair-bounce {PAIR_BOUNCE_CYCLES:.0f}",
+                 "sites": sites,
+                 "saving_cycles_per_pair_bounce_one_form_everywhere": per_form,
+                 "saving_cycles_per_pair_bounce_cheapest_per_site": round(sum(s["saving_cycles"] for s in sites) / DEPTH, 2),
+                 "go_threshold_cycles": round(0.015 * PAIR_BOUNCE_CYCLES, 2),
+                 "built_saving_cycles_per_pair_bounce": round(sum(s["built_saving_cycles"] for s in sites) / DEPTH, 2),
+                 "built_predicted_valu_instructions_per_segment_saved": round(sum(s["built_valu_instructions_saved"] for s in sites) / (2 * DEPTH), 3)}
+        with open(args.split_out, "w") as f:
+            json.dump(split, f, indent=1)
+            f.write("\n")
+        print(json.dumps(split))
 
 
 if __name__ == "__main__":
