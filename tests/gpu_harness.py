@@ -1,6 +1,6 @@
 """What the material renderer's GPU test files share (tests/test_gpu_materials*.py, _nee, _lights, _gloss, _camera, _environment, _film,
-_features, _glass_physics, _deep_plans): the `apt` fixture, the comparisons, one Scene and the scenes that more than one file renders.
-A plain module beside materials_ref.py, imported the same way: `from gpu_harness import apt  # noqa: F401` brings the fixture.
+_features, _glass_physics, _deep_plans, _material_matrix): the `apt` fixture, the comparisons, one Scene and the scenes that more than one
+file renders.  A plain module beside materials_ref.py, imported the same way: `from gpu_harness import apt  # noqa: F401` brings the fixture.
 
 A Scene's host half -- the tables the restatements read -- needs no device: the tensors are made on first use."""
 import contextlib
@@ -204,7 +204,23 @@ def _build(apt, name):
         a, b = (7, 19) if ns == 40 else (11, 97)
         sph = gd.with_lamps(sph, ns, [a, b], radius=[1.5, 2.0], emission=[(40.0, 30.0, 20.0), 25.0])
         return Scene(apt, sph, _glossy(apt, mat, 2), ns, [a, b], a, grid=ns > 64)
+    if name == "big1030g":                                 # big1030x2 with every second mirror rough metal (Scene.plain: gloss-free again)
+        sph, mat, ns, idx = lr.sixteen_lamps(gd)
+        return Scene(apt, sph, _glossy(apt, mat, 2), ns, [ns - 1, idx[5]], ns - 1, grid=True)
     base, kind = name.split("-")                           # "<diff8|demo9|big1030>-<stock|lamp>": the closed rooms, their light listed alone
+    assert kind in ("stock", "lamp")
+    if base in ("gloss8", "gloss9"):                       # closed rooms for every kernel of materials.hip: the ball (sphere 6) rough metal and a
+        if base == "gloss8":                               # weak second light, the light (sphere 7) the stock one or smallpt's lamp; two listed
+            sph, mat = gd.gen_spheres(), np.array([1, 1, 1, 1, 1, 1, 0, 1], dtype=np.int32)
+            mat[6] = gd.gloss(0.3)
+        else:                                              # the demo scene with its glass ball; with a grid of its own (form 2 at 9 spheres)
+            sph, mat = gd.gen_spheres_materials(gloss=0.25)
+        ns = int(np.asarray(mat).size)
+        sph = np.array(sph, dtype=F)
+        sph[:10 * ns].reshape(10, ns)[4:7, 6] = [3.0, 6.0, 9.0]
+        if kind == "lamp":
+            sph = gd.with_lamp(sph, ns, 7)
+        return Scene(apt, sph, mat, ns, [7, 6], 7, grid=ns != 8)
     if base == "diff8":                                    # 8-sphere form: DIFF walls and light, the mirror SPEC
         sph, mat, light = gd.gen_spheres(), np.array([1, 1, 1, 1, 1, 1, 0, 1], dtype=np.int32), 7
     elif base == "demo9":                                  # tile form: gen_spheres + the glass ball
@@ -215,7 +231,6 @@ def _build(apt, name):
         sph, mat = gd.gen_scene_materials(1030, seed=5)
         light = 1029
     ns = int(np.asarray(mat).size)
-    assert kind in ("stock", "lamp")
     if kind == "lamp":                                     # smallpt's small lamp in the light's place
         sph = gd.with_lamp(sph, ns, light)
     return Scene(apt, sph, mat, ns, [light], light, grid=base == "big1030")
@@ -237,6 +252,17 @@ def pinhole(apt, w, h, aperture=0.0):
 
 def lens(apt, w, h):
     return pinhole(apt, w, h, aperture=1.5)
+
+
+def inside_pinhole(apt, w, h, aperture=0.0):
+    """A look-at camera whose eye is INSIDE the closed rooms (x in [1, 99], y in [0, 81.6], z in [0, 170]); pinhole / lens put theirs
+    at z = 210, behind the front wall, from where a closed room renders black.  It sees the open scenes' balls as well."""
+    return apt.gen_data.camera(width=w, height=h, aperture=aperture, eye=(20.0, 60.0, 160.0), target=(70.0, 20.0, 60.0), up=(0.1, 1.0, 0.05),
+                               vfov_deg=55.0, offset=0.0)
+
+
+def inside_lens(apt, w, h):
+    return inside_pinhole(apt, w, h, aperture=2.5)
 
 
 def sky_and_sun(apt, sample=True):
