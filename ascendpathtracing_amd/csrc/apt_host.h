@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "../../include/render_mi355x.h"
+#include "pt_core.h"   // kGridSpheresPerCell
 
 // everything the library exports is named in apt_exports.map; APT_API marks the C++-linkage render_do forwarder
 #define APT_API __attribute__((visibility("default")))
@@ -84,4 +85,10 @@ namespace apt {
 apt_context &default_context(); // process-wide, constructed on first use (thread-safe static)
 // What both forms of the film resolve refuse (host_helpers.cpp; include/render_mi355x.h "film"): APT_OK or the error record set.
 int film_resolve_check(const apt_film_resolve *r, const void *film, const void *table, const void *out, const void *u8, const char *what);
+// The cell size of both grid builders, in sphere centres per cell: the default context's "grid_spheres_per_cell" knob, or
+// kGridSpheresPerCell while that is 0.
+inline double grid_spheres_per_cell() {
+    const double knob = default_context().snapshot().debug.grid_spheres_per_cell;
+    return knob > 0.0 ? knob : kGridSpheresPerCell;
+}
 }

@@ -488,12 +488,6 @@ int apt_build_lights_host(const float *sph, uint32_t ns, const uint32_t *indices
     return APT_OK;
 }
 
-// Uniform grid for scenes with many spheres (apt_render_params.accel).  Spheres whose radius exceeds 8x the median
-// radius, or that are not finite (pt_core.h grid_is_large), are "large" (the walls and the light of the generated scenes, r >= 600):
-// they go to an always-tested list; the others are binned by their bounding boxes, inflated by `margin`
-// so that any ray the fp32 intersection formula can possibly accept passes through the interior of a
-// cell that lists the sphere (the formula's absolute error on disc is ~1e-3 at these coordinates; the
-// margin is 0.05 + 1e-4 * coordinate scale).  Cells are sized for kGridSpheresPerCell = 0.5 sphere centres each (apt_set_debug("grid_spheres_per_cell", v) overrides: tuning knob).
 uint32_t apt_materials_flags_host(const uint32_t *materials_host, uint32_t num_spheres) {
     if (!materials_host) return 0u;
     for (uint32_t k = 0; k < num_spheres; ++k) {
@@ -511,6 +505,12 @@ uint32_t apt_grid_flags(const void *grid_head_host, uint32_t num_spheres) {
     return (h.magic == apt::kGridMagic && h.num_spheres == num_spheres && h.off_cellslot != 0u) ? (uint32_t)APT_FLAG_GRID_SLOTS : 0u;
 }
 
+// Uniform grid for scenes with many spheres (apt_render_params.accel).  Spheres whose radius exceeds 8x the median
+// radius, or that are not finite (pt_core.h grid_is_large), are "large" (the walls and the light of the generated scenes, r >= 600):
+// they go to an always-tested list; the others are binned by their bounding boxes, inflated by `margin`
+// so that any ray the fp32 intersection formula can possibly accept passes through the interior of a
+// cell that lists the sphere (the formula's absolute error on disc is ~1e-3 at these coordinates; the
+// margin is 0.05 + 1e-4 * coordinate scale).  Cells are sized for kGridSpheresPerCell = 0.5 sphere centres each (apt_set_debug("grid_spheres_per_cell", v) overrides: tuning knob).
 int apt_build_grid_host(const float *sph, uint32_t ns, void *grid, size_t *out_bytes) {
     apt::clear_error();
     if (!sph || ns == 0 || !out_bytes) return set_error(APT_ERR_ARG, "apt_build_grid_host: spheres/out_bytes must be non-null, num_spheres non-zero%s");
@@ -531,10 +531,8 @@ int apt_build_grid_host(const float *sph, uint32_t ns, void *grid, size_t *out_b
     // sphere centres per cell (boxes overlap ~4 cells each).  The nested walk (round 1, 64 spp): 74.4 / 70.7 / 70.3 / 70.8 / 72.2 ms at 2 / 1 / 0.7 /
     // 0.5 / 0.35; the sample-queue kernel's grid form (round 3): 66.8 / 60.1 / 58.8 / 58.4 / 59.0 / 60.5 / 63.6 ms at 2 / 1 / 0.7 / 0.5 / 0.35 / 0.25 /
     // 0.18 -- a cell step is cheaper there than a pair slot, so smaller cells pay a little longer.
-    const double knob = apt::default_context().snapshot().debug.grid_spheres_per_cell;   // apt_set_debug("grid_spheres_per_cell", v): tuning knob
-    const double per_cell = knob > 0.0 ? knob : apt::kGridSpheresPerCell;
     apt::GridHeader h;
-    apt::grid_header_from_stats(ns, (uint32_t)small.size(), (uint32_t)large.size(), lo, hi, scale, per_cell, h);
+    apt::grid_header_from_stats(ns, (uint32_t)small.size(), (uint32_t)large.size(), lo, hi, scale, apt::grid_spheres_per_cell(), h);
     std::vector<uint32_t> count(h.ncells + 1, 0);
     for (uint32_t k : small) {
         uint32_t x0, x1, y0, y1, z0, z1;

@@ -3,6 +3,7 @@
 //     pt_core.h     the reference's arithmetic, shared with the host helpers
 //     pt_trace.h    scene access + bounce loops (8-sphere SGPR path, LDS tiles, grid walk)
 //     pt_kernels.h  the __global__ kernels
+// What the host code acquires from HIP -- device memory, streams, events, the current device -- it holds through hip_own.h's owners.
 // One lane = one path; the whole bounce loop lives in registers (the reference moves 64-ray tiles through
 // a 16 KB scratch buffer with a free-list allocator, src/allocator.h -- no counterpart here).  No MFMA:
 // this is branchy fp32 VALU work whose separately rounded mul/add an MFMA chain could not reproduce.
@@ -21,6 +22,7 @@
 #include "../../include/render_mi355x.h"
 #include "apt_host.h"
 #include "apt_materials.h"
+#include "hip_own.h"
 #include "pt_core.h"
 #include "pt_dispatch.h"
 
@@ -33,26 +35,34 @@ namespace {
 using apt::clear_error;
 int fail(int code, const char *fmt, const char *detail = "") { return apt::set_error(code, fmt, detail); }
 int hip_fail(hipError_t e) { return fail(APT_ERR_DEVICE, "HIP: %s", hipGetErrorString(e)); }
-// the outcome of the launches just made
-int launched() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? APT_OK : hip_fail(e);
-}
+// a HIP call whose failure ends the entry: APT_ERR_DEVICE "HIP: ...", and the owners release what the entry holds
+#define HIP_TRY(call) do { if (hipError_t e_ = (call); e_ != hipSuccess) return hip_fail(e_); } while (0)
+int launched() { HIP_TRY(hipGetLastError()); return APT_OK; }   // the outcome of the launches just made
 
 // Run-time settings -> template arguments: with_mode / with_flag, pt_dispatch.h.
 
 int no_leaf_plan() { return fail(APT_ERR_ARG, "samples too large: its pairwise-sum plan needs more than 64 leaves (every count <= 7688 fits, and 8192)%s"); }
 int make_leaf_prog(uint32_t samples, LeafProg &lp) { return make_leaf_plan(samples, lp) ? APT_OK : no_leaf_plan(); }   // the plan itself: pt_leaf.h
 
-// materials: the *_materials entries, which do not read light_index with APT_FLAG_EMISSION (include/render_mi355x.h)
-int check_params(const apt_render_params *p, bool materials = false) {
+// The workgroups of one launch as a grid size, or the entry's own refusal `msg` when one launch does not take that many.
+int one_launch(uint64_t blocks, const char *msg, unsigned *grid = nullptr) {
+    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, msg);
+    if (grid) *grid = (unsigned)blocks;
+    return APT_OK;
+}
+
+// What of the record an entry reads, and so checks: the mirror entries all of it, the *_materials entries not light_index with
+// APT_FLAG_EMISSION (include/render_mi355x.h), the feature planes neither mode nor light_index.
+enum class Reads { All, Materials, Features };
+int check_params(const apt_render_params *p, Reads reads = Reads::All) {
     if (!p) return fail(APT_ERR_ARG, "params is null%s");
     if (p->struct_size != sizeof(apt_render_params)) return fail(APT_ERR_STRUCT, "apt_render_params.struct_size mismatch%s");
     if (!p->width || !p->height || !p->samples) return fail(APT_ERR_ARG, "width/height/samples must be non-zero%s");
-    if (p->mode > APT_MODE_ORACLE) return fail(APT_ERR_ARG, "unknown mode%s");
+    if (reads != Reads::Features && p->mode > APT_MODE_ORACLE) return fail(APT_ERR_ARG, "unknown mode%s");
     if (p->num_spheres == 0) return fail(APT_ERR_SCENE, "num_spheres is 0%s");
+    if (reads == Reads::Features) return APT_OK;
     if (p->light_index >= (int32_t)p->num_spheres) return fail(APT_ERR_SCENE, "light_index out of range%s");
-    if (!materials && (p->flags & APT_FLAG_EMISSION) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_EMISSION needs a light_index >= 0%s");
+    if (reads == Reads::All && (p->flags & APT_FLAG_EMISSION) && p->light_index < 0) return fail(APT_ERR_SCENE, "APT_FLAG_EMISSION needs a light_index >= 0%s");
     return APT_OK;
 }
 
@@ -107,19 +117,16 @@ uint32_t *status_word(apt_context &ctx, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     if (cs != hipStreamCaptureStatusNone) return nullptr;
-    uint32_t *fresh = nullptr, *spare = nullptr;
-    if (hipMalloc(&fresh, sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipMemset(fresh, 0, sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(fresh); return nullptr; }
-    uint32_t *w = ctx.status_adopt(dev, fresh, &spare);
-    if (spare) (void)hipFree(spare);      // another thread was first (or the device index is beyond the table)
+    apt::DeviceBuffer<uint32_t> fresh;
+    if (fresh.alloc(1) != hipSuccess || hipMemset(fresh.get(), 0, sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    uint32_t *spare = nullptr;
+    uint32_t *w = ctx.status_adopt(dev, fresh.release(), &spare);
+    apt::DeviceBuffer<uint32_t> loser(spare);   // another thread was first (or the device index is beyond the table)
     return w;
 }
 
 // What a render call needs from its context: one consistent copy of the values and the status word of the current device.
-struct Launch {
-    apt_context::Values cv;
-    uint32_t *status;
-};
+struct Launch { apt_context::Values cv; uint32_t *status; };
 Launch launch_state(apt_context &ctx, void *stream) { return Launch{ctx.snapshot(), status_word(ctx, (hipStream_t)stream)}; }
 
 TraceArgs make_trace_args(const apt_render_params *p, const Launch &ls) {
@@ -154,8 +161,8 @@ apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls, const
 struct PathRange {
     uint64_t n_image, b, c;
     bool band;
+    unsigned grid = 0;   // workgroups of one lane per path: paths_launch_range
     uint64_t plane() const { return band ? c : n_image; }
-    uint64_t blocks() const { return (c + kBlock - 1) / kBlock; }   // of one lane per path
     template <class T> T *base(T *buf) const { return band ? buf - b : buf; }
 };
 // -> APT_OK with r.c == 0 for an empty range: the call is a no-op, the caller returns APT_OK without launching anything
@@ -167,6 +174,11 @@ int path_range(const apt_render_params *p, PathRange &r) {
     if (r.b + r.c > r.n_image) return fail(APT_ERR_ARG, "path range beyond the image%s");
     r.band = p->flags & APT_FLAG_BAND_BUFFERS;
     return APT_OK;
+}
+// The pixel range of a frame launch among the image's pixels.
+int pixel_range(const apt_render_params *p, uint64_t pixel_begin, uint64_t pixel_count) {
+    const uint64_t npix = (uint64_t)p->width * p->height;
+    return (pixel_begin > npix || pixel_count > npix - pixel_begin) ? fail(APT_ERR_ARG, "pixel range beyond the image%s") : APT_OK;
 }
 
 FrameArgs make_frame_args(const apt_render_params *p, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
@@ -184,26 +196,23 @@ size_t sphere_table_bytes(uint32_t num_spheres) { return ((size_t)num_spheres * 
 // chip better (C1, the reference's own CPU-runnable configuration, is 262 144 paths = 1024 workgroups of it: launch-bound either way).
 constexpr uint64_t kTwoPathBufferMin = 1ull << 20;
 
-// What a buffer-mode launch, mirror or material, checks after its params: pointers, the path range, the size of one launch.
-// -> APT_OK with r.c == 0 for an empty range, as path_range.
-int paths_launch_range(const apt_render_params *p, const float *rays, const float *spheres, const float *colors, PathRange &r) {
-    if (!rays || !spheres || !colors) return fail(APT_ERR_ARG, "rays/spheres/colors must be non-null%s");
+// What a launch of one lane per path checks after its params: pointers (`pointers`: the entry's are non-null, `which` names them), the
+// path range, the size of one launch (r.grid).  -> APT_OK with r.c == 0 for an empty range, as path_range.
+int paths_launch_range(const apt_render_params *p, bool pointers, PathRange &r, const char *which = "rays/spheres/colors must be non-null%s") {
+    if (!pointers) return fail(APT_ERR_ARG, which);
     if (int rc = path_range(p, r); rc || r.c == 0) return rc;
-    if (r.blocks() > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
-    return APT_OK;
+    return one_launch((r.c + kBlock - 1) / kBlock, "path_count too large for one launch; shard it%s", &r.grid);
 }
 
 // The same for a frame launch: pointers (`pointers`: the entry's are non-null), the pixel range, the plan, the size of one launch.
 // -> APT_OK with an all-zero fs (fs.blocks == 0) for an empty range: the call is a no-op, the caller returns APT_OK without launching
 int frame_launch_shape(const apt_render_params *p, bool pointers, uint64_t pixel_begin, uint64_t pixel_count, FrameShape &fs) {
     if (!pointers) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");
-    const uint64_t npix = (uint64_t)p->width * p->height;
-    if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
+    if (int rc = pixel_range(p, pixel_begin, pixel_count)) return rc;
     fs = FrameShape{};
     if (pixel_count == 0) return APT_OK;
     if (!frame_shape(p->samples, pixel_count, fs)) return no_leaf_plan();
-    if (fs.blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
-    return APT_OK;
+    return one_launch(fs.blocks, "pixel_count too large for one launch; shard it%s");
 }
 
 // ---- the two mirror render launches, on an explicit snapshot of a context's values ---------
@@ -212,13 +221,13 @@ int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, 
     int rc = check_params(p);
     if (rc) return rc;
     PathRange r;
-    if ((rc = paths_launch_range(p, rays, spheres, colors, r)) || r.c == 0) return rc;
+    if ((rc = paths_launch_range(p, rays && spheres && colors, r)) || r.c == 0) return rc;
     const uint64_t n = r.plane(), b = r.b, c = r.c;
     hipStream_t st = (hipStream_t)stream;
     const bool ns8 = p->num_spheres == 8;
     const TraceArgs ta = make_trace_args(p, ls);
     const bool retire = p->flags & APT_FLAG_RETIRE;
-    const dim3 grid((unsigned)r.blocks());
+    const dim3 grid(r.grid);
     rays = r.base(rays);
     colors = r.base(colors);
     with_mode(p->mode, [&](auto m) {
@@ -241,9 +250,10 @@ int do_render_paths(const Launch &ls, const apt_render_params *p, void *stream, 
     return launched();
 }
 
-// The sample-queue kernels' launch shape (pt_queue.h): colour buffers, pixels per wave, dynamic LDS.  -> false: too many waves.
-bool queue_launch_shape(const apt::Debug &dbg, const LeafProg &lp, bool rr, bool grid, uint64_t pixel_count, bool retire, QueueArgs &qa,
-                        uint64_t &waves, size_t &qlds) {
+// The sample-queue kernels' launch shape (pt_queue.h): colour buffers, pixels per wave, dynamic LDS, one wave per workgroup.
+struct QueueShape { QueueArgs qa; unsigned waves; size_t lds; };
+int queue_launch_shape(const apt::Debug &dbg, const LeafProg &lp, bool rr, bool grid, uint64_t pixel_count, bool retire, QueueShape &q) {
+    QueueArgs &qa = q.qa;
     // a unit = one pairwise leaf of a pixel (8-sphere form) or of half a pixel (grid form); buffers for ~512 resp. ~384 items in flight
     const uint32_t subs = queue_unit_subs(grid), unit_items = subs * lp.maxleaf, window = subs == 4u ? 512u : 384u;
     qa.nbuf = dbg.queue_nbuf ? dbg.queue_nbuf : std::max(2u, std::min(16u, (window + unit_items - 1u) / unit_items));
@@ -253,9 +263,8 @@ bool queue_launch_shape(const apt::Debug &dbg, const LeafProg &lp, bool rr, bool
     // for frames too small to fill the chip's ~3800 wave slots a few times over
     const uint64_t ppw = dbg.queue_ppw ? dbg.queue_ppw : std::max<uint64_t>(4, std::min<uint64_t>(16, pixel_count / 8192u));
     qa.ppw = (uint32_t)ppw;
-    waves = (pixel_count + ppw - 1) / ppw;
-    qlds = queue_lds_bytes(queue_pool_entries(grid), rr, qa.nbuf, lp.nleaves > 1, qa.buf_bytes, subs) + dbg.queue_lds_pad;   // the pad: experiments only, lowers the occupancy
-    return waves <= 0x7fffffffull;
+    q.lds = queue_lds_bytes(queue_pool_entries(grid), rr, qa.nbuf, lp.nleaves > 1, qa.buf_bytes, subs) + dbg.queue_lds_pad;   // the pad: experiments only, lowers the occupancy
+    return one_launch((pixel_count + ppw - 1) / ppw, "pixel_count too large for one launch; shard it%s", &q.waves);
 }
 
 int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, const float *spheres,
@@ -275,12 +284,10 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
     const bool retire = p->flags & APT_FLAG_RETIRE, rrk = ta.rr_start != 0;
     if (retire && ns8 && group == 8 && p->depth > 0) {
         // 8-sphere scene with compaction: one wave per workgroup, a stream of `ppw` pixels per wave (pt_queue.h)
-        QueueArgs qa;
-        uint64_t waves;
-        size_t qlds;
-        if (!queue_launch_shape(dbg, lp, rrk, false, pixel_count, true, qa, waves, qlds)) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+        QueueShape q;
+        if ((rc = queue_launch_shape(dbg, lp, rrk, false, pixel_count, true, q))) return rc;
         with_mode(p->mode, [&](auto m) { with_flag(rrk, [&](auto rr) {
-            hipLaunchKernelGGL((render_frame_queue8_kernel<m, rr>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta, lp, qa);
+            hipLaunchKernelGGL((render_frame_queue8_kernel<m, rr>), dim3(q.waves), dim3(64), q.lds, st, spheres, fa, ta, lp, q.qa);
         }); });
         return launched();
     }
@@ -289,10 +296,8 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
         // the grid carries the pair-slot tables that form needs is written in the buffer on the DEVICE: rather than reading it back in
         // the launch path, both kernels are launched and each asks grid_queue_usable() -- the one not chosen returns at once.
         // (apt_set_debug("grid_walk", 1): measurement knob, the nested item walk of render_frame_kernel only.)
-        QueueArgs qa;
-        uint64_t waves;
-        size_t qlds;
-        if (!queue_launch_shape(dbg, lp, rrk, true, pixel_count, retire, qa, waves, qlds)) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+        QueueShape q;
+        if ((rc = queue_launch_shape(dbg, lp, rrk, true, pixel_count, retire, q))) return rc;
         // APT_FLAG_GRID_SLOTS: the caller vouches for the grid (apt_grid_flags): this launch is the frame's only one, and a grid that does not
         // keep the promise is reported through the status word (grid_walk == 3 tells the kernel to report instead of returning silently)
         // (Only with a status word to report through: without one -- a context's first launch inside a stream capture, a device index beyond
@@ -302,7 +307,7 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
         ta_q.grid_walk = vouched ? 3u : 0u;
         // (the walk statistics behind apt_set_trace_counter are a template flag: a frame without a counter does not carry them)
         with_mode(p->mode, [&](auto m) { with_flag(rrk, [&](auto rr) { with_flag(ta.traced != nullptr, [&](auto stats) {
-            hipLaunchKernelGGL((render_frame_queue8_kernel<m, rr, kSceneGrid, stats>), dim3((unsigned)waves), dim3(64), qlds, st, spheres, fa, ta_q, lp, qa);
+            hipLaunchKernelGGL((render_frame_queue8_kernel<m, rr, kSceneGrid, stats>), dim3(q.waves), dim3(64), q.lds, st, spheres, fa, ta_q, lp, q.qa);
         }); }); });
         if ((rc = launched()) || vouched) return rc;
         ta.grid_walk = 2;
@@ -345,11 +350,11 @@ int do_mat_paths(apt_context *ctx, const apt_render_params *p, void *stream, con
                  float *colors) {
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
-    int rc = check_params(p, true);
+    int rc = check_params(p, Reads::Materials);
     if (rc || (rc = check_mat_args(p, ma))) return rc;
     const Launch ls = launch_state(*ctx, stream);
     PathRange r;
-    if ((rc = paths_launch_range(p, rays, spheres, colors, r)) || r.c == 0) return rc;
+    if ((rc = paths_launch_range(p, rays && spheres && colors, r)) || r.c == 0) return rc;
     if ((rc = check_lights_status(ma, ls.status))) return rc;
     apt::mat_render_paths(apt::MatPathsCall{make_mat_trace(p, ls, ma), r.base(rays), spheres, ma.materials, r.base(colors), r.plane(), r.b, r.c,
                                             stream, ls.cv.has_env ? &ls.cv.env : nullptr});
@@ -359,7 +364,7 @@ int do_mat_frame(apt_context *ctx, const apt_render_params *p, void *stream, con
                  uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
-    int rc = check_params(p, true);
+    int rc = check_params(p, Reads::Materials);
     if (rc || (rc = check_mat_args(p, ma))) return rc;
     const Launch ls = launch_state(*ctx, stream);
     const bool film = ma.film != apt::MatFilm::None;   // (its null film is refused last: by mat_render_frame)
@@ -381,13 +386,10 @@ int do_features(apt_context *ctx, const apt_render_params *p, void *stream, cons
                 float *features) {
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
-    if (!p) return fail(APT_ERR_ARG, "params is null%s");
-    if (p->struct_size != sizeof(apt_render_params)) return fail(APT_ERR_STRUCT, "apt_render_params.struct_size mismatch%s");
-    if (!p->width || !p->height || !p->samples) return fail(APT_ERR_ARG, "width/height/samples must be non-zero%s");
-    if (p->num_spheres == 0) return fail(APT_ERR_SCENE, "num_spheres is 0%s");
+    int rc = check_params(p, Reads::Features);
+    if (rc) return rc;
     if (p->accel && !(p->flags & APT_FLAG_GRID_SLOTS)) return fail(APT_ERR_ARG, "features: accel (grid) needs APT_FLAG_GRID_SLOTS (apt_grid_flags of the built grid)%s");
     const Launch ls = launch_state(*ctx, stream);
-    int rc;
     FrameShape fs;
     if ((rc = frame_launch_shape(p, spheres != nullptr, pixel_begin, pixel_count, fs)) || fs.blocks == 0) return rc;
     if (!apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "features: the frame takes a pairwise-sum plan of at most 44 leaves, as a film's does (every samples <= 4199 has one)%s");
@@ -409,18 +411,37 @@ int do_features(apt_context *ctx, const apt_render_params *p, void *stream, cons
 struct apt_multi {
     struct Band {
         int device = 0;
-        hipStream_t stream = nullptr;
-        hipEvent_t start = nullptr, stop = nullptr;
-        float *sph = nullptr;          // the scene table on this device
-        float *fb = nullptr;           // [3][max stripe] per stripe, stripes back to back
-        uint8_t *u8 = nullptr;
-        uint64_t pixels = 0;           // total pixels of this band
+        apt::Stream stream;
+        apt::Event start, stop;
+        apt::DeviceBuffer<float> sph;  // the scene table on this device
+        apt::DeviceBuffer<float> fb;   // [3][max stripe] per stripe, stripes back to back
+        apt::DeviceBuffer<uint8_t> u8;
     };
-    std::vector<Band> bands;
+    std::vector<Band> bands;           // the bands set up so far
     apt_render_params params;
     uint32_t stripes = 1;
     uint64_t max_stripe = 0;
     int root = 0;
+    // Sets up the next band, on `device`, which it leaves current.  What a failure leaves half made goes with the handle.
+    hipError_t add_band(int device, const float *spheres_host, size_t sph_bytes) {
+        hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess) return e;
+        Band &bd = bands.emplace_back();
+        bd.device = device;
+        int can = 0;   // let the root's copy engine read this device (no-op if already on)
+        if (device != root && hipDeviceCanAccessPeer(&can, device, root) == hipSuccess && can && hipDeviceEnablePeerAccess(root, 0) != hipSuccess) (void)hipGetLastError();
+        if ((e = bd.stream.create(hipStreamNonBlocking)) != hipSuccess) return e;
+        if ((e = bd.start.create()) != hipSuccess || (e = bd.stop.create()) != hipSuccess) return e;
+        if ((e = bd.sph.alloc(sph_bytes / sizeof(float))) != hipSuccess) return e;
+        if ((e = hipMemcpy(bd.sph.get(), spheres_host, sph_bytes, hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = bd.fb.alloc((size_t)stripes * 3 * max_stripe)) != hipSuccess) return e;
+        return bd.u8.alloc((size_t)stripes * 3 * max_stripe);
+    }
+    // every band's stream, events and memory go with the band's own device current; the root device is left current
+    ~apt_multi() {
+        apt::DeviceScope to_root(root);
+        for (; !bands.empty(); bands.pop_back()) (void)hipSetDevice(bands.back().device);
+    }
 };
 
 extern "C" {
@@ -440,11 +461,11 @@ void apt_context_destroy(apt_context *ctx) {
     if (!ctx) return;
     uint32_t *words[apt::kMaxStatusDevices];
     ctx->status_release(words);
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    for (int d = 0; d < apt::kMaxStatusDevices; ++d)
-        if (words[d] && hipSetDevice(d) == hipSuccess) (void)hipFree(words[d]);
-    if (have_cur) (void)hipSetDevice(cur);
+    {
+        apt::DeviceScope back;
+        for (int d = 0; d < apt::kMaxStatusDevices; ++d)
+            if (words[d] && hipSetDevice(d) == hipSuccess) { apt::DeviceBuffer<uint32_t> freed(words[d]); }   // with its device current
+    }
     (void)hipGetLastError();
     delete ctx;
 }
@@ -465,16 +486,13 @@ int apt_context_get_debug(apt_context *ctx, const char *key, double *value) {
 int apt_context_check(apt_context *ctx, void *stream) {
     clear_error();
     if (!ctx) return fail(APT_ERR_ARG, "context is null%s");
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     uint32_t *w = status_word(*ctx, (hipStream_t)stream);
     if (!w) return APT_OK;                       // no word could be made: nothing was ever reported into it
     uint32_t bits = 0;
-    e = hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e);
+    HIP_TRY(hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
     if (!bits) return APT_OK;
-    e = hipMemset(w, 0, sizeof bits);
-    if (e != hipSuccess) (void)hipGetLastError();
+    if (hipMemset(w, 0, sizeof bits) != hipSuccess) (void)hipGetLastError();
     std::string what;
     if (bits & APT_DEV_QUEUE_GUARD) what += " queue-loop-bound";
     if (bits & APT_DEV_GRID_TURNS) what += " grid-walk-bound";
@@ -600,9 +618,9 @@ int apt_render_frame_features(const apt_render_params *p, void *stream, const fl
 int apt_film_resolve_device(const apt_film_resolve *r, void *stream, const float *film, uint64_t pixel_count, const float *table_dev,
                             float *out, uint8_t *u8) {
     clear_error();
-    const int rc = apt::film_resolve_check(r, film, table_dev, out, u8, "apt_film_resolve_device");
+    int rc = apt::film_resolve_check(r, film, table_dev, out, u8, "apt_film_resolve_device");
     if (rc || pixel_count == 0) return rc;
-    if ((pixel_count + kBlock - 1) / kBlock > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    if ((rc = one_launch((pixel_count + kBlock - 1) / kBlock, "pixel_count too large for one launch; shard it%s"))) return rc;
     apt::film_resolve(*r, stream, film, pixel_count, table_dev, out, u8);
     return launched();
 }
@@ -656,38 +674,18 @@ int apt_render_host(uint32_t blockDim, const uint8_t *rays, const uint8_t *spher
     // colours outside it would be copied back from memory no kernel wrote.  (path_begin 0 with path_count 0 or N is the whole frame.)
     if (p.path_begin != 0 || (p.path_count != 0 && p.path_count != n)) return fail(APT_ERR_ARG, "apt_render_host: the default parameters carry a path sub-range; it renders whole frames only%s");
     const size_t sph_bytes = sphere_table_bytes(p.num_spheres);
-    float *d_rays = nullptr, *d_sph = nullptr, *d_col = nullptr;
-    hipError_t e = hipMalloc(&d_rays, n * 24);
-    if (e == hipSuccess) e = hipMalloc(&d_sph, sph_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_col, n * 12);
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 24, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_sph, spheres, sph_bytes, hipMemcpyHostToDevice);
-    int rc = APT_OK;
-    if (e == hipSuccess) {
-        (void)blockDim;
-        rc = do_render_paths(ls, &p, nullptr, d_rays, d_sph, d_col);
-        if (rc == APT_OK) e = hipMemcpy(colors, d_col, n * 12, hipMemcpyDeviceToHost); // synchronises the null stream
-    }
-    (void)hipFree(d_rays); (void)hipFree(d_sph); (void)hipFree(d_col);
-    if (rc != APT_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e);
+    apt::DeviceBuffer<float> d_rays, d_sph, d_col;
+    HIP_TRY(d_rays.alloc(n * 6)); HIP_TRY(d_sph.alloc(sph_bytes / sizeof(float))); HIP_TRY(d_col.alloc(n * 3));
+    HIP_TRY(hipMemcpy(d_rays.get(), rays, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_sph.get(), spheres, sph_bytes, hipMemcpyHostToDevice));
+    (void)blockDim;
+    if (int rc = do_render_paths(ls, &p, nullptr, d_rays.get(), d_sph.get(), d_col.get())) return rc;
+    HIP_TRY(hipMemcpy(colors, d_col.get(), n * 12, hipMemcpyDeviceToHost)); // synchronises the null stream
     return apt_context_check(&apt::default_context(), nullptr);   // a kernel may have reported a failure (clears and sets the error record itself)
 }
 
 // ---- one process, several GPUs ---------------------------------------------------------------------------
-void apt_multi_destroy(apt_multi *m) {
-    clear_error();
-    if (!m) return;
-    for (auto &b : m->bands) {
-        if (hipSetDevice(b.device) != hipSuccess) continue;
-        if (b.start) (void)hipEventDestroy(b.start);
-        if (b.stop) (void)hipEventDestroy(b.stop);
-        if (b.stream) (void)hipStreamDestroy(b.stream);
-        (void)hipFree(b.sph); (void)hipFree(b.fb); (void)hipFree(b.u8);
-    }
-    (void)hipSetDevice(m->root);
-    delete m;
-}
+void apt_multi_destroy(apt_multi *m) { clear_error(); delete m; }
 
 int apt_multi_create(const int *device_ids, uint32_t num_bands, uint32_t stripes, const apt_render_params *p,
                      const float *spheres_host, apt_multi **out) {
@@ -708,28 +706,14 @@ int apt_multi_create(const int *device_ids, uint32_t num_bands, uint32_t stripes
     uint64_t b0, c0;
     split_range(npix, 0, parts, b0, c0);
     m->max_stripe = c0;
-    m->bands.resize(num_bands);
+    m->bands.reserve(num_bands);
     const size_t sph_bytes = sphere_table_bytes(p->num_spheres);
     hipError_t e = hipSuccess;
-    for (uint32_t b = 0; b < num_bands && e == hipSuccess; ++b) {
-        apt_multi::Band &bd = m->bands[b];
-        bd.device = device_ids[b];
-        e = hipSetDevice(bd.device);
-        if (e == hipSuccess && bd.device != m->root) { // let the root's copy engine read this device (no-op if already on)
-            int can = 0;
-            (void)hipDeviceCanAccessPeer(&can, bd.device, m->root);
-            if (can) { hipError_t pe = hipDeviceEnablePeerAccess(m->root, 0); if (pe != hipSuccess) (void)hipGetLastError(); }
-        }
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&bd.stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreate(&bd.start);
-        if (e == hipSuccess) e = hipEventCreate(&bd.stop);
-        if (e == hipSuccess) e = hipMalloc(&bd.sph, sph_bytes);
-        if (e == hipSuccess) e = hipMemcpy(bd.sph, spheres_host, sph_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&bd.fb, (size_t)stripes * 3 * m->max_stripe * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&bd.u8, (size_t)stripes * 3 * m->max_stripe);
+    {
+        apt::DeviceScope to_root(m->root);
+        for (uint32_t b = 0; b < num_bands && e == hipSuccess; ++b) e = m->add_band(device_ids[b], spheres_host, sph_bytes);
     }
-    (void)hipSetDevice(m->root);
-    if (e != hipSuccess) { rc = hip_fail(e); apt_multi_destroy(m); apt::set_error(rc, "apt_multi_create: HIP: %s", hipGetErrorString(e)); return rc; }
+    if (e != hipSuccess) { delete m; return fail(APT_ERR_DEVICE, "apt_multi_create: HIP: %s", hipGetErrorString(e)); }
     *out = m;
     return APT_OK;
 }
@@ -742,52 +726,51 @@ int apt_multi_render(apt_multi *m, float *fb_root, uint8_t *u8_root, float *band
     const uint64_t nb = m->bands.size(), parts = nb * m->stripes;
     int rc = APT_OK;
     hipError_t e = hipSuccess;
+    apt::DeviceScope to_root(m->root);
     for (uint64_t b = 0; b < nb && rc == APT_OK && e == hipSuccess; ++b) {
         apt_multi::Band &bd = m->bands[b];
         e = hipSetDevice(bd.device);
         if (e != hipSuccess) break;
-        Launch ls = launch_state(apt::default_context(), bd.stream);   // (the status word is per device: taken with the band's device current)
+        Launch ls = launch_state(apt::default_context(), bd.stream.get());   // (the status word is per device: taken with the band's device current)
         // the statistics block of the default context is an address on ITS device: only bands on the root device may count into it
         if (bd.device != m->root) ls.cv.trace_counter = nullptr;
-        e = hipEventRecord(bd.start, bd.stream);
+        e = hipEventRecord(bd.start.get(), bd.stream.get());
         for (uint32_t s = 0; s < m->stripes && rc == APT_OK && e == hipSuccess; ++s) {
             uint64_t begin, count;
             split_range(npix, (uint64_t)s * nb + b, parts, begin, count);   // interleaved: stripe s*nb + b belongs to band b
-            float *fb = bd.fb + (size_t)s * 3 * m->max_stripe;
-            uint8_t *u8 = bd.u8 + (size_t)s * 3 * m->max_stripe;
-            rc = do_render_frame(ls, &m->params, bd.stream, bd.sph, begin, count, fb, u8_root ? u8 : nullptr);
+            float *fb = bd.fb.get() + (size_t)s * 3 * m->max_stripe;
+            uint8_t *u8 = bd.u8.get() + (size_t)s * 3 * m->max_stripe;
+            rc = do_render_frame(ls, &m->params, bd.stream.get(), bd.sph.get(), begin, count, fb, u8_root ? u8 : nullptr);
             if (rc != APT_OK) break;
-            if (s + 1 == m->stripes) e = hipEventRecord(bd.stop, bd.stream);  // kernels only: the copies follow
+            if (s + 1 == m->stripes) e = hipEventRecord(bd.stop.get(), bd.stream.get());  // kernels only: the copies follow
         }
         for (uint32_t s = 0; s < m->stripes && rc == APT_OK && e == hipSuccess; ++s) {
             uint64_t begin, count;
             split_range(npix, (uint64_t)s * nb + b, parts, begin, count);
-            const float *fb = bd.fb + (size_t)s * 3 * m->max_stripe;
-            const uint8_t *u8 = bd.u8 + (size_t)s * 3 * m->max_stripe;
+            const float *fb = bd.fb.get() + (size_t)s * 3 * m->max_stripe;
+            const uint8_t *u8 = bd.u8.get() + (size_t)s * 3 * m->max_stripe;
             for (int ch = 0; ch < 3 && e == hipSuccess; ++ch)   // band-local planes [3][count] -> planes of the full frame
                 e = hipMemcpyPeerAsync(fb_root + (size_t)ch * npix + begin, m->root, fb + (size_t)ch * count, bd.device,
-                                       count * sizeof(float), bd.stream);
+                                       count * sizeof(float), bd.stream.get());
             if (u8_root && e == hipSuccess)
-                e = hipMemcpyPeerAsync(u8_root + begin * 3, m->root, u8, bd.device, count * 3, bd.stream);
+                e = hipMemcpyPeerAsync(u8_root + begin * 3, m->root, u8, bd.device, count * 3, bd.stream.get());
         }
     }
-    for (auto &bd : m->bands) { // wait for every band (also after an error: nothing may still be writing)
-        if (hipSetDevice(bd.device) == hipSuccess) { hipError_t se = hipStreamSynchronize(bd.stream); if (e == hipSuccess) e = se; }
-    }
+    for (auto &bd : m->bands)   // wait for every band (also after an error: nothing may still be writing)
+        if (hipSetDevice(bd.device) == hipSuccess) { hipError_t se = hipStreamSynchronize(bd.stream.get()); if (e == hipSuccess) e = se; }
     if (band_kernel_ms && rc == APT_OK && e == hipSuccess)
         for (uint64_t b = 0; b < nb; ++b) {
             (void)hipSetDevice(m->bands[b].device);
-            if (hipEventElapsedTime(&band_kernel_ms[b], m->bands[b].start, m->bands[b].stop) != hipSuccess) band_kernel_ms[b] = -1.0f;
+            if (hipEventElapsedTime(&band_kernel_ms[b], m->bands[b].start.get(), m->bands[b].stop.get()) != hipSuccess) band_kernel_ms[b] = -1.0f;
         }
     int dev_rc = APT_OK;
     std::string dev_msg;
     if (rc == APT_OK && e == hipSuccess)   // the device status words of every device that rendered (each check clears its word)
         for (auto &bd : m->bands)
-            if (hipSetDevice(bd.device) == hipSuccess && apt_context_check(&apt::default_context(), bd.stream) != APT_OK && dev_rc == APT_OK) {
+            if (hipSetDevice(bd.device) == hipSuccess && apt_context_check(&apt::default_context(), bd.stream.get()) != APT_OK && dev_rc == APT_OK) {
                 dev_rc = apt_last_status();
                 dev_msg = apt_last_error();
             }
-    (void)hipSetDevice(m->root);
     if (rc != APT_OK) return rc;             // (the error record still describes the launch that failed: no check ran after it)
     if (e != hipSuccess) return hip_fail(e);
     return dev_rc == APT_OK ? APT_OK : fail(dev_rc, "apt_multi_render: %s", dev_msg.c_str());
@@ -798,94 +781,64 @@ int apt_build_grid_device(const float *spheres_dev, uint32_t ns, void *stream, v
     clear_error();
     if (!spheres_dev || ns == 0 || !out_bytes) return fail(APT_ERR_ARG, "apt_build_grid_device: spheres/out_bytes must be non-null, num_spheres non-zero%s");
     hipStream_t st = (hipStream_t)stream;
-    // workspace: radii, the two ordered lists, statistics (freed on return; a build step, not a render call)
-    float *rad = nullptr;
-    uint32_t *large = nullptr, *small = nullptr, *count = nullptr, *cursor = nullptr, *sums = nullptr, *long_count = nullptr;
-    uint2 *long_cells = nullptr;
-    bool break_out = false;
-    GridBuildStats *stats_d = nullptr;
-    hipError_t e = hipMalloc(&rad, (size_t)ns * 4);
-    if (e == hipSuccess) e = hipMalloc(&large, (size_t)ns * 4);
-    if (e == hipSuccess) e = hipMalloc(&small, (size_t)ns * 4);
-    if (e == hipSuccess) e = hipMalloc(&stats_d, sizeof(GridBuildStats));
+    // The workspace (a build step, not a render call) is released on return: after the stream's last synchronise, or on a failure path
+    // by a release that itself waits for the device.
+    apt::DeviceBuffer<float> rad;
+    apt::DeviceBuffer<uint32_t> large, small, count, cursor, sums, long_count;
+    apt::DeviceBuffer<uint2> long_cells;
+    apt::DeviceBuffer<GridBuildStats> stats_d;
+    // classify: radii, the two ordered lists, statistics
+    HIP_TRY(rad.alloc(ns)); HIP_TRY(large.alloc(ns)); HIP_TRY(small.alloc(ns)); HIP_TRY(stats_d.alloc(1));
+    hipLaunchKernelGGL(grid_classify_kernel, dim3(1), dim3(kGB), 0, st, spheres_dev, ns, rad.get(), large.get(), small.get(), stats_d.get());
     GridBuildStats stt;
-    int rc = APT_OK;
-    GridHeader h;
-    size_t words = 0;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(grid_classify_kernel, dim3(1), dim3(kGB), 0, st, spheres_dev, ns, rad, large, small, stats_d);
-        e = hipMemcpyAsync(&stt, stats_d, sizeof stt, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    HIP_TRY(hipMemcpyAsync(&stt, stats_d.get(), sizeof stt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    GridHeader h;   // header
+    grid_header_from_stats(ns, stt.nsmall, stt.nlarge, stt.lo, stt.hi, stt.scale, apt::grid_spheres_per_cell(), h);
+    // count and scan: where each cell's list starts, and the item count
+    const uint64_t nc1 = (uint64_t)h.ncells + 1, nblk = (nc1 + kGB - 1) / kGB;
+    HIP_TRY(count.alloc(nc1)); HIP_TRY(cursor.alloc(h.ncells)); HIP_TRY(sums.alloc(nblk));
+    HIP_TRY(hipMemsetAsync(count.get(), 0, nc1 * 4, st)); HIP_TRY(hipMemsetAsync(cursor.get(), 0, (size_t)h.ncells * 4, st));
+    if (stt.nsmall) hipLaunchKernelGGL(grid_count_kernel, dim3((stt.nsmall + 255) / 256), dim3(256), 0, st, h, spheres_dev, rad.get(), small.get(), stt.nsmall, count.get());
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3((unsigned)nblk), dim3(kGB), 0, st, count.get(), nc1, sums.get());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kGB), 0, st, sums.get(), (uint32_t)nblk);
+    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblk), dim3(kGB), 0, st, count.get(), nc1, sums.get());
+    uint32_t nitems = 0;
+    HIP_TRY(hipMemcpyAsync(&nitems, count.get() + h.ncells, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t words = grid_header_offsets(h, nitems);
+    *out_bytes = words * 4;
+    if (!grid_dev) return APT_OK;                                             // size query
+    if (capacity < words * 4) return fail(APT_ERR_ARG, "apt_build_grid_device: capacity too small (see *out_bytes)%s");
+    uint32_t *w = (uint32_t *)grid_dev;   // fill
+    HIP_TRY(hipMemsetAsync(w, 0, words * 4, st));
+    HIP_TRY(hipMemcpyAsync(w, &h, sizeof h, hipMemcpyHostToDevice, st));
+    if (h.nlarge) HIP_TRY(hipMemcpyAsync(w + h.off_large, large.get(), (size_t)h.nlarge * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w + h.off_cells, count.get(), nc1 * 4, hipMemcpyDeviceToDevice, st));
+    if (stt.nsmall) hipLaunchKernelGGL(grid_fill_kernel, dim3((stt.nsmall + 255) / 256), dim3(256), 0, st, h, spheres_dev, rad.get(), small.get(), stt.nsmall, count.get(), cursor.get(), w + h.off_items);
+    // sort: short cell lists on the device, long ones (clustered scenes) reported and sorted here
+    HIP_TRY(long_cells.alloc(nitems / (kGridSortInline + 1u) + 1u)); HIP_TRY(long_count.alloc(1));
+    HIP_TRY(hipMemsetAsync(long_count.get(), 0, 4, st));
+    hipLaunchKernelGGL(grid_sort_cells_kernel, dim3((h.ncells + 255) / 256), dim3(256), 0, st, h.ncells, count.get(), w + h.off_items, long_count.get(), long_cells.get());
+    uint32_t nlong = 0;
+    HIP_TRY(hipMemcpyAsync(&nlong, long_count.get(), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (nlong) {
+        std::vector<uint2> cells(nlong);
+        std::vector<uint32_t> host_items(nitems);
+        HIP_TRY(hipMemcpy(cells.data(), long_cells.get(), (size_t)nlong * sizeof(uint2), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(host_items.data(), w + h.off_items, (size_t)nitems * 4, hipMemcpyDeviceToHost));
+        for (const uint2 &c : cells) std::sort(host_items.begin() + c.x, host_items.begin() + c.y);
+        // only the long cells go back: the short ones were sorted in place by the kernel above (the copy out saw them sorted already)
+        HIP_TRY(hipMemcpy(w + h.off_items, host_items.data(), (size_t)nitems * 4, hipMemcpyHostToDevice));
     }
-    if (e == hipSuccess) {
-        const double knob = apt::default_context().snapshot().debug.grid_spheres_per_cell;   // apt_set_debug("grid_spheres_per_cell", v)
-        const double per_cell = knob > 0.0 ? knob : kGridSpheresPerCell;
-        grid_header_from_stats(ns, stt.nsmall, stt.nlarge, stt.lo, stt.hi, stt.scale, per_cell, h);
-        const uint64_t nc1 = (uint64_t)h.ncells + 1, nblk = (nc1 + kGB - 1) / kGB;
-        e = hipMalloc(&count, nc1 * 4);
-        if (e == hipSuccess) e = hipMalloc(&cursor, (size_t)h.ncells * 4);
-        if (e == hipSuccess) e = hipMalloc(&sums, nblk * 4);
-        if (e == hipSuccess) e = hipMemsetAsync(count, 0, nc1 * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, (size_t)h.ncells * 4, st);
-        uint32_t nitems = 0;
-        if (e == hipSuccess) {
-            if (stt.nsmall) hipLaunchKernelGGL(grid_count_kernel, dim3((stt.nsmall + 255) / 256), dim3(256), 0, st, h, spheres_dev, rad, small, stt.nsmall, count);
-            hipLaunchKernelGGL(scan_blocks_kernel, dim3((unsigned)nblk), dim3(kGB), 0, st, count, nc1, sums);
-            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kGB), 0, st, sums, (uint32_t)nblk);
-            hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblk), dim3(kGB), 0, st, count, nc1, sums);
-            e = hipMemcpyAsync(&nitems, count + h.ncells, 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
-        if (e == hipSuccess) {
-            words = grid_header_offsets(h, nitems);
-            *out_bytes = words * 4;
-            if (!grid_dev) rc = APT_OK;                                       // size query
-            else if (capacity < words * 4) rc = fail(APT_ERR_ARG, "apt_build_grid_device: capacity too small (see *out_bytes)%s");
-            else {
-                uint32_t *w = (uint32_t *)grid_dev;
-                e = hipMemsetAsync(w, 0, words * 4, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(w, &h, sizeof h, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess && h.nlarge) e = hipMemcpyAsync(w + h.off_large, large, (size_t)h.nlarge * 4, hipMemcpyDeviceToDevice, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(w + h.off_cells, count, nc1 * 4, hipMemcpyDeviceToDevice, st);
-                if (e == hipSuccess) {
-                    if (stt.nsmall) hipLaunchKernelGGL(grid_fill_kernel, dim3((stt.nsmall + 255) / 256), dim3(256), 0, st, h, spheres_dev, rad, small, stt.nsmall, count, cursor, w + h.off_items);
-                    // short cell lists are sorted on the device, long ones (clustered scenes) reported and sorted here
-                    const uint32_t max_long = nitems / (kGridSortInline + 1u) + 1u;
-                    e = hipMalloc(&long_cells, (size_t)max_long * sizeof(uint2));
-                    if (e == hipSuccess) e = hipMalloc(&long_count, 4);
-                    if (e == hipSuccess) e = hipMemsetAsync(long_count, 0, 4, st);
-                    uint32_t nlong = 0;
-                    if (e == hipSuccess) {
-                        hipLaunchKernelGGL(grid_sort_cells_kernel, dim3((h.ncells + 255) / 256), dim3(256), 0, st, h.ncells, count, w + h.off_items, long_count, long_cells);
-                        e = hipMemcpyAsync(&nlong, long_count, 4, hipMemcpyDeviceToHost, st);
-                        if (e == hipSuccess) e = hipStreamSynchronize(st);
-                    }
-                    if (e == hipSuccess && nlong) {
-                        std::vector<uint2> cells(nlong);
-                        std::vector<uint32_t> host_items(nitems);
-                        e = hipMemcpy(cells.data(), long_cells, (size_t)nlong * sizeof(uint2), hipMemcpyDeviceToHost);
-                        if (e == hipSuccess) e = hipMemcpy(host_items.data(), w + h.off_items, (size_t)nitems * 4, hipMemcpyDeviceToHost);
-                        if (e == hipSuccess) {
-                            for (const uint2 &c : cells) std::sort(host_items.begin() + c.x, host_items.begin() + c.y);
-                            // only the long cells go back: the short ones were sorted in place by the kernel above (the copy out saw them sorted already)
-                            e = hipMemcpy(w + h.off_items, host_items.data(), (size_t)nitems * 4, hipMemcpyHostToDevice);
-                        }
-                    }
-                    if (e != hipSuccess) break_out = true;
-                    const uint32_t ng = ns > nitems ? ns : nitems;
-                    if (!break_out) hipLaunchKernelGGL(grid_geom_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, spheres_dev, ns, w + h.off_items, nitems,
-                                       reinterpret_cast<float4 *>(w + h.off_geom), reinterpret_cast<float4 *>(w + h.off_item_geom));
-                    if (!break_out && h.off_cellslot) hipLaunchKernelGGL(grid_slots_kernel, dim3((std::max(apt::grid_bordered_cells(h.n) + 1u, ns) + 255u) / 256u), dim3(256), 0, st, w, h, spheres_dev);
-                    if (e == hipSuccess) e = hipGetLastError();
-                    if (e == hipSuccess) e = hipStreamSynchronize(st);       // the workspace is freed below
-                }
-            }
-        }
-    }
-    (void)hipFree(rad); (void)hipFree(large); (void)hipFree(small); (void)hipFree(stats_d);
-    (void)hipFree(count); (void)hipFree(cursor); (void)hipFree(sums); (void)hipFree(long_count); (void)hipFree(long_cells);
-    if (rc != APT_OK) return rc;
-    return e == hipSuccess ? APT_OK : hip_fail(e);
+    const uint32_t ng = ns > nitems ? ns : nitems;   // geometry, pair slots
+    hipLaunchKernelGGL(grid_geom_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, spheres_dev, ns, w + h.off_items, nitems,
+                       reinterpret_cast<float4 *>(w + h.off_geom), reinterpret_cast<float4 *>(w + h.off_item_geom));
+    if (h.off_cellslot) hipLaunchKernelGGL(grid_slots_kernel, dim3((std::max(apt::grid_bordered_cells(h.n) + 1u, ns) + 255u) / 256u), dim3(256), 0, st, w, h, spheres_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return APT_OK;
 }
 
 int apt_selftest_sqrt(int variant, void *stream, uint64_t first_bits, uint64_t count, uint64_t *device_result2) {
@@ -921,9 +874,9 @@ int apt_test_scene(const apt_render_params *p, void *stream, const float *rays, 
     if (rc) return rc;
     if (!rays || !spheres || !out) return fail(APT_ERR_ARG, "rays/spheres/out must be non-null%s");
     const uint64_t n = (uint64_t)p->width * p->height * 4u * p->samples;
-    const uint64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "image too large for one launch%s");
-    hipLaunchKernelGGL(test_scene_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, rays, spheres,
+    unsigned blocks;
+    if ((rc = one_launch((n + kBlock - 1) / kBlock, "image too large for one launch%s", &blocks))) return rc;
+    hipLaunchKernelGGL(test_scene_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, rays, spheres,
                        out, n, p->num_spheres, p->light_index, p->eps);
     return launched();
 }
@@ -932,14 +885,11 @@ int apt_gen_rays_device(const apt_render_params *p, void *stream, float *rays) {
     clear_error();
     int rc = check_params(p);
     if (rc) return rc;
-    if (!rays) return fail(APT_ERR_ARG, "rays must be non-null%s");
     PathRange r;
-    if ((rc = path_range(p, r)) || r.c == 0) return rc;
-    const uint64_t blocks = (r.c + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
+    if ((rc = paths_launch_range(p, rays != nullptr, r, "rays must be non-null%s")) || r.c == 0) return rc;
     Camera cam;
     camera_init(cam, p->width, p->height);
-    hipLaunchKernelGGL(gen_rays_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, cam, p->width,
+    hipLaunchKernelGGL(gen_rays_kernel, dim3(r.grid), dim3(kBlock), 0, (hipStream_t)stream, cam, p->width,
                        p->height, p->samples, p->seed, r.plane(), r.b, r.c, r.base(rays));
     return launched();
 }
@@ -949,11 +899,8 @@ int apt_gen_rays_camera_device(const apt_render_params *p, const apt_camera *cam
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = apt_camera_check_host(cam))) return rc;      // (clears and sets the error record itself)
-    if (!rays) return fail(APT_ERR_ARG, "rays must be non-null%s");
     PathRange r;
-    if ((rc = path_range(p, r)) || r.c == 0) return rc;
-    const uint64_t blocks = (r.c + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "path_count too large for one launch; shard it%s");
+    if ((rc = paths_launch_range(p, rays != nullptr, r, "rays must be non-null%s")) || r.c == 0) return rc;
     apt::mat_gen_rays_camera(apt::CamRaysCall{cam, p->width, p->height, p->samples, p->seed, r.base(rays), r.plane(), r.b, r.c, stream});
     return launched();
 }
@@ -972,11 +919,12 @@ int apt_gen_rays_mt_device_ex(const apt_render_params *p, void *stream, const ui
     if (blk_lo < first_block) return fail(APT_ERR_ARG, "path range starts before the checkpoint window%s");
     const uint64_t cp_lo = (blk_lo - first_block) / stride, cp_hi = (blk_hi - first_block + stride - 1) / stride;
     if (cp_hi > num_checkpoints) return fail(APT_ERR_ARG, "not enough MT19937 checkpoints for this path range%s");
-    if (cp_hi - cp_lo > 0x7fffffffull) return fail(APT_ERR_ARG, "too many checkpoints for one launch%s");
+    unsigned grid;
+    if ((rc = one_launch(cp_hi - cp_lo, "too many checkpoints for one launch%s", &grid))) return rc;
     Camera cam;
     camera_init(cam, p->width, p->height);
     // one workgroup per checkpoint the range touches (workgroups of untouched checkpoints would only skip)
-    hipLaunchKernelGGL(gen_rays_mt_kernel, dim3((unsigned)(cp_hi - cp_lo)), dim3(kBlock), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(gen_rays_mt_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
                        checkpoints + cp_lo * kMtN, stride, first_block + cp_lo * stride, num_blocks, cam, p->width, p->height,
                        p->samples, r.plane(), b, b + c, r.base(rays));
     return launched();
@@ -1002,18 +950,17 @@ int apt_render_frame_mt(const apt_render_params *p, void *stream, const uint32_t
     const bool pow2_kernel = (1u << log2_s) == p->samples && p->samples >= 8 && p->samples <= 256;
     LeafProg lp;
     if ((rc = make_leaf_prog(p->samples, lp))) return rc;
-    const uint64_t npix = (uint64_t)p->width * p->height;
-    if (pixel_begin > npix || pixel_count > npix - pixel_begin) return fail(APT_ERR_ARG, "pixel range beyond the image%s");
-    if (pixel_count == 0) return APT_OK;
+    if ((rc = pixel_range(p, pixel_begin, pixel_count)) || pixel_count == 0) return rc;
     const uint64_t g_lo = pixel_begin / kMtGroupPixels, g_hi = (pixel_begin + pixel_count + kMtGroupPixels - 1) / kMtGroupPixels;
     if (g_lo < first_group || g_hi - first_group > num_checkpoints) return fail(APT_ERR_ARG, "apt_render_frame_mt: the checkpoint table does not cover the pixel range%s");
-    if (g_hi - g_lo > 0x7fffffffull) return fail(APT_ERR_ARG, "pixel_count too large for one launch; shard it%s");
+    unsigned groups;
+    if ((rc = one_launch(g_hi - g_lo, "pixel_count too large for one launch; shard it%s", &groups))) return rc;
     if ((rc = refuse_camera(apt::default_context().snapshot(), "apt_render_frame_mt"))) return rc;
     const TraceArgs ta = make_trace_args(p, launch_state(apt::default_context(), stream));
     const FrameArgs fa = make_frame_args(p, pixel_begin, pixel_count, fb, fb_u8);
     MtFrameArgs ma;
     ma.checkpoints = checkpoints + (g_lo - first_group) * 624; ma.first_group = g_lo; ma.log2_s = log2_s;
-    const dim3 grid((unsigned)(g_hi - g_lo));
+    const dim3 grid(groups);
     hipStream_t st = (hipStream_t)stream;
     with_mode(p->mode, [&](auto m) {
         if (pow2_kernel) hipLaunchKernelGGL((render_frame_mt_kernel<m>), grid, dim3(kBlock), 0, st, spheres, fa, ta, ma);
@@ -1037,18 +984,18 @@ int apt_decode_color_band(const apt_render_params *p, void *stream, const float 
     // decode_color_kernel4 adds ONE leaf and relies on lp.nleaves == 1 (which every count <= 128 has)
     const bool quad = wide && p->samples <= 8u * kDecode4Blocks && lp.nleaves == 1 && p->samples % 4 == 0 && ((uintptr_t)colors & 15u) == 0;
     const uint64_t lanes = npix * 3 * 4 * (quad ? 2 : (wide ? 8 : 1));
-    const uint64_t blocks = (lanes + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return fail(APT_ERR_ARG, "band too large for one launch%s");
+    unsigned blocks;
+    if ((rc = one_launch((lanes + kBlock - 1) / kBlock, "band too large for one launch%s", &blocks))) return rc;
     // grid caps measured on the C2 buffer (profiles/microbench/decode_rates.hip): 8-lane form 4.9 / 5.4 / 6.1 / 5.5 TB/s at 256 x 64 / 256 / 1024 /
     // one round for S = 64 (S = 256: 5.1 / 5.5 / 5.6 / 5.7; below 64 samples the smaller grid wins); float4 form 4.3 / 6.1 / 4.6 TB/s at S = 8 / 16 / 32 with its cap of 256 x 256 (8-lane form: 1.2 / 2.3 / 4.1)
     if (quad)
-        hipLaunchKernelGGL(decode_color_kernel4, dim3((unsigned)std::min<uint64_t>(blocks, 256u * 256u)), dim3(kBlock), 0, (hipStream_t)stream, colors,
+        hipLaunchKernelGGL(decode_color_kernel4, dim3(std::min(blocks, 256u * 256u)), dim3(kBlock), 0, (hipStream_t)stream, colors,
                            p->samples, npix, lp, fb, fb_u8);
     else if (wide)
-        hipLaunchKernelGGL(decode_color_kernel8, dim3((unsigned)std::min<uint64_t>(blocks, p->samples >= 64 ? 256u * 1024u : 256u * 256u)), dim3(kBlock), 0, (hipStream_t)stream, colors,
+        hipLaunchKernelGGL(decode_color_kernel8, dim3(std::min(blocks, p->samples >= 64 ? 256u * 1024u : 256u * 256u)), dim3(kBlock), 0, (hipStream_t)stream, colors,
                            p->samples, npix, lp, fb, fb_u8);
     else
-        hipLaunchKernelGGL(decode_color_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, colors,
+        hipLaunchKernelGGL(decode_color_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, colors,
                            p->samples, npix, lp, fb, fb_u8);
     return launched();
 }

@@ -367,3 +367,53 @@ def test_two_ranks_over_rccl_pipelined_gather_of_different_frames(apt, oracle, t
     for k in range(6):
         fb_w, u8_w, _, _ = oracle.render_frame(oracle.make_params(96, 64, 64, depth=8, seed=100 + k), sph, threads=oracle.max_threads())
         assert np.array_equal(bits(z[f"fb{k}"]), bits(fb_w)) and np.array_equal(z[f"u8{k}"], u8_w), k
+
+
+@pytest.mark.parametrize("ns", [9, 60])
+def test_device_grid_build_answers_a_size_query_a_small_capacity_and_a_build(apt, ns):
+    """apt_build_grid_device's three answers on the two smallest generated scenes (without and with a populated cell grid): a size query
+    returns the byte count and writes nothing; a capacity four bytes short is refused with that count in *out_bytes and the buffer
+    untouched; the exact capacity gives apt_build_grid_host's bytes."""
+    L = apt._lib.lib()
+    scene = apt.gen_data.gen_scene(ns, seed=1)
+    host = apt.gen_data.build_grid(scene, ns)
+    d_scene = dev(scene)
+    st = apt.render._stream_handle(None)
+    nbytes = ctypes.c_size_t(0)
+    assert L.apt_build_grid_device(d_scene.data_ptr(), ns, st, None, 0, ctypes.byref(nbytes)) == 0
+    B = nbytes.value
+    assert B == host.nbytes
+    buf = torch.full((B,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    nbytes.value = 0
+    assert L.apt_build_grid_device(d_scene.data_ptr(), ns, st, buf.data_ptr(), B - 4, ctypes.byref(nbytes)) == 1    # APT_ERR_ARG
+    assert b"capacity too small" in L.apt_last_error() and nbytes.value == B
+    torch.cuda.synchronize()
+    assert bool((buf == 0xA5).all())
+    nbytes.value = 0
+    assert L.apt_build_grid_device(d_scene.data_ptr(), ns, st, buf.data_ptr(), B, ctypes.byref(nbytes)) == 0 and nbytes.value == B
+    torch.cuda.synchronize()
+    assert np.array_equal(buf.cpu().numpy().view(np.uint32), host)
+
+
+def test_multi_gpu_object_is_created_rendered_and_closed_repeatedly(apt, oracle):
+    """apt_multi through create -> render -> close three times on device 0 ([0, 0], 2 stripes), with a refused create ([0, 99]) between
+    the cycles: every frame is the single-launch frame bit for bit, the refusal is reported as apt_multi_create's, and no call moves
+    the current device."""
+    sph_host = oracle.gen_spheres()
+    p = apt.make_params(37, 23, 16, depth=6, seed=11)
+    ref, ref8 = apt.render.render_frame(p, dev(sph_host))
+    cur = torch.cuda.current_device()
+    for cycle in range(3):
+        mg = apt.render.MultiGpu(p, sph_host, [0, 0], stripes=2)
+        assert torch.cuda.current_device() == cur
+        fb, u8 = mg.render()
+        assert torch.cuda.current_device() == cur
+        assert torch.equal(fb.view(torch.int32), ref.view(torch.int32)) and torch.equal(u8, ref8)
+        mg.close()
+        assert torch.cuda.current_device() == cur
+        if cycle < 2:
+            with pytest.raises(apt.AptError):
+                apt.render.MultiGpu(p, sph_host, [0, 99])
+            assert apt._lib.lib().apt_last_error().startswith(b"apt_multi_create:")
+            assert torch.cuda.current_device() == cur

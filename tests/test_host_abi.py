@@ -167,6 +167,38 @@ def test_compute_entries_fail_loudly_without_a_gpu(apt):
     assert apt._lib.lib().apt_device_count() == 0
 
 
+def test_entries_that_hold_device_resources_fail_at_their_first_hip_call_without_a_gpu(apt):
+    """apt_build_grid_device and apt_render_host with valid arguments on a machine without a device: the first allocation fails, the
+    entry returns APT_ERR_DEVICE "HIP: ..." from there (what it holds goes with its scope), and a second call gives the same.
+    apt_multi_create refuses device 0 where there is none and leaves *out alone."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    L = apt._lib.lib()
+    sph = np.ascontiguousarray(apt.gen_data.gen_spheres(), dtype=np.float32)
+    sph_p = sph.ctypes.data_as(ctypes.c_void_p)
+    nbytes = ctypes.c_size_t(0)
+    scratch = np.zeros(1 << 16, dtype=np.uint8)
+    for grid, cap in ((None, 0), (scratch.ctypes.data_as(ctypes.c_void_p), scratch.size)):   # a size query, then with a buffer
+        for _ in range(2):
+            assert L.apt_build_grid_device(sph_p, 8, None, grid, cap, ctypes.byref(nbytes)) == apt._lib.APT_ERR_DEVICE
+            assert L.apt_last_status() == apt._lib.APT_ERR_DEVICE and L.apt_last_error().startswith(b"HIP:"), L.apt_last_error()
+    assert not scratch.any()
+    assert L.apt_set_default_params(ctypes.byref(apt.default_params())) == 0               # 16 x 16 x 1: 1024 paths
+    rays = np.ascontiguousarray(apt.gen_data.gen_rays(16, 16, 1, seed=0), dtype=np.float32).ravel()
+    colors = np.zeros(3 * 1024, dtype=np.float32)
+    assert rays.size == 6 * 1024 and sph.size == 128
+    for _ in range(2):
+        assert L.apt_render_host(8, rays.ctypes.data_as(ctypes.c_void_p), sph_p, colors.ctypes.data_as(ctypes.c_void_p)) == apt._lib.APT_ERR_DEVICE
+        assert L.apt_last_status() == apt._lib.APT_ERR_DEVICE and L.apt_last_error().startswith(b"HIP:"), L.apt_last_error()
+    assert not colors.any()
+    ids = (ctypes.c_int * 1)(0)
+    out = ctypes.c_void_p(0xDEAD)
+    p = apt.default_params()
+    assert L.apt_multi_create(ids, 1, 1, ctypes.byref(p), sph_p, ctypes.byref(out)) == apt._lib.APT_ERR_DEVICE
+    assert b"device id out of range" in L.apt_last_error() and out.value == 0xDEAD
+
+
 def test_grid_builder_layout(apt):
     """apt_build_grid_host: header, always-tested list (walls + light), every small sphere listed in every
     cell its inflated sphere touches (checked per cell against the definition), ascending sphere order inside a cell."""
