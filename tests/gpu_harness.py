@@ -1,5 +1,5 @@
 """What the material renderer's GPU test files share (tests/test_gpu_materials*.py, _nee, _lights, _gloss, _camera, _environment, _film,
-_features, _glass_physics, _deep_plans, _material_matrix): the `apt` fixture, the comparisons, one Scene and the scenes that more than one
+_features, _glass_physics, _deep_plans, _material_matrix, _degenerate_scenes): the `apt` fixture, the comparisons, one Scene and the scenes that more than one
 file renders.  A plain module beside materials_ref.py, imported the same way: `from gpu_harness import apt  # noqa: F401` brings the fixture.
 
 A Scene's host half -- the tables the restatements read -- needs no device: the tensors are made on first use."""
