@@ -16,6 +16,7 @@ APT_FLAG_BAND_BUFFERS = 8
 APT_FLAG_GRID_SLOTS = 16
 APT_FLAG_NEE = 32
 APT_FLAG_GLOSS = 64
+APT_FLAG_MIS = 128                      # with APT_FLAG_GLOSS and a light mode (APT_FLAG_NEE or a light table): GLOSS hits sample the lights too
 APT_ERR_DEVICE = 4
 APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH = 1, 2, 4, 8      # bits of the device status word (apt_context_check)
 APT_DEV_BAD_MATERIAL = 16

@@ -1,6 +1,6 @@
 // apt_materials.h -- what render_kernels.hip (argument checks, C-ABI) hands to the material kernels' launches (include/render_mi355x.h
 // "per-sphere materials").  The material kernels live in translation units of their own (materials.hip, environment.hip, film.hip,
-// features.hip), so
+// features.hip, mis.hip), so
 // that the code object of render_kernels.hip -- every kernel the mirror renderer had before -- is built exactly as before.  Which of
 // them serves a call is decided behind mat_render_frame / mat_render_paths (materials.hip).
 // Plain data only: the kernels' own argument types are internal to each translation unit.
@@ -24,6 +24,7 @@ struct MatTrace {                 // the parts of apt_render_params the material
     const uint32_t *lights;       // the *_lights entries: the light table (device), which then stands for `light` / `nee`; else null.
                                   // Never set without a status word: a table that is not this scene's is reported through it.
     bool gloss;                   // APT_FLAG_GLOSS: the material table may hold APT_MAT_GLOSS words (the gloss instantiations)
+    bool mis;                     // APT_FLAG_MIS with `gloss` and a light mode (`nee` or `lights`): GLOSS hits sample the lights too
 };
 
 enum class MatFilm { None, Store, Add };   // Store: pass 0; Add: a later pass

@@ -1,5 +1,5 @@
 // pt_mat_launch.h -- the launch path of the material kernels, shared by the translation units that hold them (materials.hip,
-// environment.hip, film.hip): a call's plain data (apt_materials.h) as the kernels' own argument types (pt_materials.h), and one frame
+// environment.hip, film.hip, mis.hip): a call's plain data (apt_materials.h) as the kernels' own argument types (pt_materials.h), and one frame
 // and one buffer launcher.  Each translation unit instantiates a launcher with the scene-form bits it pins -- the instantiations its
 // code object holds -- and wraps it in a function of its own; materials.hip routes a call to one of them.  Host code only.
 #pragma once
@@ -11,6 +11,8 @@ namespace apt {   // the wrappers of the code objects behind mat_render_frame / 
 void env_launch_frame(const MatFrameCall &call);    // environment.hip
 void env_launch_paths(const MatPathsCall &call);
 void film_launch_frame(const MatFrameCall &call);   // film.hip: call.film is not None
+void mis_launch_frame(const MatFrameCall &call);    // mis.hip: call.t.mis, with or without a film
+void mis_launch_paths(const MatPathsCall &call);
 } // namespace apt
 
 namespace {
@@ -65,12 +67,17 @@ MatEnv mat_env(const apt_environment &e, bool gloss, bool film_add) {
     return m;
 }
 
-// PIN: the scene-form bits a translation unit pins (kMatGloss, kMatCamera, kMatEnv, kMatFilm).  A pinned bit is set in every kernel
+// PIN: the scene-form bits a translation unit pins (kMatGloss, kMatCamera, kMatEnv, kMatFilm, kMatMis).  A pinned bit is set in every kernel
 // the launcher names, whatever the call says -- what the call says then travels as data (MatEnv::gloss, the camera record) -- and is
 // resolved here, at compile time: with_flag would instantiate the kernels without it as well.
 template <int PIN, int BIT, class F> void with_pinned(bool b, F &&f) {
     if constexpr ((PIN & BIT) != 0) f(std::true_type{});
     else with_flag(b, f);
+}
+// The film tail of a frame launch: a pinned bit, except for the launcher that pins kMatMis, which holds both tails and takes the call's.
+template <int PIN, class F> void with_film(bool film, F &&f) {
+    if constexpr ((PIN & kMatMis) != 0) with_flag(film, f);
+    else f(std::integral_constant<bool, (PIN & kMatFilm) != 0>{});
 }
 template <int PIN> MatEnvArg<PIN> mat_env_arg(const apt_environment *e, bool gloss, bool film_add) {
     if constexpr ((PIN & kMatEnv) != 0) return mat_env(*e, gloss, film_add);
@@ -103,10 +110,13 @@ template <int PIN> void launch_mat_frame(const apt::MatFrameCall &c) {
     const MatEnvArg<PIN> ev = mat_env_arg<PIN>(c.env, c.t.gloss, c.film == apt::MatFilm::Add);
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) { with_flag(f.s.group == 8, [&](auto g8) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
+        // (kMatMis stands for a light mode: without a table its kernels are the APT_FLAG_NEE ones, which is what the call then carries)
+        with_pinned<PIN, kMatMis>(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
             with_pinned<PIN, kMatCamera>(c.camera != nullptr, [&](auto cam) { with_pinned<PIN, kMatGloss>(c.t.gloss, [&](auto gl) {
-                hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam) | (PIN & (kMatEnv | kMatFilm)), g8 ? 8 : 1>),
-                                   dim3((unsigned)f.s.blocks), dim3(kBlock), f.s.lds, st, c.spheres, c.materials, f.fa, ka, f.s.lp, cx.t, ev);
+                with_film<PIN>(c.film != apt::MatFilm::None, [&](auto film) {
+                    hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam) | (PIN & (kMatEnv | kMatMis)) | (film ? kMatFilm : 0), g8 ? 8 : 1>),
+                                       dim3((unsigned)f.s.blocks), dim3(kBlock), f.s.lds, st, c.spheres, c.materials, f.fa, ka, f.s.lp, cx.t, ev);
+                });
             }); });
         }); });
     }); }); });
@@ -118,8 +128,8 @@ template <int PIN> void launch_mat_paths(const apt::MatPathsCall &c) {
     const uint64_t blocks = (c.c + kBlock - 1) / kBlock;    // <= 2^31 - 1: checked by the caller
     hipStream_t st = (hipStream_t)c.stream;
     with_flag(c.t.ns == 8, [&](auto ns8) { with_flag(c.t.grid != nullptr, [&](auto gr) {
-        with_flag(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_pinned<PIN, kMatGloss>(c.t.gloss, [&](auto gl) {
-            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl) | (PIN & kMatEnv)>), dim3((unsigned)blocks),
+        with_pinned<PIN, kMatMis>(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) { with_pinned<PIN, kMatGloss>(c.t.gloss, [&](auto gl) {
+            hipLaunchKernelGGL((render_paths_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl) | (PIN & (kMatEnv | kMatMis))>), dim3((unsigned)blocks),
                                dim3(kBlock), 0, st, c.rays, c.spheres, c.materials, c.colors, c.n, c.b, c.c, ka, ev);
         }); }); });
     }); });

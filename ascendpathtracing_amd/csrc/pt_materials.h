@@ -31,8 +31,10 @@ constexpr int kMatEnv = 64;     // a context's environment (apt_context_set_envi
 static_assert((kMatEnv & (kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatEnv must be a bit of its own");
 constexpr int kMatFilm = 128;   // the film entries (include/render_mi355x.h "film") in the same template argument, frame kernels with kMatEnv only: the tail is frame_film
 static_assert((kMatFilm & (kMatEnv | kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatFilm must be a bit of its own");
+constexpr int kMatMis = 256;    // APT_FLAG_MIS in the same template argument (mis.hip: with kMatEnv, kMatGloss and a light mode): GLOSS hits sample the lights too
+static_assert((kMatMis & (kMatFilm | kMatEnv | kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatMis must be a bit of its own");
 constexpr uint32_t kMatEnvFilmAdd = 2u;   // MatEnv::gloss of a kMatFilm launch, next to bit 0: pass > 0, the tail adds to the film instead of storing
-constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv | kMatFilm); }
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv | kMatFilm | kMatMis); }
 // The contract's limit (include/render_mi355x.h "camera"): a frame with a camera takes a plan of at most this many leaves.  Nothing in
 // the kernels needs it any more; lifting it is a feature with its own tests above 4199 samples, not part of any clean-up.
 constexpr uint32_t kCamMaxLeaves = 44;
@@ -96,6 +98,15 @@ struct MatSun {
     bool may;                   // this bounce may sample: E samples and d + 1 < depth (wave-uniform)
     MatShadow sh;               // g is not read
 };
+// APT_FLAG_MIS's part of a path's state (kMatMis only; "Multiple importance sampling" in the header): the last sampling bounce was a
+// GLOSS one, and the density p_b under which it drew its direction.  g: G1(l) of the current GLOSS bounce, which multiplies T only after
+// the bounce's shadow segment has used T (1 for every other bounce).
+struct MatMis {
+    float pb;
+    bool gl;
+    float g;
+};
+constexpr float kMisPi = 0x1.921fb6p+1f, kMisTwoPi = 0x1.921fb6p+2f;   // RN(pi), RN(2 * pi)
 template <int LM>
 __device__ __forceinline__ MatLight load_mat_light(const float *__restrict__ sph, const TraceArgs &ta) {
     MatLight lt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1};
@@ -249,10 +260,56 @@ __device__ __forceinline__ void mat_basis(float nx, float ny, float nz, float &t
     bx = b; by = sg + (ny * ny) * a; bz = -ny;
 }
 
+// G1 of the separable Smith term for a frame direction of z component z (a2 = alpha * alpha): the GLOSS block's own operations.
+__device__ __forceinline__ float mat_g1(float a2, float z) { return (2.0f * z) / (z + sqrtf(a2 + (1.0f - a2) * (z * z))); }
+// The GGX density of the unit half vector m in the frame, without the cancellation of (m.z^2)(a2 - 1) + 1: k = (m.x^2 + m.y^2) + a2 *
+// m.z^2 >= ~a2 > 0, D = a2 / ((pi * k) * k) <= ~1 / (pi * a2) <= 2^32 / pi.
+__device__ __forceinline__ float mat_ggx_d(float a2, float mx, float my, float mz) {
+    const float k = (mx * mx + my * my) + a2 * (mz * mz);
+    return a2 / ((kMisPi * k) * k);
+}
+// The light-sampling density of a sphere of r2 seen from a point at squared distance d2 > r2, chosen with probability P:
+// "Direct light sampling"'s x, cmax and omc, then P / (2 * pi * omc).
+__device__ __forceinline__ float mat_light_pdf(float r2, float d2, float P) {
+    const float x = r2 / d2;
+    const float cmax = sqrtf(1.0f - x);
+    const float omc = x / (1.0f + cmax);
+    return P / (kMisTwoPi * omc);
+}
+// P of the table entry that lists sphere k: cdf[i] - cdf[i - 1], exact (both are multiples of 2^-24).  The table lists distinct spheres
+// in the caller's order, so the entry is found by a scan; only a path that hits a listed light right after a GLOSS sampling bounce asks.
+__device__ __forceinline__ float mat_light_prob(const MatTable &tb, int k) {
+    float P = 0.0f;
+    for (uint32_t i = 0; i < tb.n; ++i)
+        if (tb.idx()[i] == (uint32_t)k) P = tb.cdf()[i] - (i ? tb.cdf()[i - 1u] : 0.0f);
+    return P;
+}
+
 // A path's stream keys, made once per path: the bounce's, APT_FLAG_NEE's direction (LM != kLmNone), the table's selection (kLmTable).
 struct MatKeys {
     uint64_t bounce, nee, pick;
 };
+// "Direct light sampling"'s sample step for a sphere light of r2 at w0 = c - h, d2 = dot(w0, w0) > r2: a direction l of the light's cone
+// from the nkey stream, and omc = 1 - cos_max.  The DIFF hits' and, with APT_FLAG_MIS, the GLOSS hits' (one hit per bounce: one draw).
+__device__ __forceinline__ void mat_cone_sample(float r2, float wx0, float wy0, float wz0, float d2, uint64_t nkey, uint32_t d, float &lx,
+                                                float &ly, float &lz, float &omc) {
+    const float x = r2 / d2;
+    const float cmax = sqrtf(1.0f - x);
+    omc = x / (1.0f + cmax);                                  // 1 - cos_max
+    float v1, v2;
+    mat_uniforms(nkey, d, v1, v2);
+    const float cos_a = 1.0f - v1 * omc;
+    const float sin_a = sqrtf(1.0f - cos_a * cos_a);
+    float sp, cp;
+    mat_sincos(v2, sp, cp);
+    const float dl = sqrtf(d2);
+    const float wx = wx0 / dl, wy = wy0 / dl, wz = wz0 / dl;
+    float ax, ay, az, ex, ey, ez;
+    mat_basis(wx, wy, wz, ax, ay, az, ex, ey, ez);
+    const float ca = cp * sin_a, sa = sp * sin_a;
+    const float qx = (ax * ca + ex * sa) + wx * cos_a, qy = (ay * ca + ey * sa) + wy * cos_a, qz = (az * ca + ez * sa) + wz * cos_a;
+    mat_normalise(qx, qy, qz, lx, ly, lz);
+}
 template <int LM>
 __device__ __forceinline__ MatKeys mat_path_keys(uint64_t seed, uint64_t path) {
     return MatKeys{mat_path_key(seed, path), LM ? nee_path_key(seed, path) : 0, LM == kLmTable ? light_path_key(seed, path) : 0};
@@ -290,9 +347,12 @@ struct MatHit {
 // spherical-cap form, weight G1(l)).  A direction drawn below the horizon ends the path (s.live).  It does not sample, like SPEC.
 // EV (kMatEnv): every hit clears su.sampled, and a DIFF hit that may (su.may) draws the sun's shadow segment -> su.sh, "Direct light
 // sampling"'s arithmetic with w = sun_dir and omc = sun_omc; without EV env and su are not read.
-template <int LM, int SC, bool GL, bool EV = false, class ENV = MatNoEnv>
+// MI (kMatMis; "Multiple importance sampling" in the header): a GLOSS hit that may is a sampling bounce too: it picks and samples a
+// light as a DIFF hit does -> sh, with the balance-heuristic weight, and leaves its own density in mi; the light step weights the
+// emission of a light that such a bounce could have sampled instead of leaving it out.  Without MI mi is not read.
+template <int LM, int SC, bool GL, bool EV = false, bool MI = false, class ENV = MatNoEnv>
 __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys key, uint32_t d, const MatLight &lt, bool may, bool &sampled,
-                                          MatShadow &sh, const MatTable &tb, int &kprev, const ENV &env, MatSun &su) {
+                                          MatShadow &sh, const MatTable &tb, int &kprev, const ENV &env, MatSun &su, MatMis &mi) {
     const int k = h.k;
     float hx = s.dx * h.t, hy = s.dy * h.t, hz = s.dz * h.t;
     hx = s.ox + hx; hy = s.oy + hy; hz = s.oz + hz;
@@ -307,6 +367,18 @@ __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys k
         }
     }
     if (!counted) { s.lx = s.lx + s.tx * h.em.x; s.ly = s.ly + s.ty * h.em.y; s.lz = s.lz + s.tz * h.em.z; }
+    if constexpr (MI) {
+        if (counted && mi.gl) {                               // the light a GLOSS bounce could have sampled: the BSDF strategy's share
+            const float wx0 = h.geo.x - s.ox, wy0 = h.geo.y - s.oy, wz0 = h.geo.z - s.oz;   // (that bounce's w0, d2 and omc, bit for bit)
+            const float r2k = LM == kLmNee ? lt.r2 : (SC == kScene8 ? h.geo.w : tb.sph[(size_t)k]);
+            const float pl = mat_light_pdf(r2k, mat_dot(wx0, wy0, wz0, wx0, wy0, wz0), LM == kLmTable ? mat_light_prob(tb, k) : 1.0f);
+            const float sum = mi.pb + pl;
+            const float wb = (sum > 0.0f && sum < __builtin_inff()) ? mi.pb / sum : 1.0f;   // no finite positive sum: in full
+            s.lx = s.lx + (s.tx * h.em.x) * wb; s.ly = s.ly + (s.ty * h.em.y) * wb; s.lz = s.lz + (s.tz * h.em.z) * wb;
+        }
+        mi.gl = false;
+        mi.g = 1.0f;
+    }
     if (LM == kLmNee) sampled = false;
     if (LM == kLmTable) kprev = -1;
     if constexpr (EV) su.sampled = false;
@@ -342,22 +414,8 @@ __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys k
             const float wx0 = cur.cx - hx, wy0 = cur.cy - hy, wz0 = cur.cz - hz;
             const float d2 = mat_dot(wx0, wy0, wz0, wx0, wy0, wz0);
             if (d2 > cur.r2) {                                // h strictly outside the light (false for NaN)
-                const float x = cur.r2 / d2;
-                const float cmax = sqrtf(1.0f - x);
-                const float omc = x / (1.0f + cmax);          // 1 - cos_max
-                float v1, v2;
-                mat_uniforms(key.nee, d, v1, v2);
-                const float cos_a = 1.0f - v1 * omc;
-                const float sin_a = sqrtf(1.0f - cos_a * cos_a);
-                float sp, cp;
-                mat_sincos(v2, sp, cp);
-                const float dl = sqrtf(d2);
-                const float wx = wx0 / dl, wy = wy0 / dl, wz = wz0 / dl;
-                float ax, ay, az, ex, ey, ez;
-                mat_basis(wx, wy, wz, ax, ay, az, ex, ey, ez);
-                const float ca = cp * sin_a, sa = sp * sin_a;
-                const float qx = (ax * ca + ex * sa) + wx * cos_a, qy = (ay * ca + ey * sa) + wy * cos_a, qz = (az * ca + ez * sa) + wz * cos_a;
-                mat_normalise(qx, qy, qz, sh.dx, sh.dy, sh.dz);
+                float omc;
+                mat_cone_sample(cur.r2, wx0, wy0, wz0, d2, key.nee, d, sh.dx, sh.dy, sh.dz, omc);
                 const float cosl = mat_dot(sh.dx, sh.dy, sh.dz, nlx, nly, nlz);
                 sh.w = cosl * (2.0f * omc);
                 if (LM == kLmTable) { sh.w = sh.w * invp; sh.g = cur.idx; }
@@ -407,7 +465,49 @@ __device__ __forceinline__ void mat_shade(MatPath &s, const MatHit &h, MatKeys k
         if (!(lz > 0.0f)) s.live = false;                     // below the horizon: the path ends here, L keeps its value
         const float a2 = h.alpha * h.alpha;
         const float g = (2.0f * lz) / (lz + sqrtf(a2 + (1.0f - a2) * (lz * lz)));   // G1(l), separable Smith
-        s.tx = s.tx * g; s.ty = s.ty * g; s.tz = s.tz * g;
+        if constexpr (MI) {
+            mi.g = g;                                         // T *= g after the shadow segment (trace_mat)
+            if (may) {                                        // a sampling bounce, also when the path ends here (l below the horizon): the
+                                                              // light strategy's share must not depend on what the other strategy drew
+                const float g1v = mat_g1(a2, vz);
+                mi.pb = (g1v * mat_ggx_d(a2, mx, my, mz)) / (4.0f * vz);
+                mi.gl = true;
+                MatLight chosen;                              // as the DIFF block: the lane's light, or lt itself
+                const MatLight &cur = LM == kLmTable ? chosen : lt;
+                float P = 1.0f;
+                if (LM == kLmTable) {
+                    float u, unused;
+                    mat_uniforms(key.pick, d, u, unused);
+                    const uint32_t i = mat_light_pick(tb, u);
+                    P = tb.cdf()[i] - (i ? tb.cdf()[i - 1u] : 0.0f);
+                    mat_light_geometry<SC>(tb, (int)min(tb.idx()[i], tb.ns - 1u), chosen);
+                    kprev = k;                                // sampled, whatever follows
+                }
+                if (k != cur.idx) {
+                    const float wx0 = cur.cx - hx, wy0 = cur.cy - hy, wz0 = cur.cz - hz;
+                    const float d2 = mat_dot(wx0, wy0, wz0, wx0, wy0, wz0);
+                    if (d2 > cur.r2) {
+                        float cx, cy, cz, omc;
+                        mat_cone_sample(cur.r2, wx0, wy0, wz0, d2, key.nee, d, cx, cy, cz, omc);
+                        if (LM == kLmNee) sampled = true;
+                        const float wlx = mat_dot(cx, cy, cz, tx, ty, tz), wly = mat_dot(cx, cy, cz, bx, by, bz), wlz = mat_dot(cx, cy, cz, nlx, nly, nlz);
+                        if (wlz > 0.0f) {
+                            float hmx, hmy, hmz;
+                            mat_normalise(vx + wlx, vy + wly, vz + wlz, hmx, hmy, hmz);
+                            const float pb = (g1v * mat_ggx_d(a2, hmx, hmy, hmz)) / (4.0f * vz);
+                            const float pl = P / (kMisTwoPi * omc);
+                            const float sum = pb + pl;
+                            sh.dx = cx; sh.dy = cy; sh.dz = cz;
+                            sh.w = mat_g1(a2, wlz) * (pb / sum);
+                            sh.g = cur.idx;
+                            sh.want = sum > 0.0f && sum < __builtin_inff();   // false for NaN: a vanishing v.z
+                        }
+                    }
+                }
+            }
+        } else {
+            s.tx = s.tx * g; s.ty = s.ty * g; s.tz = s.tz * g;
+        }
         const float qx = (tx * lx + bx * ly) + nlx * lz, qy = (ty * lx + by * ly) + nly * lz, qz = (tz * lx + bz * ly) + nlz * lz;
         mat_normalise(qx, qy, qz, ndx, ndy, ndz);
     } else {
@@ -587,7 +687,8 @@ __device__ __forceinline__ MatScene8 load_mat_scene8(const float *__restrict__ s
 // EV (kMatEnv; env: the environment, else not read): a live path that finds no sphere gathers the sky and -- unless the bounce before
 // sampled it -- the sun before it ends, and after a DIFF bounce that drew one (mat_shade) the sun's shadow segment goes through the
 // same hit routine under the same vote, after the light's: the sun is visible iff it finds no sphere.
-template <int SC, int LM, bool GL, bool EV = false, class ENV = MatNoEnv>
+// MI (kMatMis): a GLOSS bounce may draw a shadow segment as well (mat_shade), which goes the same way; its G1(l) multiplies T after it.
+template <int SC, int LM, bool GL, bool EV = false, bool MI = false, class ENV = MatNoEnv>
 __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, const uint32_t *__restrict__ mat, const MatScene8 &m8,
                                               const GridHeader &gh, const MatLight &lt, const MatTable &tb, float4 *tile, MatPath &s,
                                               const TraceArgs &ta, uint64_t path, const ENV &env = ENV()) {
@@ -599,6 +700,7 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
     uint32_t traced = 0, n_cells = 0, n_tests = 0;           // the last two: walk statistics of the grid form
     bool sampled = false;                                    // kLmNee: the previous bounce sampled the light
     int kprev = -1;                                          // kLmTable: the sphere of the previous bounce if it was a sampling bounce, else -1
+    MatMis mi = {0.0f, false, 1.0f};
     for (uint32_t d = 0; d < ta.depth; ++d) {
         MatHit h;
         h.alpha = 0.0f;
@@ -655,7 +757,7 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
         su.may = false;
         if constexpr (EV) su.may = env.sample && d + 1 < ta.depth;   // no sample at the last bounce, as for the lights
         if (s.live) {
-            mat_shade<LM, SC, GL, EV>(s, h, key, d, lt, may, sampled, sh, tb, kprev, env, su);
+            mat_shade<LM, SC, GL, EV, MI>(s, h, key, d, lt, may, sampled, sh, tb, kprev, env, su, mi);
             ++traced;
         }
         if (may && (SC == kSceneTiles ? __syncthreads_or(sh.want) : __any(sh.want))) {
@@ -680,6 +782,10 @@ __device__ __forceinline__ uint32_t trace_mat(const float *__restrict__ sph, con
                     s.lx = s.lx + (s.tx * lt.ex) * sh.w; s.ly = s.ly + (s.ty * lt.ey) * sh.w; s.lz = s.lz + (s.tz * lt.ez) * sh.w;
                 }
             }
+        }
+        if constexpr (MI) {
+            s.tx = s.tx * mi.g; s.ty = s.ty * mi.g; s.tz = s.tz * mi.g;   // G1(l) of a GLOSS bounce, else 1: the light's segment used T before it
+            mi.g = 1.0f;
         }
         if constexpr (EV) {
             if (su.may && (SC == kSceneTiles ? __syncthreads_or(su.sh.want) : __any(su.sh.want))) {
@@ -750,6 +856,8 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
     constexpr int LM = mat_light_mode(SCN);
     constexpr bool GL = (SCN & kMatGloss) != 0;
     constexpr bool EV = (SCN & kMatEnv) != 0;
+    constexpr bool MI = (SCN & kMatMis) != 0;
+    static_assert(!MI || (EV && GL && LM != kLmNone), "the kMatMis kernels are gloss, environment kernels with a light mode");
     __shared__ float4 tab[mat_tab_entries(SCN)];
     __shared__ float4 tile[SC == kSceneTiles ? kTile : 1];
     GridHeader gh;
@@ -764,7 +872,7 @@ __global__ __launch_bounds__(kBlock) void render_paths_mat_kernel(const float *_
     const uint64_t p = begin + (valid ? local : 0);
     MatPath s;
     mat_path_init(s, rays[p], rays[n_total + p], rays[2 * n_total + p], rays[3 * n_total + p], rays[4 * n_total + p], rays[5 * n_total + p]);
-    const uint32_t traced = trace_mat<SC, LM, GL, EV>(sph, mat, m8, gh, lt, tb, tile, s, ta, p, ev);
+    const uint32_t traced = trace_mat<SC, LM, GL, EV, MI>(sph, mat, m8, gh, lt, tb, tile, s, ta, p, ev);
     if (valid) {
         colors[p] = s.lx;
         colors[n_total + p] = s.ly;
@@ -812,6 +920,8 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     constexpr bool GL = (SCN & kMatGloss) != 0;
     constexpr bool EV = (SCN & kMatEnv) != 0;
     constexpr bool FILM = (SCN & kMatFilm) != 0;
+    constexpr bool MI = (SCN & kMatMis) != 0;
+    static_assert(!MI || (EV && GL && LM != kLmNone), "the kMatMis kernels are gloss, environment kernels with a light mode");
     static_assert(!FILM || EV, "the film kernels are environment kernels: store-or-add travels in MatEnv::gloss");
     bool film_add = false;
     if constexpr (FILM) {   // (launch-uniform) the word's bit 0 is what every other reader of ev.gloss takes it for
@@ -858,7 +968,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         }
         MatPath s;
         mat_path_init(s, rox, roy, roz, rdx, rdy, rdz);
-        traced += trace_mat<SC, LM, GL, EV>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k, ev);
+        traced += trace_mat<SC, LM, GL, EV, MI>(sph, mat, m8, gh, lt, tb, tile, s, ta, pbase + k, ev);
         return Col{s.lx, s.ly, s.lz};
     };
     auto add = [](const Col &a, const Col &b) { return Col{a.r + b.r, a.g + b.g, a.b + b.b}; };

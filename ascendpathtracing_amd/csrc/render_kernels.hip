@@ -150,9 +150,11 @@ apt::MatTrace make_mat_trace(const apt_render_params *p, const Launch &ls, const
     // context's first launch inside a stream capture, a device index beyond the context's table) it would do so silently: the tile
     // form, which needs no promise, renders the same image then.  (ta.grid is null for the 8-sphere scene: make_trace_args.)
     // A light table stands for APT_FLAG_NEE and light_index, which its entries do not read.
+    // APT_FLAG_MIS is read only next to APT_FLAG_GLOSS and a light mode (the flag or a table); everywhere else the bit is ignored.
     const uint32_t *lights = m.with_lights ? static_cast<const uint32_t *>(m.lights) : nullptr;
-    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, !lights && (p->flags & APT_FLAG_NEE) != 0, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced, lights,
-                         (p->flags & APT_FLAG_GLOSS) != 0};
+    const bool nee = !lights && (p->flags & APT_FLAG_NEE) != 0, gloss = (p->flags & APT_FLAG_GLOSS) != 0;
+    return apt::MatTrace{ta.ns, ta.depth, ta.rr_start, ta.light, nee, ta.eps, ta.seed, ta.status ? ta.grid : nullptr, ta.status, ta.traced, lights,
+                         gloss, (p->flags & APT_FLAG_MIS) != 0 && gloss && (nee || lights)};
 }
 
 // The path range [b, b + c) of a buffer-mode call (path_count 0: to the end of the image) among the image's n_image paths.  With

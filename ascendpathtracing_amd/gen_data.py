@@ -87,11 +87,17 @@ def gloss(alpha):
 _gloss_word = gloss     # (gen_spheres_materials has an argument of that name)
 
 
-def materials_flags(table):
+def materials_flags(table, mis=False):
     """apt_materials_flags_host: the flags a material table earns -- APT_FLAG_GLOSS when it holds a well-formed gloss word, else 0.
-    `table`: the host array of codes (gen_spheres_materials / gen_scene_materials).  OR the result into make_params(flags=)."""
+    `table`: the host array of codes (gen_spheres_materials / gen_scene_materials).  OR the result into make_params(flags=).
+    mis=True: APT_FLAG_MIS as well, when -- and only when -- the table earns APT_FLAG_GLOSS: the rough-metal hits then sample the lights
+    too (multiple importance sampling, balance heuristic), which is what makes the highlight of a small lamp converge.  The launch reads
+    the bit next to APT_FLAG_NEE or a light table only; render_frame, render_do_ex, Film.add_pass and render_frame_film take it in
+    params.flags like every other flag."""
+    from ._lib import APT_FLAG_MIS
     t = np.ascontiguousarray(np.asarray(table).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32).ravel()
-    return int(lib().apt_materials_flags_host(t.ctypes.data, t.size))
+    flags = int(lib().apt_materials_flags_host(t.ctypes.data, t.size))
+    return flags | (APT_FLAG_MIS if mis and flags else 0)
 
 
 def gen_spheres_materials(gloss=None):

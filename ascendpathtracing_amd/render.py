@@ -323,7 +323,10 @@ def render_do_ex(params: RenderParams, stream, rays, spheres, colors, materials=
     expectation at the same depth, less noise for a small light; it needs light_index >= 0.
     lights (materials only): a light table on the GPU (gen_data.build_lights, as a contiguous int32 CUDA tensor) -> every diffuse hit
     samples ONE of the listed spheres (apt_render_paths_lights); APT_FLAG_NEE and light_index are not read then.  A table that is not
-    this scene's renders nothing and check_device_status() raises lights-mismatch."""
+    this scene's renders nothing and check_device_status() raises lights-mismatch.
+    APT_FLAG_MIS in params.flags (gen_data.materials_flags(table, mis=True)): read only next to APT_FLAG_GLOSS and a light mode
+    (APT_FLAG_NEE or lights) -- the rough-metal hits then sample the light too, weighted against their own sampler by the balance
+    heuristic: the same expectation at the same depth, far less noise in the highlight of a small lamp.  Every other launch ignores the bit."""
     _default.render_do_ex(params, stream, rays, spheres, colors, materials, lights)
 
 
@@ -339,8 +342,8 @@ def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None,
     """Fused ray-generate + trace + decode for pixels [pixel_begin, pixel_begin+pixel_count).
     Returns (fb float32 [3][count], fb_u8 uint8 [count][3]); not synchronised.  materials: as render_do_ex (apt_render_frame_materials),
     its rule for params.accel included: a grid needs APT_FLAG_GRID_SLOTS, changes which spheres are tested and never the image; a grid
-    that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE, lights: as render_do_ex
-    (apt_render_frame_lights)."""
+    that is not this scene's renders nothing and check_device_status() raises grid-mismatch.  APT_FLAG_NEE, lights, APT_FLAG_MIS: as
+    render_do_ex (apt_render_frame_lights)."""
     return _default.render_frame(params, spheres, pixel_begin, pixel_count, stream, fb, fb_u8, materials, lights)
 
 
@@ -348,7 +351,7 @@ def render_frame_film(params: RenderParams, spheres, materials, film=None, pass_
                       stream=None):
     """apt_render_frame_film: one pass of a film.  The pixel range rendered as render_frame(materials=, lights=) would with the seed
     apt_film_pass_seed(params.seed, pass_index), unclipped, stored in `film` (float32 [3][count]; None: a new tensor) for pass 0 and
-    added to it for a later pass.  Returns the film; not synchronised."""
+    added to it for a later pass.  Returns the film; not synchronised.  The flags travel in params.flags, APT_FLAG_MIS among them."""
     return _default.render_frame_film(params, spheres, materials, film, pass_index, lights, pixel_begin, pixel_count, stream)
 
 

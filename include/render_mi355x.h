@@ -95,7 +95,11 @@ enum {
     APT_FLAG_GLOSS = 64u,  /* EXTENSION, *_materials and *_lights entries only (every other entry ignores the bit): the CALLER states  */
                            /* that the material table may hold APT_MAT_GLOSS words ("GLOSS" below; apt_materials_flags_host() says so */
                            /* for a table).  Without it such a word is a bad code as before and every launch is the one it was.       */
-    APT_FLAG_RR = 2u       /* EXTENSION (not in the reference; BASELINE config 5): Russian */
+    APT_FLAG_MIS = 128u,   /* EXTENSION: multiple importance sampling of the lights at GLOSS hits ("Multiple importance sampling" below). */
+                           /* Read only next to APT_FLAG_GLOSS, by the *_materials entries with APT_FLAG_NEE and by the *_lights entries  */
+                           /* (their film entries and buffer mode included); every other launch ignores the bit and is the one it was.    */
+                           /* Unbiased; changes the image by noise only, and at depth 1 by nothing.                                      */
+    APT_FLAG_RR = 2u      /* EXTENSION (not in the reference; BASELINE config 5): Russian */
                            /* roulette.  After shading bounce d (0-based) with d+1 >=       */
                            /* rr_start, a path that is alive with q = max(r,g,b) > 0        */
                            /* survives with probability p = clamp(q, 0.05, 0.95): u =       */
@@ -296,7 +300,8 @@ int render_frame(const apt_render_params *p, void *stream, const float *spheres,
  *             a2 = alpha * alpha; g = (2 * l.z) / (l.z + sqrt(a2 + (1 - a2) * (l.z * l.z))); T *= g per channel     (G1(l))
  *             q = (t * l.x + bt * l.y) + nl * l.z per component; d = q / sqrt(dot(q, q)).
  *             For direct light sampling and the light tables below a GLOSS hit is a bounce that does not sample, like SPEC: it draws
- *             no shadow segment, leaves `sampled` false, and whatever the path hits next adds its emission in full.
+ *             no shadow segment, leaves `sampled` false, and whatever the path hits next adds its emission in full -- unless the
+ *             launch carries APT_FLAG_MIS ("Multiple importance sampling" below).
  *     skip    o = h.  A branch that leaves on the sphere's OUTER side does not test sphere k on the next segment (skip = k; a convex
  *             sphere cannot be re-hit going outward, while the near root of a wall of radius 1e5 is fp32 noise of ~5e-3 >> eps):
  *             DIFF, SPEC, GLOSS and the REFR reflection leave outward iff `into`, the REFR refraction iff `!into`; otherwise skip = none.
@@ -416,6 +421,59 @@ int apt_render_paths_lights(const apt_render_params *p, void *stream, const floa
                             const void *lights, float *colors);
 int apt_context_render_paths_lights(apt_context *ctx, const apt_render_params *p, void *stream, const float *rays, const float *spheres,
                                     const uint32_t *materials, const void *lights, float *colors);
+
+/* ---- Multiple importance sampling of the lights at GLOSS hits (APT_FLAG_MIS; EXTENSION) ---------------------------------------------------
+ * Opt-in and additive (APT_ABI_VERSION is unchanged, no entry is added).  The bit is read only in a launch that also carries APT_FLAG_GLOSS
+ * and that samples lights: a *_materials entry with APT_FLAG_NEE, or a *_lights entry -- the film entries and buffer mode included,
+ * through the same flag word.  Every other launch ignores it and is the launch it was: the mirror entries, the feature planes, a
+ * *_materials launch without APT_FLAG_NEE, any launch without APT_FLAG_GLOSS.  A table without a GLOSS word renders the image of the
+ * launch without the bit, bit for bit.
+ *
+ * Without the bit a GLOSS hit reaches a light only when the direction it draws happens to find it: the noisiest thing the renderer
+ * draws is the broad highlight of a small lamp.  With it a GLOSS hit samples the light as well, and the two strategies -- the light's
+ * cone and the visible-normal sampler -- share every direction by the balance heuristic.  The arithmetic, in the terms of "per-sphere
+ * materials", "Direct light sampling" and "several lights" above (fp32, every operation rounded on its own: no FMA; IEEE sqrt and
+ * division; dot as the chain above).  PI = 0x1.921fb6p+1f and 2PI = 0x1.921fb6p+2f are RN(pi) and RN(2 pi).  A path carries, next to
+ * `sampled` and `kprev`, one more bit `glprev` (false at its start) and one float `pbprev`.  In the frame (t, bt, nl) of a GLOSS hit,
+ * with a2 = alpha * alpha:
+ *     G1(z)   = (2 * z) / (z + sqrt(a2 + (1 - a2) * (z * z)))                                     (the GLOSS block's own G1, of a z component)
+ *     D(m)    = a2 / ((PI * k) * k) with k = (m.x * m.x + m.y * m.y) + a2 * (m.z * m.z)          (GGX of a UNIT half vector: m.x^2 + m.y^2
+ *               stands for 1 - m.z^2, so there is no cancellation of (m.z^2)(a2 - 1) + 1; k >= ~a2 > 0 for every q >= 1, and at q = 1,
+ *               a2 = 2^-32, D <= ~2^32 / pi stays inside fp32)
+ *     pb(m)   = (G1(v.z) * D(m)) / (4 * v.z)                        (the density under which the visible-normal sampler draws l = reflect(v, m))
+ *     pl(r2, d2, P) = P / (2PI * omc) with x = r2 / d2, cmax = sqrt(1 - x), omc = x / (1 + cmax)     (the density of the cone sampler)
+ *   GLOSS   a GLOSS hit on sphere k at h, bounce d with d + 1 < depth, is a SAMPLING BOUNCE -- whether or not its own direction l is
+ *           accepted: a path that ends here (!(l.z > 0)) still takes the light sample below first; tying the light sample to what the
+ *           other strategy drew would scale it by that strategy's acceptance rate.  T *= G1(l) takes effect after the shadow step.
+ *           glprev = true; pbprev = pb(m) of the drawn m.
+ *           choice  as a DIFF hit: with APT_FLAG_NEE the light is j = light_index, P = 1, and the predicate is k != j and d2 > r2
+ *                   (then, and only then, sampled = true); with a table i is drawn from the lkey stream, j = g[i], P = cdf[i] - cdf[i-1]
+ *                   (cdf[-1] = 0; exact), the predicate is S(j, k, h), and sampled = true, kprev = k either way.
+ *           sample  predicate true: "Direct light sampling"'s sample step for sphere j up to l -- the same nkey stream, (v1, v2), omc
+ *                   and operations (a bounce has one hit, so a DIFF and a GLOSS hit never draw from the same counter) --, called c here.
+ *                   wl = (dot(c, t), dot(c, bt), dot(c, nl)).  !(wl.z > 0): nothing is added and no segment is traced.  Otherwise
+ *                   m' = (v + wl) / sqrt(dot(v + wl, v + wl)) (three additions, three divisions); p_b = pb(m'); p_l = pl(r2_j, d2, P);
+ *                   sum = p_b + p_l.  !(sum > 0 and sum < inf) -- a vanishing v.z makes p_b NaN or inf, a vanishing omc p_l inf --:
+ *                   nothing is added and no segment is traced.  Otherwise wgt = G1(wl.z) * (p_b / sum).
+ *           shadow  the DIFF sample's: from h along c, every sphere but this bounce's skip sphere, visible iff the arg-min IS j;
+ *                   visible: L += (T * e_j) * wgt per channel, T being the throughput after `T *= albedo` and before G1(l) and
+ *                   roulette.  (BRDF * cos / p_l is albedo * G1(wl) * p_b / p_l; the balance heuristic multiplies it by p_l / sum.)
+ *   light   at the next hit, on sphere m from origin o: where the rules above LEAVE OUT emission(m) -- `sampled` and m == light_index,
+ *           or, with a table, `sampled`, m listed and S(m, kprev, o) -- and glprev is set, it is weighted instead:
+ *           p_l' = pl(r2_m, dot(c_m - o, c_m - o), P_m) with P_m = 1 or the P of the entry that lists m: that light's own density
+ *           from o, the sampling bounce's operations on the sampling bounce's values, bit for bit;  sum = pbprev + p_l';
+ *           w = (sum > 0 and sum < inf) ? pbprev / sum : 1;  L += (T * emission(m)) * w per channel.  Then glprev = false.
+ *           Everything else is unchanged: emission after a DIFF sample is left out, after SPEC, REFR, an unsampled bounce or of an
+ *           unlisted emitter added in full; the camera ray, roulette, the APT_DEV_* bits, the grid rules and the trace counter are
+ *           as above, and a traced shadow segment counts.
+ *   sun     the sun sample of "environment" stays a DIFF-only matter: a miss after a GLOSS hit adds the sun in full, as without the bit.
+ * Finite: with finite inputs D, G1 and both densities are finite or are caught by the `sum` test, whose failure gives the light sample
+ * nothing and the next hit the emission in full -- both sides take the same decision only approximately (p_b is evaluated at m' on one
+ * side and at the drawn m on the other), which is the balance heuristic's own fp32 rounding and no bias beyond it.
+ * Properties: a frame with the bit has the expectation of the same frame without it at the same depth (the image changes by noise
+ * only) and is the same frame bit for bit at depth 1; a one-light table equals APT_FLAG_NEE with that light bit for bit, trace counter
+ * included; a table with the bit but no GLOSS word renders the flagless image bit for bit.  A table that is not the scene's is reported
+ * with APT_DEV_LIGHTS_MISMATCH and nothing is written, as without the bit. */
 
 /* HOST demo scene: gen_spheres' 8 spheres plus smallpt's glass ball (r 16.5 at (73, 16.5, 78), albedo 0.999) as sphere 8, light 7.
  * spheres = HOST float[128] ([10][9] planes, zero padded like gen_spheres), materials = HOST uint32_t[9]: walls and light DIFF,
