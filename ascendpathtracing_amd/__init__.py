@@ -14,8 +14,8 @@ reference's own interfaces for that path:
 There is no CPU fallback: every compute entry raises if the HIP library or a GPU is missing.
 """
 from . import _lib  # noqa: F401
-from ._lib import (APT_FLAG_RETIRE, APT_FLAG_RR, APT_FLAG_EMISSION, APT_FLAG_BAND_BUFFERS, APT_FLAG_GRID_SLOTS, APT_FLAG_NEE, APT_FLAG_GLOSS, APT_FLAG_MIS, APT_ENV_SAMPLE_SUN, APT_TONEMAP_CLIP, APT_TONEMAP_REINHARD, APT_CURVE_LINEAR, APT_CURVE_SRGB, APT_FEATURE_PLANES, APT_FEATURE_COVERAGE, APT_FEATURE_DEPTH, APT_FEATURE_NORMAL, APT_FEATURE_ALBEDO, APT_MODE_KERNEL, APT_MODE_ORACLE, RenderParams, AptError, default_params,
+from ._lib import (APT_FLAG_RETIRE, APT_FLAG_RR, APT_FLAG_EMISSION, APT_FLAG_BAND_BUFFERS, APT_FLAG_GRID_SLOTS, APT_FLAG_NEE, APT_FLAG_GLOSS, APT_FLAG_MIS, APT_FLAG_PIXEL_LIST, APT_ENV_SAMPLE_SUN, APT_TONEMAP_CLIP, APT_TONEMAP_REINHARD, APT_CURVE_LINEAR, APT_CURVE_SRGB, APT_FEATURE_PLANES, APT_FEATURE_COVERAGE, APT_FEATURE_DEPTH, APT_FEATURE_NORMAL, APT_FEATURE_ALBEDO, APT_MODE_KERNEL, APT_MODE_ORACLE, RenderParams, AptError, default_params,
                    make_params, MAT_SPEC, MAT_DIFF, MAT_REFR, MAT_GLOSS)
 
-__all__ = ["APT_FLAG_RETIRE", "APT_FLAG_RR", "APT_FLAG_EMISSION", "APT_FLAG_BAND_BUFFERS", "APT_FLAG_GRID_SLOTS", "APT_FLAG_NEE", "APT_FLAG_GLOSS", "APT_FLAG_MIS", "APT_ENV_SAMPLE_SUN", "APT_TONEMAP_CLIP", "APT_TONEMAP_REINHARD", "APT_CURVE_LINEAR", "APT_CURVE_SRGB", "APT_FEATURE_PLANES", "APT_FEATURE_COVERAGE", "APT_FEATURE_DEPTH", "APT_FEATURE_NORMAL", "APT_FEATURE_ALBEDO", "APT_MODE_KERNEL", "APT_MODE_ORACLE", "RenderParams", "AptError", "default_params",
+__all__ = ["APT_FLAG_RETIRE", "APT_FLAG_RR", "APT_FLAG_EMISSION", "APT_FLAG_BAND_BUFFERS", "APT_FLAG_GRID_SLOTS", "APT_FLAG_NEE", "APT_FLAG_GLOSS", "APT_FLAG_MIS", "APT_FLAG_PIXEL_LIST", "APT_ENV_SAMPLE_SUN", "APT_TONEMAP_CLIP", "APT_TONEMAP_REINHARD", "APT_CURVE_LINEAR", "APT_CURVE_SRGB", "APT_FEATURE_PLANES", "APT_FEATURE_COVERAGE", "APT_FEATURE_DEPTH", "APT_FEATURE_NORMAL", "APT_FEATURE_ALBEDO", "APT_MODE_KERNEL", "APT_MODE_ORACLE", "RenderParams", "AptError", "default_params",
            "make_params", "MAT_SPEC", "MAT_DIFF", "MAT_REFR", "MAT_GLOSS"]

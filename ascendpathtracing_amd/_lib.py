@@ -17,10 +17,12 @@ APT_FLAG_GRID_SLOTS = 16
 APT_FLAG_NEE = 32
 APT_FLAG_GLOSS = 64
 APT_FLAG_MIS = 128                      # with APT_FLAG_GLOSS and a light mode (APT_FLAG_NEE or a light table): GLOSS hits sample the lights too
+APT_FLAG_PIXEL_LIST = 256               # apt_render_frame_film only: pixel_begin carries the device address of a uint32 pixel list ("List passes")
 APT_ERR_DEVICE = 4
 APT_DEV_QUEUE_GUARD, APT_DEV_GRID_TURNS, APT_DEV_LDS_BASE, APT_DEV_GRID_MISMATCH = 1, 2, 4, 8      # bits of the device status word (apt_context_check)
 APT_DEV_BAD_MATERIAL = 16
 APT_DEV_LIGHTS_MISMATCH = 32
+APT_DEV_LIST_RANGE = 64                 # a list pass: an entry of the pixel list is beyond the image
 APT_ENV_SAMPLE_SUN = 1                  # apt_environment.flags: DIFF hits sample the sun directly
 APT_TONEMAP_CLIP, APT_TONEMAP_REINHARD = 0, 1   # apt_film_resolve.tonemap
 APT_CURVE_LINEAR, APT_CURVE_SRGB = 0, 1         # apt_film_curve_host
@@ -145,6 +147,21 @@ DENOISE_PROTOTYPES = {
     "apt_film_denoise_last_error": (S, []),
 }
 
+# libadaptive_mi355x.so (include/render_mi355x_adaptive.h), the third library: its prototypes by the same rules, in its header's order.
+# tests/test_adaptive_cpu.py holds the table to that header and to the library's exports.
+ADAPTIVE_LIB_PATH = os.environ.get("APT_ADAPTIVE_LIB_PATH") or os.path.join(_HERE, "libadaptive_mi355x.so")
+ADAPTIVE_PROTOTYPES = {
+    "apt_film_select_default_host": (I, [P, U32]),
+    "apt_film_select_work_words": (U64, [U64]),
+    "apt_film_select_device": (I, [P, P, P, P, U64, P, P, P]),
+    "apt_film_select_host": (I, [P, P, P, U64, P, P, P]),
+    "apt_film_accumulate_list_device": (I, [P, P, P, U64, U64, P, P, P]),
+    "apt_film_accumulate_list_host": (I, [P, P, U64, U64, P, P, P]),
+    "apt_film_mean_device": (I, [P, P, P, U32, U64, P]),
+    "apt_film_mean_host": (I, [P, P, U32, U64, P]),
+    "apt_film_adaptive_last_error": (S, []),
+}
+
 
 class AptError(RuntimeError):
     pass
@@ -232,6 +249,24 @@ def film_denoise_record(passes, iterations=None, **fields):
     return rec
 
 
+class ApFilmSelect(ctypes.Structure):
+    """apt_film_select (include/render_mi355x_adaptive.h): the uniform passes in the film, the pass counts below which a pixel is always
+    and from which it is never selected, the relative error that is enough and the luminance floor under it."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("base_passes", ctypes.c_uint32), ("min_passes", ctypes.c_uint32),
+                ("max_passes", ctypes.c_uint32), ("threshold", ctypes.c_float), ("floor", ctypes.c_float)]
+
+
+def film_select_record(base_passes, **fields):
+    """apt_film_select_default_host's record for `base_passes`, with any of min_passes, max_passes, threshold, floor replaced."""
+    rec = ApFilmSelect()
+    adaptive_check(adaptive_lib().apt_film_select_default_host(ctypes.byref(rec), base_passes), "apt_film_select_default_host")
+    for k, v in fields.items():
+        if k not in ("min_passes", "max_passes", "threshold", "floor"):
+            raise AptError(f"film_select_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 _lib = None
 
 
@@ -284,6 +319,33 @@ def denoise_lib():
     return _denoise_lib
 
 
+_adaptive_lib = None
+
+
+def adaptive_lib():
+    """The loaded libadaptive_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
+    global _adaptive_lib
+    if _adaptive_lib is None:
+        if not os.path.exists(ADAPTIVE_LIB_PATH):
+            raise AptError(f"{ADAPTIVE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
+        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
+        try:
+            h = ctypes.CDLL(ADAPTIVE_LIB_PATH)
+        except OSError as e:
+            raise AptError(f"cannot load {ADAPTIVE_LIB_PATH}: {e}") from e
+        for name, (restype, argtypes) in ADAPTIVE_PROTOTYPES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _adaptive_lib = h
+    return _adaptive_lib
+
+
+def adaptive_check(rc, what):
+    if rc != APT_OK:
+        raise AptError(f"{what} failed ({rc}): {adaptive_lib().apt_film_adaptive_last_error().decode()}")
+
+
 def denoise_check(rc, what):
     if rc != APT_OK:
         raise AptError(f"{what} failed ({rc}): {denoise_lib().apt_film_denoise_last_error().decode()}")
@@ -298,7 +360,8 @@ def build_id():
     csrc = os.path.join(_HERE, "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")))
     files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map"), os.path.join(os.path.dirname(_HERE), "include", "render_mi355x.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h")]
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h"),
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -1,6 +1,6 @@
 // apt_materials.h -- what render_kernels.hip (argument checks, C-ABI) hands to the material kernels' launches (include/render_mi355x.h
 // "per-sphere materials").  The material kernels live in translation units of their own (materials.hip, environment.hip, film.hip,
-// features.hip, mis.hip), so
+// features.hip, mis.hip, film_list.hip), so
 // that the code object of render_kernels.hip -- every kernel the mirror renderer had before -- is built exactly as before.  Which of
 // them serves a call is decided behind mat_render_frame / mat_render_paths (materials.hip).
 // Plain data only: the kernels' own argument types are internal to each translation unit.
@@ -41,6 +41,8 @@ struct MatFrameCall {             // render_frame with materials: pixels [pixel_
     const apt_camera *camera;     // the context's camera (checked when it was set), or null: the reference's
     const apt_environment *env;   // the context's environment ("environment" in the header; checked when it was set), or null
     MatFilm film;                 // the film entries ("film" in the header): fb is the film and fb_u8 null
+    const uint32_t *list = nullptr;   // APT_FLAG_PIXEL_LIST ("List passes" in the header; film entries only, film == Store): the device list
+                                  // of pixel_count image pixels, checked by the entry; pixel_begin is 0 and fb the compact scratch
 };
 
 struct MatPathsCall {             // render_do_ex with materials: paths [b, b + c) of buffers whose planes hold n paths (already shifted)

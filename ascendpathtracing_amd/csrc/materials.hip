@@ -1,5 +1,6 @@
 // materials.hip -- the material kernels' translation unit (pt_materials.h): the kernels a launch without an environment or a film
-// runs, and the one place that routes a material launch to its code object (this one, environment.hip's, film.hip's or mis.hip's).
+// runs, and the one place that routes a material launch to its code object (this one, environment.hip's, film.hip's, mis.hip's or
+// film_list.hip's).
 // render_kernels.hip checks the arguments and calls in through apt_materials.h; keeping these kernels out of its code object leaves
 // every kernel that was there before byte for byte as it was (`make asm` writes this code object to materials.s).
 #include <hip/hip_runtime.h>
@@ -57,7 +58,8 @@ void selftest_direction(void *stream, const double *d3, uint64_t count, uint64_t
 // and the film's with an environment only.  A frame without a camera set gets apt_camera_default_host's record there, the reference's
 // camera bit for bit; a film without an environment the all-zero record, the same image bit for bit; and APT_FLAG_GLOSS travels as
 // data (tests/test_gpu_environment.py holds all three against the launches without an environment).  The same holds for the kernels of
-// APT_FLAG_MIS (mis.hip; call.t.mis), which hold both tails.
+// APT_FLAG_MIS (mis.hip; call.t.mis), which hold both tails.  A list call (film_list.hip; call.list, a film call) has kernels of its
+// own for both.
 int mat_render_frame(const MatFrameCall &call) {
     if (!call.env && call.film == MatFilm::None && !call.t.mis) { launch_mat_frame<0>(call); return APT_OK; }
     MatFrameCall c = call;
@@ -71,7 +73,8 @@ int mat_render_frame(const MatFrameCall &call) {
     black.struct_size = sizeof black;
     if (!c.env) c.env = &black;
     if (!c.fb) return set_error(APT_ERR_ARG, "film must be non-null%s");   // a film entry's last refusal: after the camera record's
-    if (c.t.mis) mis_launch_frame(c);
+    if (c.list) film_list_launch_frame(c);
+    else if (c.t.mis) mis_launch_frame(c);
     else if (c.film != MatFilm::None) film_launch_frame(c);
     else env_launch_frame(c);
     return APT_OK;

@@ -55,6 +55,36 @@ __device__ __forceinline__ FrameLane<GROUP> frame_lane(const FrameArgs &fa, uint
     return f;
 }
 
+// The same mapping for a list launch (APT_FLAG_PIXEL_LIST; pt_materials.h kMatList): lane pl's pixel is list[pl], the list's address
+// travelling in fa.fb_u8, which a film launch never reads, and fa.pixel_count its length.  The pixel alone decides the camera ray, the
+// path indices and so the roulette keys: a listed pixel gets the bits a launch over the whole image gives it.  Lanes past the end
+// read list[0], never past it.  An entry beyond the image makes its lanes invalid (`beyond`, for the status word): like the lanes past
+// the end they trace entry 0's pixel (pixel 0 when that entry is beyond the image itself) and write nothing.
+template <int GROUP>
+__device__ __forceinline__ FrameLane<GROUP> frame_lane_list(const FrameArgs &fa, bool &beyond, uint32_t tid = threadIdx.x) {
+    FrameLane<GROUP> f;
+    const uint32_t *const list = reinterpret_cast<const uint32_t *>(fa.fb_u8);
+    const uint64_t npix = (uint64_t)fa.width * fa.height;
+    const uint64_t L = (uint64_t)xcd_chunked_block<16>(blockIdx.x, gridDim.x) * kBlock + tid;
+    f.j = (GROUP == 8) ? (uint32_t)(L & 7) : 0u;
+    f.sub = (uint32_t)(L / GROUP) & 3u;
+    f.pl = L / (4 * GROUP);
+    const bool listed = f.pl < fa.pixel_count;
+    uint64_t q = list[listed ? f.pl : 0];
+    beyond = listed && q >= npix;
+    f.valid = listed && q < npix;
+    if (q >= npix) {
+        q = list[0];
+        if (q >= npix) q = 0;
+    }
+    f.q = q;
+    const uint32_t q32 = (uint32_t)q;               // < width * height <= 2^32 (the entry's check): a 32-bit division
+    f.pi = q32 / fa.height; f.pj = q32 - f.pi * fa.height;
+    f.sy = f.sub >> 1; f.sx = f.sub & 1;
+    f.pbase = (f.q * 4 + f.sub) * fa.samples;
+    return f;
+}
+
 // decode_color: data_visualization.py:36-57
 // The 8-bit pixels of a workgroup (kBlock / (4 * GROUP) consecutive pixels, 3 bytes each: a whole number of dwords that starts on a
 // dword when the image does) leave as DWORD stores assembled in LDS (u8pack, the kernel's) instead of three byte stores per pixel from

@@ -1,5 +1,5 @@
 // pt_mat_launch.h -- the launch path of the material kernels, shared by the translation units that hold them (materials.hip,
-// environment.hip, film.hip, mis.hip): a call's plain data (apt_materials.h) as the kernels' own argument types (pt_materials.h), and one frame
+// environment.hip, film.hip, mis.hip, film_list.hip): a call's plain data (apt_materials.h) as the kernels' own argument types (pt_materials.h), and one frame
 // and one buffer launcher.  Each translation unit instantiates a launcher with the scene-form bits it pins -- the instantiations its
 // code object holds -- and wraps it in a function of its own; materials.hip routes a call to one of them.  Host code only.
 #pragma once
@@ -13,6 +13,7 @@ void env_launch_paths(const MatPathsCall &call);
 void film_launch_frame(const MatFrameCall &call);   // film.hip: call.film is not None
 void mis_launch_frame(const MatFrameCall &call);    // mis.hip: call.t.mis, with or without a film
 void mis_launch_paths(const MatPathsCall &call);
+void film_list_launch_frame(const MatFrameCall &call);   // film_list.hip: call.list is set (a film call), with or without call.t.mis
 } // namespace apt
 
 namespace {
@@ -67,16 +68,17 @@ MatEnv mat_env(const apt_environment &e, bool gloss, bool film_add) {
     return m;
 }
 
-// PIN: the scene-form bits a translation unit pins (kMatGloss, kMatCamera, kMatEnv, kMatFilm, kMatMis).  A pinned bit is set in every kernel
+// PIN: the scene-form bits a translation unit pins (kMatGloss, kMatCamera, kMatEnv, kMatFilm, kMatMis, kMatList).  A pinned bit is set in every kernel
 // the launcher names, whatever the call says -- what the call says then travels as data (MatEnv::gloss, the camera record) -- and is
 // resolved here, at compile time: with_flag would instantiate the kernels without it as well.
 template <int PIN, int BIT, class F> void with_pinned(bool b, F &&f) {
     if constexpr ((PIN & BIT) != 0) f(std::true_type{});
     else with_flag(b, f);
 }
-// The film tail of a frame launch: a pinned bit, except for the launcher that pins kMatMis, which holds both tails and takes the call's.
+// The film tail of a frame launch: a pinned bit, except for the launcher that pins kMatMis WITHOUT kMatFilm (mis.hip's), which holds
+// both tails and takes the call's.
 template <int PIN, class F> void with_film(bool film, F &&f) {
-    if constexpr ((PIN & kMatMis) != 0) with_flag(film, f);
+    if constexpr ((PIN & kMatMis) != 0 && (PIN & kMatFilm) == 0) with_flag(film, f);
     else f(std::integral_constant<bool, (PIN & kMatFilm) != 0>{});
 }
 template <int PIN> MatEnvArg<PIN> mat_env_arg(const apt_environment *e, bool gloss, bool film_add) {
@@ -99,6 +101,8 @@ MatFrame mat_frame(const apt::MatFrameCall &c, const Camera &cam) {
     f.fa.cam = cam;
     f.fa.width = c.width; f.fa.height = c.height; f.fa.samples = c.samples; f.fa.seed = c.t.seed;
     f.fa.pixel_begin = c.pixel_begin; f.fa.pixel_count = c.pixel_count; f.fa.fb = c.fb; f.fa.fb_u8 = c.fb_u8;
+    // a list launch (kMatList kernels): the list's address in the word a film launch never reads
+    if (c.list) f.fa.fb_u8 = reinterpret_cast<uint8_t *>(const_cast<uint32_t *>(c.list));
     (void)frame_shape(c.samples, c.pixel_count, f.s);
     return f;
 }
@@ -114,7 +118,7 @@ template <int PIN> void launch_mat_frame(const apt::MatFrameCall &c) {
         with_pinned<PIN, kMatMis>(c.t.nee, [&](auto nee) { with_flag(c.t.lights != nullptr, [&](auto lt) {
             with_pinned<PIN, kMatCamera>(c.camera != nullptr, [&](auto cam) { with_pinned<PIN, kMatGloss>(c.t.gloss, [&](auto gl) {
                 with_film<PIN>(c.film != apt::MatFilm::None, [&](auto film) {
-                    hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam) | (PIN & (kMatEnv | kMatMis)) | (film ? kMatFilm : 0), g8 ? 8 : 1>),
+                    hipLaunchKernelGGL((render_frame_mat_kernel<mat_scene_form(ns8, gr, nee, lt, gl, cam) | (PIN & (kMatEnv | kMatMis | kMatList)) | (film ? kMatFilm : 0), g8 ? 8 : 1>),
                                        dim3((unsigned)f.s.blocks), dim3(kBlock), f.s.lds, st, c.spheres, c.materials, f.fa, ka, f.s.lp, cx.t, ev);
                 });
             }); });

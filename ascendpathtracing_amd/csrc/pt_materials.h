@@ -33,8 +33,10 @@ constexpr int kMatFilm = 128;   // the film entries (include/render_mi355x.h "fi
 static_assert((kMatFilm & (kMatEnv | kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatFilm must be a bit of its own");
 constexpr int kMatMis = 256;    // APT_FLAG_MIS in the same template argument (mis.hip: with kMatEnv, kMatGloss and a light mode): GLOSS hits sample the lights too
 static_assert((kMatMis & (kMatFilm | kMatEnv | kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatMis must be a bit of its own");
+constexpr int kMatList = 512;   // APT_FLAG_PIXEL_LIST in the same template argument (film_list.hip: with kMatFilm): the lane's pixel comes from a list, FrameArgs::fb_u8 its address
+static_assert((kMatList & (kMatMis | kMatFilm | kMatEnv | kMatGloss | kMatCamera | kMatLights | kMatNee | kScene8 | kSceneTiles | kSceneGrid)) == 0, "kMatList must be a bit of its own");
 constexpr uint32_t kMatEnvFilmAdd = 2u;   // MatEnv::gloss of a kMatFilm launch, next to bit 0: pass > 0, the tail adds to the film instead of storing
-constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv | kMatFilm | kMatMis); }
+constexpr int mat_scene_of(int scn) { return scn & ~(kMatNee | kMatLights | kMatCamera | kMatGloss | kMatEnv | kMatFilm | kMatMis | kMatList); }
 // The contract's limit (include/render_mi355x.h "camera"): a frame with a camera takes a plan of at most this many leaves.  Nothing in
 // the kernels needs it any more; lifting it is a feature with its own tests above 4199 samples, not part of any clean-up.
 constexpr uint32_t kCamMaxLeaves = 44;
@@ -904,12 +906,28 @@ __global__ __launch_bounds__(kBlock) void gen_rays_camera_kernel(CameraEx cam, u
     }
 }
 
+// The lane mapping of the fused frame kernel: pt_frame.h's, by range or (LIST) by list; a list's entries beyond the image are reported
+// once per wave, before the bounce: nothing of it lives across the trace.
+template <int GROUP, bool LIST>
+__device__ __forceinline__ FrameLane<GROUP> mat_frame_lane(const FrameArgs &fa, const TraceArgs &ta) {
+    if constexpr (LIST) {
+        bool beyond;
+        const FrameLane<GROUP> f = frame_lane_list<GROUP>(fa, beyond);
+        if (__any(beyond)) report_status(ta, APT_DEV_LIST_RANGE);
+        return f;
+    } else {
+        return frame_lane<GROUP>(fa);
+    }
+}
+
 // ---- kernel: fused frame ------------------------------------------------------------------------------------------------------
 // render_frame_kernel (pt_kernels.h) without its retirement queue and two-path form: pt_frame.h's lanes per sub-pixel (GROUP),
 // camera and decode, the same pairwise leaves and tail; the sample is a material path and its colour is L.
 // SCN: the scene form and kMatNee / kMatLights / kMatGloss, as for the buffer kernel, and kMatCamera: only then is `ct` read.
 // kMatEnv (both kernels): only then does `ev` hold anything -- the environment.
 // kMatFilm (with kMatEnv): fa.fb is a film and the tail is frame_film, not frame_decode; fa.fb_u8 is not read.
+// kMatList (with kMatFilm): fa.fb_u8 is the address of a uint32 list of fa.pixel_count image pixels and lane pl traces list[pl]
+// (pt_frame.h frame_lane_list); the film, compact, is still indexed by pl.  An entry beyond the image: APT_DEV_LIST_RANGE.
 template <int SCN, int GROUP>
 __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *__restrict__ sph, const uint32_t *__restrict__ mat,
                                                                   FrameArgs fa, MatKernelArgs ka, LeafProg lp, CameraTail ct,
@@ -923,6 +941,8 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     constexpr bool MI = (SCN & kMatMis) != 0;
     static_assert(!MI || (EV && GL && LM != kLmNone), "the kMatMis kernels are gloss, environment kernels with a light mode");
     static_assert(!FILM || EV, "the film kernels are environment kernels: store-or-add travels in MatEnv::gloss");
+    constexpr bool LIST = (SCN & kMatList) != 0;
+    static_assert(!LIST || FILM, "the list kernels are film kernels: a film launch never reads fa.fb_u8, which carries the list");
     bool film_add = false;
     if constexpr (FILM) {   // (launch-uniform) the word's bit 0 is what every other reader of ev.gloss takes it for
         film_add = (ev.gloss & kMatEnvFilmAdd) != 0;
@@ -946,7 +966,7 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
     const MatLight lt = load_mat_light<LM>(sph, ta);
 
     const uint32_t lane = threadIdx.x & 63;
-    const FrameLane<GROUP> fl = frame_lane<GROUP>(fa);
+    const FrameLane<GROUP> fl = mat_frame_lane<GROUP, LIST>(fa, ta);
     const uint32_t j = fl.j, sub = fl.sub;
     const uint64_t pl = fl.pl;
     const bool valid = fl.valid;
@@ -1032,7 +1052,13 @@ __global__ __launch_bounds__(kBlock) void render_frame_mat_kernel(const float *_
         for (int ch = 0; ch < 3; ++ch) res[ch] = stack_lds[ch * kStackSlots + (threadIdx.x >> 3)];
     }
 
-    if constexpr (FILM) {
+    if constexpr (LIST) {   // the lane's slot and whether it writes, from the list again: one load here instead of values kept across the trace
+        bool beyond;
+        const FrameLane<GROUP> tl = frame_lane_list<GROUP>(fa, beyond);
+        frame_film<GROUP>(fa, tl.pl, tl.valid, res, film_add);
+        count_traced(ta, tl.valid ? traced : 0);
+        return;
+    } else if constexpr (FILM) {
         frame_film<GROUP>(fa, pl, valid, res, film_add);
     } else {
         __shared__ uint32_t u8pack[frame_u8_words(GROUP)];

@@ -91,6 +91,7 @@ struct MatArgs {
     bool with_lights = false;
     const void *lights = nullptr;
     apt::MatFilm film = apt::MatFilm::None;   // the film entries ("film" in the header): fb is a film, fb_u8 null
+    bool list = false;                        // APT_FLAG_PIXEL_LIST on a film entry: pixel_begin is a device list's address, pixel_count its length
 };
 // check_materials, then what the *_lights entries refuse on top of it.
 int check_mat_args(const apt_render_params *p, const MatArgs &m) {
@@ -183,6 +184,14 @@ int pixel_range(const apt_render_params *p, uint64_t pixel_begin, uint64_t pixel
     return (pixel_begin > npix || pixel_count > npix - pixel_begin) ? fail(APT_ERR_ARG, "pixel range beyond the image%s") : APT_OK;
 }
 
+// The pixel list of a list pass ("List passes" in the header) in the range's place: its address and its length.
+int pixel_list(const apt_render_params *p, uint64_t list_address, uint64_t list_count) {
+    const uint64_t npix = (uint64_t)p->width * p->height;
+    if (list_address == 0 || (list_address & 3u)) return fail(APT_ERR_ARG, "pixel list: pixel_begin must carry a non-null, 4-byte aligned device address%s");
+    if (list_count > npix) return fail(APT_ERR_ARG, "pixel list: more entries than the image has pixels%s");
+    return npix > (1ull << 32) ? fail(APT_ERR_ARG, "pixel list: an image of more than 2^32 pixels has no 32-bit pixel indices%s") : APT_OK;
+}
+
 FrameArgs make_frame_args(const apt_render_params *p, uint64_t pixel_begin, uint64_t pixel_count, float *fb, uint8_t *fb_u8) {
     FrameArgs fa;
     camera_init(fa.cam, p->width, p->height);
@@ -208,9 +217,9 @@ int paths_launch_range(const apt_render_params *p, bool pointers, PathRange &r, 
 
 // The same for a frame launch: pointers (`pointers`: the entry's are non-null), the pixel range, the plan, the size of one launch.
 // -> APT_OK with an all-zero fs (fs.blocks == 0) for an empty range: the call is a no-op, the caller returns APT_OK without launching
-int frame_launch_shape(const apt_render_params *p, bool pointers, uint64_t pixel_begin, uint64_t pixel_count, FrameShape &fs) {
+int frame_launch_shape(const apt_render_params *p, bool pointers, uint64_t pixel_begin, uint64_t pixel_count, FrameShape &fs, bool list = false) {
     if (!pointers) return fail(APT_ERR_ARG, "spheres/fb must be non-null%s");
-    if (int rc = pixel_range(p, pixel_begin, pixel_count)) return rc;
+    if (int rc = list ? pixel_list(p, pixel_begin, pixel_count) : pixel_range(p, pixel_begin, pixel_count)) return rc;
     fs = FrameShape{};
     if (pixel_count == 0) return APT_OK;
     if (!frame_shape(p->samples, pixel_count, fs)) return no_leaf_plan();
@@ -371,12 +380,14 @@ int do_mat_frame(apt_context *ctx, const apt_render_params *p, void *stream, con
     const Launch ls = launch_state(*ctx, stream);
     const bool film = ma.film != apt::MatFilm::None;   // (its null film is refused last: by mat_render_frame)
     FrameShape fs;
-    if ((rc = frame_launch_shape(p, spheres && (fb || film), pixel_begin, pixel_count, fs)) || fs.blocks == 0) return rc;
+    if ((rc = frame_launch_shape(p, spheres && (fb || film), pixel_begin, pixel_count, fs, ma.list)) || fs.blocks == 0) return rc;
     if ((rc = check_lights_status(ma, ls.status))) return rc;
     if ((ls.cv.has_camera || ls.cv.has_env || film) && !apt::mat_camera_fits(p->samples)) return fail(APT_ERR_ARG, "camera / environment: a frame with a camera or an environment set takes a pairwise-sum plan of at most 44 leaves (every samples <= 4199 has one)%s");
-    if ((rc = apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples, pixel_begin,
-                                                      pixel_count, fb, fb_u8, stream, ls.cv.has_camera ? &ls.cv.camera : nullptr,
-                                                      ls.cv.has_env ? &ls.cv.env : nullptr, ma.film})))
+    // (a list call: the range starts at 0 and the list's address travels on its own)
+    if ((rc = apt::mat_render_frame(apt::MatFrameCall{make_mat_trace(p, ls, ma), spheres, ma.materials, p->width, p->height, p->samples,
+                                                      ma.list ? 0 : pixel_begin, pixel_count, fb, fb_u8, stream,
+                                                      ls.cv.has_camera ? &ls.cv.camera : nullptr, ls.cv.has_env ? &ls.cv.env : nullptr, ma.film,
+                                                      ma.list ? reinterpret_cast<const uint32_t *>((uintptr_t)pixel_begin) : nullptr})))
         return rc;
     return launched();
 }
@@ -502,7 +513,8 @@ int apt_context_check(apt_context *ctx, void *stream) {
     if (bits & APT_DEV_GRID_MISMATCH) what += " grid-mismatch";
     if (bits & APT_DEV_BAD_MATERIAL) what += " bad-material";
     if (bits & APT_DEV_LIGHTS_MISMATCH) what += " lights-mismatch";
-    if (bits & ~(uint32_t)(APT_DEV_QUEUE_GUARD | APT_DEV_GRID_TURNS | APT_DEV_LDS_BASE | APT_DEV_GRID_MISMATCH | APT_DEV_BAD_MATERIAL | APT_DEV_LIGHTS_MISMATCH)) what += " unknown-bits";
+    if (bits & APT_DEV_LIST_RANGE) what += " list-range";
+    if (bits & ~(uint32_t)(APT_DEV_QUEUE_GUARD | APT_DEV_GRID_TURNS | APT_DEV_LDS_BASE | APT_DEV_GRID_MISMATCH | APT_DEV_BAD_MATERIAL | APT_DEV_LIGHTS_MISMATCH | APT_DEV_LIST_RANGE)) what += " unknown-bits";
     return fail(APT_ERR_DEVICE, "a kernel reported a failure through the device status word:%s (the frame it wrote is incomplete)", what.c_str());
 }
 
@@ -591,7 +603,9 @@ int apt_context_render_paths_lights(apt_context *ctx, const apt_render_params *p
 int apt_context_render_frame_film(apt_context *ctx, const apt_render_params *p, void *stream, const float *spheres,
                                   const uint32_t *materials, const void *lights, uint64_t pixel_begin, uint64_t pixel_count, float *film,
                                   uint32_t pass) {
-    const MatArgs ma{materials, lights != nullptr, lights, pass ? apt::MatFilm::Add : apt::MatFilm::Store};
+    // APT_FLAG_PIXEL_LIST ("List passes" in the header): the launch stores whatever `pass` is, which then only selects the seed
+    const bool list = p && p->struct_size == sizeof(apt_render_params) && (p->flags & APT_FLAG_PIXEL_LIST) != 0;
+    const MatArgs ma{materials, lights != nullptr, lights, pass && !list ? apt::MatFilm::Add : apt::MatFilm::Store, list};
     apt_render_params q;
     if (p && p->struct_size == sizeof q) {   // (anything else is check_params' to refuse)
         q = *p;

@@ -45,6 +45,21 @@ def _dev_materials(t, num_spheres):
     return t.data_ptr()
 
 
+def _dev_u32(t, name, numel=None):
+    """uint32 words travel in int32 tensors, as the material words do."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise _lib.AptError(f"{name} must be a contiguous int32 tensor on the GPU (it holds uint32 words)")
+    if numel is not None and t.numel() != numel:
+        raise _lib.AptError(f"{name} has {t.numel()} elements, expected {numel}")
+    return t.data_ptr()
+
+
+def _dev_pixel_list(t):
+    if not (isinstance(t, torch.Tensor) and t.numel() >= 1):
+        raise _lib.AptError("pixel_list must hold at least one entry")
+    return _dev_u32(t, "pixel_list")
+
+
 def _dev_lights(t):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= 16):
         raise _lib.AptError("lights must be a contiguous int32 tensor on the GPU holding a light table (gen_data.build_lights)")
@@ -177,8 +192,19 @@ class Context:
         return fb, fb_u8
 
     def render_frame_film(self, params, spheres, materials, film=None, pass_index=0, lights=None, pixel_begin=0, pixel_count=None,
-                          stream=None):
+                          stream=None, pixel_list=None):
         require_gpu()
+        if pixel_list is not None:       # a list pass (APT_FLAG_PIXEL_LIST): the list's address travels in pixel_begin
+            if pixel_begin != 0:
+                raise _lib.AptError("render_frame_film: pixel_list takes no pixel_begin")
+            if pixel_count is None:
+                pixel_count = pixel_list.numel()
+            if pixel_count > pixel_list.numel():
+                raise _lib.AptError(f"pixel_list has {pixel_list.numel()} entries, fewer than pixel_count = {pixel_count}")
+            pixel_begin = _dev_pixel_list(pixel_list)
+            params = params.copy(flags=params.flags | _lib.APT_FLAG_PIXEL_LIST)
+        elif params.flags & _lib.APT_FLAG_PIXEL_LIST:
+            raise _lib.AptError("render_frame_film: APT_FLAG_PIXEL_LIST is set by pixel_list=, which holds the list")
         if pixel_count is None:
             pixel_count = params.width * params.height - pixel_begin
         if film is None:
@@ -348,11 +374,64 @@ def render_frame(params: RenderParams, spheres, pixel_begin=0, pixel_count=None,
 
 
 def render_frame_film(params: RenderParams, spheres, materials, film=None, pass_index=0, lights=None, pixel_begin=0, pixel_count=None,
-                      stream=None):
+                      stream=None, pixel_list=None):
     """apt_render_frame_film: one pass of a film.  The pixel range rendered as render_frame(materials=, lights=) would with the seed
     apt_film_pass_seed(params.seed, pass_index), unclipped, stored in `film` (float32 [3][count]; None: a new tensor) for pass 0 and
-    added to it for a later pass.  Returns the film; not synchronised.  The flags travel in params.flags, APT_FLAG_MIS among them."""
-    return _default.render_frame_film(params, spheres, materials, film, pass_index, lights, pixel_begin, pixel_count, stream)
+    added to it for a later pass.  Returns the film; not synchronised.  The flags travel in params.flags, APT_FLAG_MIS among them.
+    pixel_list (an int32 device tensor of image pixel indices; pixel_count: how many of them, None: all): a list pass
+    (APT_FLAG_PIXEL_LIST) -- `film` is then a compact scratch [3][count] whose word c * count + i is STORED with what pass
+    `pass_index` over the whole image gives pixel pixel_list[i]; an entry beyond the image leaves its slot untouched and
+    check_device_status() raises list-range."""
+    return _default.render_frame_film(params, spheres, materials, film, pass_index, lights, pixel_begin, pixel_count, stream, pixel_list)
+
+
+def film_select(record, moments, extra, work=None, pixel_list=None, count=None, stream=None):
+    """apt_film_select_device (libadaptive_mi355x.so, include/render_mi355x_adaptive.h): the pixels of a film -- moments float32 [2][N],
+    extra int32 [N] -- that `record` (_lib.film_select_record) sends another pass to, in ascending order -> (pixel_list int32 [N], of
+    which the first `count` are written, count int32 [1]), both on the device; not synchronised.  work: int32, at least
+    apt_film_select_work_words(N) elements.  None: new tensors."""
+    require_gpu()
+    n = moments.numel() // 2
+    L = _lib.adaptive_lib()
+    words = L.apt_film_select_work_words(n)
+    if work is None:
+        work = torch.empty(words, dtype=torch.int32, device=moments.device)
+    if work.numel() < words:
+        raise _lib.AptError(f"work has {work.numel()} elements, fewer than apt_film_select_work_words = {words}")
+    if pixel_list is None:
+        pixel_list = torch.empty(n, dtype=torch.int32, device=moments.device)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int32, device=moments.device)
+    _lib.adaptive_check(L.apt_film_select_device(ctypes.byref(record), _stream_handle(stream), _dev_f32(moments, "moments", 2 * n),
+                                                 _dev_u32(extra, "extra", n), n, _dev_u32(work, "work"), _dev_u32(pixel_list, "pixel_list", n),
+                                                 _dev_u32(count, "count", 1)), "apt_film_select_device")
+    return pixel_list, count
+
+
+def film_accumulate_list(pass_planes, pixel_list, list_count, film, moments, extra, stream=None):
+    """apt_film_accumulate_list_device: the compact planes of ONE list pass (the first 3 * list_count floats of `pass_planes`) added
+    to the pixels the first list_count entries of pixel_list name: film [3][N], moments [2][N], extra [N] += 1.  Not synchronised."""
+    require_gpu()
+    n = film.numel() // 3
+    if pass_planes.numel() < 3 * list_count or pixel_list.numel() < list_count:
+        raise _lib.AptError("film_accumulate_list: pass_planes or pixel_list is shorter than list_count asks")
+    _lib.adaptive_check(_lib.adaptive_lib().apt_film_accumulate_list_device(
+        _stream_handle(stream), _dev_f32(pass_planes, "pass_planes"), _dev_u32(pixel_list, "pixel_list"), list_count, n,
+        _dev_f32(film, "film", 3 * n), _dev_f32(moments, "moments", 2 * n), _dev_u32(extra, "extra", n)), "apt_film_accumulate_list_device")
+    return film, moments, extra
+
+
+def film_mean(film, base_passes, extra=None, out=None, stream=None):
+    """apt_film_mean_device: film [3][N] over each pixel's own number of passes, base_passes + extra[p] (extra None: base_passes
+    everywhere) -> out float32 [3][N] (None: a new tensor), which Film.resolve takes as a source.  Not synchronised."""
+    require_gpu()
+    n = film.numel() // 3
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.float32, device=film.device)
+    _lib.adaptive_check(_lib.adaptive_lib().apt_film_mean_device(
+        _stream_handle(stream), _dev_f32(film, "film", 3 * n), None if extra is None else _dev_u32(extra, "extra", n), base_passes, n,
+        _dev_f32(out, "out", 3 * n)), "apt_film_mean_device")
+    return out
 
 
 def render_frame_features(params: RenderParams, spheres, features=None, pixel_begin=0, pixel_count=None, stream=None):
@@ -396,9 +475,11 @@ class Film:
     (include/render_mi355x.h "film"): add_pass renders one more independent frame into it, resolve turns the mean into a displayable
     image.  `buffer` is the [3][count] tensor of sums, `passes` how many frames it holds.  moments=True (a whole image only) also
     keeps `moments`, the [2][count] sums of each pass's luminance and its square (include/render_mi355x_denoise.h), which denoise() needs: a
-    pass is then rendered into a scratch film and added from there, to the same bits."""
+    pass is then rendered into a scratch film and added from there, to the same bits.  adaptive=True (needs moments=True) also keeps
+    `extra`, int32 [count]: the passes each pixel received beyond `passes` through add_adaptive_pass (include/render_mi355x_adaptive.h),
+    `rounds` of them so far; without it the film is what it was."""
 
-    def __init__(self, width, height, pixel_begin=0, pixel_count=None, device="cuda", moments=False):
+    def __init__(self, width, height, pixel_begin=0, pixel_count=None, device="cuda", moments=False, adaptive=False):
         self.width, self.height, self.pixel_begin = width, height, pixel_begin
         self.pixel_count = width * height - pixel_begin if pixel_count is None else pixel_count
         if moments and (pixel_begin != 0 or self.pixel_count != width * height):
@@ -408,15 +489,30 @@ class Film:
         self._scratch = torch.empty((3, self.pixel_count), dtype=torch.float32, device=device) if moments else None
         self.passes = 0
         self._tables = {}
+        if adaptive and not moments:
+            raise _lib.AptError("Film: adaptive=True needs moments=True: the selection reads them")
+        self.adaptive, self.rounds = bool(adaptive), 0
+        self.extra = self.pixel_list = self._count = self._work = None
+        if adaptive:
+            n = self.pixel_count
+            self.extra = torch.zeros(n, dtype=torch.int32, device=device)
+            self.pixel_list = torch.empty(n, dtype=torch.int32, device=device)
+            self._count = torch.zeros(1, dtype=torch.int32, device=device)
+            self._work = torch.empty(_lib.adaptive_lib().apt_film_select_work_words(n), dtype=torch.int32, device=device)
 
     def reset(self):
-        """Forget the passes: the next one stores, the moments too."""
+        """Forget the passes: the next one stores, the moments too; an adaptive film forgets its rounds as well."""
         self.passes = 0
+        self.rounds = 0
+        if self.extra is not None:
+            self.extra.zero_()
 
     def add_pass(self, params, spheres, materials, lights=None, stream=None, context=None):
         """One more frame of `params` (its width and height must be the film's), with pass index self.passes."""
         if (params.width, params.height) != (self.width, self.height):
             raise _lib.AptError("Film.add_pass: params.width / height are not the film's")
+        if self.rounds:
+            raise _lib.AptError("Film.add_pass: the film has had adaptive rounds, and pass index `passes` has been used by one: reset() first")
         ctx = _default if context is None else context
         if self.moments is None:
             ctx.render_frame_film(params, spheres, materials, self.buffer, self.passes, lights, self.pixel_begin, self.pixel_count, stream)
@@ -430,6 +526,31 @@ class Film:
         self.passes += 1
         return self
 
+    def add_adaptive_pass(self, params, spheres, materials, lights=None, stream=None, context=None, **select_fields):
+        """One adaptive round -> how many pixels it rendered.  Select (apt_film_select_default_host's record for `passes`, with any of
+        min_passes, max_passes, threshold, floor replaced) the pixels whose mean luminance is still uncertain, read their number back
+        (one 4-byte copy: this synchronises `stream`), render them as a list pass with pass index passes + rounds -- to the bits a whole
+        pass of that index would give them -- and add it to the film, the moments and `extra`.  `rounds` advances even when nothing
+        was selected.  The film needs adaptive=True and at least 2 passes; `pixel_list` then holds the round's list."""
+        if not self.adaptive:
+            raise _lib.AptError("Film.add_adaptive_pass: the film was not made with adaptive=True")
+        if self.passes < 2:
+            raise _lib.AptError("Film.add_adaptive_pass: the variance of the mean needs at least 2 uniform passes")
+        if (params.width, params.height) != (self.width, self.height):
+            raise _lib.AptError("Film.add_adaptive_pass: params.width / height are not the film's")
+        ctx = _default if context is None else context
+        rec = _lib.film_select_record(self.passes, **select_fields)
+        film_select(rec, self.moments, self.extra, self._work, self.pixel_list, self._count, stream)
+        with torch.cuda.stream(_torch_stream(stream)):
+            count = int(self._count.cpu()[0])
+        if count:
+            scratch = self._scratch.view(-1)[:3 * count]
+            ctx.render_frame_film(params, spheres, materials, scratch, self.passes + self.rounds, lights, 0, count, stream,
+                                  pixel_list=self.pixel_list)
+            film_accumulate_list(scratch, self.pixel_list, count, self.buffer, self.moments, self.extra, stream)
+        self.rounds += 1
+        return count
+
     def denoise(self, params, spheres, iterations=None, features=None, stream=None, context=None, **sigmas):
         """The film's mean through apt_film_denoise_device -> float32 [3][count], the denoised mean radiance; resolve(source=...)
         makes an image of it.  The film needs moments=True and at least 2 passes.  iterations and sigma_n, sigma_z, sigma_c, sigma_a,
@@ -439,6 +560,8 @@ class Film:
             raise _lib.AptError("Film.denoise: the film keeps no moments (Film(..., moments=True))")
         if self.passes < 2:
             raise _lib.AptError("Film.denoise: the variance of the mean needs at least 2 passes")
+        if self.rounds and bool(self.extra.any()):
+            raise _lib.AptError("Film.denoise: pixels of the film hold extra adaptive passes, and the filter divides by ONE pass count")
         if features is None:
             features = self.features(params, spheres, stream, context)
         rec = _lib.film_denoise_record(self.passes, iterations, **sigmas)
@@ -457,6 +580,8 @@ class Film:
         """The film divided by its passes (fp32, as the resolve's first step) -> float32 [3][count]."""
         if self.passes == 0:
             raise _lib.AptError("Film.mean: the film holds no pass")
+        if self.rounds:
+            return film_mean(self.buffer, self.passes, self.extra)
         return self.buffer / torch.tensor(self.passes, dtype=torch.float32, device=self.buffer.device)
 
     def resolve(self, exposure=1.0, tonemap="clip", white=None, curve="srgb", want_float=False, stream=None, source=None):
@@ -471,6 +596,8 @@ class Film:
             raise _lib.AptError(f"Film.resolve: unknown tone operator {tonemap!r}")
         if curve not in self._tables:
             self._tables[curve] = torch.from_numpy(gen_data.film_curve(curve)).to(self.buffer.device)
+        if source is None and self.rounds:   # every pixel over its own pass count first: then a source of mean radiance like any other
+            source = film_mean(self.buffer, self.passes, self.extra, stream=stream)
         rec = _lib.film_resolve_record(self.passes if source is None else 1, exposure, tm,
                                        0.0 if white is None else 1.0 / (float(white) * float(white)))
         film = _dev_f32(self.buffer, "film") if source is None else _dev_f32(source, "source", 3 * self.pixel_count)

@@ -99,6 +99,8 @@ enum {
                            /* Read only next to APT_FLAG_GLOSS, by the *_materials entries with APT_FLAG_NEE and by the *_lights entries  */
                            /* (their film entries and buffer mode included); every other launch ignores the bit and is the one it was.    */
                            /* Unbiased; changes the image by noise only, and at depth 1 by nothing.                                      */
+    APT_FLAG_PIXEL_LIST = 256u, /* EXTENSION, apt_render_frame_film / apt_context_render_frame_film only (every other entry ignores the bit): */
+                           /* the launch renders the pixels of a DEVICE list instead of a range, "List passes" in "film" below.         */
     APT_FLAG_RR = 2u      /* EXTENSION (not in the reference; BASELINE config 5): Russian */
                            /* roulette.  After shading bounce d (0-based) with d+1 >=       */
                            /* rr_start, a path that is alive with q = max(r,g,b) > 0        */
@@ -198,7 +200,8 @@ enum {
     APT_DEV_LDS_BASE = 4u,     /* sample-queue kernels: the dynamic LDS region does not start at LDS address 0 (a build problem)    */
     APT_DEV_GRID_MISMATCH = 8u, /* APT_FLAG_GRID_SLOTS: the grid at `accel` is not this scene's or has no pair-slot tables          */
     APT_DEV_BAD_MATERIAL = 16u, /* *_materials entries: a path hit a sphere whose material code is not an APT_MAT_* value            */
-    APT_DEV_LIGHTS_MISMATCH = 32u /* *_lights entries: the light table is not one for this scene (magic, num_spheres, 1 <= n <= Ns)  */
+    APT_DEV_LIGHTS_MISMATCH = 32u, /* *_lights entries: the light table is not one for this scene (magic, num_spheres, 1 <= n <= Ns)  */
+    APT_DEV_LIST_RANGE = 64u   /* APT_FLAG_PIXEL_LIST: an entry of the pixel list is >= width * height; its slot was left untouched   */
 };
 int  apt_context_check(apt_context *ctx, void *stream);
 int  apt_check(void *stream);
@@ -663,6 +666,23 @@ int apt_set_environment(const apt_environment *env_or_null);
  *     salt keeps a pass seed from being the roulette key of path `pass` (splitmix64(seed ^ splitmix64(path))).  The seed is computed
  *     on the host: the kernel receives a seed as it always has.
  *   - Passes are the caller's loop; the entry keeps no state.  A caller may run bands, or resume a film another process wrote.
+ *
+ * List passes.  APT_FLAG_PIXEL_LIST in p->flags, read by the two film entries above and by nothing else:
+ *   - pixel_begin carries the DEVICE address of a uint32_t list of image pixel indices (x-major, as everywhere), the way `accel`
+ *     carries an address; pixel_count is the list's length.  film is a compact scratch [3][pixel_count] float32: word
+ *     c * pixel_count + i receives entry i's pixel.
+ *   - A lane derives its camera ray, its sub-pixel, its path indices and its roulette keys from the image pixel alone, so entry i
+ *     receives EXACTLY the bits a launch over the whole image with the same `pass` computes for pixel list[i].
+ *   - The launch always STORES that (float)v, whatever `pass` is: `pass` only selects the seed, apt_film_pass_seed(p->seed, pass).  A
+ *     list launch has nothing of its own to add to; summing is render_mi355x_adaptive.h's apt_film_accumulate_list_*.
+ *   - Everything else is the film entry's: flags, the context's camera and environment, the grid behind `accel`, roulette,
+ *     APT_FLAG_MIS, the trace counter, the 44-leaf plan limit, every refusal and their order.  In the place of the pixel-range check:
+ *     APT_ERR_ARG for a list address that is 0 or not 4-byte aligned, for pixel_count > width * height, and for
+ *     width * height > 2^32; pixel_count == 0 is APT_OK with nothing launched.
+ *   - An entry >= width * height makes its lanes invalid, exactly as lanes past the range are: they write nothing, so the entry's three
+ *     scratch words are left untouched, and the kernel ORs APT_DEV_LIST_RANGE into the status word (without a status word such
+ *     entries are skipped silently).  Lanes past the end of the list read list[0], never past the end.
+ *   - A list may repeat an entry here: each slot has its own owner lane.
  *
  * Resolve.  apt_film_resolve_device (DEVICE pointers, asynchronous on `stream`) and apt_film_resolve_host (HOST pointers, the CPU twin:
  * the same operations, the same bits).  Every step is one IEEE fp32 operation (no FMA).  Per value s of the film:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of two builds' `make asm` output:
    python profiles/isa_compare.py OLD_CSRC [NEW_CSRC]     (NEW_CSRC: this tree's ascendpathtracing_amd/csrc)
-Runs `make -B asm` in both directories.  For every kernel of the seven code objects -- render_kernels.s, materials.s, environment.s, film.s,
-features.s, selftest_seeded.s and denoise.s -- it compares the instruction lines
+Runs `make -B asm` in both directories.  For every kernel of the eight code objects -- render_kernels.s, materials.s, environment.s, film.s,
+features.s, mis.s, selftest_seeded.s and denoise.s -- it compares the instruction lines
 between the symbol and its .Lfunc_end (labels, directives and comments dropped; block labels renumbered per function, since a
 function's index in the file moves them; differences counted by a sequence diff) and the kernel-resource-usage remarks (registers,
 spills, scratch, LDS, occupancy).  Kernels of render_kernels.s are matched by symbol; those of the other files by demangled name
@@ -68,7 +68,7 @@ def main():
     with ThreadPoolExecutor(2) as ex:
         ro, rn = ex.map(build, (old, new))
     differ = 0
-    for s in ("render_kernels.s", "materials.s", "environment.s", "film.s", "features.s", "selftest_seeded.s", "denoise.s"):
+    for s in ("render_kernels.s", "materials.s", "environment.s", "film.s", "features.s", "mis.s", "selftest_seeded.s", "denoise.s"):
         if s not in ("render_kernels.s", "materials.s") and not os.path.exists(os.path.join(old, s)):   # an old build from before there was one
             continue
         ko, kn = kernels(os.path.join(old, s)), kernels(os.path.join(new, s))
