@@ -36,17 +36,15 @@ def pass_seed(seed, k):
 
 
 def render_pass(params, spheres, materials, env=None, table=None, pass_index=0, rays=None, pixel_begin=0, pixel_count=None):
-    """One pass of `params` (an oracle.Params; its seed is the film's base seed) -> float32 planes [3][count].  rays: a callable
-    seed -> camera rays (camera_ref.rays with the pass's seed), or None: the reference camera's."""
+    """One pass of `params` (an oracle.Params; its seed is the film's base seed, its flags are read by materials_ref.trace_params) ->
+    (float32 planes [3][count], segments).  rays: a callable seed -> camera rays (camera_ref.rays with the pass's seed), or None: the
+    reference camera's."""
     from oracle import oracle
     q = oracle.Params.from_buffer_copy(bytes(params))
     q.seed = pass_seed(params.seed, pass_index)
     w, h, s = q.width, q.height, q.samples
     r = oracle.gen_rays_counter(q) if rays is None else rays(q.seed)
-    n = r.shape[1]
-    rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
-    L, bad, seg = mr.trace(r, spheres, materials, q.num_spheres, q.depth, q.eps, q.seed, np.arange(n, dtype=U), env, rr,
-                           light=q.light_index, nee=bool(q.flags & mr.FLAG_NEE), table=table, gloss=bool(q.flags & mr.FLAG_GLOSS))
+    L, bad, seg = mr.trace_params(q, r, spheres, materials, env, table)
     assert not bad.any()
     pre = oracle.decode_color(L, w, h, s)[0]                   # float64 [W*H][3]: the mean before the clip
     assert pre.dtype == np.float64

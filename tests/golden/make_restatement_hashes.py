@@ -4,8 +4,9 @@ bad-material mask that THE RESTATEMENT (tests/materials_ref.py) gives, and its s
 
     python tests/golden/make_restatement_hashes.py [OUT.json]
 
-The committed file was first written from the five modules the restatement once was, each case through the module that owned it, and
-this script's output was byte-identical to it.  Run it again only when the header's arithmetic changes on purpose: the file is what
+The committed file was first written from the six modules the restatement once was, each case through the module that owned it, and
+this script's output was byte-identical to it.  A record of APT_FLAG_MIS that the flag does not reach would hold nothing: the script
+fails unless every room case's colours differ from those of the same case traced with mis=False.  Run it again only when the header's arithmetic changes on purpose: the file is what
 holds the restatement, which every GPU test of the material kernels compares against, to what it computed before.  The case list, the
 scenes, the rays and the digest are the test's own, so there is one list.
 """
@@ -18,12 +19,17 @@ import test_restatement_frozen as fz  # noqa: E402
 
 
 def main():
-    import __graft_entry__ as g
-    g.build()
-    from ascendpathtracing_amd import gen_data
+    from gpu_harness import load_host
     from oracle import oracle
-    world = fz.scenes(gen_data)
-    results = {fz.key(case[0], depth, rr): fz.restated(gen_data, oracle, world, case, depth, rr) for case in fz.cases() for depth, rr in fz.VARIANTS}
+    pkg = load_host()
+    gen_data = pkg.gen_data
+    world = {**fz.scenes(gen_data), **fz.mis_scenes(pkg)}
+    results = {}
+    for case in fz.cases():
+        for depth, rr in fz.variants(case):
+            results[fz.key(case[0], depth, rr)] = d = fz.restated(gen_data, oracle, world, case, depth, rr)
+            if case[2].startswith("harness/"):
+                assert d["L"] != fz.restated(gen_data, oracle, world, case, depth, rr, mis=False)["L"], (case[0], depth, rr)
     out = sys.argv[1] if len(sys.argv) > 1 else fz.HASHES
     with open(out, "w") as f:
         f.write(fz.dump(results))

@@ -1,6 +1,8 @@
 """What the material renderer's GPU test files share (tests/test_gpu_materials*.py, _nee, _lights, _gloss, _camera, _environment, _film,
-_features, _glass_physics, _deep_plans, _material_matrix, _degenerate_scenes): the `apt` fixture, the comparisons, one Scene and the scenes that more than one
-file renders.  A plain module beside materials_ref.py, imported the same way: `from gpu_harness import apt  # noqa: F401` brings the fixture.
+_features, _glass_physics, _deep_plans, _material_matrix, _mis, _film_list, _degenerate_scenes): the `apt` fixture, the comparisons, one
+Scene and the scenes that more than one file renders; and, for the CPU tests that restate them (test_mis_cpu, test_degenerate_scenes_cpu,
+test_restatement_frozen, the CPU halves of the matrices), the device-free `host` fixture.  A plain module beside materials_ref.py,
+imported the same way: `from gpu_harness import apt  # noqa: F401` brings the fixture.  tests/mat_rows.py holds what the row matrices share.
 
 A Scene's host half -- the tables the restatements read -- needs no device: the tensors are made on first use."""
 import contextlib
@@ -25,6 +27,21 @@ def apt():
     _lib.require_gpu()
     pkg.gen_data, pkg.render = gen_data, render
     return pkg
+
+
+def load_host():
+    """The package without a device: scenes, cameras, environments and light tables are host data."""
+    import __graft_entry__ as g
+    g.build()
+    import ascendpathtracing_amd as pkg
+    from ascendpathtracing_amd import gen_data
+    pkg.gen_data = gen_data
+    return pkg
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
 
 
 def dev(a, dtype=None):
@@ -162,8 +179,9 @@ class Scene:
         return out.cpu().numpy()
 
     def frame_ref(self, p, mode="plain", cam=None, env=None, gloss=True):
-        """materials_ref's whole frame for the launch `p` -> (fb, u8, segments), computed once.  The key holds every input of the
-        restatement but the scene: p without its grid (which changes no image), table or not, the words, the camera and the environment."""
+        """materials_ref's whole frame for the launch `p` (APT_FLAG_MIS read from its flags, like the others) -> (fb, u8, segments),
+        computed once.  The key holds every input of the restatement but the scene: p without its grid (which changes no image), table or
+        not, the words, the camera and the environment."""
         key = (bytes(oracle_params(p)), mode == "table", bool(gloss), None if cam is None else bytes(cam), None if env is None else bytes(env))
         if key not in self.ref:
             rays = None if cam is None else cr.rays(cr.from_ctypes(cam), p.width, p.height, p.samples, seed=p.seed)

@@ -1,12 +1,14 @@
 """NumPy restatement of the material renderer (include/render_mi355x.h "per-sphere materials", "Direct light sampling", "several
-lights", the GLOSS block and "environment"), for the tests only.  It is the one restatement: every GPU test of the material kernels
-compares against this module bit for bit, and tests/test_restatement_frozen.py holds it to recorded bytes.
+lights", the GLOSS block, "environment" and "Multiple importance sampling"), for the tests only.  It is the one restatement: every GPU
+test of the material kernels compares against this module bit for bit, and tests/test_restatement_frozen.py holds it to recorded bytes.
 
 The whole bounce in one place (_trace_chunk): plain, direct light sampling (nee=True, the sphere `light`), a light table (table=the
-words), the rough-metal material (gloss=True: the launch carries APT_FLAG_GLOSS), roulette, and an environment (env=an Env) with its
-three changes -- the miss, `sampled_sun` cleared at every hit, the sun sample after a DIFF bounce.  A block that cannot reach the result
-for the given arguments is not run: the GLOSS block without the flag or without a gloss word in the table, the light sample without
-`nee` and without a table, the sky and the sun without an environment.
+words), the rough-metal material (gloss=True: the launch carries APT_FLAG_GLOSS), roulette, an environment (env=an Env) with its
+three changes -- the miss, `sampled_sun` cleared at every hit, the sun sample after a DIFF bounce -- and APT_FLAG_MIS (mis=True) with
+its three: the GLOSS hit's light sample, the weighted emission at the next hit, the density of the GLOSS bounce's own direction kept
+for it.  A block that cannot reach the result for the given arguments is not run: the GLOSS block without the flag or without a gloss
+word in the table, the light sample without `nee` and without a table, the sky and the sun without an environment, the blocks of
+APT_FLAG_MIS without a gloss word or without a light mode.
 
 float32 arrays vectorised over paths, every constant an np.float32 (NumPy >= 2 promotes by NEP 50: float32 op float32 stays float32),
 one separately rounded operation per step in the header's order, f32() on the intermediates -- f32 fails on a float64 one; NumPy's
@@ -23,7 +25,10 @@ F = np.float32
 U = np.uint64
 MISS = F(1e20)
 SPEC, DIFF, REFR, GLOSS = 0, 1, 2, 3
-FLAG_RR, FLAG_NEE, FLAG_GLOSS = 2, 32, 64
+FLAG_RR, FLAG_NEE, FLAG_GLOSS, FLAG_MIS = 2, 32, 64, 128
+PI = F(float.fromhex("0x1.921fb6p+1"))        # RN(pi)
+TWO_PI = F(float.fromhex("0x1.921fb6p+2"))    # RN(2 * pi)
+INF = F(np.inf)
 ENV_SAMPLE_SUN = 1
 MAT_SALT = U(0x6A09E667F3BCC909)
 NEE_SALT = U(0xBB67AE8584CAA73B)
@@ -176,6 +181,44 @@ def gloss_sample(d, nl, alpha, u1, u2):
     return newd, g, lz > F(0)
 
 
+def g1(a2, z):
+    """G1 of the separable Smith term for a frame direction of z component z."""
+    return f32((F(2) * z) / (z + np.sqrt(a2 + (F(1) - a2) * (z * z))))
+
+
+def ggx_d(a2, m):
+    """D(m) of a unit half vector in the frame: k = (m.x^2 + m.y^2) + a2 * m.z^2; a2 / ((pi * k) * k)."""
+    k = (m[0] * m[0] + m[1] * m[1]) + a2 * (m[2] * m[2])
+    return f32(a2 / ((PI * k) * k))
+
+
+def light_pdf(r2, d2, P):
+    """P / (2 * pi * omc) with "Direct light sampling"'s x, cmax and omc."""
+    x = r2 / d2
+    cmax = np.sqrt(F(1) - x)
+    omc = x / (F(1) + cmax)
+    return f32(P / (TWO_PI * omc))
+
+
+def gloss_frame(d, nl, alpha, u1, u2):
+    """The GLOSS block's v and drawn m (both in the frame (t, bt, nl)) and the frame itself -> (v, m, t, bt)."""
+    t, bt = basis(*nl)
+    w = [-d[0], -d[1], -d[2]]
+    v = [dot(*w, *t), dot(*w, *bt), dot(*w, *nl)]
+    s0x, s0y = alpha * v[0], alpha * v[1]
+    sl = np.sqrt(dot(s0x, s0y, v[2], s0x, s0y, v[2]))
+    sx, sy, sz = s0x / sl, s0y / sl, v[2] / sl
+    sn, cs = sincos(u1)
+    z = (F(1) - u2) * (F(1) + sz) - sz
+    r2 = F(1) - z * z
+    r = np.sqrt(np.where(r2 > F(0), r2, F(0)))
+    m0 = [alpha * (r * cs + sx), alpha * (r * sn + sy), z + sz]
+    ml = np.sqrt(dot(*m0, *m0))
+    m = [m0[i] / ml for i in range(3)]
+    f32(*v, *m)
+    return v, m, t, bt
+
+
 def light_sample(h, nl, nkey, bounce, lc, lr2):
     """The header's `sample` step of "Direct light sampling" for hit points h with oriented normals nl
     -> (ok: h strictly outside the light, l, cosl, wgt)."""
@@ -321,11 +364,11 @@ def roulette(T, alive, key, bounce):
 
 # ---- the renderer -------------------------------------------------------------------------------------------------------------------------
 def trace(rays, spheres, materials, ns, depth, eps, seed, paths, env=None, rr_start=0, light=-1, nee=False, table=None, gloss=True,
-          chunk=1 << 16):
+          chunk=1 << 16, mis=False):
     """rays float32 [6][n], spheres the padded [10][Ns] table, materials the words [Ns], paths uint64 [n] (path indices); env: an Env or
     None (no environment); gloss: the launch carries APT_FLAG_GLOSS; nee / light: APT_FLAG_NEE; table: the *_lights entries (then nee /
-    light are not read) -> (L float32 [3][n], bad bool [n]: the path hit a bad material word, segments int: the lights' and the sun's
-    shadow segments included)."""
+    light are not read); mis: the launch carries APT_FLAG_MIS (read only with `gloss` and with `nee` or a table) -> (L float32 [3][n],
+    bad bool [n]: the path hit a bad material word, segments int: the lights' and the sun's shadow segments included)."""
     rays = np.asarray(rays, dtype=F).reshape(6, -1)
     n = rays.shape[1]
     tb = None if table is None else (table if isinstance(table, Table) else Table(table))
@@ -337,18 +380,19 @@ def trace(rays, spheres, materials, ns, depth, eps, seed, paths, env=None, rr_st
     for lo in range(0, n, step):
         hi = min(n, lo + step)
         L[:, lo:hi], bad_all[lo:hi], seg = _trace_chunk(rays[:, lo:hi], spheres, materials, ns, depth, eps, seed,
-                                                         np.asarray(paths, dtype=U)[lo:hi], rr_start, light, nee and tb is None, tb, gloss, env)
+                                                         np.asarray(paths, dtype=U)[lo:hi], rr_start, light, nee and tb is None, tb, gloss, env, mis)
         segments += seg
     return L, bad_all, segments
 
 
-def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start, light, nee, tb, gloss, env):
+def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start, light, nee, tb, gloss, env, mis):
     assert not nee or 0 <= light < ns
     sph = np.asarray(spheres, dtype=F).ravel()[:10 * ns].reshape(10, ns)
     codes, alphas = decode(materials, gloss)
     top = GLOSS if gloss else REFR
     has_gloss = gloss and bool((codes == GLOSS).any())
     lit = nee or tb is not None
+    mis = bool(mis) and has_gloss and lit
     sun = env is not None and env.samples_sun
     eps = F(eps)
     o = [rays[k].copy() for k in range(3)]
@@ -361,6 +405,8 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
     sampled = np.zeros(n, dtype=bool)
     sampled_sun = np.zeros(n, dtype=bool)
     kprev = np.full(n, -1, dtype=np.int64)
+    glprev = np.zeros(n, dtype=bool)                     # mis: the last sampling bounce was a GLOSS one ...
+    pbprev = np.zeros(n, F)                              # ... and drew its direction under this density
     bad_any = np.zeros(n, dtype=bool)
     segments = 0
     mkey, rkey = mat_key(seed, paths), rr_key(seed, paths)
@@ -368,6 +414,10 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
     lkey = light_key(seed, paths) if tb is not None else None
     skey = sun_key(seed, paths) if sun else None
     geo = (sph[1], sph[2], sph[3], sph[0])
+    if mis and tb is not None:                           # P[i] = cdf[i] - cdf[i-1], exact; per entry and per listed sphere
+        P_entry = f32(tb.cdf - np.concatenate([np.zeros(1, F), tb.cdf[:-1]]))
+        P_sphere = np.zeros(ns, F)
+        P_sphere[tb.idx] = P_entry
     with np.errstate(all="ignore"):
         for dd in range(depth):
             # hit, code
@@ -393,16 +443,28 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
             nr = [h[i] - sph[1 + i][g] for i in range(3)]
             ln = np.sqrt(dot(*nr, *nr))
             nu = [nr[i] / ln for i in range(3)]
-            # light: an emission that the previous bounce's sample stood for is left out
+            # light: an emission that the previous bounce's sample stood for is left out -- after a DIFF sample; after a GLOSS one (mis)
+            # it is weighted by the balance of that bounce's density and the light sampler's
             Ln = [L[i] + T[i] * sph[4 + i][g] for i in range(3)]
             if lit:
+                if mis or not nee:
+                    w0 = [sph[1 + i][g] - o[i] for i in range(3)]
+                    d2o = f32(dot(*w0, *w0))
                 if nee:
                     noem = sampled & (k == light)
                 else:
-                    w0 = [sph[1 + i][g] - o[i] for i in range(3)]
-                    noem = sampled & tb.listed[g] & (g != kprev) & (f32(dot(*w0, *w0)) > sph[0][g])
+                    noem = sampled & tb.listed[g] & (g != kprev) & (d2o > sph[0][g])
+                if mis:
+                    pl = light_pdf(sph[0][g], d2o, F(1) if nee else P_sphere[g])
+                    tot = pbprev + pl
+                    wb = np.where((tot > F(0)) & (tot < INF), pbprev / tot, F(1))
+                    Lw = [L[i] + (T[i] * sph[4 + i][g]) * wb for i in range(3)]
+                    f32(wb, *Lw)
+                    Ln = [np.where(noem & glprev, Lw[i], Ln[i]) for i in range(3)]
+                    noem = noem & ~glprev
                 Ln = [np.where(noem, L[i], Ln[i]) for i in range(3)]
             Tn = [T[i] * sph[7 + i][g] for i in range(3)]
+            Ta = Tn                                                          # T after `T *= albedo`: what every light sample of this bounce uses
             # orient, draws
             ddn = dot(*d, *nu)
             into = ddn < F(0)
@@ -448,14 +510,16 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
                 Tw = [np.where(is_g, Tn[i] * gw, Tw[i]) for i in range(3)]
                 ended = live & is_g & ~up                                # drawn below the horizon: the path ends, L keeps its value
             Tn = Tw
-            # sample + shadow: DIFF hits of live paths, never at the last bounce
+            # sample + shadow: DIFF hits of live paths and, with mis, GLOSS hits (whether or not their own direction was accepted: a path
+            # that ends here still adds its light sample); never at the last bounce
             new_sampled = np.zeros(n, dtype=bool)
             if lit and dd + 1 < depth:
                 bounce = live & is_d
+                taking = bounce | (live & is_g) if mis else bounce
                 if nee:
                     j = np.full(n, light, dtype=np.int64)
                     ok, l, cosl, wgt = light_sample(h, nl, nkey, dd, [sph[1 + i][light] for i in range(3)], sph[0][light])
-                    can = bounce & (k != light) & ok
+                    can = taking & (k != light) & ok
                     new_sampled = can
                 else:
                     u, _ = uniforms(lkey, dd)
@@ -464,9 +528,27 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
                     j = tb.idx[i_sel]
                     ok, l, cosl, wgt = light_sample(h, nl, nkey, dd, [sph[1 + i][j] for i in range(3)], sph[0][j])
                     wgt = wgt * tb.invp[i_sel]
-                    can = bounce & (j != k) & ok
-                    new_sampled = bounce                                     # sampled, whatever the chosen light allowed
+                    can = taking & (j != k) & ok
+                    new_sampled = taking                                     # sampled, whatever the chosen light allowed
                 want = can & (cosl > F(0))
+                if mis:                                                      # a GLOSS hit's sample: G1(l) times the balance of the two densities
+                    alpha = alphas[g]
+                    a2 = alpha * alpha
+                    vf, mf, tf, btf = gloss_frame(d, nl, alpha, u1, u2)
+                    g1v = g1(a2, vf[2])
+                    new_pb = f32((g1v * ggx_d(a2, mf)) / (F(4) * vf[2]))     # the density of the direction this bounce drew
+                    wl = [dot(*l, *tf), dot(*l, *btf), dot(*l, *nl)]
+                    hm0 = [vf[i] + wl[i] for i in range(3)]
+                    hl = np.sqrt(dot(*hm0, *hm0))
+                    hm = [hm0[i] / hl for i in range(3)]
+                    pb = (g1v * ggx_d(a2, hm)) / (F(4) * vf[2])
+                    w0 = [sph[1 + i][j] - h[i] for i in range(3)]
+                    pl = light_pdf(sph[0][j], dot(*w0, *w0), F(1) if nee else P_entry[i_sel])
+                    tot = pb + pl
+                    wg = g1(a2, wl[2]) * (pb / tot)
+                    f32(pb, pl, tot, wg)
+                    wgt = np.where(is_g, wg, wgt)
+                    want = want & (~is_g | ((tot > F(0)) & (tot < INF)))
                 rows = np.nonzero(want)[0]
                 segments += rows.size
                 if rows.size:
@@ -474,10 +556,10 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
                     _, ks = _intersect([h[i][rows] for i in range(3)], [l[i][rows] for i in range(3)], geo, eps, sskip)
                     vis = np.zeros(n, dtype=bool)
                     vis[rows] = ks == j[rows]
-                    add = [(Tn[i] * sph[4 + i][j]) * wgt for i in range(3)]
+                    add = [(Ta[i] * sph[4 + i][j]) * wgt for i in range(3)]
                     f32(wgt, *add)
                     Ln = [np.where(vis, Ln[i] + add[i], Ln[i]) for i in range(3)]
-            # sun sample: after the light's; the sun is visible iff the shadow segment finds no sphere
+            # sun sample: after the light's, at DIFF hits alone; the sun is visible iff the shadow segment finds no sphere
             new_sampled_sun = np.zeros(n, dtype=bool)
             if sun and dd + 1 < depth:
                 bounce = live & is_d
@@ -504,6 +586,9 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
             if lit:
                 sampled = np.where(live, new_sampled, sampled)
                 kprev = np.where(live, k, kprev)
+            if mis and dd + 1 < depth:                                       # read at the next hit alone
+                glprev = np.where(live, live & is_g, glprev)
+                pbprev = np.where(live, new_pb, pbprev)
             if sun:
                 sampled_sun = np.where(live, new_sampled_sun, sampled_sun)  # cleared at every hit, set by a sampling DIFF bounce
             if ended is not None:
@@ -516,18 +601,25 @@ def _trace_chunk(rays, spheres, materials, ns, depth, eps, seed, paths, rr_start
     return np.stack(L), bad_any, segments
 
 
+def trace_params(q, rays, spheres, materials, env=None, table=None, paths=None, seed=None):
+    """trace() of `rays` for the launch `q` (an oracle.Params), the one place that unpacks one: APT_FLAG_RR / APT_FLAG_NEE /
+    APT_FLAG_GLOSS / APT_FLAG_MIS are read from q.flags.  paths: the rays' path indices (None: 0 .. n - 1); seed: in q.seed's place (a
+    film pass's)."""
+    rays = np.asarray(rays, dtype=F).reshape(6, -1)
+    rr = (q.rr_start or 3) if q.flags & FLAG_RR else 0
+    return trace(rays, spheres, materials, q.num_spheres, q.depth, q.eps, q.seed if seed is None else seed,
+                 np.arange(rays.shape[1], dtype=U) if paths is None else paths, env, rr, light=q.light_index, nee=bool(q.flags & FLAG_NEE),
+                 table=table, gloss=bool(q.flags & FLAG_GLOSS), mis=bool(q.flags & FLAG_MIS))
+
+
 def render_frame(params, spheres, materials, env=None, table=None, pixel_begin=0, pixel_count=None, rays=None):
     """-> (fb float32 [3][count], u8 [count][3], bad [N], segments) of apt_render_frame_materials (table: apt_render_frame_lights) with the
-    environment `env` set, for `params` (an oracle.Params); APT_FLAG_NEE / APT_FLAG_GLOSS / APT_FLAG_RR are read from params.flags.
-    rays: a camera's (camera_ref.rays)."""
+    environment `env` set, for `params` (an oracle.Params), whose flags trace_params reads.  rays: a camera's (camera_ref.rays)."""
     from oracle import oracle
     w, h, s = params.width, params.height, params.samples
     if rays is None:
         rays = oracle.gen_rays_counter(params)
-    n = rays.shape[1]
-    rr = (params.rr_start or 3) if params.flags & FLAG_RR else 0
-    L, bad, seg = trace(rays, spheres, materials, params.num_spheres, params.depth, params.eps, params.seed, np.arange(n, dtype=U), env, rr,
-                        light=params.light_index, nee=bool(params.flags & FLAG_NEE), table=table, gloss=bool(params.flags & FLAG_GLOSS))
+    L, bad, seg = trace_params(params, rays, spheres, materials, env, table)
     _, fb, u8 = oracle.decode_color(L, w, h, s)
     if pixel_count is None:
         pixel_count = w * h - pixel_begin

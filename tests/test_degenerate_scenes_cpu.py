@@ -24,22 +24,13 @@ import pytest
 
 import degenerate_scenes as ds
 import materials_ref as mr
+from gpu_harness import host  # noqa: F401
 
 F, U = np.float32, np.uint64
 DEPTH, EPS, SEED = 6, 1e-4, 3
 MODES = ("plain", "nee", "table")
 TIE_SCENES = ("twins", "cluster40", "tiles1030", "twins8")
 LIGHT_SCENES = ("nested", "lights")
-
-
-@pytest.fixture(scope="module")
-def host():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import gen_data
-    pkg.gen_data = gen_data
-    return pkg
 
 
 _BUILT = {}

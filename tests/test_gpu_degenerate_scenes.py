@@ -60,10 +60,7 @@ def paths_ref(sc, p, mode):
     q = oracle_params(p)
     key = ("paths", bytes(q), mode == "table")
     if key not in sc.ref:
-        n = sc.rays.shape[1]
-        rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
-        L, bad, _ = mr.trace(sc.rays, sc.sph, sc.mat, sc.ns, q.depth, q.eps, q.seed, np.arange(n, dtype=U), None, rr, light=q.light_index,
-                             nee=bool(q.flags & mr.FLAG_NEE), table=sc.table if mode == "table" else None, gloss=bool(q.flags & mr.FLAG_GLOSS))
+        L, bad, _ = mr.trace_params(q, sc.rays, sc.sph, sc.mat, table=sc.table if mode == "table" else None)
         assert not bad.any()
         sc.ref[key] = L
     return sc.ref[key]

@@ -4,8 +4,8 @@ select it, and held bit for bit to the restatement: film_ref's pass of the WHOLE
 pixels (tests/adaptive_ref.py), with the status word clean, the trace counter equal to the restatement's segments of the listed
 pixels' paths, the scratch stored over NaN and the floats after 3 * count untouched.
 
-The rows are generated below; kernel_of() restates the routing (materials.hip, pt_mat_launch.h) and names a row's kernel as the ISA
-names it.  One row per kernel (`k` rows) rotating over the lists of adaptive_ref.gpu_lists -- every pixel in order, one entry, 17 and
+The rows are generated below; mat_rows.mat_kernel() restates the routing (materials.hip, pt_mat_launch.h) and names a row's kernel as
+the ISA names it.  One row per kernel (`k` rows) rotating over the lists of adaptive_ref.gpu_lists -- every pixel in order, one entry, 17 and
 1001 strided entries that wrap round the image, a descending list, a list with repeated entries --, samples 3 (GROUP 1) and 8 / 9
 (GROUP 8), depth 1 / 3 / 5, roulette, the reference camera / the context's camera with a lens, no environment / the sun sampled / not
 sampled, pass index 0 / 2; frames are 48 x 32, 24 x 16 on the 220-sphere scene.  On top of them the rows about one rule: 129 samples
@@ -15,24 +15,16 @@ list against the plain film entry.
 The CPU tests hold the rows to film_list.s's kernel list (names only) and to these classes; tests/test_adaptive_cpu.py holds the lists
 to telling a list pass from three wrong renderers."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import adaptive_ref as ar
-import camera_ref as cr
 import film_ref as fr
 import materials_ref as mr
-import mis_ref as mi
 from gpu_harness import apt, assert_bits_equal, bits_equal, dev, inside_lens, oracle_params, scene, sky_and_sun  # noqa: F401
-from test_gpu_launch_matrix import _kernel_name
+from mat_rows import code_object_kernels, mat_kernel, needs_hipcc, rays_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ascendpathtracing_amd", "csrc")
 F, U, U32 = np.float32, np.uint64, np.uint32
 MODES = ("plain", "nee", "table")
 NS = {"gloss8-lamp": 8, "gloss9-lamp": 9, "open8": 8, "open40": 40, "open220": 220}
@@ -43,16 +35,10 @@ GUARD = 8
 APT_ERR_ARG = 1
 
 
-def kernel_of(ns, grid, mode, samples, mis):
-    form = 0 if ns == 8 else (2 if grid else 1)
-    scn = form | (8 if mode == "table" else (4 if mode == "nee" else 0)) | 16 | 32 | 64 | 128 | 512 | (256 if mis else 0)
-    return f"render_frame_mat_kernel<{scn}, {8 if samples >= 8 else 1}>"
-
-
 def _row(var, scene_name, mode, grid=False, mis=False, s=3, depth=3, rr=False, cam=None, env=None, seed=3, lst="strided17", k=0):
     w, h = (24, 16) if scene_name == "open220" or s > 100 else (48, 32)
     r = dict(var=var, scene=scene_name, mode=mode, grid=grid, mis=mis, s=s, depth=depth, rr=rr, cam=cam, env=env, seed=seed, list=lst, k=k, w=w, h=h,
-             kernel=kernel_of(NS[scene_name], grid, mode, s, mis))
+             kernel=mat_kernel("film", NS[scene_name], grid, mode, s, mis=mis, listed=True)[1])
     r["id"] = "|".join(str(x) for x in (r["kernel"], var, scene_name + ("+grid" if grid else ""), mode + ("+mis" if mis else ""), f"s{s}",
                                         f"d{depth}" + ("rr" if rr else ""), cam or "ref", env or "noenv", lst, f"pass{k}"))
     return r
@@ -106,15 +92,10 @@ def test_rows_are_well_formed():
         assert all(v.max() < npix for v in lists.values())
 
 
-@pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or shutil.which("c++filt") is None,
-                    reason="needs hipcc and c++filt")
+@needs_hipcc
 def test_every_kernel_of_film_list_s_has_exactly_one_row():
     """Kernel names only: no instruction is looked at."""
-    subprocess.run(["make", "-s", "-C", CSRC, "film_list.s"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(os.path.join(CSRC, "film_list.s")).read()
-    mangled = sorted(set(re.findall(r"^\s*\.amdhsa_kernel (\S+)$", text, re.M)))
-    demangled = subprocess.run(["c++filt"], input="\n".join(mangled) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-    names = {_kernel_name(d) for d in demangled}
+    names = code_object_kernels("film_list")
     render = sorted(n for n in names if n.startswith("render_frame_mat_kernel"))
     assert names - set(render) == {"gen_rays_camera_kernel"}
     assert render == sorted(r["kernel"] for r in K_ROWS) and len(render) == KERNELS
@@ -145,42 +126,21 @@ def _params(pkg, sc, r, grid=False):
 _WHOLE = {}
 
 
-def _tracer(pkg, r, k):
-    """-> (trace(path indices) -> (L, segments), rays [6][n]) of pass k of the row's WHOLE frame."""
-    from oracle import oracle
+def _inputs(pkg, r):
+    """What the restatement reads of the row -> (the launch as an oracle.Params, spheres, words, camera record, Env, table)."""
     sc = scene(pkg, r["scene"])
     q = oracle_params(_params(pkg, sc, r))
     assert not r["mis"] or (q.flags & mr.FLAG_GLOSS and r["mode"] != "plain")
-    seed = fr.pass_seed(q.seed, k)
-    cam = _camera(pkg, r)
-    if cam is None:
-        q1 = oracle.Params.from_buffer_copy(bytes(q))
-        q1.seed = seed
-        rays = oracle.gen_rays_counter(q1)
-    else:
-        rays = cr.rays(cr.from_ctypes(cam), q.width, q.height, q.samples, seed=seed)
     env = None if r["env"] is None else mr.Env.from_ctypes(_env(pkg, r))
-    table = sc.table if r["mode"] == "table" else None
-    rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
-
-    def trace(paths):
-        L, bad, seg = mi.trace(rays[:, paths], sc.sph, sc.mat, sc.ns, q.depth, q.eps, seed, paths.astype(U), env, rr, light=q.light_index,
-                               nee=bool(q.flags & mr.FLAG_NEE), table=table, gloss=bool(q.flags & mr.FLAG_GLOSS), mis=bool(q.flags & mi.FLAG_MIS))
-        assert not bad.any()
-        return L, seg
-    return trace, rays
+    return q, sc.sph, sc.mat, _camera(pkg, r), env, sc.table if r["mode"] == "table" else None
 
 
 def whole(pkg, r, k):
-    """The planes [3][W * H] of pass k of the row's whole frame, and its segments: film_ref.render_pass's steps, computed once."""
+    """The planes [3][W * H] of pass k of the row's whole frame, and its segments: film_ref.render_pass, computed once."""
     key = (r["scene"], r["mode"], r["mis"], r["s"], r["depth"], r["rr"], r["cam"], r["env"], r["seed"], r["w"], r["h"], k)
     if key not in _WHOLE:
-        from oracle import oracle
-        trace, rays = _tracer(pkg, r, k)
-        L, seg = trace(np.arange(rays.shape[1], dtype=np.int64))
-        pre = oracle.decode_color(L, r["w"], r["h"], r["s"])[0]
-        assert pre.dtype == np.float64
-        _WHOLE[key] = (np.ascontiguousarray(pre.T).astype(F), seg)
+        q, sph, mat, cam, env, table = _inputs(pkg, r)
+        _WHOLE[key] = fr.render_pass(q, sph, mat, env, table, pass_index=k, rays=None if cam is None else (lambda seed: rays_of(q, cam, seed)))
     return _WHOLE[key]
 
 
@@ -188,11 +148,13 @@ def listed_segments(pkg, r, lst, k):
     """The segments of the paths of the listed pixels inside the image, an entry counted as often as it is listed: what the trace
     counter of a list launch holds.  Their colours are traced again on the way: they must be the whole frame's."""
     from oracle import oracle
-    trace, _ = _tracer(pkg, r, k)
+    q, sph, mat, cam, env, table = _inputs(pkg, r)
+    seed = fr.pass_seed(q.seed, k)
     inside = lst[lst < r["w"] * r["h"]].astype(np.int64)
     per = 4 * r["s"]
     paths = (inside[:, None] * per + np.arange(per)[None, :]).ravel()
-    L, seg = trace(paths)
+    L, bad, seg = mr.trace_params(q, rays_of(q, cam, seed)[:, paths], sph, mat, env, table, paths=paths.astype(U), seed=seed)
+    assert not bad.any()
     pre = oracle.decode_color(L, inside.size, 1, r["s"])[0]
     assert_bits_equal(np.ascontiguousarray(pre.T).astype(F), whole(pkg, r, k)[0][:, inside])
     return seg

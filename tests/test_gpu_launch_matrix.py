@@ -15,16 +15,11 @@ every arm and both arithmetic modes, the numeric edges that apply to it --
 The CPU test checks that the rows name exactly the render kernels the code object holds, so that a kernel added later without a row fails
 the CPU suite."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ascendpathtracing_amd", "csrc")
+from mat_rows import code_object_kernels, needs_hipcc
 
 K, O = 0, 1
 RETIRE, RR, EMISSION, BAND, GRID_SLOTS = 1, 2, 4, 8, 16
@@ -188,23 +183,6 @@ ROWS = _rows()
 
 
 # ---- CPU: the rows cover the code object ---------------------------------------------------------------------------------------------
-def _kernel_name(demangled):
-    """'void (anonymous namespace)::render_frame_kernel<0, 0, 8, false, true>(float const*, ...)' -> 'render_frame_kernel<0, 0, 8, false, true>'"""
-    s = demangled.strip()
-    if s.startswith("void "):
-        s = s[5:]
-    s = s.replace("(anonymous namespace)::", "")
-    depth = 0
-    for i, ch in enumerate(s):                # cut the parameter list: the first '(' outside the template argument list
-        if ch == "<":
-            depth += 1
-        elif ch == ">":
-            depth -= 1
-        elif ch == "(" and depth == 0:
-            return s[:i]
-    return s
-
-
 def test_rows_are_well_formed():
     ids = [r["id"] for r in ROWS]
     assert len(ids) == len(set(ids))
@@ -224,15 +202,9 @@ def test_rows_are_well_formed():
     assert {("nan" if e != e else e) for e in (r["eps"] for r in ROWS) if not (0 < e < 1e20)} == {0.0, -1.0, 1e21, "nan"}
 
 
-@pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or shutil.which("c++filt") is None,
-                    reason="needs hipcc and c++filt")
+@needs_hipcc
 def test_every_render_kernel_of_the_code_object_has_a_row():
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(os.path.join(CSRC, "render_kernels.s")).read()
-    mangled = sorted(set(re.findall(r"^\s*\.amdhsa_kernel (\S+)$", text, re.M)))
-    assert mangled
-    demangled = subprocess.run(["c++filt"], input="\n".join(mangled) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-    names = {_kernel_name(d) for d in demangled}
+    names = code_object_kernels("render_kernels")
     render = {n for n in names if n.startswith(("render_paths", "render_frame"))}
     assert names - render == NOT_RENDER_KERNELS, "a kernel that is neither a render kernel nor in the exclusion list"
     rowset = {r["kernel"] for r in ROWS}

@@ -3,9 +3,9 @@ materials.hip, environment.hip and film.hip, and features.hip's features_kernel<
 that select it and compared with the NumPy restatements (materials_ref, film_ref, features_ref): fb bit for bit, fb_u8 exactly, the trace
 counter against the restatement's segments, the status word clean, and a grid launch against the same launch without its grid.
 
-The rows are generated below.  kernel_of() restates the routing of materials.hip and pt_mat_launch.h and names, for a row's
+The rows are generated below.  mat_rows.mat_kernel() restates the routing of materials.hip and pt_mat_launch.h and names, for a row's
 parameters, the kernel as the ISA names it; the rows are made by walking every (code object, scene form, light mode, GROUP, camera,
-gloss) and asking kernel_of() for the name, so every kernel has
+gloss) and asking it for the name, so every kernel has
 
   a carrier   a whole frame at an odd depth >= 3 whose expected image is non-trivial and changes in bits when one of the row's own axes
               is taken away (test_carrier_rows_would_show_a_failure, on the restatement alone);
@@ -28,10 +28,6 @@ A buffer row has no fb: its colours are compared per path, and for the carrier c
 The CPU tests hold the rows to the kernel lists of the four code objects (a kernel added without a row fails the suite), to these
 classes, and the carriers to their two conditions."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 import time
 
 import numpy as np
@@ -41,11 +37,9 @@ import camera_ref as cr
 import features_ref as ft
 import film_ref as fr
 import materials_ref as mr
-from gpu_harness import Scene, apt, assert_bits_equal, bits_equal, dev, inside_lens, inside_pinhole, oracle_params, scene, sky_and_sun  # noqa: F401
-from test_gpu_launch_matrix import _kernel_name
+from gpu_harness import Scene, apt, assert_bits_equal, bits_equal, dev, host, inside_lens, inside_pinhole, oracle_params, scene, sky_and_sun  # noqa: F401
+from mat_rows import code_object_kernels, mat_kernel, needs_hipcc, rays_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ascendpathtracing_amd", "csrc")
 F, U = np.float32, np.uint64
 
 MODES = ("plain", "nee", "table")
@@ -64,32 +58,12 @@ COUNTS = {"materials": 90, "environment": 27, "film": 18, "features": 3}
 NOT_RENDER_KERNELS = {"gen_rays_camera_kernel", "selftest_direction_kernel", "film_resolve_kernel"}
 
 
-# ---- the routing, restated ---------------------------------------------------------------------------------------------------------------
-def kernel_of(entry, ns, grid, mode, gloss, camera, env, samples):
-    """materials.hip's routing and pt_mat_launch.h's scene form -> (code object, the kernel as the ISA names it)."""
-    form = 0 if ns == 8 else (2 if grid else 1)
-    if entry == "features":
-        return "features", f"features_kernel<{form}>"
-    scn = form + (8 if mode == "table" else (4 if mode == "nee" else 0))
-    group = 8 if samples >= 8 else 1
-    if entry == "film":
-        return "film", f"render_frame_mat_kernel<{scn | 16 | 32 | 64 | 128}, {group}>"
-    if entry == "frame":
-        if env:
-            return "environment", f"render_frame_mat_kernel<{scn | 16 | 32 | 64}, {group}>"
-        return "materials", f"render_frame_mat_kernel<{scn | (16 if camera else 0) | (32 if gloss else 0)}, {group}>"
-    assert entry == "paths"
-    if env:
-        return "environment", f"render_paths_mat_kernel<{scn | 32 | 64}>"
-    return "materials", f"render_paths_mat_kernel<{scn | (32 if gloss else 0)}>"
-
-
 # ---- the rows ----------------------------------------------------------------------------------------------------------------------------
 def _row(var, entry, scene_name, mode="plain", grid=False, gloss=True, cam=None, env=None, s=1, depth=5, rr=False, rng=None, u8="whole",
          paths="whole", seed=3, w=W, h=H, accel8=False):
     """accel8: the 8-sphere scene launched with another scene's grid in accel, which the 8-sphere form ignores."""
     assert not accel8 or (NS[scene_name] == 8 and not grid and entry == "frame")
-    co, kernel = kernel_of(entry, NS[scene_name], grid or accel8, mode, gloss, cam is not None, env is not None, s)
+    co, kernel = mat_kernel(entry, NS[scene_name], grid or accel8, mode, s, gloss, cam is not None, env is not None)
     r = dict(var=var, entry=entry, scene=scene_name, mode=mode, grid=grid, gloss=gloss, cam=cam, env=env, s=s, depth=depth, rr=rr, range=rng,
              u8=u8, paths=paths, seed=seed, w=w, h=h, accel8=accel8, co=co, kernel=kernel, group=8 if s >= 8 else 1)
     rid = f"{co}|{kernel}|{var}|{scene_name}{'+grid' if grid else ''}|{mode}|s{s}|d{depth}{'rr' if rr else ''}"
@@ -219,7 +193,7 @@ def claimed_dispatches():
     out = []
     for r in ROWS:
         for grid in ((True, False) if r["grid"] else (False,)):
-            k = kernel_of(r["entry"], NS[r["scene"]], grid, r["mode"], r["gloss"], r["cam"] is not None, r["env"] is not None, r["s"])[1]
+            k = mat_kernel(r["entry"], NS[r["scene"]], grid, r["mode"], r["s"], r["gloss"], r["cam"] is not None, r["env"] is not None)[1]
             out += [k] * (2 if r["entry"] == "film" else 1)
     return out
 
@@ -290,18 +264,12 @@ def test_rows_are_well_formed():
     assert sum(NS[r["scene"]] == 1030 for r in ROWS) == 6
 
 
-@pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or shutil.which("c++filt") is None,
-                    reason="needs hipcc and c++filt")
+@needs_hipcc
 def test_every_material_kernel_of_the_code_objects_has_a_row():
     """Kernel names only: no instruction is looked at."""
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     other = set()
     for co, count in COUNTS.items():
-        text = open(os.path.join(CSRC, co + ".s")).read()
-        mangled = sorted(set(re.findall(r"^\s*\.amdhsa_kernel (\S+)$", text, re.M)))
-        assert mangled, co
-        demangled = subprocess.run(["c++filt"], input="\n".join(mangled) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-        names = {_kernel_name(d) for d in demangled}
+        names = code_object_kernels(co)
         render = {n for n in names if n.startswith(("render_frame_mat_kernel", "render_paths_mat_kernel", "features_kernel"))}
         other |= names - render
         rowset = {r["kernel"] for r in ROWS if r["co"] == co}
@@ -311,17 +279,6 @@ def test_every_material_kernel_of_the_code_objects_has_a_row():
 
 
 # ---- what a row expects: the restatements ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def host():
-    """The package without a device: scenes, cameras, environments and light tables are host data."""
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import gen_data
-    pkg.gen_data = gen_data
-    return pkg
-
-
 def _camera(pkg, r, aperture=None):
     """aperture: instead of the lens's own."""
     if r["cam"] is None:
@@ -343,16 +300,11 @@ def _params(sc, r, grid=False, **kw):
 
 def _trace_pixels(sc, p, r, cam, env, seed, b, c):
     """materials_ref.trace over the paths of pixels [b, b + c) alone -> (L [3][all paths], zero outside the range; the range's segments)."""
-    from oracle import oracle
     q = oracle_params(p)
-    q.seed = seed
-    s_ = q.samples
-    rays = oracle.gen_rays_counter(q) if cam is None else cr.rays(cr.from_ctypes(cam), q.width, q.height, s_, seed=seed)
-    lo, hi = b * 4 * s_, (b + c) * 4 * s_
-    rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
-    part, bad, seg = mr.trace(rays[:, lo:hi], sc.sph, sc.mat if r["gloss"] else sc.plain, sc.ns, q.depth, q.eps, seed, np.arange(lo, hi, dtype=U),
-                              None if env is None else mr.Env.from_ctypes(env), rr, light=q.light_index, nee=bool(q.flags & mr.FLAG_NEE),
-                              table=sc.table if r["mode"] == "table" else None, gloss=bool(q.flags & mr.FLAG_GLOSS))
+    rays = rays_of(q, cam, seed)
+    lo, hi = b * 4 * q.samples, (b + c) * 4 * q.samples
+    part, bad, seg = mr.trace_params(q, rays[:, lo:hi], sc.sph, sc.mat if r["gloss"] else sc.plain, None if env is None else mr.Env.from_ctypes(env),
+                                     sc.table if r["mode"] == "table" else None, paths=np.arange(lo, hi, dtype=U), seed=seed)
     assert not bad.any()
     L = np.zeros((3, rays.shape[1]), dtype=F)
     L[:, lo:hi] = part
@@ -403,12 +355,10 @@ def want(pkg, r, **change):
     else:
         n = w * h * 4 * s_
         pb, pc = _path_range(r, n)
-        rays = oracle.gen_rays_counter(oracle_params(p))
         q = oracle_params(p)
-        rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
-        L, bad, seg = mr.trace(rays[:, pb:pb + pc], sc.sph, sc.mat if r["gloss"] else sc.plain, sc.ns, q.depth, q.eps, q.seed,
-                               np.arange(pb, pb + pc, dtype=U), None if env is None else mr.Env.from_ctypes(env), rr, light=q.light_index,
-                               nee=bool(q.flags & mr.FLAG_NEE), table=sc.table if r["mode"] == "table" else None, gloss=bool(q.flags & mr.FLAG_GLOSS))
+        rays = rays_of(q, None, q.seed)
+        L, bad, seg = mr.trace_params(q, rays[:, pb:pb + pc], sc.sph, sc.mat if r["gloss"] else sc.plain, None if env is None else mr.Env.from_ctypes(env),
+                                      sc.table if r["mode"] == "table" else None, paths=np.arange(pb, pb + pc, dtype=U))
         assert not bad.any()
         out = (L, seg)
     _WANT[key] = out

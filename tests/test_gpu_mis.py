@@ -1,36 +1,27 @@
 """APT_FLAG_MIS on the GPU (include/render_mi355x.h "Multiple importance sampling"): every kernel of mis.hip -- 24 frame kernels (3 scene
 forms x APT_FLAG_NEE / a light table x 2 groups, each with the decode tail and with the film tail) and 6 buffer kernels -- reached
-through the entry and the parameters that select it and held to the NumPy restatement tests/mis_ref.py: fb bit for bit, fb_u8 exactly,
+through the entry and the parameters that select it and held to the NumPy restatement tests/materials_ref.py: fb bit for bit, fb_u8 exactly,
 the trace counter against the restatement's segments, the status word clean.  Every row's image must also differ from the same launch
 without the flag, so a router that silently ignores the bit fails.
 
-The rows are generated below; kernel_of() restates the routing (materials.hip, pt_mat_launch.h) and names a row's kernel as the ISA
-names it.  One row per kernel (`k` rows), rotating over them: samples 1 / 7 (GROUP 1) and 8 / 9 (GROUP 8), depth 2 / 3 / 4, roulette,
+The rows are generated below; mat_rows.mat_kernel() restates the routing (materials.hip, pt_mat_launch.h) and names a row's kernel as
+the ISA names it.  One row per kernel (`k` rows), rotating over them: samples 1 / 7 (GROUP 1) and 8 / 9 (GROUP 8), depth 2 / 3 / 4, roulette,
 the reference camera / a pinhole / a thin lens, no environment / a sky with the sampled sun, and the scenes -- the 8-sphere lamp room
 whose rough ball is itself a listed light, the 9-sphere room by tiles and behind its grid (built on the host and on the device), the
 1030-sphere scene by tiles and behind its grid.  On top of them the rows that are about one rule: depth 1, a one-light table against
 APT_FLAG_NEE, a table without gloss words, a two-leaf plan, a camera inside a listed light, a table of another scene.
 
 The CPU tests hold the rows to mis.s's kernel list (names only) and to these classes."""
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-import camera_ref as cr
 import film_ref as fr
 import lights_ref as lr
 import materials_ref as mr
-import mis_ref as mi
-from gpu_harness import Scene, apt, assert_bits_equal, bits_equal, dev, inside_lens, inside_pinhole, oracle_params, same, scene, sky_and_sun  # noqa: F401
-from test_gpu_launch_matrix import _kernel_name
+from gpu_harness import Scene, apt, assert_bits_equal, bits_equal, dev, host, inside_lens, inside_pinhole, oracle_params, same, scene, sky_and_sun  # noqa: F401
+from mat_rows import code_object_kernels, mat_kernel, needs_hipcc, rays_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ascendpathtracing_amd", "csrc")
-F, U = np.float32, np.uint64
+F = np.float32
 MODES = ("nee", "table")
 SAMPLES = {1: (1, 7), 8: (8, 9)}
 TWO_LEAVES = 136
@@ -40,17 +31,9 @@ KERNELS = 30
 BIG_ROWS = 6                                  # rows on the 1030-sphere scene: the budget of tests/test_gpu_material_matrix.py
 
 
-def kernel_of(entry, ns, grid, mode, samples):
-    form = 0 if ns == 8 else (2 if grid else 1)
-    scn = form | (8 if mode == "table" else 4) | 32 | 64 | 256
-    if entry == "paths":
-        return f"render_paths_mat_kernel<{scn}>"
-    return f"render_frame_mat_kernel<{scn | 16 | (128 if entry == 'film' else 0)}, {8 if samples >= 8 else 1}>"
-
-
 def _row(var, entry, scene_name, mode, grid=False, s=1, depth=3, rr=False, cam=None, env=None, seed=3, w=16, h=8, builder="host", **extra):
     r = dict(var=var, entry=entry, scene=scene_name, mode=mode, grid=grid, s=s, depth=depth, rr=rr, cam=cam, env=env, seed=seed, w=w, h=h,
-             builder=builder, kernel=kernel_of(entry, NS[scene_name], grid, mode, s), **extra)
+             builder=builder, kernel=mat_kernel(entry, NS[scene_name], grid, mode, s, mis=True)[1], **extra)
     r["id"] = "|".join(str(x) for x in (r["kernel"], var, scene_name + ("+grid" + ("-dev" if builder == "device" else "") if grid else ""), mode,
                                         f"s{s}", f"d{depth}" + ("rr" if rr else ""), cam or "ref", env or "noenv"))
     return r
@@ -98,31 +81,16 @@ def test_rows_are_well_formed():
     assert all(r["w"] * r["h"] <= 128 for r in ROWS)
 
 
-@pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or shutil.which("c++filt") is None,
-                    reason="needs hipcc and c++filt")
+@needs_hipcc
 def test_every_kernel_of_mis_s_has_exactly_one_row():
     """Kernel names only: no instruction is looked at."""
-    subprocess.run(["make", "-s", "-C", CSRC, "mis.s"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(os.path.join(CSRC, "mis.s")).read()
-    mangled = sorted(set(re.findall(r"^\s*\.amdhsa_kernel (\S+)$", text, re.M)))
-    demangled = subprocess.run(["c++filt"], input="\n".join(mangled) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-    names = {_kernel_name(d) for d in demangled}
+    names = code_object_kernels("mis")
     render = sorted(n for n in names if n.startswith(("render_frame_mat_kernel", "render_paths_mat_kernel")))
     assert names - set(render) == {"gen_rays_camera_kernel"}
     assert render == sorted(r["kernel"] for r in K_ROWS) and len(render) == KERNELS
 
 
 # ---- what a row expects ------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def host():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import gen_data
-    pkg.gen_data = gen_data
-    return pkg
-
-
 _SCENES = {}
 
 
@@ -160,55 +128,33 @@ def _params(pkg, sc, r, grid=False, mis=True, mode=None):
                      flags=pkg.APT_FLAG_MIS if mis else 0, **kw)
 
 
-def _rays(pkg, r, q, seed):
-    from oracle import oracle
-    cam = _camera(pkg, r)
-    if cam is None:
-        q = oracle.Params.from_buffer_copy(bytes(q))
-        q.seed = seed
-        return oracle.gen_rays_counter(q)
-    return cr.rays(cr.from_ctypes(cam), q.width, q.height, q.samples, seed=seed)
-
-
 _WANT = {}
 
 
 def want(pkg, r, mis=True, mode=None):
-    """mis_ref's expectation of the row (mis=False: of the same launch without the flag; mode: of another light mode), computed once:
-    frame (fb, u8, segments); film ([planes of pass 0, of pass 1], [segments], clip of pass 0); paths (L, segments)."""
+    """The restatement's expectation of the row (mis=False: of the same launch without the flag; mode: of another light mode), computed
+    once: frame (fb, u8, segments); film ([planes of pass 0, of pass 1], [segments], the frame entry's fb); paths (L, segments)."""
     key = (r["id"], mis, mode)
     if key in _WANT:
         return _WANT[key]
-    from oracle import oracle
     sc = _scene(pkg, r)
-    q = oracle_params(_params(pkg, sc, r, mis=mis, mode=mode))
+    mode = mode or r["mode"]
+    p = _params(pkg, sc, r, mis=mis, mode=mode)
+    q = oracle_params(p)
     mat = sc.plain if r.get("plain") else sc.mat
-    env = None if r["env"] is None else mr.Env.from_ctypes(_env(pkg, r))
-    table = sc.table if (mode or r["mode"]) == "table" else None
-    rr = (q.rr_start or 3) if q.flags & mr.FLAG_RR else 0
-
-    def trace(seed):
-        rays = _rays(pkg, r, q, seed)
-        L, bad, seg = mi.trace(rays, sc.sph, mat, sc.ns, q.depth, q.eps, seed, np.arange(rays.shape[1], dtype=U), env, rr, light=q.light_index,
-                               nee=bool(q.flags & mr.FLAG_NEE), table=table, gloss=bool(q.flags & mr.FLAG_GLOSS), mis=bool(q.flags & mi.FLAG_MIS))
-        assert not bad.any()
-        return L, seg
-
+    cam, env = _camera(pkg, r), _env(pkg, r)
+    menv = None if env is None else mr.Env.from_ctypes(env)
+    table = sc.table if mode == "table" else None
     if r["entry"] == "paths":
-        out = trace(q.seed)
+        L, bad, seg = mr.trace_params(q, rays_of(q, cam, q.seed), sc.sph, mat, menv, table)
+        assert not bad.any()
+        out = (L, seg)
     elif r["entry"] == "frame":
-        L, seg = trace(q.seed)
-        _, fb, u8 = oracle.decode_color(L, q.width, q.height, q.samples)
-        out = (fb, u8, seg)
+        out = sc.frame_ref(p, mode, cam, env, gloss=not r.get("plain"))
     else:
-        planes, segs, clip0 = [], [], None
-        for k in (0, 1):
-            L, seg = trace(fr.pass_seed(q.seed, k))
-            pre, fb, _ = oracle.decode_color(L, q.width, q.height, q.samples)
-            planes.append(np.ascontiguousarray(pre.T).astype(F))
-            segs.append(seg)
-            clip0 = fb if k == 0 else clip0
-        out = (planes, segs, clip0)
+        rays = None if cam is None else (lambda seed: rays_of(q, cam, seed))
+        passes = [fr.render_pass(q, sc.sph, mat, menv, table, pass_index=k, rays=rays) for k in (0, 1)]
+        out = ([planes for planes, _ in passes], [seg for _, seg in passes], sc.frame_ref(p, mode, cam, env, gloss=not r.get("plain"))[0])
     _WANT[key] = out
     return out
 
@@ -242,7 +188,7 @@ def _launch(apt, r, mis=True, mode=None):
         nan = torch.full((3, r["w"] * r["h"]), float("nan"), dtype=torch.float32, device="cuda")     # pass 0 stores over NaN
         snaps, traced = sc.film_passes(p, mode, env, cam, 2, film=nan, checkpoints=(1, 2))
         return [snaps[1], snaps[2]], traced
-    rays = _rays(apt, r, oracle_params(p), p.seed)
+    rays = rays_of(oracle_params(p), cam, p.seed)
     colors = torch.full((3 * rays.shape[1],), float("nan"), dtype=torch.float32, device="cuda")
     d_rays = dev(rays.ravel())
     _, traced = sc._launch(None, env, True, True, lambda: apt.render.render_do_ex(

@@ -1,7 +1,8 @@
-"""CPU-only: APT_FLAG_MIS (include/render_mi355x.h "Multiple importance sampling") -- the restatement tests/mis_ref.py against
-tests/materials_ref.py bit for bit wherever the flag changes nothing, against the float64 quadrature of tests/mis_physics.py (which
-shares no text with it) where it does, its finiteness at the edges of the roughness and of the geometry, the variance it is there to
-remove, and the Python side of the flag.
+"""CPU-only: APT_FLAG_MIS (include/render_mi355x.h "Multiple importance sampling") in the restatement tests/materials_ref.py
+(trace(mis=True)) -- the flagless bytes wherever the flag is not read, the float64 quadrature of tests/mis_physics.py (which shares no
+text with it) where it is, its finiteness at the edges of the roughness and of the geometry, the variance it is there to remove, and the
+Python side of the flag.  What the flag computes, and that the flagless trace is what it was before the flag existed, is held by the
+recorded bytes of tests/test_restatement_frozen.py.
 
 The physics rule: N copies of one ray, |mean - expectation| <= 5 joint standard errors per channel, the joint standard error being
 sqrt(se^2 + quad_err^2) with se the standard error of the mean and quad_err the quadrature's own error (its difference between n and
@@ -14,23 +15,12 @@ import pytest
 import lights_ref as lr
 import materials_ref as mr
 import mis_physics as mp
-import mis_ref as mi
-from gpu_harness import scene, sky_and_sun
+from gpu_harness import host, scene, sky_and_sun  # noqa: F401
 
 F, U = np.float32, np.uint64
 EPS = 1e-4
 QS = {"0.05": 3277, "0.3": 19661, "1-2^-16": 65535}      # gen_data.gloss(alpha)'s q
 N_COPIES = 16384
-
-
-@pytest.fixture(scope="module")
-def host():
-    import __graft_entry__ as g
-    g.build()
-    import ascendpathtracing_amd as pkg
-    from ascendpathtracing_amd import gen_data
-    pkg.gen_data = gen_data
-    return pkg
 
 
 def _bits_equal(a, b):
@@ -44,7 +34,7 @@ def _same(a, b):
 # ---- the flag's Python side ---------------------------------------------------------------------------------------------------------
 def test_the_flag_and_materials_flags(host):
     from ascendpathtracing_amd import _lib
-    assert _lib.APT_FLAG_MIS == 128 == host.APT_FLAG_MIS == mi.FLAG_MIS
+    assert _lib.APT_FLAG_MIS == 128 == host.APT_FLAG_MIS == mr.FLAG_MIS
     gd = host.gen_data
     glossy, plain = [1, gd.gloss(0.3), 0], [1, 2, 0]
     assert gd.gloss(0.05) >> 8 == QS["0.05"] and gd.gloss(0.3) >> 8 == QS["0.3"] and gd.gloss(1 - 2.0 ** -16) >> 8 == QS["1-2^-16"]
@@ -56,13 +46,13 @@ def test_the_flag_and_materials_flags(host):
     assert re.search(r"APT_FLAG_MIS\s*=\s*128u", header) and re.search(r"#define APT_ABI_VERSION\s+3\b", header)
 
 
-# ---- the restatement against materials_ref ------------------------------------------------------------------------------------------
+# ---- where the flag is not read -----------------------------------------------------------------------------------------------------
 def _rays(oracle, ns, w, h, s, depth, seed):
     return oracle.gen_rays_counter(oracle.make_params(w, h, s, depth=depth, num_spheres=ns, seed=seed))
 
 
 @pytest.mark.parametrize("name", ["gloss8-lamp", "gloss9-lamp", "open8", "open40"])
-def test_without_the_flag_the_restatement_is_materials_ref(host, oracle, name):
+def test_where_the_flag_is_not_read_the_result_is_the_flagless_bytes(host, oracle, name):
     sc = scene(host, name)
     env = mr.Env.from_ctypes(sky_and_sun(host, True))
     for depth in (1, 2, 5):
@@ -72,13 +62,11 @@ def test_without_the_flag_the_restatement_is_materials_ref(host, oracle, name):
             for e in (None, env):
                 for rr in (0, 2):
                     a = (rays, sc.sph, sc.mat, sc.ns, depth, EPS, depth, paths, e, rr)
-                    want = mr.trace(*a, **kw)
-                    assert _same(mi.trace(*a, mis=False, **kw), want), (name, depth, kw.keys(), rr)
                     if depth == 1 or not kw:                                   # depth 1, or no light mode: the flag is not read
-                        assert _same(mi.trace(*a, mis=True, **kw), want), (name, depth, kw.keys(), rr)
+                        assert _same(mr.trace(*a, mis=True, **kw), mr.trace(*a, **kw)), (name, depth, kw.keys(), rr)
                     plain = (rays, sc.sph, sc.plain, sc.ns, depth, EPS, depth, paths, e, rr)
-                    assert _same(mi.trace(*plain, mis=True, **kw), mr.trace(*plain, **kw)), (name, depth, "no gloss word")
-                    assert _bits_equal(mi.trace(*a, mis=True, gloss=False, **kw)[0], mr.trace(*a, gloss=False, **kw)[0])   # no APT_FLAG_GLOSS
+                    assert _same(mr.trace(*plain, mis=True, **kw), mr.trace(*plain, **kw)), (name, depth, "no gloss word")
+                    assert _bits_equal(mr.trace(*a, mis=True, gloss=False, **kw)[0], mr.trace(*a, gloss=False, **kw)[0])   # no APT_FLAG_GLOSS
 
 
 @pytest.mark.parametrize("name", ["gloss8-lamp", "gloss9-lamp", "open40"])
@@ -89,8 +77,8 @@ def test_a_one_light_table_is_nee_with_the_flag(host, oracle, name):
     for depth in (2, 3, 5):
         rays = _rays(oracle, sc.ns, 12, 8, 2, depth, 7 + depth)
         a = (rays, sc.sph, sc.mat, sc.ns, depth, EPS, 7 + depth, np.arange(rays.shape[1], dtype=U), None, 2 if depth == 5 else 0)
-        nee = mi.trace(*a, light=sc.light, nee=True, mis=True)
-        assert _same(mi.trace(*a, table=one, mis=True), nee), (name, depth)
+        nee = mr.trace(*a, light=sc.light, nee=True, mis=True)
+        assert _same(mr.trace(*a, table=one, mis=True), nee), (name, depth)
         assert np.isfinite(nee[0]).all()
         changed += not _bits_equal(nee[0], mr.trace(*a, light=sc.light, nee=True)[0])
     assert changed, "the flag changed no image of this scene"
@@ -109,7 +97,7 @@ def test_both_estimators_have_the_quadrature_as_their_mean(alpha, mode):
     kw = dict(light=mp.LAMP, nee=True) if mode == "nee" else dict(table=lr.build_table(table, 2, [mp.LAMP]))
     se = {}
     for mis in (False, True):
-        L, bad, _ = mi.trace(rays, table, mat, 2, 2, EPS, 5, np.arange(N_COPIES, dtype=U), mis=mis, **kw)
+        L, bad, _ = mr.trace(rays, table, mat, 2, 2, EPS, 5, np.arange(N_COPIES, dtype=U), mis=mis, **kw)
         assert not bad.any() and np.isfinite(L).all()
         L = L.astype(np.float64)
         mean, se[mis] = L.mean(axis=1), L.std(axis=1, ddof=1) / math.sqrt(N_COPIES)
@@ -147,7 +135,7 @@ def test_every_colour_is_finite_at_the_edges(q, lamp):
     n = rays.shape[1]
     for kw in (dict(light=mp.LAMP, nee=True), dict(table=lr.build_table(table, 2, [mp.LAMP, mp.BALL]))):
         for depth, rr in ((2, 0), (4, 2)):
-            L, bad, seg = mi.trace(rays, table, mat, 2, depth, EPS, 9, np.arange(n, dtype=U), None, rr, mis=True, **kw)
+            L, bad, seg = mr.trace(rays, table, mat, 2, depth, EPS, 9, np.arange(n, dtype=U), None, rr, mis=True, **kw)
             assert not bad.any() and np.isfinite(L).all() and (L >= 0).all(), (q, lamp, depth)
             assert seg > 0 and L.any()
 
@@ -173,7 +161,7 @@ def test_the_flag_removes_the_variance_of_a_small_lamps_highlight(oracle):
             cover = oracle.decode_color(np.tile((k == mp.BALL).astype(F), (3, 1)), w, h, s)[0][:, 0] == 1.0
             assert cover.sum() >= 8
         for mis in (False, True):
-            L, bad, _ = mi.trace(rays, table, mat, 2, 2, EPS, seed, np.arange(n, dtype=U), light=mp.LAMP, nee=True, mis=mis)
+            L, bad, _ = mr.trace(rays, table, mat, 2, 2, EPS, seed, np.arange(n, dtype=U), light=mp.LAMP, nee=True, mis=mis)
             assert not bad.any() and np.isfinite(L).all()
             pre[mis].append(oracle.decode_color(L, w, h, s)[0][cover])          # the float64 mean before the clip, per pixel
     var = {m: float(np.array(pre[m]).var(axis=0, ddof=1).sum()) for m in pre}
