@@ -162,6 +162,18 @@ ADAPTIVE_PROTOTYPES = {
     "apt_film_adaptive_last_error": (S, []),
 }
 
+# libhistory_mi355x.so (include/render_mi355x_history.h), the fourth library: its prototypes by the same rules, in its header's order.
+# tests/test_history_cpu.py holds the table to that header and to the library's exports.
+HISTORY_LIB_PATH = os.environ.get("APT_HISTORY_LIB_PATH") or os.path.join(_HERE, "libhistory_mi355x.so")
+HISTORY_PROTOTYPES = {
+    "apt_film_history_default_host": (I, [P]),
+    "apt_film_history_device": (I, [P, P, P, P, P, P, P, P, U32, U32, P]),
+    "apt_film_history_host": (I, [P, P, P, P, P, P, P, U32, U32, P]),
+    "apt_film_history_export_device": (I, [P, P, U64, P, P]),
+    "apt_film_history_export_host": (I, [P, U64, P, P]),
+    "apt_film_history_last_error": (S, []),
+}
+
 
 class AptError(RuntimeError):
     pass
@@ -267,6 +279,24 @@ def film_select_record(base_passes, **fields):
     return rec
 
 
+class ApFilmHistory(ctypes.Structure):
+    """apt_film_history (include/render_mi355x_history.h): the clamp of the history length, the plane and normal tolerances of a
+    reprojected tap and the least accepted bilinear weight of a valid pixel."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_history", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("tol_plane", ctypes.c_float), ("tol_normal", ctypes.c_float), ("min_weight", ctypes.c_float)]
+
+
+def film_history_record(**fields):
+    """apt_film_history_default_host's record, with any of max_history, tol_plane, tol_normal, min_weight replaced."""
+    rec = ApFilmHistory()
+    history_check(history_lib().apt_film_history_default_host(ctypes.byref(rec)), "apt_film_history_default_host")
+    for k, v in fields.items():
+        if k not in ("max_history", "tol_plane", "tol_normal", "min_weight"):
+            raise AptError(f"film_history_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 _lib = None
 
 
@@ -341,6 +371,33 @@ def adaptive_lib():
     return _adaptive_lib
 
 
+_history_lib = None
+
+
+def history_lib():
+    """The loaded libhistory_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
+    global _history_lib
+    if _history_lib is None:
+        if not os.path.exists(HISTORY_LIB_PATH):
+            raise AptError(f"{HISTORY_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
+        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
+        try:
+            h = ctypes.CDLL(HISTORY_LIB_PATH)
+        except OSError as e:
+            raise AptError(f"cannot load {HISTORY_LIB_PATH}: {e}") from e
+        for name, (restype, argtypes) in HISTORY_PROTOTYPES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _history_lib = h
+    return _history_lib
+
+
+def history_check(rc, what):
+    if rc != APT_OK:
+        raise AptError(f"{what} failed ({rc}): {history_lib().apt_film_history_last_error().decode()}")
+
+
 def adaptive_check(rc, what):
     if rc != APT_OK:
         raise AptError(f"{what} failed ({rc}): {adaptive_lib().apt_film_adaptive_last_error().decode()}")
@@ -361,7 +418,8 @@ def build_id():
     files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")))
     files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map"), os.path.join(os.path.dirname(_HERE), "include", "render_mi355x.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h")]
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h"),
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_history.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

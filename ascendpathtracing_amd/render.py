@@ -470,6 +470,93 @@ def film_denoise(record, film, moments, features, width, height, work=None, out=
     return out
 
 
+def film_history(record, cur, cur_features, cur_cam, out_hist, prev=None, stream=None):
+    """apt_film_history_device (libhistory_mi355x.so, include/render_mi355x_history.h): the history of the previous frame -- prev =
+    (prev_hist float32 [6][N], prev_features [APT_FEATURE_PLANES][N], prev_cam), None: the first frame -- reprojected to the surfaces
+    the current camera `cur_cam` (an ApCamera) sees and blended with `cur`, the current frame's MEAN radiance [3][N], by `record`
+    (_lib.film_history_record) -> out_hist float32 [6][N], a (width, height) image given by out_hist's shape (6, width, height).
+    Returns out_hist; not synchronised."""
+    require_gpu()
+    if not (isinstance(out_hist, torch.Tensor) and out_hist.dim() == 3 and out_hist.shape[0] == 6):
+        raise _lib.AptError("out_hist must have the shape (6, width, height)")
+    width, height = int(out_hist.shape[1]), int(out_hist.shape[2])
+    n = width * height
+    p_hist, p_feat, p_cam = (None, None, None) if prev is None else prev
+    _lib.history_check(_lib.history_lib().apt_film_history_device(
+        ctypes.byref(record), _stream_handle(stream), ctypes.byref(cur_cam), None if p_cam is None else ctypes.byref(p_cam),
+        _dev_f32(cur, "cur", 3 * n), _dev_f32(cur_features, "cur_features", _lib.APT_FEATURE_PLANES * n),
+        None if p_feat is None else _dev_f32(p_feat, "prev_features", _lib.APT_FEATURE_PLANES * n),
+        None if p_hist is None else _dev_f32(p_hist, "prev_hist", 6 * n), width, height, _dev_f32(out_hist, "out_hist", 6 * n)),
+        "apt_film_history_device")
+    return out_hist
+
+
+def film_history_export(hist, film=None, moments=None, stream=None):
+    """apt_film_history_export_device: a history buffer [6][N] as the (film [3][N], moments [2][N]) pair that film_denoise takes with a
+    record of passes = 2 (None: new tensors).  Not synchronised."""
+    require_gpu()
+    n = hist.numel() // 6
+    if film is None:
+        film = torch.empty((3, n), dtype=torch.float32, device=hist.device)
+    if moments is None:
+        moments = torch.empty((2, n), dtype=torch.float32, device=hist.device)
+    _lib.history_check(_lib.history_lib().apt_film_history_export_device(
+        _stream_handle(stream), _dev_f32(hist, "hist", 6 * n), n, _dev_f32(film, "film", 3 * n), _dev_f32(moments, "moments", 2 * n)),
+        "apt_film_history_export_device")
+    return film, moments
+
+
+class History:
+    """Temporal accumulation over the frames of a moving camera (include/render_mi355x_history.h): push(mean, features, camera) blends
+    one more frame -- Film.mean() and Film.features() of a film rendered with `camera` -- into the history reprojected from the frame
+    before.  Owns the two ping-pong history buffers, the previous features and the previous camera.  `frames`: how many were pushed
+    since the last reset()."""
+
+    def __init__(self, width, height, device="cuda", **record_fields):
+        self.width, self.height = width, height
+        self.record = _lib.film_history_record(**record_fields)
+        self._hist = [torch.empty((6, width, height), dtype=torch.float32, device=device) for _ in range(2)]
+        self._features = self._camera = None
+        self.frames = 0
+
+    def reset(self):
+        """Forget the history: the next push is a first frame."""
+        self.frames = 0
+        self._features = self._camera = None
+
+    def push(self, mean, features, camera=None, stream=None):
+        """One more frame: mean float32 [3][N], features [APT_FEATURE_PLANES][N] (kept by reference until the next push: hand over a
+        tensor that is not written again), camera an ApCamera (None: apt_camera_default_host's record, what a frame without a
+        context camera is rendered from).  Returns self; not synchronised."""
+        from . import gen_data
+        cam = gen_data.default_camera(self.width, self.height) if camera is None else camera.copy()
+        out = self._hist[self.frames & 1]
+        prev = None if self.frames == 0 else (self._hist[(self.frames - 1) & 1], self._features, self._camera)
+        film_history(self.record, mean, features, cam, out, prev, stream)
+        self._features, self._camera = features, cam
+        self.frames += 1
+        return self
+
+    @property
+    def buffer(self):
+        """The current history, float32 (6, width, height)."""
+        if self.frames == 0:
+            raise _lib.AptError("History: no frame was pushed")
+        return self._hist[(self.frames - 1) & 1]
+
+    def radiance(self):
+        """The accumulated mean radiance, float32 [3][N]: a view of the current buffer; Film.resolve(source=...) takes it."""
+        return self.buffer[:3].reshape(3, -1)
+
+    def length(self):
+        """The per-pixel history length, float32 [N]: a view."""
+        return self.buffer[5].reshape(-1)
+
+    def denoise_inputs(self, stream=None):
+        """-> (film [3][N], moments [2][N]) for render.film_denoise with _lib.film_denoise_record(2) and the last pushed features."""
+        return film_history_export(self.buffer, stream=stream)
+
+
 class Film:
     """An unclipped float32 accumulation buffer for the pixels [pixel_begin, pixel_begin + pixel_count) of a width x height image
     (include/render_mi355x.h "film"): add_pass renders one more independent frame into it, resolve turns the mean into a displayable
