@@ -5,9 +5,10 @@
 // v_pk_*_f32 is two operations for one slot.  The intersections are already packed (two spheres per
 // instruction); the shading step of ONE path only fills the second half for the x/y components.  With two
 // paths A and B in a lane, every register pair holds (A, B) of one quantity and the whole shading step runs
-// packed: 36 instead of 48 instructions per path and bounce.  The intersections stay as they are -- eight
-// spheres in four packed pairs per path, reading ray component A or B out of its pair through op_sel (free) --
-// and run for A, then for B, so the scalar arg-min masks of A are consumed before B needs the registers.
+// packed: 36 instead of 48 instructions per path and bounce.  The intersections of the general form stay as they are -- eight
+// spheres in four packed pairs per path, reading ray component A or B out of its pair through op_sel (free) -- and run for A, then
+// for B, so the scalar arg-min masks of A are consumed before B needs the registers.  A table that shares planes is intersected for
+// both paths at once, one sphere per instruction (intersect2_ns8_planes below).
 //
 // Same arithmetic as bounce_ns8_v2 (pt_trace.h), operation for operation: v_pk_{add,mul,fma}_f32 round each half
 // like the scalar instruction.  Used for the frame kernel without APT_FLAG_RETIRE and APT_FLAG_RR only.
@@ -18,25 +19,12 @@
 
 namespace {
 
-// The sphere pairs whose root stage a wave of the two-path bounce branches round when none of its lanes can hit either sphere
-// (intersect_ns8_v2's SKIP; bit j = pair (2j, 2j+1)).  Decided by counting (profiles/pair_skip_counts.json):
-//   * pair (6,7) of a table that shares planes -- the reference scene's mirror ball and light: a whole wave misses both in 81 % of its
-//     first bounces and 45 % of all eight, where the test (2 VALU) pays from 10 % on;
-//   * no wall pair: a ray inside the room always has one of two opposite walls in front of it (0 of 4.1 million waves);
-//   * nothing in the general form: its pairing is whatever the table's order makes it (bench.py's general scene: 0 for every pair);
-//   * not path B of the LAST bounce: with that one the headline kernel keeps two VGPRs in scratch (at 12 % there it would pay nothing).
-// From the second bounce on, pair (6,7) takes the per-sphere form with the ray's direction (SKIP bit 7; profiles/pair67_split_counts.json):
-// whatever way a ray points, its line crosses the light's sphere (r = 600) for a large share of the room, so "both discriminants negative"
-// falls from 0.81 to 0.12 of the waves over eight bounces, while no lane can reach the ball in 0.97 .. 0.81 of them and neither sphere in
-// 0.85 .. 0.51; a wave then solves the light alone (0.06 .. 0.31), the ball alone (0.03 .. 0.10) or both (0.00 .. 0.13).  Camera rays
-// (FIRST) gain nothing from the direction -- the counts of the two predicates agree to four digits there -- and keep the two-instruction
-// test.  Path B of the last bounce stays off: the per-sphere form puts the same two VGPRs of the headline kernel into scratch.
-template <bool PLANES, bool FIRST> constexpr int kPairSkip = !PLANES ? 0 : FIRST ? 0x8 : 0x80;
-template <bool PLANES, bool FIRST> constexpr int kPairSkipLastB = 0;
-
 struct PathPair { // .x = path A, .y = path B
     f2 ox, oy, oz, dx, dy, dz; // rays
     f2 rx, ry, rz;             // throughputs
+#ifdef APT_COUNT_PAIR_SKIP
+    uint32_t hitA, hitB;       // measurement build only: table offset (index * 16) of the sphere each path has just left, ~0u when unknown
+#endif
 };
 
 // first: the pair has no throughputs yet -- path_init's (1, 1, 1) and alive = 1 stand
@@ -51,6 +39,133 @@ __device__ __forceinline__ PathState unpack_path(const PathPair &p, int which, u
     return s;
 }
 
+// One path's arg-min state of the (A, B)-packed intersection below: intersect_ns8_v2's best / b0 / b1 / b2 / any, its key update and
+// its tail, statement for statement.
+template <int MODE>
+struct ArgMin8 {
+    uint32_t best;
+    uint64_t b0 = 0, b1 = 0, b2 = 0, any = 0;
+    __device__ __forceinline__ void update64(uint64_t keys, int k) {
+        const uint32_t nb = min3_u32(best, (uint32_t)keys, (uint32_t)(keys >> 32));
+        const uint64_t better = __builtin_amdgcn_ballot_w64(nb != best); // strict '<': lowest index wins ties
+        best = nb;
+        b0 = (k & 1) ? (b0 | better) : (b0 & ~better);
+        b1 = (k & 2) ? (b1 | better) : (b1 & ~better);
+        b2 = (k & 4) ? (b2 | better) : (b2 & ~better);
+        if (MODE == kModeOracle) any |= better;
+    }
+    __device__ __forceinline__ Hit8 finish(const TraceArgs &ta, const KeyConsts &kc) {
+        const float tmin = bits_f32(best + kc.bias);
+        if (MODE == kModeOracle) { b0 |= ~any; b1 |= ~any; b2 |= ~any; }
+        uint32_t addr;
+        {
+            const uint32_t a0 = select_const(b0, 16), a1 = select_const(b1, 32), a2 = select_const(b2, 64);
+            asm("v_or3_b32 %0, %1, %2, %3" : "=v"(addr) : "v"(a0), "v"(a1), "v"(a2));
+        }
+        uint64_t light_mask = __builtin_amdgcn_ballot_w64(addr == (uint32_t)ta.light * 16u);
+        if (MODE == kModeOracle) light_mask &= any;
+        return Hit8{tmin, addr, light_mask};
+    }
+};
+
+// (c, c) - v and v - (c, c), c = half HALF of a scalar register pair: v_pk_add_f32 with the constant broadcast by op_sel.  Left to the
+// compiler a broadcast scalar becomes an SGPR pair (c, c) of its own -- two registers per constant, twice what the kernel has.
+template <int HALF>
+__device__ __forceinline__ f2 pair_half_minus(f2 cpair, f2 v) {
+    f2 r;
+    if (HALF == 0) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "s"(cpair), "v"(v));
+    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "s"(cpair), "v"(v));
+    return r;
+}
+template <int HALF>
+__device__ __forceinline__ f2 minus_pair_half(f2 v, f2 cpair) {
+    f2 r;
+    if (HALF == 0) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(v), "s"(cpair));
+    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(v), "s"(cpair));
+    return r;
+}
+
+// The spheres whose root stage the (A, B)-packed intersection puts behind the joint test (bit k = sphere k).  Decided by counting
+// (profiles/ab_stage_counts.json; one C2 frame, per bounce the share of the waves in which no lane can reach
+// the sphere in either path): the ball 0.970 .. 0.795 and the light 0.844 .. 0.539 over eight bounces, at every bounce site, path B
+// of the last bounce included (this form compiles without scratch there); no wall -- the room lies INSIDE every wall's sphere
+// (c < 0), so a wall is never behind a ray that is in the room: 0 of 4.1 million waves for spheres 2 .. 5, and 0.117 for the side
+// walls (waves whose paths have all left the room), below the break-even of 0.14.  The general form has no test: the one-path
+// intersection's SKIP forms (pt_trace.h), which the two-path bounce used for pair (6,7) before, are off for every caller now.
+constexpr int kAbSkip = 0xC0;
+
+// The intersection half of a bounce for BOTH paths of a lane, shared-planes form: every packed instruction works on the (A, B) pair
+// of one quantity of ONE sphere, the sphere's constant broadcast from its SGPR.  Per path and sphere the operations are
+// intersect_pre_planes_pairs' and intersect_ns8_v2's full stage, in the same order -- cx - o, its product with d and its square
+// once per DISTINCT coordinate (13 of them: 39 packed instructions for both paths), b = (px + py) + pz, c = ((qx + qy) + qz) - r2,
+// disc = b*b - c (7 per sphere), then v_rsq_f32 per path, sqrt_rsq_step on the pair, root_pair<0> / <1> = path A's / path B's
+// (-t0, t1), one 64-bit add, v_min3_u32 and a compare each -- and the spheres are taken in ascending index, so each path's key
+// updates happen in intersect_ns8_v2's order and the strict-'<', lowest-index-wins rule holds as there.  What changes is which
+// operations share an instruction, and a packed operation rounds each half like the scalar one.
+// SKIP, bit k: sphere k's root stage is branched round (a scalar branch on an opaque flag) when, in every lane and for path A and
+// path B, sphere_reachable_mask()'s statement holds: disc < 0 or NaN, or b < -2^-60 and c > 2^-60.  Its exactness argument (above
+// intersect_ns8_v2's SKIP) is per path and per sphere and carries over unchanged: such a sphere's keys are >= key(kMissT) in both
+// paths, its v_min3_u32 would not have changed either `best`, and its compares would have set no bit.  Two v_med3_f32, one
+// v_max_f32 (a NaN drops out: a path whose med3 is NaN is outside the mask, as it is in the one-path form) and one compare.
+// amin: per path, |disc| of the walls two spheres per instruction as before; a skipped sphere's share is left out (it could only
+// have asked for the exact re-run, which finds the same miss).
+template <int MODE, int SKIP>
+__device__ __forceinline__ void intersect2_ns8_planes(const Scene8 &sc, const PathPair &s, const TraceArgs &ta, const KeyConsts &kc,
+                                                      float &aminA, float &aminB, Hit8 &hA, Hit8 &hB) {
+    struct Term { f2 p, q; };   // (c - o) * d and (c - o)^2 of one centre coordinate, both paths
+    auto term = [](auto half, f2 cpair, f2 o, f2 d) __attribute__((always_inline)) {
+        const f2 t = pair_half_minus<decltype(half)::value>(cpair, o);
+        return Term{t * d, t * t};
+    };
+    struct Pre { f2 b, c, disc; };
+    auto pre = [](const Term &x, const Term &y, const Term &z, auto half, f2 r2pair) __attribute__((always_inline)) {
+        Pre h;
+        h.b = (x.p + y.p) + z.p;
+        h.c = minus_pair_half<decltype(half)::value>((x.q + y.q) + z.q, r2pair);
+        h.disc = h.b * h.b - h.c;
+        return h;
+    };
+    ArgMin8<MODE> A, B;
+    A.best = kc.init; B.best = kc.init;
+    auto stage = [&](const Pre &h, int k) __attribute__((always_inline)) {
+        const f2 q = sqrt_rn_rsq1_pair(h.disc);
+        A.update64(root_pair<0>(h.b, q) + kc.nbias2, k);
+        B.update64(root_pair<1>(h.b, q) + kc.nbias2, k);
+    };
+    auto walls = [&](const Pre &h0, const Pre &h1, int k) __attribute__((always_inline)) {
+        aminA = minimum3_abs(aminA, h0.disc.x, h1.disc.x);
+        aminB = minimum3_abs(aminB, h0.disc.y, h1.disc.y);
+        stage(h0, k);
+        stage(h1, k + 1);
+    };
+    auto tested = [&](const Pre &h, int k) __attribute__((always_inline)) {
+        if ((SKIP >> k) & 1) {
+            const float mA = __builtin_amdgcn_fmed3f(h.disc.x, h.b.x, -h.c.x), mB = __builtin_amdgcn_fmed3f(h.disc.y, h.b.y, -h.c.y);
+            uint32_t run = any_lane(__builtin_amdgcn_ballot_w64(__builtin_fmaxf(mA, mB) >= -kBehindGuard));
+            asm("" : "+s"(run));
+            if (run == 0u) return;
+        }
+        aminA = minimum3_abs(aminA, h.disc.x, h.disc.x);
+        aminB = minimum3_abs(aminB, h.disc.y, h.disc.y);
+        stage(h, k);
+    };
+    static_assert((SKIP & 0x3F) == 0, "the walls have no test: the room lies inside their spheres");
+    // the scalar pairs of intersect_pre_planes(): every constant is one half of an aligned SGPR pair
+    const f2 X1 = {sc.cx[0], sc.cx[1]}, X2 = {sc.cx[2], sc.cx[6]}, Y1 = {sc.cy[4], sc.cy[5]}, Y2 = {sc.cy[6], sc.cy[7]}, Y3 = {sc.cy[0], sc.cy[0]};
+    const f2 Z1 = {sc.cz[2], sc.cz[3]}, Z2 = {sc.cz[0], sc.cz[6]};
+    const f2 R0 = {sc.r2[0], sc.r2[1]}, R1 = {sc.r2[2], sc.r2[3]}, R2 = {sc.r2[4], sc.r2[5]}, R3 = {sc.r2[6], sc.r2[7]};
+    using Lo = std::integral_constant<int, 0>;
+    using Hi = std::integral_constant<int, 1>;
+    const Term x2 = term(Lo{}, X2, s.ox, s.dx), y0 = term(Lo{}, Y3, s.oy, s.dy), z0 = term(Lo{}, Z2, s.oz, s.dz);   // the shared planes
+    walls(pre(term(Lo{}, X1, s.ox, s.dx), y0, z0, Lo{}, R0), pre(term(Hi{}, X1, s.ox, s.dx), y0, z0, Hi{}, R0), 0);
+    walls(pre(x2, y0, term(Lo{}, Z1, s.oz, s.dz), Lo{}, R1), pre(x2, y0, term(Hi{}, Z1, s.oz, s.dz), Hi{}, R1), 2);
+    walls(pre(x2, term(Lo{}, Y1, s.oy, s.dy), z0, Lo{}, R2), pre(x2, term(Hi{}, Y1, s.oy, s.dy), z0, Hi{}, R2), 4);
+    tested(pre(term(Hi{}, X2, s.ox, s.dx), term(Lo{}, Y2, s.oy, s.dy), term(Hi{}, Z2, s.oz, s.dz), Lo{}, R3), 6);
+    tested(pre(x2, term(Hi{}, Y2, s.oy, s.dy), z0, Hi{}, R3), 7);
+    hA = A.finish(ta, kc);
+    hB = B.finish(ta, kc);
+}
+
 // One bounce of both paths.  aliveA / aliveB: wave masks (in: before, out: after).  redoA / redoB: wave masks of
 // the lanes whose path A / B left the validity range of the fast sequences.  `ones_off`: byte offset, relative to the albedo
 // table, of an entry (1, 1, 1) -- a path that is no longer alive multiplies its throughput by it (x1 is exact).
@@ -62,8 +177,13 @@ __device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, 
                                               const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                               uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f; // per path: a finished path's request for the exact form can be ignored (trace2_ns8)
-    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES, FIRST>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
-    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES, FIRST>>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    Hit8 hA, hB;
+    if (PLANES) {
+        intersect2_ns8_planes<MODE, kAbSkip>(sc, s, ta, kc, aminA, aminB, hA, hB);
+    } else {
+        hA = intersect_ns8_v2<MODE>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+        hB = intersect_ns8_v2<MODE>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    }
     if (FIRST) {
         aliveA = ~hA.light;
         aliveB = ~hB.light;
@@ -133,6 +253,9 @@ __device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, 
     // something too small, len2 > 2^60, or a NaN; or the reciprocal of an all-ones divisor that did not converge
     redoA = __builtin_amdgcn_ballot_w64(!(aminA >= kFastMin)) | __builtin_amdgcn_ballot_w64(e1.x == kDiv3SeededStuck);
     redoB = __builtin_amdgcn_ballot_w64(!(aminB >= kFastMin)) | __builtin_amdgcn_ballot_w64(e1.y == kDiv3SeededStuck);
+#ifdef APT_COUNT_PAIR_SKIP
+    n.hitA = hA.addr; n.hitB = hB.addr;
+#endif
 }
 template <int MODE, bool PLANES>
 __device__ __forceinline__ void bounce2_ns8(const Scene8 &sc, const Tab8 tab, const PathPair &s, PathPair &n,
@@ -157,8 +280,13 @@ __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 ta
                                                  const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
                                                  uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
     float aminA = 1.0f, aminB = 1.0f;
-    const Hit8 hA = intersect_ns8_v2<MODE, PLANES, kPairSkip<PLANES, FIRST>>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
-    const Hit8 hB = intersect_ns8_v2<MODE, PLANES, kPairSkipLastB<PLANES, FIRST>>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    Hit8 hA, hB;
+    if (PLANES) {
+        intersect2_ns8_planes<MODE, kAbSkip>(sc, s, ta, kc, aminA, aminB, hA, hB);
+    } else {
+        hA = intersect_ns8_v2<MODE>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
+        hB = intersect_ns8_v2<MODE>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
+    }
     if (FIRST) {
         aliveA = ~hA.light;
         aliveB = ~hB.light;
@@ -249,6 +377,57 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
                 }
             }
         }
+        if (PLANES) {   // per SPHERE, over the lane's two paths together (profiles/ab_stage_counts.json): the block then needs 424 entries.
+            // With bb = min(bounce, 7), one per wave in which, in all 64 lanes and for path A and path B, sphere k
+            //   [136 + bb * 8 + k]  cannot be hit by sphere_reachable_mask()'s statement: disc < 0 or NaN, or b < -2^-60 and c > 2^-60
+            //   [200 + bb * 8 + k]  the same with the relaxed guard c >= 0
+            //   [264 + bb * 8 + k]  has b < -2^-60 and c > 2^-60 (the form that reads no discriminant)
+            //   [328 + bb * 8 + k]  has b < -2^-60 and c >= 0
+            // and, from the second bounce on, [392 + bb * 4 + j] per wave whose 128 paths have all just left ONE wall w (sphere 0 .. 5):
+            //   j = 0 every such wave;  1: w passes the first statement;  2: w passes the relaxed one;  3: the wall opposite w passes the first.
+            // b, c and disc are intersect_pre2's, operation for operation (the shared-planes form computes the same per sphere).
+            const uint32_t bb = count_bounce < 7u ? count_bounce : 7u;
+            auto bcd = [&](int k, float ox, float oy, float oz, float dx, float dy, float dz, float &b, float &c, float &disc) {
+                const float x = sc.cx[k] - ox, y = sc.cy[k] - oy, z = sc.cz[k] - oz;
+                b = x * dx; b = b + y * dy; b = b + z * dz;
+                c = x * x; c = c + y * y; c = c + z * z; c = c - sc.r2[k];
+                disc = b * b; disc = disc - c;
+            };
+            bool strict[8], relaxed[8];
+            for (int k = 0; k < 8; ++k) {
+                float bA, cA, dA, bB, cB, dB;
+                bcd(k, in.ox.x, in.oy.x, in.oz.x, in.dx.x, in.dy.x, in.dz.x, bA, cA, dA);
+                bcd(k, in.ox.y, in.oy.y, in.oz.y, in.dx.y, in.dy.y, in.dz.y, bB, cB, dB);
+                const bool behindA = bA < -kBehindGuard, behindB = bB < -kBehindGuard;
+                const bool reach_s = __builtin_amdgcn_fmed3f(dA, bA, -cA) >= -kBehindGuard || __builtin_amdgcn_fmed3f(dB, bB, -cB) >= -kBehindGuard;
+                const bool reach_r = (dA >= 0.0f && !(behindA && cA >= 0.0f)) || (dB >= 0.0f && !(behindB && cB >= 0.0f));
+                const bool reach_ns = !(behindA && cA > kBehindGuard && behindB && cB > kBehindGuard);
+                const bool reach_nr = !(behindA && cA >= 0.0f && behindB && cB >= 0.0f);
+                strict[k] = __builtin_amdgcn_ballot_w64(reach_s) == 0;
+                relaxed[k] = __builtin_amdgcn_ballot_w64(reach_r) == 0;
+                if (strict[k] && lane0) atomicAdd(ta.traced + 136u + bb * 8u + (uint32_t)k, 1ull);
+                if (relaxed[k] && lane0) atomicAdd(ta.traced + 200u + bb * 8u + (uint32_t)k, 1ull);
+                if (__builtin_amdgcn_ballot_w64(reach_ns) == 0 && lane0) atomicAdd(ta.traced + 264u + bb * 8u + (uint32_t)k, 1ull);
+                if (__builtin_amdgcn_ballot_w64(reach_nr) == 0 && lane0) atomicAdd(ta.traced + 328u + bb * 8u + (uint32_t)k, 1ull);
+            }
+            if (count_bounce > 0) {
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)in.hitA);
+                if (w < 6u * 16u && __builtin_amdgcn_ballot_w64(in.hitA != w || in.hitB != w) == 0) {
+                    const uint32_t k = w / 16u;
+                    bool s = false, r = false, opp = false;
+                    for (uint32_t j = 0; j < 6; ++j) {   // (wave-uniform selects: the arrays stay in registers)
+                        if (j == k) { s = strict[j]; r = relaxed[j]; }
+                        if (j == (k ^ 1u)) opp = strict[j];
+                    }
+                    if (lane0) {
+                        atomicAdd(ta.traced + 392u + bb * 4u, 1ull);
+                        if (s) atomicAdd(ta.traced + 393u + bb * 4u, 1ull);
+                        if (r) atomicAdd(ta.traced + 394u + bb * 4u, 1ull);
+                        if (opp) atomicAdd(ta.traced + 395u + bb * 4u, 1ull);
+                    }
+                }
+            }
+        }
         if (count_bounce == 0 && lane0) atomicAdd(ta.traced + 68, 1ull);
         ++count_bounce;
     };
@@ -273,6 +452,9 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
             out.rx = f2{na.rxy.x, nb.rxy.x}; out.ry = f2{na.rxy.y, nb.rxy.y}; out.rz = f2{na.rz, nb.rz};
             oa = __builtin_amdgcn_ballot_w64(na.alive != 0);
             ob = __builtin_amdgcn_ballot_w64(nb.alive != 0);
+#ifdef APT_COUNT_PAIR_SKIP
+            out.hitA = ~0u; out.hitB = ~0u;   // the exact form does not say which sphere it hit: such a wave counts under no wall
+#endif
         }
         aliveA = oa; aliveB = ob;
     };
@@ -327,8 +509,18 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
 // `planes`: scene8_shares_planes(sc), evaluated once per wave by the kernel (wave-uniform branch around two copies of the loop)
 template <int MODE>
 __device__ __forceinline__ void trace2_ns8(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta, bool planes) {
-    if (planes) trace2_ns8_t<MODE, true>(sc, tab, s, ta);
-    else trace2_ns8_t<MODE, false>(sc, tab, s, ta);
+    if (planes) {
+        // scene8_shares_planes() compared these bit for bit: naming each shared coordinate ONCE lets this arm -- its exact cold block
+        // included -- keep 13 centre coordinates in scalar registers instead of 24 (the (A, B)-packed intersection holds both paths'
+        // index accumulators at once and has no room for the rest).
+        Scene8 p = sc;
+        p.cx[3] = p.cx[4] = p.cx[5] = p.cx[7] = sc.cx[2];
+        p.cy[1] = p.cy[2] = p.cy[3] = sc.cy[0];
+        p.cz[1] = p.cz[4] = p.cz[5] = p.cz[7] = sc.cz[0];
+        trace2_ns8_t<MODE, true>(p, tab, s, ta);
+    } else {
+        trace2_ns8_t<MODE, false>(sc, tab, s, ta);
+    }
 }
 
 } // namespace
