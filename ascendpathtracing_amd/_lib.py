@@ -174,6 +174,24 @@ HISTORY_PROTOTYPES = {
     "apt_film_history_last_error": (S, []),
 }
 
+# libpost_mi355x.so (include/render_mi355x_post.h), the fifth library: its prototypes by the same rules, in its header's order; a float
+# parameter is F32.  tests/test_post_cpu.py holds the table to that header and to the library's exports.
+F32 = ctypes.c_float
+APT_METER_BINS, APT_METER_WORDS = 256, 257
+POST_LIB_PATH = os.environ.get("APT_POST_LIB_PATH") or os.path.join(_HERE, "libpost_mi355x.so")
+POST_PROTOTYPES = {
+    "apt_film_meter_default_host": (I, [P, U32]),
+    "apt_film_meter_work_words": (U64, [U64]),
+    "apt_film_meter_device": (I, [P, P, P, U64, P, P]),
+    "apt_film_meter_host": (I, [P, P, U64, P]),
+    "apt_film_exposure_host": (I, [P, P, F32, P]),
+    "apt_film_bloom_default_host": (I, [P, U32]),
+    "apt_film_bloom_work_floats": (U64, [U32, U32, U32]),
+    "apt_film_bloom_device": (I, [P, P, P, U32, U32, P, P]),
+    "apt_film_bloom_host": (I, [P, P, U32, U32, P, P]),
+    "apt_film_post_last_error": (S, []),
+}
+
 
 class AptError(RuntimeError):
     pass
@@ -297,6 +315,42 @@ def film_history_record(**fields):
     return rec
 
 
+class ApFilmMeter(ctypes.Structure):
+    """apt_film_meter (include/render_mi355x_post.h): passes in the film, the metered percentile range in 1/65536, the key luminance,
+    the exposure's clamps and the share of the way from the last frame's exposure to the metered one."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("low_q", ctypes.c_uint32), ("high_q", ctypes.c_uint32),
+                ("key", ctypes.c_float), ("min_exposure", ctypes.c_float), ("max_exposure", ctypes.c_float), ("adapt", ctypes.c_float)]
+
+
+def film_meter_record(passes, **fields):
+    """apt_film_meter_default_host's record for `passes`, with any of low_q, high_q, key, min_exposure, max_exposure, adapt replaced."""
+    rec = ApFilmMeter()
+    post_check(post_lib().apt_film_meter_default_host(ctypes.byref(rec), passes), "apt_film_meter_default_host")
+    for k, v in fields.items():
+        if k not in ("low_q", "high_q", "key", "min_exposure", "max_exposure", "adapt"):
+            raise AptError(f"film_meter_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
+class ApFilmBloom(ctypes.Structure):
+    """apt_film_bloom (include/render_mi355x_post.h): passes in the film, pyramid levels, the luminance threshold, the per-channel cap,
+    the weight of each coarser level and the weight of the glare in the output."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("threshold", ctypes.c_float), ("cap", ctypes.c_float), ("spread", ctypes.c_float), ("intensity", ctypes.c_float)]
+
+
+def film_bloom_record(passes, **fields):
+    """apt_film_bloom_default_host's record for `passes`, with any of levels, threshold, cap, spread, intensity replaced."""
+    rec = ApFilmBloom()
+    post_check(post_lib().apt_film_bloom_default_host(ctypes.byref(rec), passes), "apt_film_bloom_default_host")
+    for k, v in fields.items():
+        if k not in ("levels", "threshold", "cap", "spread", "intensity"):
+            raise AptError(f"film_bloom_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 _lib = None
 
 
@@ -393,6 +447,33 @@ def history_lib():
     return _history_lib
 
 
+_post_lib = None
+
+
+def post_lib():
+    """The loaded libpost_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
+    global _post_lib
+    if _post_lib is None:
+        if not os.path.exists(POST_LIB_PATH):
+            raise AptError(f"{POST_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
+        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
+        try:
+            h = ctypes.CDLL(POST_LIB_PATH)
+        except OSError as e:
+            raise AptError(f"cannot load {POST_LIB_PATH}: {e}") from e
+        for name, (restype, argtypes) in POST_PROTOTYPES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _post_lib = h
+    return _post_lib
+
+
+def post_check(rc, what):
+    if rc != APT_OK:
+        raise AptError(f"{what} failed ({rc}): {post_lib().apt_film_post_last_error().decode()}")
+
+
 def history_check(rc, what):
     if rc != APT_OK:
         raise AptError(f"{what} failed ({rc}): {history_lib().apt_film_history_last_error().decode()}")
@@ -419,7 +500,8 @@ def build_id():
     files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map"), os.path.join(os.path.dirname(_HERE), "include", "render_mi355x.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_history.h")]
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_history.h"),
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_post.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -506,6 +506,61 @@ def film_history_export(hist, film=None, moments=None, stream=None):
     return film, moments
 
 
+def film_meter(record, film, work=None, hist=None, stream=None):
+    """apt_film_meter_device (libpost_mi355x.so, include/render_mi355x_post.h): the luminance histogram of `film`, float32 [3][count]
+    (a whole image or a band) divided by record.passes (_lib.film_meter_record) -> `hist`, an int32 tensor of APT_METER_WORDS uint32
+    words (None: a new one), stored.  work: an int32 tensor of at least apt_film_meter_work_words(count) words (None: a new one).
+    Returns hist; not synchronised."""
+    require_gpu()
+    count = film.numel() // 3
+    words = _lib.post_lib().apt_film_meter_work_words(count)
+    if work is None:
+        work = torch.empty(max(words, 1), dtype=torch.int32, device=film.device)
+    if hist is None:
+        hist = torch.empty(_lib.APT_METER_WORDS, dtype=torch.int32, device=film.device)
+    if work.numel() < words:
+        raise _lib.AptError(f"work has {work.numel()} words, expected at least {words}")
+    _lib.post_check(_lib.post_lib().apt_film_meter_device(ctypes.byref(record), _stream_handle(stream), _dev_f32(film, "film", 3 * count), count,
+                                                          _dev_u32(work, "work"), _dev_u32(hist, "hist", _lib.APT_METER_WORDS)),
+                    "apt_film_meter_device")
+    return hist
+
+
+def film_exposure(record, hist, prev=1.0):
+    """apt_film_exposure_host: the exposure that `record` derives from the histogram `hist` (what film_meter returned, or a host array of
+    APT_METER_WORDS uint32 words) and the exposure `prev` of the frame before -> float.  A device tensor is READ BACK (257 words): this
+    synchronises torch's current stream; a meter enqueued on another stream must have been waited for."""
+    import numpy as np
+    words = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+    if words.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+        raise _lib.AptError("hist must hold 32-bit integer words")
+    words = np.ascontiguousarray(words).view(np.uint32)
+    if words.size != _lib.APT_METER_WORDS:
+        raise _lib.AptError(f"hist has {words.size} words, expected {_lib.APT_METER_WORDS}")
+    out = ctypes.c_float(0.0)
+    _lib.post_check(_lib.post_lib().apt_film_exposure_host(ctypes.byref(record), words.ctypes.data, prev, ctypes.byref(out)),
+                    "apt_film_exposure_host")
+    return out.value
+
+
+def film_bloom(record, film, width, height, work=None, out=None, stream=None):
+    """apt_film_bloom_device: the bloom of `record` (_lib.film_bloom_record) over a whole width x height image -- film float32 [3][W*H]
+    divided by record.passes -> `out` float32 [3][W*H], the MEAN radiance plus the glare (None: a new tensor; never `film` itself).
+    work: a float32 tensor of apt_film_bloom_work_floats(width, height, record.levels) elements (None: a new one).  Not synchronised."""
+    require_gpu()
+    n = width * height
+    floats = _lib.post_lib().apt_film_bloom_work_floats(width, height, record.levels)
+    if work is None:
+        work = torch.empty(max(floats, 4), dtype=torch.float32, device=film.device)
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.float32, device=film.device)
+    if work.numel() < floats:
+        raise _lib.AptError(f"work has {work.numel()} elements, expected at least {floats}")
+    _lib.post_check(_lib.post_lib().apt_film_bloom_device(ctypes.byref(record), _stream_handle(stream), _dev_f32(film, "film", 3 * n), width, height,
+                                                          _dev_f32(work, "work"), _dev_f32(out, "out", 3 * n)), "apt_film_bloom_device")
+    return out
+
+
 class History:
     """Temporal accumulation over the frames of a moving camera (include/render_mi355x_history.h): push(mean, features, camera) blends
     one more frame -- Film.mean() and Film.features() of a film rendered with `camera` -- into the history reprojected from the frame
@@ -694,6 +749,34 @@ class Film:
                                             _dev_f32(self._tables[curve], "table", 256), None if out is None else out.data_ptr(),
                                             u8.data_ptr()), "apt_film_resolve_device")
         return (u8, out) if want_float else u8
+
+    def _post_source(self, source, what, stream=None):
+        """-> (planes, passes) that the post entries read: `source` as MEAN radiance, or the film's own sums and pass count."""
+        if source is not None:
+            return source, 1
+        if self.passes == 0:
+            raise _lib.AptError(f"Film.{what}: the film holds no pass")
+        if self.rounds:                      # every pixel over its own pass count first, as resolve does
+            return film_mean(self.buffer, self.passes, self.extra, stream=stream), 1
+        return self.buffer, self.passes
+
+    def auto_exposure(self, source=None, prev=1.0, **fields):
+        """The exposure metered from the film (include/render_mi355x_post.h): film_meter, then film_exposure with `prev`, the last
+        frame's exposure -> float, for resolve(exposure=...).  source: planes of MEAN radiance [3][count] to meter in the film's place,
+        with passes = 1: what denoise(), bloom() or History.radiance() return.  low_q, high_q, key, min_exposure, max_exposure and
+        adapt replace apt_film_meter_default_host's values.  Reads the histogram back: synchronises torch's current stream."""
+        planes, passes = self._post_source(source, "auto_exposure")
+        rec = _lib.film_meter_record(passes, **fields)
+        return film_exposure(rec, film_meter(rec, planes), prev)
+
+    def bloom(self, source=None, stream=None, **fields):
+        """The film's mean plus its glare through apt_film_bloom_device -> float32 [3][count] planes of MEAN radiance for
+        resolve(source=..., exposure=...).  source: as auto_exposure's.  levels, threshold, cap, spread and intensity replace
+        apt_film_bloom_default_host's values.  A whole image only: the pyramid has no band form."""
+        if self.pixel_begin != 0 or self.pixel_count != self.width * self.height:
+            raise _lib.AptError("Film.bloom: the film is a band of the image")
+        planes, passes = self._post_source(source, "bloom", stream)
+        return film_bloom(_lib.film_bloom_record(passes, **fields), planes, self.width, self.height, stream=stream)
 
     def write_pfm(self, path):
         """apt_write_pfm of the mean; the film must cover the whole image."""
