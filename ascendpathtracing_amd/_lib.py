@@ -192,6 +192,22 @@ POST_PROTOTYPES = {
     "apt_film_post_last_error": (S, []),
 }
 
+# libmetrics_mi355x.so (include/render_mi355x_metrics.h), the sixth library: its prototypes by the same rules, in its header's order.
+# tests/test_metrics_cpu.py holds the table to that header and to the library's exports.
+APT_COMPARE_WORDS, APT_SSIM_WORDS, APT_SSIM_TAPS = 8, 2, 11
+METRICS_LIB_PATH = os.environ.get("APT_METRICS_LIB_PATH") or os.path.join(_HERE, "libmetrics_mi355x.so")
+METRICS_PROTOTYPES = {
+    "apt_film_compare_default_host": (I, [P, U32, U32]),
+    "apt_film_compare_work_doubles": (U64, [U64]),
+    "apt_film_compare_device": (I, [P, P, P, P, U64, P, P, P]),
+    "apt_film_compare_host": (I, [P, P, P, U64, P, P]),
+    "apt_film_ssim_weights_host": (I, [P]),
+    "apt_film_ssim_work_bytes": (U64, [U32, U32]),
+    "apt_film_ssim_device": (I, [P, P, P, P, U32, U32, P, P, P]),
+    "apt_film_ssim_host": (I, [P, P, P, U32, U32, P, P]),
+    "apt_film_metrics_last_error": (S, []),
+}
+
 
 class AptError(RuntimeError):
     pass
@@ -351,6 +367,24 @@ def film_bloom_record(passes, **fields):
     return rec
 
 
+class ApFilmCompare(ctypes.Structure):
+    """apt_film_compare (include/render_mi355x_metrics.h): the passes in the film and in the reference, the exposure of the clipped
+    error and of SSIM, and what the relative error adds to the squared reference."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("passes_a", ctypes.c_uint32), ("passes_b", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("exposure", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+def film_compare_record(passes_a, passes_b=1, **fields):
+    """apt_film_compare_default_host's record for the two pass counts, with any of exposure, eps replaced."""
+    rec = ApFilmCompare()
+    metrics_check(metrics_lib().apt_film_compare_default_host(ctypes.byref(rec), passes_a, passes_b), "apt_film_compare_default_host")
+    for k, v in fields.items():
+        if k not in ("exposure", "eps"):
+            raise AptError(f"film_compare_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 _lib = None
 
 
@@ -469,6 +503,33 @@ def post_lib():
     return _post_lib
 
 
+_metrics_lib = None
+
+
+def metrics_lib():
+    """The loaded libmetrics_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
+    global _metrics_lib
+    if _metrics_lib is None:
+        if not os.path.exists(METRICS_LIB_PATH):
+            raise AptError(f"{METRICS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
+        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
+        try:
+            h = ctypes.CDLL(METRICS_LIB_PATH)
+        except OSError as e:
+            raise AptError(f"cannot load {METRICS_LIB_PATH}: {e}") from e
+        for name, (restype, argtypes) in METRICS_PROTOTYPES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _metrics_lib = h
+    return _metrics_lib
+
+
+def metrics_check(rc, what):
+    if rc != APT_OK:
+        raise AptError(f"{what} failed ({rc}): {metrics_lib().apt_film_metrics_last_error().decode()}")
+
+
 def post_check(rc, what):
     if rc != APT_OK:
         raise AptError(f"{what} failed ({rc}): {post_lib().apt_film_post_last_error().decode()}")
@@ -501,7 +562,8 @@ def build_id():
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_history.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_post.h")]
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_post.h"),
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_metrics.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -561,6 +561,94 @@ def film_bloom(record, film, width, height, work=None, out=None, stream=None):
     return out
 
 
+def _dev_words(t, name, dtype, numel=None):
+    """64-bit words: uint64 results travel in int64 tensors, the rows of a reduction in float64 ones."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise _lib.AptError(f"{name} must be a contiguous {dtype} tensor on the GPU")
+    if numel is not None and t.numel() != numel:
+        raise _lib.AptError(f"{name} has {t.numel()} elements, expected {numel}")
+    return t.data_ptr()
+
+
+def film_compare(record, a, b, work=None, result=None, err_map=None, stream=None):
+    """apt_film_compare_device (libmetrics_mi355x.so, include/render_mi355x_metrics.h): film `a`, float32 [3][n] over record.passes_a,
+    against the reference `b` over record.passes_b (_lib.film_compare_record) -> `result`, an int64 tensor of APT_COMPARE_WORDS uint64
+    words (None: a new one), stored: the bits of the float64 tree sums of the squared, clipped squared, relative squared and absolute
+    error, the key of the largest difference, the bad pixels, n, 0.  work: a float64 tensor of at least
+    apt_film_compare_work_doubles(n) elements (None: a new one).  err_map: None, or float32 [n] that receives each pixel's squared
+    error.  Returns result; not synchronised.  compare_summary turns the words into numbers."""
+    require_gpu()
+    n = a.numel() // 3
+    doubles = _lib.metrics_lib().apt_film_compare_work_doubles(n)
+    if work is None:
+        work = torch.empty(max(doubles, 1), dtype=torch.float64, device=a.device)
+    if result is None:
+        result = torch.empty(_lib.APT_COMPARE_WORDS, dtype=torch.int64, device=a.device)
+    if work.numel() < doubles:
+        raise _lib.AptError(f"work has {work.numel()} elements, expected at least {doubles}")
+    _lib.metrics_check(_lib.metrics_lib().apt_film_compare_device(
+        ctypes.byref(record), _stream_handle(stream), _dev_f32(a, "a", 3 * n), _dev_f32(b, "b", 3 * n), n,
+        _dev_words(work, "work", torch.float64), _dev_words(result, "result", torch.int64, _lib.APT_COMPARE_WORDS),
+        None if err_map is None else _dev_f32(err_map, "err_map", n)), "apt_film_compare_device")
+    return result
+
+
+def film_ssim(record, a, b, width, height, work=None, result=None, ssim_map=None, stream=None):
+    """apt_film_ssim_device: the SSIM of the display luminances of the whole width x height images `a` and `b` (float32 [3][W*H], over
+    record.passes_a and record.passes_b, times record.exposure, clipped) -> `result`, an int64 tensor of APT_SSIM_WORDS uint64 words
+    (None: a new one), stored: the bits of the float64 tree sum of the windows' s, and the window count.  work: a float64 tensor of at
+    least apt_film_ssim_work_bytes(width, height) / 8 elements (None: a new one).  ssim_map: None, or float32
+    [(W - 10) * (H - 10)] that receives s.  Returns result; not synchronised."""
+    require_gpu()
+    n = width * height
+    doubles = (_lib.metrics_lib().apt_film_ssim_work_bytes(width, height) + 7) // 8
+    if work is None:
+        work = torch.empty(max(doubles, 2), dtype=torch.float64, device=a.device)
+    if result is None:
+        result = torch.empty(_lib.APT_SSIM_WORDS, dtype=torch.int64, device=a.device)
+    if work.numel() < doubles:
+        raise _lib.AptError(f"work has {work.numel()} elements, expected at least {doubles}")
+    windows = max(width - 10, 0) * max(height - 10, 0)
+    _lib.metrics_check(_lib.metrics_lib().apt_film_ssim_device(
+        ctypes.byref(record), _stream_handle(stream), _dev_f32(a, "a", 3 * n), _dev_f32(b, "b", 3 * n), width, height,
+        _dev_words(work, "work", torch.float64), _dev_words(result, "result", torch.int64, _lib.APT_SSIM_WORDS),
+        None if ssim_map is None else _dev_f32(ssim_map, "ssim_map", windows)), "apt_film_ssim_device")
+    return result
+
+
+def compare_summary(result, ssim_result=None):
+    """The words of film_compare (and of film_ssim, or None) as numbers -> dict: mse, clipped_mse, rel_mse, mae (the sums over 3 *
+    good in float64, nan when no pixel is good), psnr = 10 * log10(1 / clipped_mse), max_abs and max_index (the largest absolute
+    difference of a channel and the first pixel that reaches it; nan and -1 when no pixel is good), bad (the excluded pixels), and ssim
+    (the mean over the windows; None without ssim_result).  A device tensor is READ BACK: this synchronises torch's current stream."""
+    import math
+
+    import numpy as np
+
+    def words(t, count):
+        w = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        w = np.ascontiguousarray(w).view(np.uint64)
+        if w.size != count:
+            raise _lib.AptError(f"a result of {w.size} words, expected {count}")
+        return w
+
+    r = words(result, _lib.APT_COMPARE_WORDS)
+    sums = r[:4].view(np.float64)
+    key, bad, n = int(r[4]), int(r[5]), int(r[6])
+    good = n - bad
+    mean = [float(s) / (3 * good) if good else float("nan") for s in sums]
+    out = {"mse": mean[0], "clipped_mse": mean[1], "rel_mse": mean[2], "mae": mean[3]}
+    out["psnr"] = (10.0 * math.log10(1.0 / mean[1]) if mean[1] > 0 else float("inf")) if good else float("nan")
+    out["max_abs"] = float(np.array([key >> 32], dtype=np.uint32).view(np.float32)[0]) if good else float("nan")
+    out["max_index"] = 0xFFFFFFFF - (key & 0xFFFFFFFF) if good else -1
+    out["bad"] = bad
+    out["ssim"] = None
+    if ssim_result is not None:
+        s = words(ssim_result, _lib.APT_SSIM_WORDS)
+        out["ssim"] = float(s[:1].view(np.float64)[0]) / int(s[1])
+    return out
+
+
 class History:
     """Temporal accumulation over the frames of a moving camera (include/render_mi355x_history.h): push(mean, features, camera) blends
     one more frame -- Film.mean() and Film.features() of a film rendered with `camera` -- into the history reprojected from the frame
@@ -777,6 +865,28 @@ class Film:
             raise _lib.AptError("Film.bloom: the film is a band of the image")
         planes, passes = self._post_source(source, "bloom", stream)
         return film_bloom(_lib.film_bloom_record(passes, **fields), planes, self.width, self.height, stream=stream)
+
+    def compare(self, reference, exposure=1.0, eps=1e-2, ssim=True, source=None):
+        """How far the film is from `reference` (include/render_mi355x_metrics.h) -> compare_summary's dict: mse, clipped_mse, rel_mse,
+        mae, psnr, max_abs, max_index, bad, ssim.  reference: a Film of the same pixel range, or planes of MEAN radiance [3][count]
+        (passes = 1).  source: planes of MEAN radiance to compare in the film's place, as auto_exposure's.  exposure multiplies the means
+        before the clipped error and SSIM clip them to [0, 1]; eps is what the relative error adds to the squared reference.  ssim=True
+        needs a whole image (the windows have no band form); ssim=False leaves "ssim" None and takes a band.  Reads the words back:
+        synchronises torch's current stream."""
+        whole = self.pixel_begin == 0 and self.pixel_count == self.width * self.height
+        if ssim and not whole:
+            raise _lib.AptError("Film.compare: the film is a band of the image (ssim=False compares a band)")
+        planes, passes = self._post_source(source, "compare")
+        if isinstance(reference, Film):
+            if (reference.pixel_begin, reference.pixel_count) != (self.pixel_begin, self.pixel_count):
+                raise _lib.AptError("Film.compare: the reference film covers other pixels")
+            ref, ref_passes = reference._post_source(None, "compare")
+        else:
+            ref, ref_passes = reference, 1
+        rec = _lib.film_compare_record(passes, ref_passes, exposure=exposure, eps=eps)
+        words = film_compare(rec, planes, ref)
+        ssim_words = film_ssim(rec, planes, ref, self.width, self.height) if ssim else None
+        return compare_summary(words, ssim_words)
 
     def write_pfm(self, path):
         """apt_write_pfm of the mean; the film must cover the whole image."""
