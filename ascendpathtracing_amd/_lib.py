@@ -208,6 +208,19 @@ METRICS_PROTOTYPES = {
     "apt_film_metrics_last_error": (S, []),
 }
 
+# libupscale_mi355x.so (include/render_mi355x_upscale.h), the seventh library: its prototypes by the same rules, in its header's order.
+# tests/test_upscale_cpu.py holds the table to that header and to the library's exports.
+UPSCALE_LIB_PATH = os.environ.get("APT_UPSCALE_LIB_PATH") or os.path.join(_HERE, "libupscale_mi355x.so")
+UPSCALE_PROTOTYPES = {
+    "apt_film_upscale_default_host": (I, [P]),
+    "apt_film_upscale_work_floats": (U64, [U32, U32]),
+    "apt_film_upscale_device": (I, [P, P, P, P, U32, U32, P, U32, U32, P, P, P]),
+    "apt_film_upscale_host": (I, [P, P, P, U32, U32, P, U32, U32, P, P, P]),
+    "apt_film_upscale_patch_device": (I, [P, P, P, U64, U32, U64, P]),
+    "apt_film_upscale_patch_host": (I, [P, P, U64, U32, U64, P]),
+    "apt_film_upscale_last_error": (S, []),
+}
+
 
 class AptError(RuntimeError):
     pass
@@ -385,6 +398,24 @@ def film_compare_record(passes_a, passes_b=1, **fields):
     return rec
 
 
+class ApFilmUpscale(ctypes.Structure):
+    """apt_film_upscale (include/render_mi355x_upscale.h): the edge-stopping sigmas of the guided sum (normal, depth, coverage, albedo),
+    the floor under a demodulating albedo and the least guided weight of a resolved pixel."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("sigma_n", ctypes.c_float), ("sigma_z", ctypes.c_float),
+                ("sigma_c", ctypes.c_float), ("sigma_a", ctypes.c_float), ("albedo_floor", ctypes.c_float), ("min_weight", ctypes.c_float)]
+
+
+def film_upscale_record(**fields):
+    """apt_film_upscale_default_host's record, with any of sigma_n, sigma_z, sigma_c, sigma_a, albedo_floor, min_weight replaced."""
+    rec = ApFilmUpscale()
+    upscale_check(upscale_lib().apt_film_upscale_default_host(ctypes.byref(rec)), "apt_film_upscale_default_host")
+    for k, v in fields.items():
+        if k not in ("sigma_n", "sigma_z", "sigma_c", "sigma_a", "albedo_floor", "min_weight"):
+            raise AptError(f"film_upscale_record: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 _lib = None
 
 
@@ -530,6 +561,33 @@ def metrics_check(rc, what):
         raise AptError(f"{what} failed ({rc}): {metrics_lib().apt_film_metrics_last_error().decode()}")
 
 
+_upscale_lib = None
+
+
+def upscale_lib():
+    """The loaded libupscale_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
+    global _upscale_lib
+    if _upscale_lib is None:
+        if not os.path.exists(UPSCALE_LIB_PATH):
+            raise AptError(f"{UPSCALE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
+        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
+        try:
+            h = ctypes.CDLL(UPSCALE_LIB_PATH)
+        except OSError as e:
+            raise AptError(f"cannot load {UPSCALE_LIB_PATH}: {e}") from e
+        for name, (restype, argtypes) in UPSCALE_PROTOTYPES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _upscale_lib = h
+    return _upscale_lib
+
+
+def upscale_check(rc, what):
+    if rc != APT_OK:
+        raise AptError(f"{what} failed ({rc}): {upscale_lib().apt_film_upscale_last_error().decode()}")
+
+
 def post_check(rc, what):
     if rc != APT_OK:
         raise AptError(f"{what} failed ({rc}): {post_lib().apt_film_post_last_error().decode()}")
@@ -563,7 +621,8 @@ def build_id():
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_history.h"),
               os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_post.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_metrics.h")]
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_metrics.h"),
+              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_upscale.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -649,6 +649,111 @@ def compare_summary(result, ssim_result=None):
     return out
 
 
+def film_upscale(record, lo, lo_features, lo_width, lo_height, hi_features, width, height, work=None, out=None, resolved=None, stream=None):
+    """apt_film_upscale_device (libupscale_mi355x.so, include/render_mi355x_upscale.h): full-size radiance rebuilt from the low image --
+    lo float32 [3][lo_width * lo_height], MEAN radiance, lo_features [APT_FEATURE_PLANES][lo_width * lo_height] -- under the guidance of
+    hi_features [APT_FEATURE_PLANES][width * height] by `record` (_lib.film_upscale_record) -> (out float32 [3][width * height], mean
+    radiance; resolved int32 [width * height], 0 where the fallback decided the pixel).  work: a float32 tensor of
+    apt_film_upscale_work_floats(lo_width, lo_height) elements.  None: new tensors.  Not synchronised."""
+    require_gpu()
+    nl, n = lo_width * lo_height, width * height
+    floats = _lib.upscale_lib().apt_film_upscale_work_floats(lo_width, lo_height)
+    if work is None:
+        work = torch.empty(max(floats, 4), dtype=torch.float32, device=lo.device)
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.float32, device=lo.device)
+    if resolved is None:
+        resolved = torch.empty(n, dtype=torch.int32, device=lo.device)
+    if work.numel() < floats:
+        raise _lib.AptError(f"work has {work.numel()} elements, expected at least {floats}")
+    _lib.upscale_check(_lib.upscale_lib().apt_film_upscale_device(
+        ctypes.byref(record), _stream_handle(stream), _dev_f32(lo, "lo", 3 * nl), _dev_f32(lo_features, "lo_features", _lib.APT_FEATURE_PLANES * nl),
+        lo_width, lo_height, _dev_f32(hi_features, "hi_features", _lib.APT_FEATURE_PLANES * n), width, height, _dev_f32(work, "work"),
+        _dev_f32(out, "out", 3 * n), _dev_u32(resolved, "resolved", n)), "apt_film_upscale_device")
+    return out, resolved
+
+
+def film_upscale_patch(sums, pixel_list, list_count, passes, out, stream=None):
+    """apt_film_upscale_patch_device: the pixels that the first list_count entries of pixel_list name, in `out` float32 [3][N], replaced
+    by sums / passes -- sums: the compact planes of `passes` list passes added up (its first 3 * list_count floats, [3][list_count]).
+    Returns out; not synchronised."""
+    require_gpu()
+    n = out.numel() // 3
+    if sums.numel() < 3 * list_count or pixel_list.numel() < list_count:
+        raise _lib.AptError("film_upscale_patch: sums or pixel_list is shorter than list_count asks")
+    _lib.upscale_check(_lib.upscale_lib().apt_film_upscale_patch_device(
+        _stream_handle(stream), _dev_f32(sums, "sums"), _dev_u32(pixel_list, "pixel_list"), list_count, passes, n, _dev_f32(out, "out", 3 * n)),
+        "apt_film_upscale_patch_device")
+    return out
+
+
+class Upscaler:
+    """Guided upscaling of a film rendered at lo_width x lo_height to width x height (include/render_mi355x_upscale.h): upscale()
+    rebuilds full-size mean radiance from the low film's mean under the guidance of the full-size feature planes, unresolved() lists
+    the pixels the guides found no agreeing tap for, refine() renders those at full resolution and patches them in.  Owns the work
+    buffer, the output planes, the `resolved` words and what the list and the list passes need.  It never sets a camera: the context's
+    camera and the params are the caller's, as everywhere."""
+
+    def __init__(self, width, height, lo_width, lo_height, device="cuda", **record_fields):
+        self.width, self.height, self.lo_width, self.lo_height = width, height, lo_width, lo_height
+        self.record = _lib.film_upscale_record(**record_fields)
+        n = width * height
+        self._work = torch.empty(max(_lib.upscale_lib().apt_film_upscale_work_floats(lo_width, lo_height), 4), dtype=torch.float32, device=device)
+        self.out = torch.empty((3, n), dtype=torch.float32, device=device)
+        self.resolved = torch.empty(n, dtype=torch.int32, device=device)
+        self.pixel_list = torch.empty(n, dtype=torch.int32, device=device)
+        self._count = torch.zeros(1, dtype=torch.int32, device=device)
+        self._select_work = torch.empty(_lib.adaptive_lib().apt_film_select_work_words(n), dtype=torch.int32, device=device)
+        self._moments = torch.zeros((2, n), dtype=torch.float32, device=device)      # never read by the selection used here
+        self._scratch = self._sums = None
+        self.count = None                   # the length of pixel_list: None until unresolved() has run for the last upscale()
+
+    def upscale(self, lo_mean, lo_features, hi_features, stream=None):
+        """-> float32 [3][width * height] planes of MEAN radiance (the held output, written again by the next call) for
+        Film.resolve(source=), Film.bloom(source=) and Film.compare(source=).  Not synchronised."""
+        film_upscale(self.record, lo_mean, lo_features, self.lo_width, self.lo_height, hi_features, self.width, self.height, self._work,
+                     self.out, self.resolved, stream)
+        self.count = None
+        return self.out
+
+    def unresolved(self, stream=None):
+        """-> (pixel_list int32 [N], count): the pixels of the last upscale() that the fallback decided, ascending, through the
+        unchanged render.film_select (base_passes = 2, min_passes = max_passes = 3, `resolved` as `extra`).  Reads the count back (one
+        4-byte copy): this synchronises `stream`."""
+        rec = _lib.film_select_record(2, min_passes=3, max_passes=3)
+        film_select(rec, self._moments, self.resolved, self._select_work, self.pixel_list, self._count, stream)
+        with torch.cuda.stream(_torch_stream(stream)):
+            self.count = int(self._count.cpu()[0])
+        return self.pixel_list, self.count
+
+    def refine(self, params, spheres, materials, passes=1, lights=None, first_pass=0, stream=None, context=None):
+        """`passes` list passes (pass indices first_pass ..) of `params` at FULL resolution over the unresolved pixels, their mean
+        patched into the held output -> how many pixels were rendered.  Each pass goes into a compact scratch (a list launch always
+        stores) and is added to the sum with one fp32 add.  Calls unresolved() when it has not run since the last upscale()."""
+        if (params.width, params.height) != (self.width, self.height):
+            raise _lib.AptError("Upscaler.refine: params.width / height are not the full size")
+        if passes < 1:
+            raise _lib.AptError("Upscaler.refine: passes must be at least 1")
+        if self.count is None:
+            self.unresolved(stream)
+        count = self.count
+        if count == 0:
+            return 0
+        ctx = _default if context is None else context
+        if self._scratch is None:
+            self._scratch = torch.empty(3 * self.width * self.height, dtype=torch.float32, device=self.out.device)
+            self._sums = torch.empty(3 * self.width * self.height, dtype=torch.float32, device=self.out.device)
+        scratch, sums = self._scratch[:3 * count], self._sums[:3 * count]
+        for k in range(passes):
+            ctx.render_frame_film(params, spheres, materials, sums if k == 0 else scratch, first_pass + k, lights, 0, count, stream,
+                                  pixel_list=self.pixel_list)
+            if k:
+                with torch.cuda.stream(_torch_stream(stream)):
+                    sums.add_(scratch)
+        film_upscale_patch(sums, self.pixel_list, count, passes, self.out, stream)
+        return count
+
+
 class History:
     """Temporal accumulation over the frames of a moving camera (include/render_mi355x_history.h): push(mean, features, camera) blends
     one more frame -- Film.mean() and Film.features() of a film rendered with `camera` -- into the history reprojected from the frame
