@@ -1,6 +1,7 @@
 """ctypes binding of librender_mi355x.so (include/render_mi355x.h).  Loading fails loudly:
 there is no Python or CPU fallback for the compute path."""
 import ctypes
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -134,9 +135,10 @@ PROTOTYPES = {
 # every symbol include/render_mi355x.h declares
 ABI_SYMBOLS = [name for name in PROTOTYPES if name != CXX_RENDER_DO]
 
-# libdenoise_mi355x.so (include/render_mi355x_denoise.h), a library of its own beside librender_mi355x.so: its prototypes by the same
-# rules, in its header's order.  tests/test_denoise_cpu.py holds the table to that header and to the library's exports.
-DENOISE_LIB_PATH = os.environ.get("APT_DENOISE_LIB_PATH") or os.path.join(_HERE, "libdenoise_mi355x.so")
+# The film stages: six libraries of their own beside librender_mi355x.so, lib<stage>_mi355x.so with include/render_mi355x_<stage>.h.
+# Their prototypes by the same rules, each table in its header's order (a float parameter is F32); tests/test_<stage>_cpu.py holds a
+# table to its header and to the library's exports.  STAGES below is the one table of the stages.
+F32 = ctypes.c_float
 DENOISE_PROTOTYPES = {
     "apt_film_accumulate_device": (I, [P, P, U64, P, P, U32]),
     "apt_film_accumulate_host": (I, [P, U64, P, P, U32]),
@@ -147,9 +149,6 @@ DENOISE_PROTOTYPES = {
     "apt_film_denoise_last_error": (S, []),
 }
 
-# libadaptive_mi355x.so (include/render_mi355x_adaptive.h), the third library: its prototypes by the same rules, in its header's order.
-# tests/test_adaptive_cpu.py holds the table to that header and to the library's exports.
-ADAPTIVE_LIB_PATH = os.environ.get("APT_ADAPTIVE_LIB_PATH") or os.path.join(_HERE, "libadaptive_mi355x.so")
 ADAPTIVE_PROTOTYPES = {
     "apt_film_select_default_host": (I, [P, U32]),
     "apt_film_select_work_words": (U64, [U64]),
@@ -162,9 +161,6 @@ ADAPTIVE_PROTOTYPES = {
     "apt_film_adaptive_last_error": (S, []),
 }
 
-# libhistory_mi355x.so (include/render_mi355x_history.h), the fourth library: its prototypes by the same rules, in its header's order.
-# tests/test_history_cpu.py holds the table to that header and to the library's exports.
-HISTORY_LIB_PATH = os.environ.get("APT_HISTORY_LIB_PATH") or os.path.join(_HERE, "libhistory_mi355x.so")
 HISTORY_PROTOTYPES = {
     "apt_film_history_default_host": (I, [P]),
     "apt_film_history_device": (I, [P, P, P, P, P, P, P, P, U32, U32, P]),
@@ -174,11 +170,7 @@ HISTORY_PROTOTYPES = {
     "apt_film_history_last_error": (S, []),
 }
 
-# libpost_mi355x.so (include/render_mi355x_post.h), the fifth library: its prototypes by the same rules, in its header's order; a float
-# parameter is F32.  tests/test_post_cpu.py holds the table to that header and to the library's exports.
-F32 = ctypes.c_float
 APT_METER_BINS, APT_METER_WORDS = 256, 257
-POST_LIB_PATH = os.environ.get("APT_POST_LIB_PATH") or os.path.join(_HERE, "libpost_mi355x.so")
 POST_PROTOTYPES = {
     "apt_film_meter_default_host": (I, [P, U32]),
     "apt_film_meter_work_words": (U64, [U64]),
@@ -192,10 +184,7 @@ POST_PROTOTYPES = {
     "apt_film_post_last_error": (S, []),
 }
 
-# libmetrics_mi355x.so (include/render_mi355x_metrics.h), the sixth library: its prototypes by the same rules, in its header's order.
-# tests/test_metrics_cpu.py holds the table to that header and to the library's exports.
 APT_COMPARE_WORDS, APT_SSIM_WORDS, APT_SSIM_TAPS = 8, 2, 11
-METRICS_LIB_PATH = os.environ.get("APT_METRICS_LIB_PATH") or os.path.join(_HERE, "libmetrics_mi355x.so")
 METRICS_PROTOTYPES = {
     "apt_film_compare_default_host": (I, [P, U32, U32]),
     "apt_film_compare_work_doubles": (U64, [U64]),
@@ -208,9 +197,6 @@ METRICS_PROTOTYPES = {
     "apt_film_metrics_last_error": (S, []),
 }
 
-# libupscale_mi355x.so (include/render_mi355x_upscale.h), the seventh library: its prototypes by the same rules, in its header's order.
-# tests/test_upscale_cpu.py holds the table to that header and to the library's exports.
-UPSCALE_LIB_PATH = os.environ.get("APT_UPSCALE_LIB_PATH") or os.path.join(_HERE, "libupscale_mi355x.so")
 UPSCALE_PROTOTYPES = {
     "apt_film_upscale_default_host": (I, [P]),
     "apt_film_upscale_work_floats": (U64, [U32, U32]),
@@ -220,6 +206,26 @@ UPSCALE_PROTOTYPES = {
     "apt_film_upscale_patch_host": (I, [P, P, U64, U32, U64, P]),
     "apt_film_upscale_last_error": (S, []),
 }
+
+
+class Stage:
+    """One film stage: where its library is (APT_<STAGE>_LIB_PATH: another build of it, as APT_LIB_PATH), its prototype table, the
+    name of its public header under include/, the symbol of its error record, and the loaded library once stage_lib() has loaded it."""
+
+    def __init__(self, name, prototypes):
+        self.name, self.prototypes = name, prototypes
+        self.built_path = os.path.join(_HERE, f"lib{name}_mi355x.so")        # what the build makes
+        self.lib_path = os.environ.get(f"APT_{name.upper()}_LIB_PATH") or self.built_path
+        self.header = f"render_mi355x_{name}.h"
+        self.last_error = f"apt_film_{name}_last_error"
+        self.handle = None
+
+
+# in the order the stages were added: build_id() hashes their headers in it
+STAGES = {st.name: st for st in (Stage("denoise", DENOISE_PROTOTYPES), Stage("adaptive", ADAPTIVE_PROTOTYPES),
+                                 Stage("history", HISTORY_PROTOTYPES), Stage("post", POST_PROTOTYPES),
+                                 Stage("metrics", METRICS_PROTOTYPES), Stage("upscale", UPSCALE_PROTOTYPES))}
+DENOISE_LIB_PATH, ADAPTIVE_LIB_PATH, HISTORY_LIB_PATH, POST_LIB_PATH, METRICS_LIB_PATH, UPSCALE_LIB_PATH = (st.lib_path for st in STAGES.values())
 
 
 class AptError(RuntimeError):
@@ -294,6 +300,15 @@ class ApFilmDenoise(ctypes.Structure):
                 ("sigma_l", ctypes.c_float), ("albedo_floor", ctypes.c_float)]
 
 
+def _replace_fields(rec, what, fields, permitted):
+    """`rec` with each of `fields` set; one that is not `permitted` is refused in the name of the helper `what`."""
+    for k, v in fields.items():
+        if k not in permitted:
+            raise AptError(f"{what}: unknown field {k!r}")
+        setattr(rec, k, v)
+    return rec
+
+
 def film_denoise_record(passes, iterations=None, **fields):
     """apt_film_denoise_default_host's record for `passes`, with `iterations` and any of sigma_n, sigma_z, sigma_c, sigma_a, sigma_l,
     albedo_floor replaced."""
@@ -301,11 +316,7 @@ def film_denoise_record(passes, iterations=None, **fields):
     denoise_check(denoise_lib().apt_film_denoise_default_host(ctypes.byref(rec), passes), "apt_film_denoise_default_host")
     if iterations is not None:
         rec.iterations = iterations
-    for k, v in fields.items():
-        if k not in ("sigma_n", "sigma_z", "sigma_c", "sigma_a", "sigma_l", "albedo_floor"):
-            raise AptError(f"film_denoise_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_denoise_record", fields, ("sigma_n", "sigma_z", "sigma_c", "sigma_a", "sigma_l", "albedo_floor"))
 
 
 class ApFilmSelect(ctypes.Structure):
@@ -319,11 +330,7 @@ def film_select_record(base_passes, **fields):
     """apt_film_select_default_host's record for `base_passes`, with any of min_passes, max_passes, threshold, floor replaced."""
     rec = ApFilmSelect()
     adaptive_check(adaptive_lib().apt_film_select_default_host(ctypes.byref(rec), base_passes), "apt_film_select_default_host")
-    for k, v in fields.items():
-        if k not in ("min_passes", "max_passes", "threshold", "floor"):
-            raise AptError(f"film_select_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_select_record", fields, ("min_passes", "max_passes", "threshold", "floor"))
 
 
 class ApFilmHistory(ctypes.Structure):
@@ -337,11 +344,7 @@ def film_history_record(**fields):
     """apt_film_history_default_host's record, with any of max_history, tol_plane, tol_normal, min_weight replaced."""
     rec = ApFilmHistory()
     history_check(history_lib().apt_film_history_default_host(ctypes.byref(rec)), "apt_film_history_default_host")
-    for k, v in fields.items():
-        if k not in ("max_history", "tol_plane", "tol_normal", "min_weight"):
-            raise AptError(f"film_history_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_history_record", fields, ("max_history", "tol_plane", "tol_normal", "min_weight"))
 
 
 class ApFilmMeter(ctypes.Structure):
@@ -355,11 +358,7 @@ def film_meter_record(passes, **fields):
     """apt_film_meter_default_host's record for `passes`, with any of low_q, high_q, key, min_exposure, max_exposure, adapt replaced."""
     rec = ApFilmMeter()
     post_check(post_lib().apt_film_meter_default_host(ctypes.byref(rec), passes), "apt_film_meter_default_host")
-    for k, v in fields.items():
-        if k not in ("low_q", "high_q", "key", "min_exposure", "max_exposure", "adapt"):
-            raise AptError(f"film_meter_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_meter_record", fields, ("low_q", "high_q", "key", "min_exposure", "max_exposure", "adapt"))
 
 
 class ApFilmBloom(ctypes.Structure):
@@ -373,11 +372,7 @@ def film_bloom_record(passes, **fields):
     """apt_film_bloom_default_host's record for `passes`, with any of levels, threshold, cap, spread, intensity replaced."""
     rec = ApFilmBloom()
     post_check(post_lib().apt_film_bloom_default_host(ctypes.byref(rec), passes), "apt_film_bloom_default_host")
-    for k, v in fields.items():
-        if k not in ("levels", "threshold", "cap", "spread", "intensity"):
-            raise AptError(f"film_bloom_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_bloom_record", fields, ("levels", "threshold", "cap", "spread", "intensity"))
 
 
 class ApFilmCompare(ctypes.Structure):
@@ -391,11 +386,7 @@ def film_compare_record(passes_a, passes_b=1, **fields):
     """apt_film_compare_default_host's record for the two pass counts, with any of exposure, eps replaced."""
     rec = ApFilmCompare()
     metrics_check(metrics_lib().apt_film_compare_default_host(ctypes.byref(rec), passes_a, passes_b), "apt_film_compare_default_host")
-    for k, v in fields.items():
-        if k not in ("exposure", "eps"):
-            raise AptError(f"film_compare_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_compare_record", fields, ("exposure", "eps"))
 
 
 class ApFilmUpscale(ctypes.Structure):
@@ -409,11 +400,7 @@ def film_upscale_record(**fields):
     """apt_film_upscale_default_host's record, with any of sigma_n, sigma_z, sigma_c, sigma_a, albedo_floor, min_weight replaced."""
     rec = ApFilmUpscale()
     upscale_check(upscale_lib().apt_film_upscale_default_host(ctypes.byref(rec)), "apt_film_upscale_default_host")
-    for k, v in fields.items():
-        if k not in ("sigma_n", "sigma_z", "sigma_c", "sigma_a", "albedo_floor", "min_weight"):
-            raise AptError(f"film_upscale_record: unknown field {k!r}")
-        setattr(rec, k, v)
-    return rec
+    return _replace_fields(rec, "film_upscale_record", fields, ("sigma_n", "sigma_z", "sigma_c", "sigma_a", "albedo_floor", "min_weight"))
 
 
 _lib = None
@@ -446,183 +433,49 @@ def lib():
     return _lib
 
 
-_denoise_lib = None
-
-
-def denoise_lib():
-    """The loaded libdenoise_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
-    global _denoise_lib
-    if _denoise_lib is None:
-        if not os.path.exists(DENOISE_LIB_PATH):
-            raise AptError(f"{DENOISE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+def stage_lib(name):
+    """The loaded library of the film stage `name`; raises AptError when it has not been built.  As lib(): no fallback."""
+    st = STAGES[name]
+    if st.handle is None:
+        if not os.path.exists(st.lib_path):
+            raise AptError(f"{st.lib_path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
         lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
         try:
-            h = ctypes.CDLL(DENOISE_LIB_PATH)
+            h = ctypes.CDLL(st.lib_path)
         except OSError as e:
-            raise AptError(f"cannot load {DENOISE_LIB_PATH}: {e}") from e
-        for name, (restype, argtypes) in DENOISE_PROTOTYPES.items():
-            fn = getattr(h, name)
+            raise AptError(f"cannot load {st.lib_path}: {e}") from e
+        for symbol, (restype, argtypes) in st.prototypes.items():
+            fn = getattr(h, symbol)
             fn.restype, fn.argtypes = restype, argtypes
-        _denoise_lib = h
-    return _denoise_lib
+        st.handle = h
+    return st.handle
 
 
-_adaptive_lib = None
-
-
-def adaptive_lib():
-    """The loaded libadaptive_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
-    global _adaptive_lib
-    if _adaptive_lib is None:
-        if not os.path.exists(ADAPTIVE_LIB_PATH):
-            raise AptError(f"{ADAPTIVE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
-        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
-        try:
-            h = ctypes.CDLL(ADAPTIVE_LIB_PATH)
-        except OSError as e:
-            raise AptError(f"cannot load {ADAPTIVE_LIB_PATH}: {e}") from e
-        for name, (restype, argtypes) in ADAPTIVE_PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _adaptive_lib = h
-    return _adaptive_lib
-
-
-_history_lib = None
-
-
-def history_lib():
-    """The loaded libhistory_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
-    global _history_lib
-    if _history_lib is None:
-        if not os.path.exists(HISTORY_LIB_PATH):
-            raise AptError(f"{HISTORY_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
-        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
-        try:
-            h = ctypes.CDLL(HISTORY_LIB_PATH)
-        except OSError as e:
-            raise AptError(f"cannot load {HISTORY_LIB_PATH}: {e}") from e
-        for name, (restype, argtypes) in HISTORY_PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _history_lib = h
-    return _history_lib
-
-
-_post_lib = None
-
-
-def post_lib():
-    """The loaded libpost_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
-    global _post_lib
-    if _post_lib is None:
-        if not os.path.exists(POST_LIB_PATH):
-            raise AptError(f"{POST_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
-        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
-        try:
-            h = ctypes.CDLL(POST_LIB_PATH)
-        except OSError as e:
-            raise AptError(f"cannot load {POST_LIB_PATH}: {e}") from e
-        for name, (restype, argtypes) in POST_PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _post_lib = h
-    return _post_lib
-
-
-_metrics_lib = None
-
-
-def metrics_lib():
-    """The loaded libmetrics_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
-    global _metrics_lib
-    if _metrics_lib is None:
-        if not os.path.exists(METRICS_LIB_PATH):
-            raise AptError(f"{METRICS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
-        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
-        try:
-            h = ctypes.CDLL(METRICS_LIB_PATH)
-        except OSError as e:
-            raise AptError(f"cannot load {METRICS_LIB_PATH}: {e}") from e
-        for name, (restype, argtypes) in METRICS_PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _metrics_lib = h
-    return _metrics_lib
-
-
-def metrics_check(rc, what):
+def stage_check(name, rc, what):
     if rc != APT_OK:
-        raise AptError(f"{what} failed ({rc}): {metrics_lib().apt_film_metrics_last_error().decode()}")
+        raise AptError(f"{what} failed ({rc}): {getattr(stage_lib(name), STAGES[name].last_error)().decode()}")
 
 
-_upscale_lib = None
+denoise_lib, adaptive_lib, history_lib, post_lib, metrics_lib, upscale_lib = (functools.partial(stage_lib, name) for name in STAGES)
+denoise_check, adaptive_check, history_check, post_check, metrics_check, upscale_check = (functools.partial(stage_check, name) for name in STAGES)
 
 
-def upscale_lib():
-    """The loaded libupscale_mi355x.so; raises AptError when it has not been built.  As lib(): no fallback."""
-    global _upscale_lib
-    if _upscale_lib is None:
-        if not os.path.exists(UPSCALE_LIB_PATH):
-            raise AptError(f"{UPSCALE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C ascendpathtracing_amd/csrc` (there is no CPU fallback)")
-        lib()                           # the one HIP runtime of the process is loaded first, as lib() arranges it
-        try:
-            h = ctypes.CDLL(UPSCALE_LIB_PATH)
-        except OSError as e:
-            raise AptError(f"cannot load {UPSCALE_LIB_PATH}: {e}") from e
-        for name, (restype, argtypes) in UPSCALE_PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _upscale_lib = h
-    return _upscale_lib
-
-
-def upscale_check(rc, what):
-    if rc != APT_OK:
-        raise AptError(f"{what} failed ({rc}): {upscale_lib().apt_film_upscale_last_error().decode()}")
-
-
-def post_check(rc, what):
-    if rc != APT_OK:
-        raise AptError(f"{what} failed ({rc}): {post_lib().apt_film_post_last_error().decode()}")
-
-
-def history_check(rc, what):
-    if rc != APT_OK:
-        raise AptError(f"{what} failed ({rc}): {history_lib().apt_film_history_last_error().decode()}")
-
-
-def adaptive_check(rc, what):
-    if rc != APT_OK:
-        raise AptError(f"{what} failed ({rc}): {adaptive_lib().apt_film_adaptive_last_error().decode()}")
-
-
-def denoise_check(rc, what):
-    if rc != APT_OK:
-        raise AptError(f"{what} failed ({rc}): {denoise_lib().apt_film_denoise_last_error().decode()}")
+def public_headers():
+    """The public headers under include/: librender_mi355x.so's, then the stages' in the table's order."""
+    include = os.path.join(os.path.dirname(_HERE), "include")
+    return [os.path.join(include, h) for h in ["render_mi355x.h"] + [st.header for st in STAGES.values()]]
 
 
 def build_id():
     """Identifies the build of the library by its SOURCES (sha256 over ascendpathtracing_amd/csrc/*.{h,hip,cpp}, the Makefile and the
-    public header, first 16 hex digits): what profiles/summarize.py stamps the recorded PMC traffic with and bench.py compares
+    public headers, first 16 hex digits): what profiles/summarize.py stamps the recorded PMC traffic with and bench.py compares
     before it reports that traffic for the library it is running."""
     import glob
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")))
-    files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map"), os.path.join(os.path.dirname(_HERE), "include", "render_mi355x.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_denoise.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_adaptive.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_history.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_post.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_metrics.h"),
-              os.path.join(os.path.dirname(_HERE), "include", "render_mi355x_upscale.h")]
+    files += [os.path.join(csrc, "Makefile"), os.path.join(csrc, "apt_exports.map")] + public_headers()
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

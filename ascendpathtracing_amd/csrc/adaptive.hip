@@ -15,9 +15,12 @@
 #include "../../include/render_mi355x_adaptive.h"
 #include "adaptive_host.h"
 #include "adaptive_ops.h"
+#include "film_stage_launch.h"
 
 using apt::AdSelect;
+using apt::blocks_for;
 using apt::kAdBlock;
+using apt::launched;
 
 namespace {
 
@@ -123,26 +126,19 @@ __global__ __launch_bounds__(kAdBlock) void film_mean_kernel(MeanArgs a) {
     apt::ad_mean(a.film, a.extra, a.base, a.out, a.n, i);                     // (extra null or not: launch-uniform)
 }
 
-// -> APT_OK when the runtime took the launches, APT_ERR_DEVICE with its text otherwise
-int launched() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return APT_OK;
-    return apt::ad_set_error(APT_ERR_DEVICE, "%s", hipGetErrorString(e));
-}
-
 } // namespace
 
 extern "C" {
 
 int apt_film_select_device(const apt_film_select *s, void *stream, const float *moments, const uint32_t *extra, uint64_t pixel_count,
                            uint32_t *work, uint32_t *list, uint32_t *count) {
-    apt::ad_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_select_check(s, moments, extra, pixel_count, work, list, count, "apt_film_select_device");
     if (rc) return rc;
     SelArgs a;
     a.mom = moments; a.extra = extra; a.work = work; a.list = list; a.n = (uint32_t)pixel_count;   // <= 2^28: the check above
     a.s = AdSelect{s->base_passes, s->min_passes, s->max_passes, s->threshold, s->floor};
-    const unsigned blocks = (unsigned)apt_film_select_work_words(pixel_count);                      // <= 2^20
+    const unsigned blocks = (unsigned)apt_film_select_work_words(pixel_count);                      // = blocks_for(pixel_count, kAdBlock)
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(film_select_count_kernel, dim3(blocks), dim3(kAdBlock), 0, st, a);
     hipLaunchKernelGGL(film_select_scan_kernel, dim3(1), dim3(kAdBlock), 0, st, work, (uint32_t)blocks, count);
@@ -152,23 +148,23 @@ int apt_film_select_device(const apt_film_select *s, void *stream, const float *
 
 int apt_film_accumulate_list_device(void *stream, const float *pass_planes, const uint32_t *list, uint64_t list_count, uint64_t pixel_count,
                                     float *film, float *moments, uint32_t *extra) {
-    apt::ad_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_accumulate_list_check(pass_planes, list, list_count, pixel_count, film, moments, extra, "apt_film_accumulate_list_device");
     if (rc || list_count == 0) return rc;
     AccListArgs a;
     a.pass = pass_planes; a.list = list; a.film = film; a.mom = moments; a.extra = extra; a.count = list_count; a.n = pixel_count;
-    const unsigned blocks = (unsigned)((list_count + kAdBlock - 1) / kAdBlock);                     // list_count <= 2^28
+    const unsigned blocks = blocks_for(list_count, kAdBlock);
     hipLaunchKernelGGL(film_accumulate_list_kernel, dim3(blocks), dim3(kAdBlock), 0, (hipStream_t)stream, a);
     return launched();
 }
 
 int apt_film_mean_device(void *stream, const float *film, const uint32_t *extra, uint32_t base_passes, uint64_t pixel_count, float *out) {
-    apt::ad_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_mean_check(film, base_passes, pixel_count, out, "apt_film_mean_device");
     if (rc) return rc;
     MeanArgs a;
     a.film = film; a.extra = extra; a.out = out; a.n = pixel_count; a.base = base_passes;
-    const unsigned blocks = (unsigned)((pixel_count + kAdBlock - 1) / kAdBlock);
+    const unsigned blocks = blocks_for(pixel_count, kAdBlock);
     hipLaunchKernelGGL(film_mean_kernel, dim3(blocks), dim3(kAdBlock), 0, (hipStream_t)stream, a);
     return launched();
 }

@@ -1,14 +1,12 @@
-// adaptive_host.h -- what adaptive.hip (the device entries) and adaptive_host.cpp (the host entries) of libadaptive_mi355x.so share:
-// the per-thread error record behind apt_film_adaptive_last_error() and one check function per entry pair
-// (include/render_mi355x_adaptive.h).
+// adaptive_host.h -- what adaptive.hip (the device entries) and adaptive_host.cpp (the host entries) of libadaptive_mi355x.so share
+// beside film_stage_host.h: one check function per entry pair (include/render_mi355x_adaptive.h).
 #pragma once
 #include <stdint.h>
 
 #include "../../include/render_mi355x_adaptive.h"
+#include "film_stage_host.h"
 
 namespace apt {
-void ad_clear_error();                                          // every entry calls this first
-int ad_set_error(int code, const char *fmt, const char *what);  // returns `code`; fmt holds one %s
 // What both forms of an entry refuse, in the header's order: APT_OK or the error record set.
 int film_select_check(const apt_film_select *s, const void *moments, const void *extra, uint64_t pixel_count, const void *work, const void *list,
                       const void *count, const char *what);

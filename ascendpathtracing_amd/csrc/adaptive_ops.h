@@ -8,19 +8,13 @@
 
 #include "../../include/render_mi355x_adaptive.h"
 #include "apt_hd.h"
+#include "film_stage_ops.h"
 
 namespace apt {
 
 constexpr uint32_t kAdBlock = 256;   // pixels per workgroup of the select: one word of its work buffer each
 
 struct AdSelect { uint32_t base, min_passes, max_passes; float threshold, floor_; };   // apt_film_select, checked
-
-APT_HD float ad_lum(float r, float g, float b) {   // render_mi355x_denoise.h's lum
-    float l = 0.2126f * r;
-    l = l + 0.7152f * g;
-    return l + 0.0722f * b;
-}
-APT_HD float ad_max(float a, float b) { return a > b ? a : b; }
 
 // ---- select: does the pixel with these moments and this many extra passes get another one? --------------------------------------------
 APT_HD bool ad_selected(float m0, float m1, uint32_t extra, const AdSelect &s) {
@@ -30,10 +24,10 @@ APT_HD bool ad_selected(float m0, float m1, uint32_t extra, const AdSelect &s) {
     const float n = (float)(uint32_t)nu;            // < 2^24: exact
     const float lm = m0 / n;
     const float sq = m1 / n;
-    const float d = ad_max(sq - lm * lm, 0.0f);
+    const float d = fs_max(sq - lm * lm, 0.0f);
     const float v = d / (float)((uint32_t)nu - 1u);
     const float e = sqrtf(v);
-    const float r = ad_max(lm, s.floor_);
+    const float r = fs_max(lm, s.floor_);
     const float t = s.threshold * r;
     return e > t;
 }
@@ -44,7 +38,7 @@ APT_HD void ad_accumulate(const float *pass, const uint32_t *list, uint64_t coun
     const uint64_t p = list[i];
     if (p >= n) return;
     const float r = pass[i], g = pass[count + i], b = pass[2 * count + i];
-    const float l = ad_lum(r, g, b);
+    const float l = fs_lum(r, g, b);
     const float l2 = l * l;
     film[p] = film[p] + r; film[n + p] = film[n + p] + g; film[2 * n + p] = film[2 * n + p] + b;
     mom[p] = mom[p] + l; mom[n + p] = mom[n + p] + l2;

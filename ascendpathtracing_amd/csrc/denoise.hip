@@ -13,6 +13,7 @@
 #include "../../include/render_mi355x_denoise.h"
 #include "denoise_host.h"
 #include "denoise_ops.h"
+#include "film_stage_launch.h"
 
 using apt::DnRec;
 using apt::DnSigma;
@@ -88,15 +89,15 @@ namespace {
 void film_accumulate(void *stream, const float *pass_planes, uint64_t pixel_count, float *film, float *moments, uint32_t pass) {
     AccArgs a;
     a.pass = pass_planes; a.film = film; a.mom = moments; a.n = pixel_count; a.first = pass == 0 ? 1u : 0u;
-    const uint64_t blocks = (pixel_count + kDnBlock - 1) / kDnBlock;      // <= 2^31 - 1: checked by the caller
-    hipLaunchKernelGGL(film_accumulate_kernel, dim3((unsigned)blocks), dim3(kDnBlock), 0, (hipStream_t)stream, a);
+    const unsigned blocks = apt::blocks_for(pixel_count, kDnBlock);        // <= 2^31 - 1: checked by the caller
+    hipLaunchKernelGGL(film_accumulate_kernel, dim3(blocks), dim3(kDnBlock), 0, (hipStream_t)stream, a);
 }
 
 void film_denoise(const apt_film_denoise &d, void *stream, const float *film, const float *moments, const float *features, uint32_t width,
                   uint32_t height, float *work, float *out) {
     const uint32_t n = width * height;                                     // <= 2^28: checked by the caller
     DnRec *const g0 = reinterpret_cast<DnRec *>(work), *const g1 = g0 + n, *const c[2] = {g1 + n, g1 + 2 * (size_t)n};
-    const unsigned blocks = (n + kDnBlock - 1) / kDnBlock;
+    const unsigned blocks = apt::blocks_for(n, kDnBlock);
     PrepArgs p;
     p.film = film; p.mom = moments; p.feat = features; p.g0 = g0; p.g1 = g1; p.c0 = c[0]; p.n = n;
     p.K = (float)d.passes; p.K1 = (float)(d.passes - 1); p.floor_ = d.albedo_floor;
@@ -115,34 +116,25 @@ void film_denoise(const apt_film_denoise &d, void *stream, const float *film, co
     hipLaunchKernelGGL(denoise_finish_kernel, dim3(blocks), dim3(kDnBlock), 0, (hipStream_t)stream, f);
 }
 
-// -> APT_OK when the runtime took the launches, APT_ERR_DEVICE with its text otherwise
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return APT_OK;
-    apt::dn_set_error(APT_ERR_DEVICE, "%s", hipGetErrorString(e));
-    (void)what;
-    return APT_ERR_DEVICE;
-}
-
 } // namespace
 
 extern "C" {
 
 int apt_film_accumulate_device(void *stream, const float *pass_planes, uint64_t pixel_count, float *film, float *moments, uint32_t pass) {
-    apt::dn_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_accumulate_check(pass_planes, pixel_count, film, moments, "apt_film_accumulate_device");
     if (rc || pixel_count == 0) return rc;
     film_accumulate(stream, pass_planes, pixel_count, film, moments, pass);
-    return launched("apt_film_accumulate_device");
+    return apt::launched();
 }
 
 int apt_film_denoise_device(const apt_film_denoise *d, void *stream, const float *film, const float *moments, const float *features,
                             uint32_t width, uint32_t height, float *work, float *out) {
-    apt::dn_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_denoise_check(d, film, moments, features, width, height, work, out, "apt_film_denoise_device");
     if (rc) return rc;
     film_denoise(*d, stream, film, moments, features, width, height, work, out);
-    return launched("apt_film_denoise_device");
+    return apt::launched();
 }
 
 } // extern "C"

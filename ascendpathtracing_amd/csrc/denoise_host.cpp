@@ -1,57 +1,41 @@
-// denoise_host.cpp -- the host side of libdenoise_mi355x.so (include/render_mi355x_denoise.h): the library's own per-thread error
-// record, the checks that the device and the host form of each entry share, the defaults and the CPU twins.  Compiled with the
+// denoise_host.cpp -- the host side of libdenoise_mi355x.so (include/render_mi355x_denoise.h): the checks that the device and the host form of each entry share, the defaults and the CPU twins.  Compiled with the
 // product's -ffp-contract=off -fno-fast-math: a twin is a loop over the pixels and the call of denoise_ops.h that denoise.hip's
 // kernel makes for its lane, so both give the same bits.
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <cmath>
-#include <string>
 
 #include "../../include/render_mi355x_denoise.h"
 #include "denoise_host.h"
 #include "denoise_ops.h"
 
-namespace {
-thread_local std::string t_dn_err;
-}
+using apt::stage_set_error;
 
-namespace apt {
-void dn_clear_error() { t_dn_err.clear(); }
-int dn_set_error(int code, const char *fmt, const char *what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, fmt, what);
-    t_dn_err = buf;
-    return code;
-}
-} // namespace apt
-using apt::dn_set_error;
-
-extern "C" const char *apt_film_denoise_last_error(void) { return t_dn_err.c_str(); }
+extern "C" const char *apt_film_denoise_last_error(void) { return apt::stage_last_error(); }
 
 namespace apt {
 int film_accumulate_check(const void *pass_planes, uint64_t pixel_count, const void *film, const void *moments, const char *what) {
-    if (!pass_planes || !film || !moments) return dn_set_error(APT_ERR_ARG, "%s: pass_planes/film/moments must be non-null", what);
-    if ((pixel_count + 255) / 256 > 0x7fffffffull) return dn_set_error(APT_ERR_ARG, "%s: pixel_count too large for one launch; shard it", what);
+    if (!pass_planes || !film || !moments) return stage_set_error(APT_ERR_ARG, "%s: pass_planes/film/moments must be non-null", what);
+    if ((pixel_count + 255) / 256 > 0x7fffffffull) return stage_set_error(APT_ERR_ARG, "%s: pixel_count too large for one launch; shard it", what);
     return APT_OK;
 }
 
 int film_denoise_check(const apt_film_denoise *d, const void *film, const void *moments, const void *features, uint32_t width, uint32_t height,
                        const void *work, const void *out, const char *what) {
     if (!d || !film || !moments || !features || !work || !out)
-        return dn_set_error(APT_ERR_ARG, "%s: d/film/moments/features/work/out must be non-null", what);
-    if (d->struct_size != sizeof(apt_film_denoise)) return dn_set_error(APT_ERR_STRUCT, "%s: apt_film_denoise.struct_size mismatch", what);
-    if ((uintptr_t)work & 15u) return dn_set_error(APT_ERR_ARG, "%s: work must be 16-byte aligned", what);
-    if (!width || !height) return dn_set_error(APT_ERR_ARG, "%s: width/height must be non-zero", what);
-    if (d->passes < 2 || d->passes > (1u << 24)) return dn_set_error(APT_ERR_ARG, "%s: passes must lie in [2, 2^24]", what);
-    if (d->iterations < 1 || d->iterations > 5) return dn_set_error(APT_ERR_ARG, "%s: iterations must lie in [1, 5]", what);
+        return stage_set_error(APT_ERR_ARG, "%s: d/film/moments/features/work/out must be non-null", what);
+    if (d->struct_size != sizeof(apt_film_denoise)) return stage_set_error(APT_ERR_STRUCT, "%s: apt_film_denoise.struct_size mismatch", what);
+    if ((uintptr_t)work & 15u) return stage_set_error(APT_ERR_ARG, "%s: work must be 16-byte aligned", what);
+    if (!width || !height) return stage_set_error(APT_ERR_ARG, "%s: width/height must be non-zero", what);
+    if (d->passes < 2 || d->passes > kMaxPasses) return stage_set_error(APT_ERR_ARG, "%s: passes must lie in [2, 2^24]", what);
+    if (d->iterations < 1 || d->iterations > 5) return stage_set_error(APT_ERR_ARG, "%s: iterations must lie in [1, 5]", what);
     const float sig[5] = {d->sigma_n, d->sigma_z, d->sigma_c, d->sigma_a, d->sigma_l};
     for (float s : sig)
-        if (!(std::isfinite(s) && s >= 0.0f)) return dn_set_error(APT_ERR_ARG, "%s: every sigma must be finite and not negative", what);
-    if (!(std::isfinite(d->albedo_floor) && d->albedo_floor > 0.0f)) return dn_set_error(APT_ERR_ARG, "%s: albedo_floor must be finite and > 0", what);
-    if ((uint64_t)width * height > (1ull << 28)) return dn_set_error(APT_ERR_ARG, "%s: more than 2^28 pixels: too large for one launch", what);
+        if (!(std::isfinite(s) && s >= 0.0f)) return stage_set_error(APT_ERR_ARG, "%s: every sigma must be finite and not negative", what);
+    if (!(std::isfinite(d->albedo_floor) && d->albedo_floor > 0.0f)) return stage_set_error(APT_ERR_ARG, "%s: albedo_floor must be finite and > 0", what);
+    if ((uint64_t)width * height > kMaxPixels) return stage_set_error(APT_ERR_ARG, "%s: more than 2^28 pixels: too large for one launch", what);
     return APT_OK;
 }
 } // namespace apt
@@ -61,7 +45,7 @@ using apt::DnRec;
 extern "C" {
 
 int apt_film_accumulate_host(const float *pass_planes, uint64_t pixel_count, float *film, float *moments, uint32_t pass) {
-    apt::dn_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_accumulate_check(pass_planes, pixel_count, film, moments, "apt_film_accumulate_host");
     if (rc) return rc;
     for (uint64_t i = 0; i < pixel_count; ++i) apt::dn_accumulate(pass_planes, film, moments, pixel_count, i, pass == 0);
@@ -69,8 +53,8 @@ int apt_film_accumulate_host(const float *pass_planes, uint64_t pixel_count, flo
 }
 
 int apt_film_denoise_default_host(apt_film_denoise *d, uint32_t passes) {
-    apt::dn_clear_error();
-    if (!d) return dn_set_error(APT_ERR_ARG, "%s: the record is null", "apt_film_denoise_default_host");
+    apt::stage_clear_error();
+    if (!d) return stage_set_error(APT_ERR_ARG, "%s: the record is null", "apt_film_denoise_default_host");
     memset(d, 0, sizeof *d);
     d->struct_size = sizeof *d;
     d->passes = passes;
@@ -84,7 +68,7 @@ uint64_t apt_film_denoise_work_floats(uint32_t width, uint32_t height) { return 
 
 int apt_film_denoise_host(const apt_film_denoise *d, const float *film, const float *moments, const float *features, uint32_t width,
                           uint32_t height, float *work, float *out) {
-    apt::dn_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_denoise_check(d, film, moments, features, width, height, work, out, "apt_film_denoise_host");
     if (rc) return rc;
     const uint32_t n = width * height;                                            // <= 2^28: the check above

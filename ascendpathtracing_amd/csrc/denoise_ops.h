@@ -10,23 +10,17 @@
 
 #include "../../include/render_mi355x_denoise.h"
 #include "apt_hd.h"
+#include "film_stage_ops.h"
 
 namespace apt {
 
-struct alignas(16) DnRec { float x, y, z, w; };   // one record of the work buffer: a 16-byte load or store on the device
+using DnRec = FsRec;                              // one record of the work buffer
 struct DnSigma { float n, z, c, a, l; };          // apt_film_denoise's edge-stopping sigmas: normal, depth, coverage, albedo, luminance
-
-APT_HD float dn_lum(float r, float g, float b) {
-    float l = 0.2126f * r;
-    l = l + 0.7152f * g;
-    return l + 0.0722f * b;
-}
-APT_HD float dn_max(float a, float b) { return a > b ? a : b; }
 
 // ---- moments: pixel i of n joins the film and its luminance moments; the first pass stores ------------------------------------------
 APT_HD void dn_accumulate(const float *pass, float *film, float *mom, uint64_t n, uint64_t i, bool first) {
     const float r = pass[i], g = pass[n + i], b = pass[2 * n + i];
-    const float l = dn_lum(r, g, b);
+    const float l = fs_lum(r, g, b);
     const float l2 = l * l;
     if (first) {
         film[i] = r; film[n + i] = g; film[2 * n + i] = b;
@@ -41,17 +35,17 @@ APT_HD void dn_accumulate(const float *pass, float *film, float *mom, uint64_t n
 APT_HD void dn_prepare(const float *film, const float *mom, const float *feat, DnRec *g0, DnRec *g1, DnRec *c0, uint64_t n, uint32_t i, float K,
                        float K1, float albedo_floor) {
     const float cov = feat[APT_FEATURE_COVERAGE * n + i];
-    const float u = 1.0f - cov;
+    const float u = fs_uncovered(cov);
     float A[3], il[3];
     APT_UNROLL
     for (uint64_t ch = 0; ch < 3; ++ch) {
         const float cm = film[ch * n + i] / K;
-        A[ch] = dn_max(feat[(APT_FEATURE_ALBEDO + ch) * n + i] + u, albedo_floor);
+        A[ch] = fs_albedo(feat[(APT_FEATURE_ALBEDO + ch) * n + i], u, albedo_floor);
         il[ch] = cm / A[ch];
     }
     const float lm = mom[i] / K, q = mom[n + i] / K;
-    const float v = dn_max(q - lm * lm, 0.0f) / K1;
-    const float LA = dn_lum(A[0], A[1], A[2]);
+    const float v = fs_max(q - lm * lm, 0.0f) / K1;
+    const float LA = fs_lum(A[0], A[1], A[2]);
     const float vi = v / (LA * LA);
     g0[i] = DnRec{feat[APT_FEATURE_NORMAL * n + i], feat[(APT_FEATURE_NORMAL + 1) * n + i], feat[(APT_FEATURE_NORMAL + 2) * n + i],
                   feat[APT_FEATURE_DEPTH * n + i]};
@@ -85,9 +79,10 @@ APT_HD void dn_iterate(const DnRec *g0, const DnRec *g1, const DnRec *in, DnRec 
     e = e + 1e-6f;
     const float isd = 1.0f / e;
     const DnRec n_p = g0[ip], a_p = g1[ip], c_p = in[ip];
+    const FsGuide gp = {n_p.x, n_p.y, n_p.z, n_p.w, a_p.w, a_p.x, a_p.y, a_p.z};
     const float zz = n_p.w + 1e-6f;
     const float iz = 1.0f / zz;
-    const float lp = dn_lum(c_p.x, c_p.y, c_p.z);
+    const float lp = fs_lum(c_p.x, c_p.y, c_p.z);
 
     float Wt = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, V = 0.0f;
     APT_UNROLL
@@ -98,26 +93,14 @@ APT_HD void dn_iterate(const DnRec *g0, const DnRec *g1, const DnRec *in, DnRec 
             if ((uint32_t)qx < (uint32_t)W && (uint32_t)qy < (uint32_t)H) {
                 const int32_t iq = qx * H + qy;
                 const DnRec n_q = g0[iq], a_q = g1[iq], c_q = in[iq];
-                const float cc = a_p.w * a_q.w;
-                float dt = 0.0f + n_p.x * n_q.x;
-                dt = dt + n_p.y * n_q.y;
-                dt = dt + n_p.z * n_q.z;
-                const float xn = sg.n * dn_max(cc - dt, 0.0f);
-                const float xz = (sg.z * fabsf(n_p.w - n_q.w)) * iz;
-                const float xc = sg.c * fabsf(a_p.w - a_q.w);
-                float da = fabsf(a_p.x - a_q.x) + fabsf(a_p.y - a_q.y);
-                da = da + fabsf(a_p.z - a_q.z);
-                const float xa = sg.a * da;
-                const float lq = dn_lum(c_q.x, c_q.y, c_q.z);
+                const FsGuide gq = {n_q.x, n_q.y, n_q.z, n_q.w, a_q.w, a_q.x, a_q.y, a_q.z};
+                const FsSigma gs = {sg.n, sg.z, sg.c, sg.a};   // read at the tap, as before: it keeps the kernel's instructions
+                float xs = fs_edge_sum(gp, iz, gq, gs);
+                const float lq = fs_lum(c_q.x, c_q.y, c_q.z);
                 const float xl = fabsf(lp - lq) * isd;
-                float xs = xn + xz;
-                xs = xs + xc;
-                xs = xs + xa;
                 xs = xs + xl;
-                float t = dn_max(1.0f - xs * 0.125f, 0.0f);
-                t = t * t;
-                t = t * t;
-                const float g = dx == 0 && dy == 0 ? 1.0f : t * t;            // the centre tap: x = 0 by definition (compile time)
+                const float t = fs_edge_falloff(xs);                          // of every tap, selected below: as before
+                const float g = dx == 0 && dy == 0 ? 1.0f : t;                // the centre tap: x = 0 by definition (compile time)
                 const float hx = dx == 0 ? 0.375f : (dx == 1 || dx == -1 ? 0.25f : 0.0625f);
                 const float hy = dy == 0 ? 0.375f : (dy == 1 || dy == -1 ? 0.25f : 0.0625f);
                 const float w = (hx * hy) * g;

@@ -12,10 +12,13 @@
 
 #include "../../include/render_mi355x_history.h"
 #include "history_host.h"
+#include "film_stage_launch.h"
 #include "history_ops.h"
 
+using apt::blocks_for;
 using apt::HsArgs;
 using apt::kHsBlock;
+using apt::launched;
 
 namespace {
 
@@ -32,13 +35,6 @@ __global__ __launch_bounds__(kHsBlock) void film_history_export_kernel(const flo
     apt::hs_export(hist, film, mom, n, i);
 }
 
-// -> APT_OK when the runtime took the launch, APT_ERR_DEVICE with its text otherwise
-int launched() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return APT_OK;
-    return apt::hs_set_error(APT_ERR_DEVICE, "%s", hipGetErrorString(e));
-}
-
 } // namespace
 
 extern "C" {
@@ -46,21 +42,21 @@ extern "C" {
 int apt_film_history_device(const apt_film_history *rec, void *stream, const apt_camera *cur_cam, const apt_camera *prev_cam, const float *cur,
                             const float *cur_features, const float *prev_features, const float *prev_hist, uint32_t width, uint32_t height,
                             float *out_hist) {
-    apt::hs_clear_error();
+    apt::stage_clear_error();
     HsArgs a;
     const int rc = apt::film_history_check(rec, cur_cam, prev_cam, cur, cur_features, prev_features, prev_hist, width, height, out_hist, &a,
                                            "apt_film_history_device");
     if (rc) return rc;
-    const unsigned blocks = (unsigned)(((uint64_t)width * height + kHsBlock - 1) / kHsBlock);       // <= 2^20
+    const unsigned blocks = blocks_for((uint64_t)width * height, kHsBlock);
     hipLaunchKernelGGL(film_history_kernel, dim3(blocks), dim3(kHsBlock), 0, (hipStream_t)stream, a);
     return launched();
 }
 
 int apt_film_history_export_device(void *stream, const float *hist, uint64_t pixel_count, float *film, float *moments) {
-    apt::hs_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_history_export_check(hist, pixel_count, film, moments, "apt_film_history_export_device");
     if (rc) return rc;
-    const unsigned blocks = (unsigned)((pixel_count + kHsBlock - 1) / kHsBlock);
+    const unsigned blocks = blocks_for(pixel_count, kHsBlock);
     hipLaunchKernelGGL(film_history_export_kernel, dim3(blocks), dim3(kHsBlock), 0, (hipStream_t)stream, hist, film, moments, pixel_count);
     return launched();
 }

@@ -1,15 +1,13 @@
-// history_host.h -- what history.hip (the device entries) and history_host.cpp (the host entries) of libhistory_mi355x.so share: the
-// per-thread error record behind apt_film_history_last_error() and one check function per entry pair
-// (include/render_mi355x_history.h).
+// history_host.h -- what history.hip (the device entries) and history_host.cpp (the host entries) of libhistory_mi355x.so share
+// beside film_stage_host.h: one check function per entry pair (include/render_mi355x_history.h).
 #pragma once
 #include <stdint.h>
 
 #include "../../include/render_mi355x_history.h"
+#include "film_stage_host.h"
 
 namespace apt {
 struct HsArgs;
-void hs_clear_error();                                          // every entry calls this first
-int hs_set_error(int code, const char *fmt, const char *what);  // returns `code`; fmt holds one %s
 // What both forms of an entry refuse, in the header's order: APT_OK or the error record set.  film_history_check also fills *args
 // -- the pointers, the checked record and the cameras as the arithmetic reads them -- when it returns APT_OK.
 int film_history_check(const apt_film_history *rec, const apt_camera *cur_cam, const apt_camera *prev_cam, const float *cur,

@@ -8,6 +8,7 @@
 
 #include "../../include/render_mi355x_history.h"
 #include "apt_hd.h"
+#include "film_stage_ops.h"
 
 namespace apt {
 
@@ -38,12 +39,6 @@ APT_HD HsCam hs_cam(const apt_camera &c) {
     return k;
 }
 
-APT_HD float hs_lum(float r, float g, float b) {   // render_mi355x_denoise.h's lum
-    float l = 0.2126f * r;
-    l = l + 0.7152f * g;
-    return l + 0.0722f * b;
-}
-
 // The world point X of pixel (x, y) of camera c, whose planes hold `cov` and `depth` there (w, h: the image's size as doubles).
 APT_HD void hs_world(const HsCam &c, double w, double h, double x, double y, double cov, double depth, double *X) {
     const double a = (x + 0.5) / w - 0.5;
@@ -65,7 +60,7 @@ APT_HD void hs_pixel(const HsArgs &A, uint32_t x, uint32_t y) {
     const uint64_t n = (uint64_t)A.w * A.h;
     const uint64_t i = (uint64_t)x * A.h + y;
     const float cr = A.cur[i], cg = A.cur[n + i], cb = A.cur[2 * n + i];
-    const float l = hs_lum(cr, cg, cb);
+    const float l = fs_lum(cr, cg, cb);
     const float nw[5] = {cr, cg, cb, l, l * l};
     float S[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     float W = 0.0f, Sh = 0.0f;

@@ -18,12 +18,14 @@
 #include <stdint.h>
 
 #include "../../include/render_mi355x_metrics.h"
+#include "film_stage_launch.h"
 #include "metrics_host.h"
 #include "metrics_ops.h"
 
 using apt::kMxChunk;
 using apt::kMxCompareRowWords;
 using apt::kMxFoldRows;
+using apt::launched;
 using apt::MxRec;
 
 namespace {
@@ -283,20 +285,13 @@ __global__ __launch_bounds__(kMxBlock) void map_sum_kernel(const float *map, uin
     if (threadIdx.x == 0) work[blockIdx.x] = d2u(s[0]);
 }
 
-// -> APT_OK when the runtime took the launches, APT_ERR_DEVICE with its text otherwise
-int launched() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return APT_OK;
-    return apt::mx_set_error(APT_ERR_DEVICE, "%s", hipGetErrorString(e));
-}
-
 } // namespace
 
 extern "C" {
 
 int apt_film_compare_device(const apt_film_compare *c, void *stream, const float *a, const float *b, uint64_t pixel_count, double *work,
                             uint64_t *result, float *err_map) {
-    apt::mx_clear_error();
+    apt::stage_clear_error();
     CompareArgs g;
     const int rc = apt::film_compare_check(c, a, b, pixel_count, work, true, result, err_map, &g.p, "apt_film_compare_device");
     if (rc) return rc;
@@ -315,7 +310,7 @@ int apt_film_compare_device(const apt_film_compare *c, void *stream, const float
 
 int apt_film_ssim_device(const apt_film_compare *c, void *stream, const float *a, const float *b, uint32_t width, uint32_t height, void *work,
                          uint64_t *result, float *ssim_map) {
-    apt::mx_clear_error();
+    apt::stage_clear_error();
     SsimArgs g;
     const int rc = apt::film_ssim_check(c, a, b, width, height, work, true, result, ssim_map, &g.p, "apt_film_ssim_device");
     if (rc) return rc;

@@ -12,15 +12,10 @@
 
 #include "../../include/render_mi355x_metrics.h"
 #include "apt_hd.h"
+#include "film_stage_ops.h"
 
 namespace apt {
 
-APT_HD float mx_lum(float r, float g, float b) {
-    float l = 0.2126f * r;
-    l = l + 0.7152f * g;
-    return l + 0.0722f * b;
-}
-APT_HD float mx_max(float a, float b) { return a > b ? a : b; }
 APT_HD uint32_t mx_bits(float f) {
     uint32_t u;
     memcpy(&u, &f, sizeof u);
@@ -88,7 +83,7 @@ APT_HD MxTerms mx_pixel(const float a[3], const float b[3], uint32_t i, const Mx
     t.cse = (cc[0] + cc[1]) + cc[2];
     t.rse = (r[0] + r[1]) + r[2];
     t.ae = (ad[0] + ad[1]) + ad[2];
-    const float m = mx_max(mx_max(ad[0], ad[1]), ad[2]);
+    const float m = fs_max(fs_max(ad[0], ad[1]), ad[2]);
     t.key = ((uint64_t)mx_bits(m) << 32) | (uint64_t)(0xFFFFFFFFu - i);
     t.bad = 0;
     return t;
@@ -111,7 +106,7 @@ constexpr float kMxC1 = 1e-4f, kMxC2 = 9e-4f;
 // the display luminance of a film's pixel (r, g, b) over K frames
 APT_HD float mx_display_lum(float r, float g, float b, float K, float inv, float exposure) {
     const float mr = mx_mean(r, K, inv), mg = mx_mean(g, K, inv), mb = mx_mean(b, K, inv);
-    return mx_lum(mx_clip01(mr * exposure), mx_clip01(mg * exposure), mx_clip01(mb * exposure));
+    return fs_lum(mx_clip01(mr * exposure), mx_clip01(mg * exposure), mx_clip01(mb * exposure));
 }
 
 // one step of a pass of the filter over the five planes, from the luminances (ya, yb) of ONE source pixel (the x pass) ...
@@ -141,7 +136,6 @@ APT_HD float mx_ssim(const float f[5]) {
 constexpr uint32_t kMxChunk = 1024;                                  // terms a workgroup of a reducing kernel takes: 256 lanes x 4
 constexpr uint32_t kMxFoldRows = 4096;                               // rows a workgroup of the fold takes: 1024 lanes x 4
 constexpr uint32_t kMxCompareRowWords = 6;                           // se, cse, rse, ae, key, bad
-constexpr uint64_t kMxMaxPixels = 1ull << 28;
 
 // the rows of a reduction of n terms, level by level: r0 workgroup rows, then r1 rows of a first fold when r0 > kMxFoldRows (the last
 // fold always stores the result itself); n <= 2^28: r1 <= 64

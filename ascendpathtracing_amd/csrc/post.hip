@@ -19,9 +19,11 @@
 #include <stdint.h>
 
 #include "../../include/render_mi355x_post.h"
+#include "film_stage_launch.h"
 #include "post_host.h"
 #include "post_ops.h"
 
+using apt::launched;
 using apt::PoBloom;
 using apt::PoRec;
 
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(kPoBlock) void bloom_composite_kernel(CompositeArgs
     apt::po_composite(a.film, a.c, a.out, a.W, a.H, a.wc, a.hc, a.K, a.intensity, x, y);
 }
 
-unsigned blocks_for(int32_t w, int32_t h) { return (unsigned)(((uint32_t)(w * h) + kPoBlock - 1) / kPoBlock); }   // w * h <= 2^28
+unsigned blocks_of(int32_t w, int32_t h) { return apt::blocks_for((uint32_t)(w * h), kPoBlock); }   // a w x h level: w * h <= 2^28
 
 void film_bloom(const PoBloom &b, hipStream_t stream) {
     const uint32_t n = (uint32_t)(b.W * b.H);
@@ -148,25 +150,18 @@ void film_bloom(const PoBloom &b, hipStream_t stream) {
         d.rec = apt::PoRecSrc{j ? b.level[j - 1] : nullptr};
         d.dst = b.level[j];
         d.ws = j ? b.w[j - 1] : b.W; d.hs = j ? b.h[j - 1] : b.H; d.wd = b.w[j]; d.hd = b.h[j];
-        if (j == 0) hipLaunchKernelGGL(bloom_down_kernel<true>, dim3(blocks_for(d.wd, d.hd)), dim3(kPoBlock), 0, stream, d);
-        else hipLaunchKernelGGL(bloom_down_kernel<false>, dim3(blocks_for(d.wd, d.hd)), dim3(kPoBlock), 0, stream, d);
+        if (j == 0) hipLaunchKernelGGL(bloom_down_kernel<true>, dim3(blocks_of(d.wd, d.hd)), dim3(kPoBlock), 0, stream, d);
+        else hipLaunchKernelGGL(bloom_down_kernel<false>, dim3(blocks_of(d.wd, d.hd)), dim3(kPoBlock), 0, stream, d);
     }
     for (int32_t j = (int32_t)b.levels - 2; j >= 0; --j) {
         CombineArgs c;
         c.d = b.level[j]; c.c = b.level[j + 1]; c.wf = b.w[j]; c.hf = b.h[j]; c.wc = b.w[j + 1]; c.hc = b.h[j + 1]; c.spread = b.spread;
-        hipLaunchKernelGGL(bloom_combine_kernel, dim3(blocks_for(c.wf, c.hf)), dim3(kPoBlock), 0, stream, c);
+        hipLaunchKernelGGL(bloom_combine_kernel, dim3(blocks_of(c.wf, c.hf)), dim3(kPoBlock), 0, stream, c);
     }
     CompositeArgs f;
     f.film = b.film; f.c = b.level[0]; f.out = b.out; f.W = b.W; f.H = b.H; f.wc = b.w[0]; f.hc = b.h[0];
     f.K = b.bright.K; f.intensity = b.intensity;
-    hipLaunchKernelGGL(bloom_composite_kernel, dim3(blocks_for(b.W, b.H)), dim3(kPoBlock), 0, stream, f);
-}
-
-// -> APT_OK when the runtime took the launches, APT_ERR_DEVICE with its text otherwise
-int launched() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return APT_OK;
-    return apt::po_set_error(APT_ERR_DEVICE, "%s", hipGetErrorString(e));
+    hipLaunchKernelGGL(bloom_composite_kernel, dim3(blocks_of(b.W, b.H)), dim3(kPoBlock), 0, stream, f);
 }
 
 } // namespace
@@ -174,7 +169,7 @@ int launched() {
 extern "C" {
 
 int apt_film_meter_device(const apt_film_meter *m, void *stream, const float *film, uint64_t pixel_count, uint32_t *work, uint32_t *hist) {
-    apt::po_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_meter_check(m, film, pixel_count, work, true, hist, "apt_film_meter_device");
     if (rc) return rc;
     const uint32_t rows = apt::po_meter_rows(pixel_count);           // 0 without pixels: the fold then stores zeros and reads nothing
@@ -196,7 +191,7 @@ int apt_film_meter_device(const apt_film_meter *m, void *stream, const float *fi
 }
 
 int apt_film_bloom_device(const apt_film_bloom *b, void *stream, const float *film, uint32_t width, uint32_t height, float *work, float *out) {
-    apt::po_clear_error();
+    apt::stage_clear_error();
     PoBloom a;
     const int rc = apt::film_bloom_check(b, film, width, height, work, out, &a, "apt_film_bloom_device");
     if (rc) return rc;

@@ -1,72 +1,58 @@
-// post_host.cpp -- the host side of libpost_mi355x.so (include/render_mi355x_post.h): the library's own per-thread error record, the
-// checks that the device and the host form of each entry share, the defaults, the exposure (host only) and the CPU twins.  Compiled
+// post_host.cpp -- the host side of libpost_mi355x.so (include/render_mi355x_post.h): the checks that the device and the host form of each entry share, the defaults, the exposure (host only) and the CPU twins.  Compiled
 // with the product's -ffp-contract=off -fno-fast-math: a twin is a loop over the pixels and the call of post_ops.h that post.hip's
 // kernel makes for its lane, so both give the same bits.
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <cmath>
-#include <string>
 
 #include "../../include/render_mi355x_post.h"
 #include "post_host.h"
 #include "post_ops.h"
 
 namespace {
-thread_local std::string t_po_err;
-constexpr uint64_t kMaxPixels = 1ull << 28;
-constexpr uint32_t kMaxPasses = 1u << 24;
-
 bool positive(float v) { return std::isfinite(v) && v > 0.0f; }
 bool not_negative(float v) { return std::isfinite(v) && v >= 0.0f; }
 }
 
-namespace apt {
-void po_clear_error() { t_po_err.clear(); }
-int po_set_error(int code, const char *fmt, const char *what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, fmt, what);
-    t_po_err = buf;
-    return code;
-}
+using apt::kMaxPixels;
 
+namespace apt {
 // the whole record, whichever entry takes it
 static int meter_record_check(const apt_film_meter *m, const char *what) {
-    if (m->struct_size != sizeof(apt_film_meter)) return po_set_error(APT_ERR_STRUCT, "%s: apt_film_meter.struct_size mismatch", what);
-    if (m->passes < 1 || m->passes > kMaxPasses) return po_set_error(APT_ERR_ARG, "%s: passes must lie in [1, 2^24]", what);
+    if (m->struct_size != sizeof(apt_film_meter)) return stage_set_error(APT_ERR_STRUCT, "%s: apt_film_meter.struct_size mismatch", what);
+    if (int rc = stage_passes_check(m->passes, "passes", what)) return rc;
     if (!(1 <= m->low_q && m->low_q <= m->high_q && m->high_q <= 65536))
-        return po_set_error(APT_ERR_ARG, "%s: the percentiles must satisfy 1 <= low_q <= high_q <= 65536", what);
+        return stage_set_error(APT_ERR_ARG, "%s: the percentiles must satisfy 1 <= low_q <= high_q <= 65536", what);
     if (!positive(m->key) || !positive(m->min_exposure) || !positive(m->max_exposure))
-        return po_set_error(APT_ERR_ARG, "%s: key, min_exposure and max_exposure must be finite and positive", what);
-    if (m->min_exposure > m->max_exposure) return po_set_error(APT_ERR_ARG, "%s: min_exposure must not exceed max_exposure", what);
-    if (!(m->adapt >= 0.0f && m->adapt <= 1.0f)) return po_set_error(APT_ERR_ARG, "%s: adapt must lie in [0, 1]", what);
+        return stage_set_error(APT_ERR_ARG, "%s: key, min_exposure and max_exposure must be finite and positive", what);
+    if (m->min_exposure > m->max_exposure) return stage_set_error(APT_ERR_ARG, "%s: min_exposure must not exceed max_exposure", what);
+    if (!(m->adapt >= 0.0f && m->adapt <= 1.0f)) return stage_set_error(APT_ERR_ARG, "%s: adapt must lie in [0, 1]", what);
     return APT_OK;
 }
 
 int film_meter_check(const apt_film_meter *m, const void *film, uint64_t pixel_count, const void *work, bool need_work, const void *hist,
                      const char *what) {
-    if (!m || !hist) return po_set_error(APT_ERR_ARG, "%s: m/hist must be non-null", what);
-    if (pixel_count != 0 && (!film || (need_work && !work))) return po_set_error(APT_ERR_ARG, "%s: film/work must be non-null", what);
+    if (!m || !hist) return stage_set_error(APT_ERR_ARG, "%s: m/hist must be non-null", what);
+    if (pixel_count != 0 && (!film || (need_work && !work))) return stage_set_error(APT_ERR_ARG, "%s: film/work must be non-null", what);
     if (int rc = meter_record_check(m, what)) return rc;
-    if (pixel_count > kMaxPixels) return po_set_error(APT_ERR_ARG, "%s: pixel_count must not exceed 2^28", what);
+    if (pixel_count > kMaxPixels) return stage_set_error(APT_ERR_ARG, "%s: pixel_count must not exceed 2^28", what);
     return APT_OK;
 }
 
 int film_bloom_check(const apt_film_bloom *b, const float *film, uint32_t width, uint32_t height, float *work, float *out, PoBloom *args,
                      const char *what) {
-    if (!b || !film || !work || !out) return po_set_error(APT_ERR_ARG, "%s: b/film/work/out must be non-null", what);
-    if (b->struct_size != sizeof(apt_film_bloom)) return po_set_error(APT_ERR_STRUCT, "%s: apt_film_bloom.struct_size mismatch", what);
-    if (width == 0 || height == 0 || (uint64_t)width * height > kMaxPixels)
-        return po_set_error(APT_ERR_ARG, "%s: width * height must lie in [1, 2^28]", what);
-    if ((uintptr_t)work % 16 != 0) return po_set_error(APT_ERR_ARG, "%s: work must be 16-byte aligned", what);
-    if (out == film) return po_set_error(APT_ERR_ARG, "%s: out must not be film", what);
-    if (b->passes < 1 || b->passes > kMaxPasses) return po_set_error(APT_ERR_ARG, "%s: passes must lie in [1, 2^24]", what);
-    if (b->levels < 1 || b->levels > kPoMaxLevels) return po_set_error(APT_ERR_ARG, "%s: levels must lie in [1, 6]", what);
+    if (!b || !film || !work || !out) return stage_set_error(APT_ERR_ARG, "%s: b/film/work/out must be non-null", what);
+    if (b->struct_size != sizeof(apt_film_bloom)) return stage_set_error(APT_ERR_STRUCT, "%s: apt_film_bloom.struct_size mismatch", what);
+    if (int rc = stage_pixels_check((uint64_t)width * height, "width * height", what)) return rc;
+    if ((uintptr_t)work % 16 != 0) return stage_set_error(APT_ERR_ARG, "%s: work must be 16-byte aligned", what);
+    if (out == film) return stage_set_error(APT_ERR_ARG, "%s: out must not be film", what);
+    if (int rc = stage_passes_check(b->passes, "passes", what)) return rc;
+    if (b->levels < 1 || b->levels > kPoMaxLevels) return stage_set_error(APT_ERR_ARG, "%s: levels must lie in [1, 6]", what);
     if (!not_negative(b->threshold) || !not_negative(b->spread) || !not_negative(b->intensity))
-        return po_set_error(APT_ERR_ARG, "%s: threshold, spread and intensity must be finite and not negative", what);
-    if (!positive(b->cap)) return po_set_error(APT_ERR_ARG, "%s: cap must be finite and positive", what);
+        return stage_set_error(APT_ERR_ARG, "%s: threshold, spread and intensity must be finite and not negative", what);
+    if (!positive(b->cap)) return stage_set_error(APT_ERR_ARG, "%s: cap must be finite and positive", what);
     args->film = film; args->out = out; args->W = (int32_t)width; args->H = (int32_t)height; args->levels = b->levels;
     args->bright = PoBright{(float)b->passes, b->cap, b->threshold};
     args->spread = b->spread; args->intensity = b->intensity;
@@ -80,16 +66,16 @@ int film_bloom_check(const apt_film_bloom *b, const float *film, uint32_t width,
     return APT_OK;
 }
 } // namespace apt
-using apt::po_set_error;
+using apt::stage_set_error;
 
 extern "C" {
 
-const char *apt_film_post_last_error(void) { return t_po_err.c_str(); }
+const char *apt_film_post_last_error(void) { return apt::stage_last_error(); }
 
 int apt_film_meter_default_host(apt_film_meter *m, uint32_t passes) {
-    apt::po_clear_error();
-    if (!m) return po_set_error(APT_ERR_ARG, "%s: the record is null", "apt_film_meter_default_host");
-    if (passes < 1 || passes > kMaxPasses) return po_set_error(APT_ERR_ARG, "%s: passes must lie in [1, 2^24]", "apt_film_meter_default_host");
+    apt::stage_clear_error();
+    if (!m) return stage_set_error(APT_ERR_ARG, "%s: the record is null", "apt_film_meter_default_host");
+    if (int rc = apt::stage_passes_check(passes, "passes", "apt_film_meter_default_host")) return rc;
     memset(m, 0, sizeof *m);
     m->struct_size = sizeof *m;
     m->passes = passes;
@@ -106,7 +92,7 @@ uint64_t apt_film_meter_work_words(uint64_t pixel_count) {
 }
 
 int apt_film_meter_host(const apt_film_meter *m, const float *film, uint64_t pixel_count, uint32_t *hist) {
-    apt::po_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_meter_check(m, film, pixel_count, nullptr, false, hist, "apt_film_meter_host");
     if (rc) return rc;
     memset(hist, 0, APT_METER_WORDS * sizeof(uint32_t));
@@ -116,11 +102,11 @@ int apt_film_meter_host(const apt_film_meter *m, const float *film, uint64_t pix
 }
 
 int apt_film_exposure_host(const apt_film_meter *m, const uint32_t *hist, float prev, float *exposure) {
-    apt::po_clear_error();
+    apt::stage_clear_error();
     const char *what = "apt_film_exposure_host";
-    if (!m || !hist || !exposure) return po_set_error(APT_ERR_ARG, "%s: m/hist/exposure must be non-null", what);
+    if (!m || !hist || !exposure) return stage_set_error(APT_ERR_ARG, "%s: m/hist/exposure must be non-null", what);
     if (int rc = apt::meter_record_check(m, what)) return rc;
-    if (!(std::isfinite(prev) && prev >= 0.0f)) return po_set_error(APT_ERR_ARG, "%s: prev must be finite and not negative", what);
+    if (!(std::isfinite(prev) && prev >= 0.0f)) return stage_set_error(APT_ERR_ARG, "%s: prev must be finite and not negative", what);
     uint64_t n = 0;
     for (int b = 0; b < APT_METER_BINS; ++b) n += hist[b];
     if (n == 0) { *exposure = prev; return APT_OK; }
@@ -148,9 +134,9 @@ int apt_film_exposure_host(const apt_film_meter *m, const uint32_t *hist, float 
 }
 
 int apt_film_bloom_default_host(apt_film_bloom *b, uint32_t passes) {
-    apt::po_clear_error();
-    if (!b) return po_set_error(APT_ERR_ARG, "%s: the record is null", "apt_film_bloom_default_host");
-    if (passes < 1 || passes > kMaxPasses) return po_set_error(APT_ERR_ARG, "%s: passes must lie in [1, 2^24]", "apt_film_bloom_default_host");
+    apt::stage_clear_error();
+    if (!b) return stage_set_error(APT_ERR_ARG, "%s: the record is null", "apt_film_bloom_default_host");
+    if (int rc = apt::stage_passes_check(passes, "passes", "apt_film_bloom_default_host")) return rc;
     memset(b, 0, sizeof *b);
     b->struct_size = sizeof *b;
     b->passes = passes;
@@ -170,7 +156,7 @@ uint64_t apt_film_bloom_work_floats(uint32_t width, uint32_t height, uint32_t le
 }
 
 int apt_film_bloom_host(const apt_film_bloom *b, const float *film, uint32_t width, uint32_t height, float *work, float *out) {
-    apt::po_clear_error();
+    apt::stage_clear_error();
     apt::PoBloom a;
     const int rc = apt::film_bloom_check(b, film, width, height, work, out, &a, "apt_film_bloom_host");
     if (rc) return rc;

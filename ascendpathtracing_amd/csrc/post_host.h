@@ -1,14 +1,13 @@
-// post_host.h -- what post.hip (the device entries) and post_host.cpp (the host entries) of libpost_mi355x.so share: the per-thread
-// error record behind apt_film_post_last_error() and one check function per entry pair (include/render_mi355x_post.h).
+// post_host.h -- what post.hip (the device entries) and post_host.cpp (the host entries) of libpost_mi355x.so share beside
+// film_stage_host.h: one check function per entry pair (include/render_mi355x_post.h).
 #pragma once
 #include <stdint.h>
 
 #include "../../include/render_mi355x_post.h"
+#include "film_stage_host.h"
 
 namespace apt {
 struct PoBloom;
-void po_clear_error();                                          // every entry that returns a status calls this first
-int po_set_error(int code, const char *fmt, const char *what);  // returns `code`; fmt holds one %s
 // What both forms of an entry refuse, in the header's order: APT_OK or the error record set.  `work` is checked by the device form
 // alone (need_work).  film_bloom_check also fills *args -- the pointers, the checked record and the levels' sizes and places in work --
 // when it returns APT_OK.

@@ -11,17 +11,11 @@
 
 #include "../../include/render_mi355x_post.h"
 #include "apt_hd.h"
+#include "film_stage_ops.h"
 
 namespace apt {
 
-struct alignas(16) PoRec { float x, y, z, w; };   // one record of a pyramid level: a 16-byte load or store on the device
-
-APT_HD float po_lum(float r, float g, float b) {
-    float l = 0.2126f * r;
-    l = l + 0.7152f * g;
-    return l + 0.0722f * b;
-}
-APT_HD float po_max(float a, float b) { return a > b ? a : b; }
+using PoRec = FsRec;                              // one record of a pyramid level
 APT_HD uint32_t po_bits(float f) {
     uint32_t u;
     memcpy(&u, &f, sizeof u);
@@ -31,7 +25,7 @@ APT_HD uint32_t po_bits(float f) {
 // ---- metering: the histogram word of a pixel whose film values are (r, g, b); K = passes -------------------------------------------------
 APT_HD uint32_t po_meter_bin(float r, float g, float b, float K) {
     const float cr = r / K, cg = g / K, cb = b / K;
-    const float l = po_lum(cr, cg, cb);
+    const float l = fs_lum(cr, cg, cb);
     if (!(l > 0.0f)) return APT_METER_BINS;                       // zero, negative, NaN: word 256
     const int32_t e = (int32_t)(po_bits(l) >> 20) - 888;          // l > 0: the sign bit is clear, bits >> 20 <= 0x7F8
     return (uint32_t)(e < 0 ? 0 : (e > 255 ? 255 : e));
@@ -52,8 +46,8 @@ APT_HD void po_bright(const float *film, uint32_t n, uint32_t i, const PoBright 
         t = t < p.cap ? t : p.cap;
         x[ch] = t;
     }
-    const float l = po_lum(x[0], x[1], x[2]);
-    const float g = po_max(l - p.threshold, 0.0f) / po_max(l, 1e-6f);
+    const float l = fs_lum(x[0], x[1], x[2]);
+    const float g = fs_max(l - p.threshold, 0.0f) / fs_max(l, 1e-6f);
     APT_UNROLL
     for (uint32_t ch = 0; ch < 3; ++ch) v[ch] = x[ch] * g;
 }

@@ -14,10 +14,13 @@
 #include <stdint.h>
 
 #include "../../include/render_mi355x_upscale.h"
+#include "film_stage_launch.h"
 #include "upscale_host.h"
 #include "upscale_ops.h"
 
+using apt::blocks_for;
 using apt::kUpBlock;
+using apt::launched;
 using apt::UpArgs;
 
 namespace {
@@ -43,13 +46,6 @@ __global__ __launch_bounds__(kUpBlock) void film_upscale_patch_kernel(const floa
     apt::up_patch(sums, list, count, K, n, out, i);
 }
 
-// -> APT_OK when the runtime took the launch, APT_ERR_DEVICE with its text otherwise
-int launched() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return APT_OK;
-    return apt::up_set_error(APT_ERR_DEVICE, "%s", hipGetErrorString(e));
-}
-
 } // namespace
 
 extern "C" {
@@ -57,13 +53,13 @@ extern "C" {
 int apt_film_upscale_device(const apt_film_upscale *rec, void *stream, const float *lo, const float *lo_features, uint32_t lo_width,
                             uint32_t lo_height, const float *hi_features, uint32_t width, uint32_t height, float *work, float *out,
                             uint32_t *resolved) {
-    apt::up_clear_error();
+    apt::stage_clear_error();
     UpArgs a;
     const int rc = apt::film_upscale_check(rec, lo, lo_features, lo_width, lo_height, hi_features, width, height, work, out, resolved, &a,
                                            "apt_film_upscale_device");
     if (rc) return rc;
-    const unsigned lo_blocks = (unsigned)(((uint64_t)lo_width * lo_height + kUpBlock - 1) / kUpBlock);   // <= 2^20
-    const unsigned blocks = (unsigned)(((uint64_t)width * height + kUpBlock - 1) / kUpBlock);            // <= 2^20
+    const unsigned lo_blocks = blocks_for((uint64_t)lo_width * lo_height, kUpBlock);
+    const unsigned blocks = blocks_for((uint64_t)width * height, kUpBlock);
     hipLaunchKernelGGL(film_upscale_prepare_kernel, dim3(lo_blocks), dim3(kUpBlock), 0, (hipStream_t)stream, a);
     if (int e = launched()) return e;
     hipLaunchKernelGGL(film_upscale_kernel, dim3(blocks), dim3(kUpBlock), 0, (hipStream_t)stream, a);
@@ -72,11 +68,11 @@ int apt_film_upscale_device(const apt_film_upscale *rec, void *stream, const flo
 
 int apt_film_upscale_patch_device(void *stream, const float *sums, const uint32_t *list, uint64_t list_count, uint32_t passes,
                                   uint64_t pixel_count, float *out) {
-    apt::up_clear_error();
+    apt::stage_clear_error();
     const int rc = apt::film_upscale_patch_check(sums, list, list_count, passes, pixel_count, out, "apt_film_upscale_patch_device");
     if (rc) return rc;
     if (list_count == 0) return APT_OK;
-    const unsigned blocks = (unsigned)((list_count + kUpBlock - 1) / kUpBlock);                          // <= 2^20
+    const unsigned blocks = blocks_for(list_count, kUpBlock);
     hipLaunchKernelGGL(film_upscale_patch_kernel, dim3(blocks), dim3(kUpBlock), 0, (hipStream_t)stream, sums, list, list_count, (float)passes,
                        pixel_count, out);
     return launched();

@@ -1,15 +1,13 @@
-// upscale_host.h -- what upscale.hip (the device entries) and upscale_host.cpp (the host entries) of libupscale_mi355x.so share: the
-// per-thread error record behind apt_film_upscale_last_error() and one check function per entry pair
-// (include/render_mi355x_upscale.h).
+// upscale_host.h -- what upscale.hip (the device entries) and upscale_host.cpp (the host entries) of libupscale_mi355x.so share
+// beside film_stage_host.h: one check function per entry pair (include/render_mi355x_upscale.h).
 #pragma once
 #include <stdint.h>
 
 #include "../../include/render_mi355x_upscale.h"
+#include "film_stage_host.h"
 
 namespace apt {
 struct UpArgs;
-void up_clear_error();                                          // every entry calls this first
-int up_set_error(int code, const char *fmt, const char *what);  // returns `code`; fmt holds one %s
 // What both forms of an entry refuse, in the header's order: APT_OK or the error record set.  film_upscale_check also fills *args
 // -- the pointers, the three record arrays of `work` and the checked record -- when it returns APT_OK.
 int film_upscale_check(const apt_film_upscale *rec, const float *lo, const float *lo_features, uint32_t lo_width, uint32_t lo_height,

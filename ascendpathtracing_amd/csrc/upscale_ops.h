@@ -11,12 +11,13 @@
 
 #include "../../include/render_mi355x_upscale.h"
 #include "apt_hd.h"
+#include "film_stage_ops.h"
 
 namespace apt {
 
 constexpr uint32_t kUpBlock = 256;   // lanes per workgroup of the three kernels
 
-struct alignas(16) UpRec { float x, y, z, w; };   // one record of the work buffer: a 16-byte load or store on the device
+using UpRec = FsRec;                 // one record of the work buffer
 
 struct UpArgs {
     const float *lo, *lf, *hf;       // the low mean [3][Nl], the low and the full planes
@@ -27,16 +28,14 @@ struct UpArgs {
     float sn, sz, sc, sa, albedo_floor, min_weight;
 };
 
-APT_HD float up_max(float a, float b) { return a > b ? a : b; }
-
 // ---- prepare: the three records of low pixel i of n ----------------------------------------------------------------------------------
 APT_HD void up_prepare(const UpArgs &A, uint64_t n, uint64_t i) {
     const float cov = A.lf[APT_FEATURE_COVERAGE * n + i];
-    const float u = 1.0f - cov;
+    const float u = fs_uncovered(cov);
     float al[3], il[3];
     APT_UNROLL
     for (uint64_t ch = 0; ch < 3; ++ch) {
-        al[ch] = up_max(A.lf[(APT_FEATURE_ALBEDO + ch) * n + i] + u, A.albedo_floor);
+        al[ch] = fs_albedo(A.lf[(APT_FEATURE_ALBEDO + ch) * n + i], u, A.albedo_floor);
         il[ch] = A.lo[ch * n + i] / al[ch];
     }
     A.ci[i] = UpRec{il[0], il[1], il[2], cov};
@@ -62,12 +61,13 @@ APT_HD void up_pixel(const UpArgs &A, uint32_t x, uint32_t y) {
     const float cov_p = A.hf[APT_FEATURE_COVERAGE * n + p];
     const float z_p = A.hf[APT_FEATURE_DEPTH * n + p];
     const float nx = A.hf[APT_FEATURE_NORMAL * n + p], ny = A.hf[(APT_FEATURE_NORMAL + 1) * n + p], nz = A.hf[(APT_FEATURE_NORMAL + 2) * n + p];
-    const float u1 = 1.0f - cov_p;
+    const float u1 = fs_uncovered(cov_p);
     float Ap[3];
     APT_UNROLL
-    for (uint64_t ch = 0; ch < 3; ++ch) Ap[ch] = up_max(A.hf[(APT_FEATURE_ALBEDO + ch) * n + p] + u1, A.albedo_floor);
+    for (uint64_t ch = 0; ch < 3; ++ch) Ap[ch] = fs_albedo(A.hf[(APT_FEATURE_ALBEDO + ch) * n + p], u1, A.albedo_floor);
     const float zz = z_p + 1e-6f;
     const float iz = 1.0f / zz;
+    const FsGuide gp = {nx, ny, nz, z_p, cov_p, Ap[0], Ap[1], Ap[2]};
 
     double x0, fx, y0, fy;
     up_axis(x, A.lw, A.w, &x0, &fx);
@@ -85,23 +85,9 @@ APT_HD void up_pixel(const UpArgs &A, uint32_t x, uint32_t y) {
             if (!(qx >= 0.0 && qx <= xmax && qy >= 0.0 && qy <= ymax)) continue;
             const uint64_t q = (uint64_t)(uint32_t)qx * A.lh + (uint32_t)qy;        // inside the low image: the compares above
             const UpRec c_q = A.ci[q], n_q = A.gn[q], a_q = A.ga[q];
-            const float cc = cov_p * c_q.w;
-            float dt = 0.0f + nx * n_q.x;
-            dt = dt + ny * n_q.y;
-            dt = dt + nz * n_q.z;
-            const float xn = A.sn * up_max(cc - dt, 0.0f);
-            const float xz = (A.sz * fabsf(z_p - n_q.w)) * iz;
-            const float xc = A.sc * fabsf(cov_p - c_q.w);
-            float da = fabsf(Ap[0] - a_q.x) + fabsf(Ap[1] - a_q.y);
-            da = da + fabsf(Ap[2] - a_q.z);
-            const float xa = A.sa * da;
-            float xs = xn + xz;
-            xs = xs + xc;
-            xs = xs + xa;
-            float t = up_max(1.0f - xs * 0.125f, 0.0f);
-            t = t * t;
-            t = t * t;
-            const float g = t * t;
+            const FsGuide gq = {n_q.x, n_q.y, n_q.z, n_q.w, c_q.w, a_q.x, a_q.y, a_q.z};
+            const FsSigma gs = {A.sn, A.sz, A.sc, A.sa};   // read at the tap, as before: it keeps the kernel's instructions
+            const float g = fs_edge_falloff(fs_edge_sum(gp, iz, gq, gs));
             const float w = b * g;
             if (w > 0.0f) {
                 Wg = Wg + w;

@@ -1,5 +1,5 @@
 // adaptive_driver.cpp -- CPU sanitizer driver for the host code of adaptive sampling (include/render_mi355x_adaptive.h;
-// tests/test_adaptive_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/adaptive_host.cpp; no GPU, no HIP):
+// tests/test_film_stage_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/adaptive_host.cpp and csrc/film_stage_host.cpp; no GPU, no HIP):
 // apt_film_select_host, apt_film_accumulate_list_host and apt_film_mean_host on the sizes of the CPU test, every buffer an exactly sized
 // heap block (a stray access is ASan's to see).  What it computes is also CHECKED.
 // Prints "ok <checks>" and exits 0; a failed check prints what failed and exits 1; a sanitizer report aborts.

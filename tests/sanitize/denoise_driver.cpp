@@ -1,5 +1,5 @@
 // denoise_driver.cpp -- CPU sanitizer driver for the host code of the film's moments and its filter (include/render_mi355x_denoise.h;
-// tests/test_denoise_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/denoise_host.cpp; no GPU, no HIP):
+// tests/test_film_stage_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/denoise_host.cpp and csrc/film_stage_host.cpp; no GPU, no HIP):
 // apt_film_accumulate_host and apt_film_denoise_host on the small shapes of the CPU test, every buffer an exactly sized heap block
 // (a stray access is ASan's to see) and guard floats round `work` and `out` inside theirs.  What it computes is also CHECKED.
 // Prints "ok <checks>" and exits 0; a failed check prints what failed and exits 1; a sanitizer report aborts.

@@ -1,5 +1,5 @@
 // history_driver.cpp -- CPU sanitizer driver for the host code of temporal accumulation (include/render_mi355x_history.h;
-// tests/test_history_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/history_host.cpp; no GPU, no HIP):
+// tests/test_film_stage_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/history_host.cpp and csrc/film_stage_host.cpp; no GPU, no HIP):
 // apt_film_history_host and apt_film_history_export_host on the sizes of the CPU test, every buffer an exactly sized heap block (a
 // stray access is ASan's to see), with cameras that send taps outside the previous image, behind it and onto NaN and zero-coverage
 // pixels.  What it computes is also CHECKED.

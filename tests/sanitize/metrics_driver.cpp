@@ -1,5 +1,5 @@
 // metrics_driver.cpp -- CPU sanitizer driver for the host code of the film comparison metrics (include/render_mi355x_metrics.h;
-// tests/test_metrics_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/metrics_host.cpp; no GPU, no HIP):
+// tests/test_film_stage_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/metrics_host.cpp and csrc/film_stage_host.cpp; no GPU, no HIP):
 // apt_film_compare_host and apt_film_ssim_host on the sizes of the CPU test, every buffer an exactly sized heap block (a stray access
 // is ASan's to see), with NaN, infinite and huge pixels in the films.  What it computes is also CHECKED.
 // Prints "ok <checks>" and exits 0; a failed check prints what failed and exits 1; a sanitizer report aborts.

@@ -1,5 +1,5 @@
 // post_driver.cpp -- CPU sanitizer driver for the host code of metering and bloom (include/render_mi355x_post.h;
-// tests/test_post_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/post_host.cpp; no GPU, no HIP):
+// tests/test_film_stage_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/post_host.cpp and csrc/film_stage_host.cpp; no GPU, no HIP):
 // apt_film_meter_host, apt_film_exposure_host and apt_film_bloom_host on the sizes of the CPU test, every buffer an exactly sized
 // heap block (a stray access is ASan's to see), with NaN, infinite, negative and subnormal pixels in the films.  What it computes is
 // also CHECKED.

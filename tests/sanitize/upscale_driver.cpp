@@ -1,5 +1,5 @@
 // upscale_driver.cpp -- CPU sanitizer driver for the host code of guided film upscaling (include/render_mi355x_upscale.h;
-// tests/test_upscale_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/upscale_host.cpp; no GPU, no HIP):
+// tests/test_film_stage_sanitizers.py builds it with -fsanitize=address,undefined together with csrc/upscale_host.cpp and csrc/film_stage_host.cpp; no GPU, no HIP):
 // apt_film_upscale_host and apt_film_upscale_patch_host on the sizes of the CPU test, every buffer an exactly sized heap block (a
 // stray access is ASan's to see), `work` from posix_memalign, with NaN and zero-coverage pixels among the planes.  What it computes
 // is also CHECKED.
