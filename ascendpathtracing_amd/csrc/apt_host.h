@@ -83,6 +83,10 @@ struct apt_context {
 
 namespace apt {
 apt_context &default_context(); // process-wide, constructed on first use (thread-safe static)
+// first_plan.hip: enqueue the kernel that writes the first-bounce plan record of launch `ticket` into its slot behind the context's status
+// word (pt_first_plan.h); false when the launch failed
+struct Camera;
+bool launch_first_plan(void *stream, const float *spheres_dev, const Camera &cam, uint32_t width, uint32_t height, float eps, uint32_t *status_dev, uint64_t ticket);
 // What both forms of the film resolve refuse (host_helpers.cpp; include/render_mi355x.h "film"): APT_OK or the error record set.
 int film_resolve_check(const apt_film_resolve *r, const void *film, const void *table, const void *out, const void *u8, const char *what);
 // The cell size of both grid builders, in sphere centres per cell: the default context's "grid_spheres_per_cell" knob, or

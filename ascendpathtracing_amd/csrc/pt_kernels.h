@@ -4,6 +4,7 @@
 #pragma once
 #include "pt_trace.h"
 #include "pt_trace2.h"
+#include "pt_first_plan.h"
 #include "pt_queue.h"
 #include "pt_frame_mt.h"
 
@@ -188,7 +189,8 @@ __global__ __launch_bounds__(kBlock) void render_paths_queue_kernel(const float 
 // ---- kernel: fused frame ----------------------------------------------------------------
 // FrameArgs, the lanes' sub-pixels (GROUP), the camera in LDS and the decode: pt_frame.h
 // TWO: two samples of a lane's chain are traced at a time (pt_trace2.h); only with SC == kScene8, GROUP == 8, no
-// retirement, no roulette (the host picks the kernel).
+// retirement, no roulette (the host picks the kernel).  There first_plan_ticket(ta) (pt_trace.h: the slot ta.grid has for scenes behind a grid)
+// is the launch's first-bounce plan ticket (pt_first_plan.h; first_plan.hip makes the record), 0 = none: skip nothing.
 template <int MODE, int SC, int GROUP, bool RETIRE, bool TWO = false>
 __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? APT_GRID_WAVES : (SC == kSceneTiles ? APT_TILE_WAVES : APT_FULL_WAVES))) void render_frame_kernel(const float *__restrict__ sph, FrameArgs fa,
                                                               TraceArgs ta, LeafProg lp) {
@@ -219,6 +221,25 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
     uint32_t traced = 0;       // segments of this lane's own pixel (gated by `valid` at the end)
     uint32_t queue_traced = 0; // refill queue: segments this lane traced for ANY valid item of its wave
 
+    // The wave's first-bounce plan: its two pixels (lanes 0 .. 31 and 32 .. 63; lanes past the range trace the launch's first pixel and
+    // are read as that) against the record, on the scalar unit, once per wave; what both pixels allow.
+    uint32_t first_plan = 0;
+    const uint64_t ticket = TWO ? first_plan_ticket(ta) : 0;
+    if (TWO && ticket != 0 && ta.status) {
+        // the record of this launch's ticket, behind the context's status word; taken only when every entry carries the ticket
+        // (lane k < 14 takes entry k, its ticket and its comparison: three ballots, and the wave's scalar registers never hold the record)
+        const uint64_t *const rec = reinterpret_cast<const uint64_t *>(ta.status + first_plan_slot_word(ticket));
+        const uint32_t k = lane < 14u ? lane : 13u;
+        const uint64_t e = rec[k];
+        if (__builtin_amdgcn_ballot_w64((uint32_t)(e >> 32) != (uint32_t)ticket) == 0) {
+            const int32_t r = (int32_t)(uint32_t)e;
+            const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)pi, 0), r0 = (uint32_t)__builtin_amdgcn_readlane((int)pj, 0);
+            const uint32_t c1 = (uint32_t)__builtin_amdgcn_readlane((int)pi, 32), r1 = (uint32_t)__builtin_amdgcn_readlane((int)pj, 32);
+            const uint32_t conds0 = (uint32_t)__builtin_amdgcn_ballot_w64(first_plan_cond(k, r, fa.width, fa.height, c0, r0)) & 0x3FFFu;
+            const uint32_t conds1 = (uint32_t)__builtin_amdgcn_ballot_w64(first_plan_cond(k, r, fa.width, fa.height, c1, r1)) & 0x3FFFu;
+            first_plan = first_plan_combine(conds0) & first_plan_combine(conds1);
+        }
+    }
     const Gain3 gain = load_gain(sph, ta);
     struct Col { float r, g, b; };
     auto sample = [&](uint32_t k) __attribute__((always_inline)) -> Col {
@@ -251,7 +272,7 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
         // (no instruction: the six pairs are pinned to registers here.  Without it the allocator carries them through the bounce loop in
         // the registers the conversions wrote and pays with 6 v_mov_b32 in the loop's first pair-bounce, every turn.)
         asm("" : "+v"(pp.ox), "+v"(pp.oy), "+v"(pp.oz), "+v"(pp.dx), "+v"(pp.dy), "+v"(pp.dz));
-        trace2_ns8<MODE>(sc, tab8, pp, ta, planes);
+        trace2_ns8<MODE, true>(sc, tab8, pp, ta, planes, first_plan);
         traced += 2 * ta.depth;
         return Col2{Col{pp.rx.x * gain.r, pp.ry.x * gain.g, pp.rz.x * gain.b}, Col{pp.rx.y * gain.r, pp.ry.y * gain.g, pp.rz.y * gain.b}};
     };

@@ -68,13 +68,23 @@ struct TraceArgs {
     uint32_t emission;          // APT_FLAG_EMISSION: gain per channel = emission of sphere `light` instead of `gain`
     uint32_t rr_start;          // Russian roulette (APT_FLAG_RR): first bounce count it applies at; 0 = off
     uint64_t seed;              // keys the roulette draws
-    const uint32_t *grid;       // apt_render_params.accel (device) or null
+    const uint32_t *grid;       // apt_render_params.accel (device) or null.  ONLY kernels of a scene behind a grid (SC == kSceneGrid) may read it as
+                                // a grid: for the 8-sphere scene make_trace_args() sets it to null, and the launch of the two-path frame kernel then
+                                // puts its first-bounce plan ticket there (first_plan_ticket() below; an integer, not an address)
     uint32_t grid_walk;         // frame kernels: 0 = render_frame_kernel walks the grid (nested item walk); 2 = it returns at once when
                                 // the sample-queue kernel's grid form renders this frame (grid_queue_usable); sample-queue kernel:
                                 // 3 = APT_FLAG_GRID_SLOTS, it is the frame's only launch and reports a grid it cannot use
     unsigned long long *traced; // optional device counter of traced segments
     uint32_t *status;           // the context's device status word (include/render_mi355x.h APT_DEV_*), or null
 };
+// The first-bounce plan ticket of a launch of the two-path frame kernel of the 8-sphere scene (pt_first_plan.h), 0 = none.  It travels in
+// the argument slot `grid` has: a field of its own would move the arguments behind it in every render kernel (TraceArgs is followed by
+// the leaf plan), and the kernels' symbols and argument layouts are pinned by the tests that read the listings.  These two functions are
+// the only places that read or write the slot under that meaning.
+static_assert(sizeof(const uint32_t *) == sizeof(uint64_t), "a ticket fits the slot");
+__host__ __device__ __forceinline__ uint64_t first_plan_ticket(const TraceArgs &ta) { return (uint64_t)reinterpret_cast<uintptr_t>(ta.grid); }
+inline void set_first_plan_ticket(TraceArgs &ta, uint64_t ticket) { ta.grid = reinterpret_cast<const uint32_t *>((uintptr_t)ticket); }
+
 // Workgroup id -> the block of work it takes, XCD-aware.  The dispatcher hands consecutive workgroup ids to the 8 XCDs of an MI355X in turn,
 // and each XCD has its own L2: with the identity mapping the workgroups that write one 128-byte line of the frame (32 float pixels of a plane,
 // 42 u8 pixels) sit on different XCDs, every L2 holds -- and writes back -- a PART of the line, and the fabric saw 1.20x the frame's bytes

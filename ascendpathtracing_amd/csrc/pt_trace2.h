@@ -109,9 +109,14 @@ constexpr int kAbSkip = 0xC0;
 // v_max_f32 (a NaN drops out: a path whose med3 is NaN is outside the mask, as it is in the one-path form) and one compare.
 // amin: per path, |disc| of the walls two spheres per instruction as before; a skipped sphere's share is left out (it could only
 // have asked for the exact re-run, which finds the same miss).
-template <int MODE, int SKIP>
+// PLAN (the pair's first bounce in the frame kernel): `plan`, bit k, wave-uniform -- sphere k cannot be the first hit of any camera ray
+// of the wave's pixels (pt_first_plan.h: the wall, ball and light rules with their proofs; every key of such a sphere is above the
+// winner's or >= key(kMissT)).  Sphere k's own-coordinate terms, b, c, disc, joint test and stage then sit behind ONE scalar branch on
+// an opaque flag and cost no vector instruction; a wall whose partner is skipped takes its |disc| into `amin` alone, as a tested
+// sphere does (the minimum of the same set).  The shared terms x2, y0, z0 stay unconditional, the order stays ascending.
+template <int MODE, int SKIP, bool PLAN = false>
 __device__ __forceinline__ void intersect2_ns8_planes(const Scene8 &sc, const PathPair &s, const TraceArgs &ta, const KeyConsts &kc,
-                                                      float &aminA, float &aminB, Hit8 &hA, Hit8 &hB) {
+                                                      float &aminA, float &aminB, Hit8 &hA, Hit8 &hB, uint32_t plan = 0) {
     struct Term { f2 p, q; };   // (c - o) * d and (c - o)^2 of one centre coordinate, both paths
     auto term = [](auto half, f2 cpair, f2 o, f2 d) __attribute__((always_inline)) {
         const f2 t = pair_half_minus<decltype(half)::value>(cpair, o);
@@ -149,7 +154,26 @@ __device__ __forceinline__ void intersect2_ns8_planes(const Scene8 &sc, const Pa
         aminB = minimum3_abs(aminB, h.disc.y, h.disc.y);
         stage(h, k);
     };
+    auto wall = [&](const Pre &h, int k) __attribute__((always_inline)) {   // one wall of a pair whose spheres the plan decides one by one
+        aminA = minimum3_abs(aminA, h.disc.x, h.disc.x);
+        aminB = minimum3_abs(aminB, h.disc.y, h.disc.y);
+        stage(h, k);
+    };
+    // (a copy made HERE, for this intersection alone: the kernel's mask lives across the whole sample loop, is spilled, and read in place
+    // it comes back through a v_readlane_b32 in front of every branch; the copy is short-lived and stays in its scalar register)
+    uint32_t here = 0;
+    if (PLAN) asm volatile("s_mov_b32 %0, %1" : "=s"(here) : "s"(plan));
+    auto planned = [&](auto bit) __attribute__((always_inline)) {   // -> 0: the plan leaves sphere decltype(bit)::value out
+        // (volatile: made where it is read.  Left to the compiler the seven flags are made once per wave, live in seven spilled
+        // scalars, and each first bounce pays a v_readlane_b32 per flag to get them back)
+        uint32_t run;
+        asm volatile("s_bitcmp0_b32 %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(run) : "s"(here), "n"(decltype(bit)::value) : "scc");
+        return run;
+    };
     static_assert((SKIP & 0x3F) == 0, "the walls have no test: the room lies inside their spheres");
+    using B0 = std::integral_constant<int, 0>; using B1 = std::integral_constant<int, 1>; using B3 = std::integral_constant<int, 3>;
+    using B4 = std::integral_constant<int, 4>; using B5 = std::integral_constant<int, 5>; using B6 = std::integral_constant<int, 6>;
+    using B7 = std::integral_constant<int, 7>;   // (the bit index is an immediate of the asm statement: a type, not a value the optimiser has to fold)
     // the scalar pairs of intersect_pre_planes(): every constant is one half of an aligned SGPR pair
     const f2 X1 = {sc.cx[0], sc.cx[1]}, X2 = {sc.cx[2], sc.cx[6]}, Y1 = {sc.cy[4], sc.cy[5]}, Y2 = {sc.cy[6], sc.cy[7]}, Y3 = {sc.cy[0], sc.cy[0]};
     const f2 Z1 = {sc.cz[2], sc.cz[3]}, Z2 = {sc.cz[0], sc.cz[6]};
@@ -157,11 +181,22 @@ __device__ __forceinline__ void intersect2_ns8_planes(const Scene8 &sc, const Pa
     using Lo = std::integral_constant<int, 0>;
     using Hi = std::integral_constant<int, 1>;
     const Term x2 = term(Lo{}, X2, s.ox, s.dx), y0 = term(Lo{}, Y3, s.oy, s.dy), z0 = term(Lo{}, Z2, s.oz, s.dz);   // the shared planes
-    walls(pre(term(Lo{}, X1, s.ox, s.dx), y0, z0, Lo{}, R0), pre(term(Hi{}, X1, s.ox, s.dx), y0, z0, Hi{}, R0), 0);
-    walls(pre(x2, y0, term(Lo{}, Z1, s.oz, s.dz), Lo{}, R1), pre(x2, y0, term(Hi{}, Z1, s.oz, s.dz), Hi{}, R1), 2);
-    walls(pre(x2, term(Lo{}, Y1, s.oy, s.dy), z0, Lo{}, R2), pre(x2, term(Hi{}, Y1, s.oy, s.dy), z0, Hi{}, R2), 4);
-    tested(pre(term(Hi{}, X2, s.ox, s.dx), term(Lo{}, Y2, s.oy, s.dy), term(Hi{}, Z2, s.oz, s.dz), Lo{}, R3), 6);
-    tested(pre(x2, term(Hi{}, Y2, s.oy, s.dy), z0, Hi{}, R3), 7);
+    if (PLAN) {
+        if (planned(B0{}) != 0u) wall(pre(term(Lo{}, X1, s.ox, s.dx), y0, z0, Lo{}, R0), 0);
+        if (planned(B1{}) != 0u) wall(pre(term(Hi{}, X1, s.ox, s.dx), y0, z0, Hi{}, R0), 1);
+        wall(pre(x2, y0, term(Lo{}, Z1, s.oz, s.dz), Lo{}, R1), 2);   // (the wall the camera looks at: no rule)
+        if (planned(B3{}) != 0u) wall(pre(x2, y0, term(Hi{}, Z1, s.oz, s.dz), Hi{}, R1), 3);
+        if (planned(B4{}) != 0u) wall(pre(x2, term(Lo{}, Y1, s.oy, s.dy), z0, Lo{}, R2), 4);
+        if (planned(B5{}) != 0u) wall(pre(x2, term(Hi{}, Y1, s.oy, s.dy), z0, Hi{}, R2), 5);
+        if (planned(B6{}) != 0u) tested(pre(term(Hi{}, X2, s.ox, s.dx), term(Lo{}, Y2, s.oy, s.dy), term(Hi{}, Z2, s.oz, s.dz), Lo{}, R3), 6);
+        if (planned(B7{}) != 0u) tested(pre(x2, term(Hi{}, Y2, s.oy, s.dy), z0, Hi{}, R3), 7);
+    } else {
+        walls(pre(term(Lo{}, X1, s.ox, s.dx), y0, z0, Lo{}, R0), pre(term(Hi{}, X1, s.ox, s.dx), y0, z0, Hi{}, R0), 0);
+        walls(pre(x2, y0, term(Lo{}, Z1, s.oz, s.dz), Lo{}, R1), pre(x2, y0, term(Hi{}, Z1, s.oz, s.dz), Hi{}, R1), 2);
+        walls(pre(x2, term(Lo{}, Y1, s.oy, s.dy), z0, Lo{}, R2), pre(x2, term(Hi{}, Y1, s.oy, s.dy), z0, Hi{}, R2), 4);
+        tested(pre(term(Hi{}, X2, s.ox, s.dx), term(Lo{}, Y2, s.oy, s.dy), term(Hi{}, Z2, s.oz, s.dz), Lo{}, R3), 6);
+        tested(pre(x2, term(Hi{}, Y2, s.oy, s.dy), z0, Hi{}, R3), 7);
+    }
     hA = A.finish(ta, kc);
     hB = B.finish(ta, kc);
 }
@@ -172,14 +207,15 @@ __device__ __forceinline__ void intersect2_ns8_planes(const Scene8 &sc, const Pa
 // FIRST: the first bounce of a pair.  Both paths are alive and their throughput is (1, 1, 1) by definition: s.rx / ry / rz and
 // the incoming masks are not read, the new masks are ~light, and the new throughput IS the albedo entry (or the (1, 1, 1) entry
 // for a path that hit the light) -- no products.
-template <int MODE, bool PLANES, bool FIRST>
+// PLAN (with FIRST and PLANES only): `plan` is the wave's first-bounce plan, see intersect2_ns8_planes.
+template <int MODE, bool PLANES, bool FIRST, bool PLAN = false>
 __device__ __forceinline__ void bounce2_ns8_t(const Scene8 &sc, const Tab8 tab, const PathPair &s, PathPair &n,
                                               const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
-                                              uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
+                                              uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB, uint32_t plan = 0) {
     float aminA = 1.0f, aminB = 1.0f; // per path: a finished path's request for the exact form can be ignored (trace2_ns8)
     Hit8 hA, hB;
     if (PLANES) {
-        intersect2_ns8_planes<MODE, kAbSkip>(sc, s, ta, kc, aminA, aminB, hA, hB);
+        intersect2_ns8_planes<MODE, kAbSkip, PLAN && FIRST>(sc, s, ta, kc, aminA, aminB, hA, hB, plan);
     } else {
         hA = intersect_ns8_v2<MODE>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
         hB = intersect_ns8_v2<MODE>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
@@ -275,14 +311,14 @@ __device__ __forceinline__ void bounce2_ns8_first(const Scene8 &sc, const Tab8 t
 // albedo (or 1) -- rx / ry / rz receive those products.  No hit point, normal, square root, quotient or reflection; only the
 // albedo entries are read from LDS; the validity chain ends with the discriminants (nothing else here uses a fast sequence).
 // FIRST (depth 1: the last bounce is also the first): as in bounce2_ns8_t.
-template <int MODE, bool PLANES, bool FIRST = false>
+template <int MODE, bool PLANES, bool FIRST = false, bool PLAN = false>
 __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 tab, const PathPair &s, f2 &rx, f2 &ry, f2 &rz,
                                                  const TraceArgs &ta, const KeyConsts &kc, uint32_t ones_off,
-                                                 uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB) {
+                                                 uint64_t &aliveA, uint64_t &aliveB, uint64_t &redoA, uint64_t &redoB, uint32_t plan = 0) {
     float aminA = 1.0f, aminB = 1.0f;
     Hit8 hA, hB;
     if (PLANES) {
-        intersect2_ns8_planes<MODE, kAbSkip>(sc, s, ta, kc, aminA, aminB, hA, hB);
+        intersect2_ns8_planes<MODE, kAbSkip, PLAN && FIRST>(sc, s, ta, kc, aminA, aminB, hA, hB, plan);
     } else {
         hA = intersect_ns8_v2<MODE>(sc, s.ox.x, s.oy.x, s.oz.x, s.dx.x, s.dy.x, s.dz.x, ta, kc, aminA);
         hB = intersect_ns8_v2<MODE>(sc, s.ox.y, s.oy.y, s.oz.y, s.dx.y, s.dy.y, s.dz.y, ta, kc, aminB);
@@ -318,8 +354,8 @@ __device__ __forceinline__ void bounce2_ns8_last(const Scene8 &sc, const Tab8 ta
 // throughputs of `s` are meaningful: depth - 1 bounces produce a ray, the last one (bounce2_ns8_last) does not.
 //   depth 0: throughput 1.   depth 1: last<first>(s).   depth >= 2: first(s -> n), ping-pong steps from n, last from whichever
 //   half holds the state.
-template <int MODE, bool PLANES>
-__device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta) {
+template <int MODE, bool PLANES, bool PLAN = false>
+__device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta, uint32_t plan = 0) {
     const KeyConsts kc = make_key_consts(ta.eps);
     uint32_t ones_off = 8 * 16; // the entry after the 8 albedos (load_scene8 writes it)
     asm volatile("" : "+v"(ones_off));
@@ -441,7 +477,7 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
         bool redo_any = !fast_ok;
         if (__builtin_expect(fast_ok, 1)) {
             uint64_t redoA, redoB;
-            bounce2_ns8_t<MODE, PLANES, first>(sc, tab, in, out, ta, kc, ones_off, oa, ob, redoA, redoB);
+            bounce2_ns8_t<MODE, PLANES, first, PLAN && PLANES>(sc, tab, in, out, ta, kc, ones_off, oa, ob, redoA, redoB, plan);
             if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB, first);
         }
         if (__builtin_expect(redo_any, 0)) {
@@ -469,7 +505,7 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
         bool redo_any = !fast_ok;
         if (__builtin_expect(fast_ok, 1)) {
             uint64_t redoA, redoB;
-            bounce2_ns8_last<MODE, PLANES, first>(sc, tab, in, rx, ry, rz, ta, kc, ones_off, oa, ob, redoA, redoB);
+            bounce2_ns8_last<MODE, PLANES, first, PLAN && PLANES>(sc, tab, in, rx, ry, rz, ta, kc, ones_off, oa, ob, redoA, redoB, plan);
             if (__builtin_expect((redoA | redoB) != 0, 0)) redo_any = redo_stands(in, redoA, redoB, first);
         }
         if (__builtin_expect(redo_any, 0)) {
@@ -507,8 +543,9 @@ __device__ __forceinline__ void trace2_ns8_t(const Scene8 &sc, const Tab8 tab, P
 }
 
 // `planes`: scene8_shares_planes(sc), evaluated once per wave by the kernel (wave-uniform branch around two copies of the loop)
-template <int MODE>
-__device__ __forceinline__ void trace2_ns8(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta, bool planes) {
+// PLAN: the caller's rays are camera rays and `plan` their wave's first-bounce plan (the frame kernel); read by the shared-planes arm only.
+template <int MODE, bool PLAN = false>
+__device__ __forceinline__ void trace2_ns8(const Scene8 &sc, const Tab8 tab, PathPair &s, const TraceArgs &ta, bool planes, uint32_t plan = 0) {
     if (planes) {
         // scene8_shares_planes() compared these bit for bit: naming each shared coordinate ONCE lets this arm -- its exact cold block
         // included -- keep 13 centre coordinates in scalar registers instead of 24 (the (A, B)-packed intersection holds both paths'
@@ -517,7 +554,7 @@ __device__ __forceinline__ void trace2_ns8(const Scene8 &sc, const Tab8 tab, Pat
         p.cx[3] = p.cx[4] = p.cx[5] = p.cx[7] = sc.cx[2];
         p.cy[1] = p.cy[2] = p.cy[3] = sc.cy[0];
         p.cz[1] = p.cz[4] = p.cz[5] = p.cz[7] = sc.cz[0];
-        trace2_ns8_t<MODE, true>(p, tab, s, ta);
+        trace2_ns8_t<MODE, true, PLAN>(p, tab, s, ta, plan);
     } else {
         trace2_ns8_t<MODE, false>(sc, tab, s, ta);
     }

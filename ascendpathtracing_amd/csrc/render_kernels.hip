@@ -10,6 +10,7 @@
 // Built with -ffp-contract=off -fno-slp-vectorize (Makefile); see DESIGN.md sections 2 and 4.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <new>
 #include <stdint.h>
 #include <stdio.h>
@@ -108,8 +109,15 @@ int check_lights_status(const MatArgs &m, const uint32_t *status) {
 }
 
 // The device status word of `ctx` on the current device (include/render_mi355x.h "Device-side failure channel"), made on the
-// context's first launch there: 4 bytes of device memory, once.  Null -- the kernels then report nothing -- when it does not exist yet
-// and cannot be made now (the stream is being captured, or the allocation failed).
+// context's first launch there: one allocation of apt::kFirstPlanAllocWords words (8256 bytes), once.  Null -- the kernels then report
+// nothing -- when it does not exist yet and cannot be made now (the stream is being captured, or the allocation failed).
+// Behind the word, in the same allocation, the slots of the first-bounce plan records (pt_first_plan.h, kFirstPlanBase: layout, tickets and
+// why a record is never read as another launch's).  The ticket count is one for the process, not one per context: a ticket only has to
+// differ from every other launch's that may write the same memory, and a count no two launches share does that for every context at once.
+std::atomic<uint64_t> g_plan_ticket{1};
+uint64_t plan_ticket(uint32_t *status) {   // 0: no allocation (the capture-first case above), the frame kernel skips nothing
+    return status ? g_plan_ticket.fetch_add(1u, std::memory_order_relaxed) : 0u;
+}
 uint32_t *status_word(apt_context &ctx, hipStream_t st) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
@@ -119,7 +127,7 @@ uint32_t *status_word(apt_context &ctx, hipStream_t st) {
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     if (cs != hipStreamCaptureStatusNone) return nullptr;
     apt::DeviceBuffer<uint32_t> fresh;
-    if (fresh.alloc(1) != hipSuccess || hipMemset(fresh.get(), 0, sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (fresh.alloc(apt::kFirstPlanAllocWords) != hipSuccess || hipMemset(fresh.get(), 0, apt::kFirstPlanAllocWords * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     uint32_t *spare = nullptr;
     uint32_t *w = ctx.status_adopt(dev, fresh.release(), &spare);
     apt::DeviceBuffer<uint32_t> loser(spare);   // another thread was first (or the device index is beyond the table)
@@ -137,7 +145,7 @@ TraceArgs make_trace_args(const apt_render_params *p, const Launch &ls) {
     ta.eps = p->eps; ta.gain = p->gain; ta.traced = cv.trace_counter;
     ta.status = ls.status;
     ta.refill_lanes = cv.refill_lanes;
-    ta.grid = (p->num_spheres != 8) ? reinterpret_cast<const uint32_t *>((uintptr_t)p->accel) : nullptr;
+    ta.grid = (p->num_spheres != 8) ? reinterpret_cast<const uint32_t *>((uintptr_t)p->accel) : nullptr;   // (8 spheres: null, or the two-path frame kernel's plan ticket -- pt_trace.h first_plan_ticket)
     ta.grid_walk = 0;
     ta.emission = (p->flags & APT_FLAG_EMISSION) ? 1u : 0u;
     ta.rr_start = (p->flags & APT_FLAG_RR) ? (p->rr_start ? p->rr_start : 3u) : 0u;
@@ -330,10 +338,16 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
         if (ns8 && group == 8) {
             // With APT_FLAG_RETIRE these frames belong to the sample-queue kernel (above); what arrives here with the flag set is depth 0,
             // where there is nothing to retire.  The headline case -- >= 16 samples, every segment traced, no roulette -- runs two paths per lane.
-            if (!retire && !rrk && p->samples >= 16)
-                hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 8, false, true>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);
-            else
+            if (!retire && !rrk && p->samples >= 16) {
+                // its first-bounce plan, made on the device in front of it (the table lives there), every call; without a record: skip nothing
+                uint64_t ticket = plan_ticket(ls.status);
+                if (ticket && !apt::launch_first_plan(st, spheres, fa.cam, fa.width, fa.height, ta.eps, ls.status, ticket)) ticket = 0;
+                TraceArgs ta2 = ta;
+                set_first_plan_ticket(ta2, ticket);   // (in ta.grid's slot, null for every 8-sphere launch: make_trace_args, pt_trace.h)
+                hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 8, false, true>), grid, dim3(kBlock), lds, st, spheres, fa, ta2, lp);
+            } else {
                 hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 8, false>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);
+            }
         } else if (ns8) {
             with_flag(retire, [&](auto rt) {
                 hipLaunchKernelGGL((render_frame_kernel<m, kScene8, 1, rt>), grid, dim3(kBlock), lds, st, spheres, fa, ta, lp);

@@ -191,7 +191,7 @@ int  apt_context_set_refill_lanes(apt_context *ctx, uint32_t lanes);
  *   apt_render_host and apt_multi_render check it themselves before they return.
  * The word is allocated on a context's first launch on a device -- through ANY launching entry point, render_do / render_do_ex /
  * render_frame / apt_render_frame_mt included: the one allocation those otherwise allocation-free calls ever make -- (one hipMalloc of
- * 4 bytes, once per context and device, device indices 0..15; a device beyond that runs without a word; skipped while `stream` is being
+ * 8256 bytes -- the word, and behind it the records render_frame's two-paths-per-lane kernel reads its first-bounce plan from --, once per context and device, device indices 0..15; a device beyond that runs without a word; skipped while `stream` is being
  * captured -- a context whose FIRST launch on a device happens inside a graph capture runs without the word until a launch or an
  * apt_context_check outside a capture has made it). */
 enum {
