@@ -65,6 +65,7 @@ APT_HD uint32_t first_plan_slot_word(uint64_t ticket) { return kFirstPlanBase + 
 constexpr double kFirstPlanDepth = 4.0;      // m of (a)
 constexpr double kFirstPlanCErr = 3072.0;    // fp32 error bound of a wall's c
 constexpr double kFirstPlanMaxEps = 1.0;
+constexpr uint32_t kFirstPlanMaxSide = 1u << 24;   // a wider or higher frame has no plan: no record (first_plan_setup), no ticket (render_kernels.hip), no mask
 
 struct FpIv { double lo, hi; };
 APT_HD FpIv fp_lin(double c, FpIv x, double g) { return c >= 0 ? FpIv{c * x.lo + g, c * x.hi + g} : FpIv{c * x.hi + g, c * x.lo + g}; }
@@ -104,7 +105,7 @@ APT_HD FpIv fp_origin(double pos, FpIv d) { return FpIv{pos + 140.0 * d.lo - 0x1
 APT_HD void first_plan_setup(const Camera &cam, uint32_t width, uint32_t height, const float *sph, float eps, FirstPlanGeom &g) {
     g.ok = false;
     if (!(cam.cx[1] == 0 && cam.cx[2] == 0 && cam.cy[0] == 0 && cam.g[0] == 0 && cam.cx[0] > 0)) return;
-    if (!(width >= 1 && height >= 1 && width <= (1u << 24) && height <= (1u << 24))) return;
+    if (!(width >= 1 && height >= 1 && width <= kFirstPlanMaxSide && height <= kFirstPlanMaxSide)) return;
     if (!(eps_allows_rootkey(eps) && (double)eps <= kFirstPlanMaxEps)) return;
     g.cx0 = cam.cx[0]; g.cy1 = cam.cy[1]; g.cy2 = cam.cy[2]; g.g1 = cam.g[1]; g.g2 = cam.g[2];
     g.pos[0] = cam.pos[0]; g.pos[1] = cam.pos[1]; g.pos[2] = cam.pos[2];
@@ -271,6 +272,8 @@ APT_HD int32_t first_plan_entry(const FirstPlanGeom &g, int which) {
 // The spheres a pixel's camera rays cannot hit first (bit k = sphere k), from the record -- in two steps, so that the frame kernel can take
 // the first one entry per lane: first_plan_cond(k, ...) is entry k's own comparison with the pixel's column or row, and
 // first_plan_combine() makes the mask from the 14 results (bit k of `conds` = entry k's).
+// (int32 comparisons: for width, height <= kFirstPlanMaxSide only.  From 2^31 on n - r wraps and the all-zero record would mark the ball
+// everywhere; such a launch gets no ticket and never comes here, and first_plan_mask() answers 0 for it.)
 APT_HD bool first_plan_cond(uint32_t k, int32_t r, uint32_t width, uint32_t height, uint32_t col, uint32_t row) {
     const bool on_col = k == 0 || k == 1 || k == 4 || k == 5 || k == 9 || k == 10;
     const int32_t x = on_col ? (int32_t)col : (int32_t)row, n = on_col ? (int32_t)width : (int32_t)height;
@@ -289,6 +292,7 @@ APT_HD uint32_t first_plan_combine(uint32_t conds) {
     return m;
 }
 APT_HD uint32_t first_plan_mask(const int32_t *r, uint32_t width, uint32_t height, uint32_t col, uint32_t row) {
+    if (width > kFirstPlanMaxSide || height > kFirstPlanMaxSide) return 0;
     uint32_t conds = 0;
     for (uint32_t k = 0; k < 14; ++k) conds |= first_plan_cond(k, r[k], width, height, col, row) ? 1u << k : 0u;
     return first_plan_combine(conds);

@@ -225,12 +225,20 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
     // are read as that) against the record, on the scalar unit, once per wave; what both pixels allow.
     uint32_t first_plan = 0;
     const uint64_t ticket = TWO ? first_plan_ticket(ta) : 0;
+#ifdef APT_COUNT_FIRST_PLAN
+    bool plan_taken = false;     // every entry carried the launch's ticket
+    uint64_t plan_entry = 0;     // what this lane read
+#endif
     if (TWO && ticket != 0 && ta.status) {
         // the record of this launch's ticket, behind the context's status word; taken only when every entry carries the ticket
         // (lane k < 14 takes entry k, its ticket and its comparison: three ballots, and the wave's scalar registers never hold the record)
         const uint64_t *const rec = reinterpret_cast<const uint64_t *>(ta.status + first_plan_slot_word(ticket));
         const uint32_t k = lane < 14u ? lane : 13u;
         const uint64_t e = rec[k];
+#ifdef APT_COUNT_FIRST_PLAN
+        plan_entry = e;
+        plan_taken = __builtin_amdgcn_ballot_w64((uint32_t)(e >> 32) != (uint32_t)ticket) == 0;
+#endif
         if (__builtin_amdgcn_ballot_w64((uint32_t)(e >> 32) != (uint32_t)ticket) == 0) {
             const int32_t r = (int32_t)(uint32_t)e;
             const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)pi, 0), r0 = (uint32_t)__builtin_amdgcn_readlane((int)pj, 0);
@@ -240,6 +248,28 @@ __global__ __launch_bounds__(kBlock, TWO ? APT_TWO_WAVES : (SC == kSceneGrid ? A
             first_plan = first_plan_combine(conds0) & first_plan_combine(conds1);
         }
     }
+#ifdef APT_COUNT_FIRST_PLAN   // test build only (make variant NAME=first_plan_count EXTRA=-DAPT_COUNT_FIRST_PLAN, tests/test_gpu_first_bounce_plan_device.py):
+    // what the plan did on the DEVICE.  The statistics block (apt_set_trace_counter) must then have B + 32 = 480 entries;
+    // B = 448 is clear of what APT_COUNT_PAIR_SKIP writes (entries 4 .. 423, pt_trace2.h).  Per wave whose lane 0 holds a
+    // pixel of the range (a wave of the grid's tail holds none and is not counted):
+    //   [B + 0] += 1      [B + 1] += 1 when the record was taken (every entry carried the launch's ticket)
+    //   [B + 2 + k] += 1 for each bit k < 8 of first_plan, the mask the first pair-bounce is given
+    // and the launch's first wave (pixel 0 of the range) stores what it read: [B + 16 + k] = entry k's value, k < 14, and
+    // [B + 30] = the low word of the launch's ticket.  (No ticket or no status word: nothing was read, and nothing is stored.)
+    if (TWO && ta.traced) {
+        constexpr uint32_t B = 448;
+        if (lane == 0 && valid) {
+            atomicAdd(ta.traced + B, 1ull);
+            if (plan_taken) atomicAdd(ta.traced + B + 1, 1ull);
+            for (uint32_t k = 0; k < 8; ++k)
+                if ((first_plan >> k) & 1u) atomicAdd(ta.traced + B + 2 + k, 1ull);
+        }
+        if (valid && pl == 0 && lane < 14u && ticket != 0 && ta.status) {
+            ta.traced[B + 16 + lane] = (unsigned long long)(uint32_t)plan_entry;
+            if (lane == 0) ta.traced[B + 30] = (unsigned long long)(uint32_t)ticket;
+        }
+    }
+#endif
     const Gain3 gain = load_gain(sph, ta);
     struct Col { float r, g, b; };
     auto sample = [&](uint32_t k) __attribute__((always_inline)) -> Col {

@@ -115,7 +115,13 @@ int check_lights_status(const MatArgs &m, const uint32_t *status) {
 // why a record is never read as another launch's).  The ticket count is one for the process, not one per context: a ticket only has to
 // differ from every other launch's that may write the same memory, and a count no two launches share does that for every context at once.
 std::atomic<uint64_t> g_plan_ticket{1};
-uint64_t plan_ticket(uint32_t *status) {   // 0: no allocation (the capture-first case above), the frame kernel skips nothing
+// (A frame wider or higher than 2^24 gets no ticket either: its record would be the all-zero one, and first_plan_cond() compares in int32,
+// where a width or height from 2^31 on turns "the last 0 columns" into every column -- pt_first_plan.h.)
+uint64_t plan_ticket(uint32_t *status, uint32_t width, uint32_t height) {   // 0: no allocation (the capture-first case above), the frame kernel skips nothing
+#ifdef APT_TEST_NO_FIRST_PLAN   // test build only (make variant ... EXTRA=-DAPT_TEST_NO_FIRST_PLAN): no plan at all, to tell a rule's fault from the kernel's
+    return 0u;
+#endif
+    if (width > apt::kFirstPlanMaxSide || height > apt::kFirstPlanMaxSide) return 0u;
     return status ? g_plan_ticket.fetch_add(1u, std::memory_order_relaxed) : 0u;
 }
 uint32_t *status_word(apt_context &ctx, hipStream_t st) {
@@ -340,7 +346,7 @@ int do_render_frame(const Launch &ls, const apt_render_params *p, void *stream, 
             // where there is nothing to retire.  The headline case -- >= 16 samples, every segment traced, no roulette -- runs two paths per lane.
             if (!retire && !rrk && p->samples >= 16) {
                 // its first-bounce plan, made on the device in front of it (the table lives there), every call; without a record: skip nothing
-                uint64_t ticket = plan_ticket(ls.status);
+                uint64_t ticket = plan_ticket(ls.status, fa.width, fa.height);
                 if (ticket && !apt::launch_first_plan(st, spheres, fa.cam, fa.width, fa.height, ta.eps, ls.status, ticket)) ticket = 0;
                 TraceArgs ta2 = ta;
                 set_first_plan_ticket(ta2, ticket);   // (in ta.grid's slot, null for every 8-sphere launch: make_trace_args, pt_trace.h)

@@ -9,87 +9,21 @@ nothing, and the plan must not be vacuous.
 The rays are restated, not reproduced: origin and direction are made in float64 from the camera's definition and rounded once, without
 the kernel's fast sequences, so a ray here can differ from the kernel's in its last float32 bit.  The rules' margins (pt_first_plan.h)
 are many orders of magnitude wider than that; the frames themselves are compared bit for bit by tests/test_gpu_first_bounce_plan.py."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS = 1e-4
-RULE_BITS = (0, 1, 3, 4, 5, 6, 7)      # sphere 2, the wall the camera looks at, has no rule
+import first_plan_ref
+from first_plan_ref import RULE_BITS, camera, first_bounce_keys, jitters, masks, record
 
 
 @pytest.fixture(scope="module")
 def twin():
-    import __graft_entry__ as g
-    g.build()
-    L = ctypes.CDLL(os.path.join(ROOT, "ascendpathtracing_amd", "libfirstplan_mi355x.so"))
-    L.apt_first_plan_host.restype = ctypes.c_int
-    L.apt_first_plan_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
-    L.apt_first_plan_camera_host.restype = ctypes.c_int
-    L.apt_first_plan_camera_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
-    L.apt_first_plan_mask_host.restype = ctypes.c_uint32
-    L.apt_first_plan_mask_host.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
-    return L
+    return first_plan_ref.twin()
 
 
 @pytest.fixture(scope="module")
 def table():
-    from ascendpathtracing_amd import gen_data
-    return np.ascontiguousarray(gen_data.gen_spheres(), dtype=np.float32)
-
-
-def camera(L, w, h):
-    cam = np.zeros(12)
-    assert L.apt_first_plan_camera_host(w, h, cam.ctypes.data) == 0
-    return cam
-
-
-def record(L, w, h, sph, cam=None, eps=EPS):
-    rec = np.full(16, -1, dtype=np.int32)
-    assert L.apt_first_plan_host(w, h, sph.ctypes.data, eps, None if cam is None else cam.ctypes.data, rec.ctypes.data) == 0
-    return rec
-
-
-def masks(L, rec, w, h, cols, rows):
-    return np.array([[L.apt_first_plan_mask_host(rec.ctypes.data, w, h, int(c), int(r)) for r in rows] for c in cols], dtype=np.uint32)
-
-
-def jitters(rng, n):
-    """Offsets inside a pixel, camera_ray_t's ((s + 0.5 + tent) / 2 with s in {0, 1}, tent in [-1, 1)): the footprint's corners and
-    edges first, then uniform ones."""
-    lo, hi = -0.25, np.nextafter(1.25, 0.0)
-    edge = np.array([lo, hi, 0.0, 0.5, 1.0])
-    gx, gy = np.meshgrid(edge, edge, indexing="ij")
-    fx = np.concatenate([gx.ravel(), rng.uniform(lo, hi, n), np.full(n // 8, lo), np.full(n // 8, hi), rng.uniform(lo, hi, n // 4)])
-    fy = np.concatenate([gy.ravel(), rng.uniform(lo, hi, n), rng.uniform(lo, hi, n // 4), np.full(n // 8, lo), np.full(n // 8, hi)])
-    return fx, fy
-
-
-def first_bounce_keys(cam, w, h, sph, cols, rows, fx, fy):
-    """-> keys [pixel, jitter, sphere] (inf: no accepted root), float32 arithmetic in the kernel's order."""
-    pos, g, cx, cy = cam[0:3], cam[3:6], cam[6:9], cam[9:12]
-    a = (cols[:, None] + fx[None, :]) / w - 0.5
-    b = (rows[:, None] + fy[None, :]) / h - 0.5
-    d = np.stack([cx[k] * a + cy[k] * b + g[k] for k in range(3)], axis=-1)            # gen_data.py:41-43, float64
-    o = (pos + d * 140).astype(np.float32)
-    d = (d / np.sqrt((d * d).sum(-1, keepdims=True))).astype(np.float32)
-    f = np.float32
-    r2, C = sph[0:8], np.stack([sph[8:16], sph[16:24], sph[24:32]], axis=-1)
-    t = C[None, None, :, :] - o[:, :, None, :]                                           # c - o, per coordinate
-    p = t * d[:, :, None, :]
-    q = t * t
-    bb = (p[..., 0] + p[..., 1]) + p[..., 2]
-    cc = ((q[..., 0] + q[..., 1]) + q[..., 2]) - r2[None, None, :]
-    assert bb.dtype == f and cc.dtype == f
-    disc = bb * bb - cc
-    with np.errstate(invalid="ignore"):
-        root = np.sqrt(disc)
-        t0, t1 = bb - root, bb + root
-        k0 = np.where(t0 > f(EPS), t0, f(np.inf))
-        k1 = np.where(t1 > f(EPS), t1, f(np.inf))
-    return np.minimum(k0, k1)
+    return first_plan_ref.reference_table()
 
 
 def check_shape(L, sph, w, h, cols, rows, seed):

@@ -5,6 +5,8 @@ bounce between them.  The pixel range starts and ends mid-column, so waves strad
 import numpy as np
 import pytest
 
+import first_plan_ref
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -35,11 +37,11 @@ def modes(apt, oracle):
     return ((apt.APT_MODE_KERNEL, oracle.MODE_K), (apt.APT_MODE_ORACLE, oracle.MODE_O))
 
 
-def check(apt, oracle, sph_h, w, h, depth, mode, omode, begin=0, count=None, seed=3):
+def check(apt, oracle, sph_h, w, h, depth, mode, omode, begin=0, count=None, seed=3, eps=1e-4):
     count = w * h - begin if count is None else count
-    fb_w, u8_w, _, _ = oracle.render_frame(oracle.make_params(w, h, 16, depth=depth, mode=omode, seed=seed), sph_h, pixel_begin=begin,
+    fb_w, u8_w, _, _ = oracle.render_frame(oracle.make_params(w, h, 16, depth=depth, mode=omode, seed=seed, eps=eps), sph_h, pixel_begin=begin,
                                            pixel_count=count, threads=oracle.max_threads())
-    fb, u8 = apt.render.render_frame(apt.make_params(w, h, 16, depth=depth, mode=mode, seed=seed), dev(sph_h), pixel_begin=begin, pixel_count=count)
+    fb, u8 = apt.render.render_frame(apt.make_params(w, h, 16, depth=depth, mode=mode, seed=seed, eps=eps), dev(sph_h), pixel_begin=begin, pixel_count=count)
     torch.cuda.synchronize()
     assert np.array_equal(bits(fb), bits(fb_w)), (w, h, depth, mode, begin, count)
     assert np.array_equal(u8.cpu().numpy(), u8_w), (w, h, depth, mode, begin, count)
@@ -48,20 +50,9 @@ def check(apt, oracle, sph_h, w, h, depth, mode, omode, begin=0, count=None, see
 def plan_marks_every_rule(w, h, sph_h):
     """The plan of this shape through its CPU twin: every rule (spheres 0, 1, 3, 4, 5, 6, 7) leaves its sphere out for some pixel, so a
     frame that equals the oracle's was rendered with spheres left out, not with an empty plan."""
-    import ctypes
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    L = ctypes.CDLL(os.path.join(root, "ascendpathtracing_amd", "libfirstplan_mi355x.so"))
-    L.apt_first_plan_mask_host.restype = ctypes.c_uint32
-    sph = np.ascontiguousarray(sph_h, dtype=np.float32)
-    rec = np.zeros(16, dtype=np.int32)
-    assert L.apt_first_plan_host(ctypes.c_uint32(w), ctypes.c_uint32(h), ctypes.c_void_p(sph.ctypes.data), ctypes.c_double(1e-4), None,
-                                 ctypes.c_void_p(rec.ctypes.data)) == 0
-    seen = 0
-    for c in range(w):
-        for j in range(h):
-            seen |= L.apt_first_plan_mask_host(ctypes.c_void_p(rec.ctypes.data), w, h, c, j)
-    return seen == 0xFB
+    L = first_plan_ref.twin()
+    rec = first_plan_ref.record(L, w, h, sph_h, eps=1e-4)
+    return int(np.bitwise_or.reduce(first_plan_ref.masks(L, rec, w, h, range(w), range(h)).ravel())) == 0xFB
 
 
 @pytest.mark.parametrize("w,h", [(64, 36), (33, 19)])
@@ -104,6 +95,40 @@ def test_tables_the_plan_refuses(apt, oracle):
     for sph_h in (near, planes):
         for mode, omode in modes(apt, oracle):
             check(apt, oracle, sph_h, 64, 36, 3, mode, omode)
+
+
+FAMILY_SEED, FAMILY_FRAMES = 7, 24
+
+
+@pytest.fixture(scope="module")
+def family_frames():
+    """24 members of the test family (tests/first_plan_ref.py) that the plan accepts under the reference's camera -- the render ABI has no
+    other for this kernel -- alternately 33 x 19 and 64 x 36, eps going round the family's set; across them every rule marks pixels in
+    at least five."""
+    L = first_plan_ref.twin()
+    found, marks, i = [], {k: 0 for k in first_plan_ref.RULE_BITS}, 0
+    while len(found) < FAMILY_FRAMES:
+        w, h = ((33, 19), (64, 36))[len(found) % 2]
+        eps = first_plan_ref.FAMILY_EPS[len(found) % len(first_plan_ref.FAMILY_EPS)]
+        sph, _, _, _ = first_plan_ref.family_case(FAMILY_SEED, i, shape=(w, h), reference_camera=True)
+        rec = first_plan_ref.record(L, w, h, sph, eps=eps)
+        if rec.any():
+            seen = int(np.bitwise_or.reduce(first_plan_ref.masks(L, rec, w, h, range(w), range(h)).ravel()))
+            for k in marks:
+                marks[k] += (seen >> k) & 1
+            found.append((i, sph, eps, w, h))
+        i += 1
+    assert all(v >= 5 for v in marks.values()), marks
+    return found
+
+
+@pytest.mark.parametrize("n", range(FAMILY_FRAMES))
+def test_family_frames_equal_the_oracle(apt, oracle, family_frames, n):
+    """The product build at tables nobody rendered before: other rooms, walls at the ends of their radius range, balls that are tiny, huge,
+    far away or on the origins, lights of radius 10 .. 1e7, eps up to 1.  Depth 2, S = 16, K- and O-mode, bit for bit."""
+    member, sph_h, eps, w, h = family_frames[n]
+    for mode, omode in modes(apt, oracle):
+        check(apt, oracle, sph_h, w, h, 2, mode, omode, eps=eps, seed=100 + member)
 
 
 def test_a_captured_launch_replays(apt, oracle):
